@@ -42,6 +42,25 @@ CONFIGS = {
     3: dict(size=256, nc=3, blocks=9, batch=32, precision="bf16x3", name="configs[2] (configs[3] at 8 GPUs)"),
     5: dict(size=512, nc=1, blocks=9, batch=16, precision="bf16x3", name="configs[4]"),
 }
+DUMP_MAX_ELEMS = 1 << 21    # --dump-outputs: 8 MB of float32 per visual at most, 48 MB for all six
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: the (losses, visuals[, gnorms]) a train_instance call returned, one DIR/<name>.npy per value"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    losses, visuals = result[0], result[1]
+    gnorms = result[2] if len(result) > 2 else {}
+    arrays = [("loss_" + k, np.float64(v)) for k, v in losses.items()] + [(k, np.float64(v)) for k, v in gnorms.items()]
+    for k, v in visuals.items():
+        v = v.detach().float()
+        if v.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_MAX_ELEMS, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        arrays.append((k, v.cpu().numpy()))
+    for name, arr in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def parse_args(argv=None):
@@ -75,7 +94,16 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher test: ranks rendezvous over gloo on the CPU, exchange one all-reduce and print the line "
                          "without touching a GPU")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed train_instance returned on rank 0 as DIR/<name>.npy: "
+                         "the losses as loss_<key> and the gradient norms / latent monitors under their own keys (float64 "
+                         "scalars), the six visuals (real_A, fake_B, rec_A, real_B, fake_A, rec_B; float32).  A visual of more "
+                         "than %d elements is written as a fixed sample of its flattened elements (the sorted indices "
+                         "numpy.random.default_rng(0).choice(numel, %d, replace=False)), so a dump stays under 64 MB"
+                         % (DUMP_MAX_ELEMS, DUMP_MAX_ELEMS))
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     c = CONFIGS[3 if a.config == 4 else a.config]
     for k in ("batch", "size", "blocks", "nc", "precision"):
         if getattr(a, k) is None:
@@ -310,8 +338,11 @@ def main():
             ev = torch.cuda.Event(enable_timing=True); ev.record(); step_marks.append((ev, time.time()))
     barrier()
     dt = time.time() - t0
-    losses = (last.result() if hasattr(last, "result") else last)[0]
+    result = last.result() if hasattr(last, "result") else last
+    losses = result[0]
     ops.CONV_TIMERS[:] = []
+    if a.dump_outputs and rank == 0:    # (a replayed step's visuals are the graph's buffers: read before anything else runs)
+        dump_outputs(a.dump_outputs, result)
     if step_marks:
         print("per-step: GPU ms between step ends %s | host s at step ends %s" % (
             " ".join("%.1f" % step_marks[k][0].elapsed_time(step_marks[k + 1][0]) for k in range(len(step_marks) - 1)),

@@ -50,3 +50,25 @@ def test_bench_line_graph_replay_and_eager_agree():
         assert d["fused_paths"]["per_step"]["wgrad_s16"] == 16.0
     assert "captured HIP graph" in g["config"]["launch"] and e["config"]["launch"] == "eager"
     assert g["config"]["loss_G_A"] == e["config"]["loss_G_A"]      # the replay runs the same launches on the same inputs
+
+
+def test_bench_dump_outputs_repeat_for_the_same_arguments(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned (here a graph replay: its visuals are the graph's buffers),
+    and two runs with the same arguments start from the same inputs and compute the same outputs."""
+    import numpy as np
+    dumps, lines = [], []
+    for r in range(2):
+        d = str(tmp_path / ("run%d" % r))
+        line, _ = _bench("--warmup", "3", "--timer-every", "0", "--dump-outputs", d)
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+        lines.append(line)
+    a, b = dumps
+    visuals = ("real_A", "fake_B", "rec_A", "real_B", "fake_A", "rec_B")
+    assert sum(k.startswith("loss_") for k in a) == 13 and all(k in a for k in visuals) and len(a) == 13 + 10 + 6, sorted(a)
+    for k in visuals:
+        assert a[k].dtype == np.float32 and a[k].shape == (2, 3, 128, 128) and np.isfinite(a[k]).all(), k
+    assert abs(float(a["loss_G_A"]) - lines[0]["config"]["loss_G_A"]) < 1e-5
+    assert np.array_equal(a["real_A"], b["real_A"]) and np.array_equal(a["real_B"], b["real_B"])
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-5, atol=1e-6), k

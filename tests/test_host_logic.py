@@ -212,6 +212,31 @@ def test_bench_launches_its_own_ranks():
         assert bad.returncode != 0 and "rank exit codes" in bad.stderr
 
 
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR`: one .npy per returned value — scalars as float64, visuals as float32, a visual larger
+    than DUMP_MAX_ELEMS as the fixed sorted sample numpy.random.default_rng(0) draws — and `--steps` below 1 is refused."""
+    from collections import OrderedDict
+    import bench
+    big = torch.rand(1, 3, 1024, 1024)
+    small = torch.rand(2, 3, 8, 8)
+    losses = OrderedDict([("D_A", 0.25), ("G_A", 1.5)])
+    gnorms = OrderedDict([("gnorm_G_A_B", 3.0), ("mu_min", -0.5)])
+    bench.dump_outputs(str(tmp_path), (losses, OrderedDict([("fake_B", big), ("rec_A", small)]), gnorms))
+    assert sorted(os.listdir(tmp_path)) == ["fake_B.npy", "gnorm_G_A_B.npy", "loss_D_A.npy", "loss_G_A.npy", "mu_min.npy",
+                                            "rec_A.npy"]
+    for name, v in (("loss_D_A", 0.25), ("loss_G_A", 1.5), ("gnorm_G_A_B", 3.0), ("mu_min", -0.5)):
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.dtype == np.float64 and a.shape == () and float(a) == v
+    a = np.load(str(tmp_path / "rec_A.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy())
+    a = np.load(str(tmp_path / "fake_B.npy"))
+    idx = np.sort(np.random.default_rng(0).choice(big.numel(), bench.DUMP_MAX_ELEMS, replace=False))
+    assert a.dtype == np.float32 and np.array_equal(a, big.numpy().ravel()[idx])
+    assert 6 * bench.DUMP_MAX_ELEMS * 4 < 64 << 20          # six visuals of the headline step fit the 64 MB bound
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 _WORKER8 = """
 import os, sys
 sys.path.insert(0, %(root)r)
