@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ACGAN_HIP_LIB: load another build of the SAME library (A/B timing of kernel changes on one GPU box)
 LIB_PATH = os.environ.get("ACGAN_HIP_LIB") or os.path.join(_HERE, "libacgan_hip.so")
 
-ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 IMPL_MFMA, IMPL_DIRECT = 0, 1
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
@@ -27,7 +27,7 @@ class ConvDesc(ctypes.Structure):
 class LatentMlpParams(ctypes.Structure):
     """acg_latent_mlp_params (include/acgan_hip.h)."""
     _fields_ = [("w", c_void_p * 4), ("b", c_void_p * 4), ("gamma", c_void_p * 3), ("beta", c_void_p * 3),
-                ("run_mean", c_void_p * 3), ("run_var", c_void_p * 3)]
+                ("run_mean", c_void_p * 3), ("run_var", c_void_p * 3), ("head_act", c_int)]
 
 
 class LatentMlpGrads(ctypes.Structure):
@@ -131,13 +131,15 @@ SIGNATURES = {
     "acg_linear_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "acg_latent_mlp_supported": (c_int, [c_int, c_int, c_int]),
     "acg_latent_mlp_fwd": (c_int, [_MP, _P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
-    "acg_latent_mlp_bwd": (c_int, [_MP, _MG, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
+    "acg_latent_mlp_bwd": (c_int, [_MP, _MG, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
     "acg_segments_accumulate": (c_int, [_P, ctypes.POINTER(Segments), c_int, _P]),
     "acg_spatial_mean_fwd": (c_int, [_P, _P, c_int, c_size_t, c_int, _P]),
     "acg_spatial_mean_bwd": (c_int, [_P, _P, c_int, c_size_t, c_int, _P]),
     "acg_reduce_workspace_bytes": (c_size_t, [c_size_t]),
     "acg_mse_const_fwd": (c_int, [_P, c_size_t, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
     "acg_mse_const_bwd": (c_int, [_P, c_size_t, c_int, c_int, c_float, _P, _P, _P]),
+    "acg_bce_const_fwd": (c_int, [_P, c_size_t, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "acg_bce_const_bwd": (c_int, [_P, c_size_t, c_int, c_int, c_float, _P, _P, _P]),
     "acg_l1_fwd": (c_int, [_P, _P, c_size_t, c_int, c_int, _P, _P, c_size_t, _P]),
     "acg_l1_bwd": (c_int, [_P, _P, c_size_t, c_int, c_int, _P, _P, _P, _P]),
     "acg_mean_fwd": (c_int, [_P, c_size_t, c_int, c_int, _P, _P, c_size_t, _P]),
@@ -154,7 +156,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 117   # include/acgan_hip.h ACG_VERSION this binding was written against
+ABI_VERSION = 118   # include/acgan_hip.h ACG_VERSION this binding was written against
 
 
 class AcgError(RuntimeError):

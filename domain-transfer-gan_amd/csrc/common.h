@@ -56,3 +56,25 @@ __device__ __forceinline__ float acg_act_grad_from_y(float y, int act)
     default: return 1.f;
     }
 }
+// The convolution epilogues' activation argument: the acg_act kind in the low byte; a sigmoid carries the real output channel
+// count above it (acg_act_sigmoid_ch).  Every other activation maps the zero of a padded channel to zero, the sigmoid would
+// store 0.5 there — the epilogue writes exactly 0 instead (padded channels hold zeros).  Packed into `act` rather than a
+// field of its own: a larger Geom moves the kernel arguments of every convolution kernel.
+__host__ __device__ __forceinline__ int acg_act_kind(int act) { return act & 0xff; }
+static inline int acg_act_sigmoid_ch(int creal) { return ACG_ACT_SIGMOID | (creal << 8); }
+// The sigmoid is kept out of acg_apply_act / acg_act_grad_from_y: their run-time switch is inlined into every convolution
+// epilogue, and a case more there changed the register allocation of kernels that never see a sigmoid.  The paths a sigmoid
+// can reach (the head epilogues below, the dense layers, activation backward) call the _s variants.
+__device__ __forceinline__ float acg_apply_act_s(float v, int act)
+{
+    return act == ACG_ACT_SIGMOID ? 1.f / (1.f + expf(-v)) : acg_apply_act(v, act);
+}
+__device__ __forceinline__ float acg_act_grad_from_y_s(float y, int act)
+{
+    return act == ACG_ACT_SIGMOID ? y * (1.f - y) : acg_act_grad_from_y(y, act);
+}
+__device__ __forceinline__ float acg_apply_act_ch(float v, int act, int c)
+{
+    if (acg_act_kind(act) == ACG_ACT_SIGMOID) return c >= (act >> 8) ? 0.f : acg_apply_act_s(v, ACG_ACT_SIGMOID);
+    return acg_apply_act(v, act);
+}

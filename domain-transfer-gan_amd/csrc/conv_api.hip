@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void thin_out_conv_kernel(const float *__restr
         if (j == 0 && mok) {
             acc += bv;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = acg_apply_act(acc[k], g.act);
+            for (int k = 0; k < 4; ++k) acc[k] = acg_apply_act_ch(acc[k], g.act, k);
             float *o = out + (((long long)n * g.Hout + (gy * g.os + g.oy0)) * g.Wout + (gx * g.os + g.ox0)) * g.Cout;
             *(f32x4 *)o = acc;
             for (int c = 4; c < g.Cout; c += 4) *(f32x4 *)(o + c) = z;
@@ -275,6 +275,7 @@ static int thin_out_launch(const float *in, const float *wn, const float *bias, 
     }
 #undef THIN_LAUNCH
     ACG_CHECK_LAUNCH("thin_out_conv_kernel");
+    acg_note_kernel("thin_out_conv<LPP=%d>", lpp);
     return ACG_OK;
 }
 
@@ -723,7 +724,7 @@ __global__ void direct_fwd_kernel(acg_conv_desc d, const float *__restrict__ x, 
             for (int ci = 0; ci < d.Ci; ++ci)
                 acc += xp[ci] * wf[(((long long)tap * (c16d(d.Ci) / 8) + ci / 8) * CoP + co) * 8 + (ci & 7)];
         }
-    y[i] = acg_apply_act(acc, act);
+    y[i] = act == ACG_ACT_SIGMOID && co >= (d.Cor > 0 ? d.Cor : d.Co) ? 0.f : acg_apply_act_s(acc, act);
 }
 
 // dx[n,iy,ix,ci] = sum over padded preimages (py,px), taps, co.  Also used (with bias/act) as the
@@ -826,7 +827,8 @@ static void fwd_geom(const acg_conv_desc *d, Geom *g, Taps *t, int act)
     g->Hin = d->Hi; g->Win = d->Wi; g->Cin = d->Ci;
     g->Hout = d->Ho; g->Wout = d->Wo; g->Cout = d->Co;
     g->GH = d->Ho; g->GW = d->Wo; g->os = 1; g->oy0 = 0; g->ox0 = 0; g->is = d->stride;
-    g->reflect = d->pad_mode == ACG_PAD_REFLECT; g->act = act; g->ncols_pad = acg_ncols_pad(d->Co);
+    g->reflect = d->pad_mode == ACG_PAD_REFLECT; g->ncols_pad = acg_ncols_pad(d->Co);
+    g->act = act == ACG_ACT_SIGMOID ? acg_act_sigmoid_ch(d->Cor > 0 ? d->Cor : d->Co) : act;
     g->Mtot = (long long)d->N * d->Ho * d->Wo;
     g->thin = thin_in(d) ? 1 : 0;
     g->w_elems = (long long)wf_regular_elems(d->K, d->Ci, d->Co);
@@ -930,6 +932,7 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
                        int relu_s16 = 0, float *stats = nullptr, const acg_norm_sums *ns = nullptr,
                        const unsigned *relu_mask = nullptr)
 {
+    ACG_REQUIRE(act != ACG_ACT_SIGMOID, "dgrad / ConvTranspose2d: no sigmoid epilogue");
     Geom g; Taps t;
     g.Hin = d->Ho; g.Win = d->Wo; g.Cin = d->Co;
     g.Cout = d->Ci; g.reflect = 0; g.act = act; g.ncols_pad = acg_ncols_pad(d->Ci); g.is = 1;
@@ -1109,12 +1112,16 @@ extern "C" int acg_conv2d_fwd(const acg_conv_desc *d, const float *x, const floa
 {
     int rc = check_desc(d, "acg_conv2d_fwd");
     if (rc) return rc;
+    ACG_REQUIRE(act >= ACG_ACT_NONE && act <= ACG_ACT_SIGMOID, "acg_conv2d_fwd: unknown activation %d", act);
+    // the sigmoid stores 0 in the padded channels: it needs the real count (the head convolutions of the discriminators)
+    ACG_REQUIRE(act != ACG_ACT_SIGMOID || (d->Cor >= 1 && d->Cor <= d->Co), "acg_conv2d_fwd: sigmoid needs Cor (real Co) in 1..Co");
     hipStream_t st = (hipStream_t)stream;
     if (g_acg_conv_impl == ACG_IMPL_DIRECT) {
         const long long total = (long long)d->N * d->Ho * d->Wo * d->Co;
         hipLaunchKernelGGL(direct_fwd_kernel, dim3(acg_cdiv(total, 256)), dim3(256), 0, st, *d, x, wf, bias, y, act,
                            acg_ncols_pad(d->Co));
         ACG_CHECK_LAUNCH("direct_fwd_kernel");
+        acg_note_kernel("direct_fwd_kernel");
         return ACG_OK;
     }
     Geom g; Taps t;
@@ -1260,6 +1267,7 @@ extern "C" int acg_conv2d_fwd_s16(const acg_conv_desc *d, const void *x, const f
     Geom g; Taps t;
     fwd_geom(d, &g, &t, stats != nullptr ? (int)ACG_ACT_NONE : act);
     ACG_REQUIRE(stats == nullptr || act == ACG_ACT_NONE, "acg_conv2d_fwd_s16: statistics with an activation");
+    ACG_REQUIRE(act != ACG_ACT_SIGMOID, "acg_conv2d_fwd_s16: no sigmoid epilogue");
     g.out_s16 = out_s16;
     return acg_igemm_x3_pre_launch(x, wf, bias, (float *)y, g, t, g.w_elems, (hipStream_t)stream, stats);
 }
@@ -1614,6 +1622,7 @@ extern "C" int acg_conv_transpose2d_fwd(const acg_conv_desc *d, const float *x, 
     int rc = check_desc(d, "acg_conv_transpose2d_fwd");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    ACG_REQUIRE(act != ACG_ACT_SIGMOID, "acg_conv_transpose2d_fwd: no sigmoid epilogue");
     if (g_acg_conv_impl == ACG_IMPL_DIRECT) {
         const long long total = (long long)d->N * d->Hi * d->Wi * d->Ci;
         hipLaunchKernelGGL(direct_dgrad_kernel, dim3(acg_cdiv(total, 256)), dim3(256), 0, st, *d, x, wb, bias, y, act,

@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void igemm_conv_bf16(const float *__restrict__
 #pragma unroll
             for (int i = 0; i < MB; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = acg_apply_act(acc[i][j][r] + bv, g.act);
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = acg_apply_act_ch(acc[i][j][r] + bv, g.act, co);
         }
     }
     const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + off0), 0, 0xFFFFFFF0u, 0x00020000);
@@ -480,7 +480,7 @@ bool acg_igemm_uses_ws(const Geom &g)
 {
     static const bool no_ws = acg_debug_switch("ACG_NO_WS"); // A/B switch
     return !no_ws && g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && g.Cout >= 128 &&
-           g.Cin % 32 == 0;
+           g.Cin % 32 == 0 && acg_act_kind(g.act) != ACG_ACT_SIGMOID;   // (no sigmoid epilogue: the generic tile takes it)
 }
 
 // n_w_elems: element count of the packed weight array (hi part); the lo part of BF16X3 sits right behind it

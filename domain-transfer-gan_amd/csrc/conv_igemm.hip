@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void igemm_conv_f32(const float *__restrict__ 
 #pragma unroll
             for (int i = 0; i < MB; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = acg_apply_act(acc[i][j][r] + bv, g.act);
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = acg_apply_act_ch(acc[i][j][r] + bv, g.act, co);
         }
     }
     typedef unsigned epi_u32x4 __attribute__((ext_vector_type(4)));

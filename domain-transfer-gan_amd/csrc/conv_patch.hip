@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void conv_patch16_x3(const float *__restrict__
         for (int k = 0; k < 4; ++k) {
             const int gx = gx0 + 4 * pl + k;
             if (gy < g.GH && gx < g.GW && lr < g.Cout)
-                out[(((long long)n * g.Hout + gy) * g.Wout + gx) * g.Cout + lr] = acg_apply_act(acc[r][k] + bv, g.act);
+                out[(((long long)n * g.Hout + gy) * g.Wout + gx) * g.Cout + lr] = acg_apply_act_ch(acc[r][k] + bv, g.act, lr);
         }
     }
 }
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int w = 1; w < 4; ++w) v += red[((w * 2 + mt) * 4 + r) * 64 + lane];
             const int gx = gx0 + 4 * r + dxo;
             if (gy < g.GH && gx < g.GW)   // 16 consecutive lanes: 4 pixels x 4 channels = 64 contiguous bytes
-                out[(((long long)n * g.Hout + gy) * g.Wout + gx) * 4 + c] = acg_apply_act(v + bv, g.act);
+                out[(((long long)n * g.Hout + gy) * g.Wout + gx) * 4 + c] = acg_apply_act_ch(v + bv, g.act, c);
         }
     }
 }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void conv_thinrow_x3(const float *__restrict__
 bool acg_conv_thinrow_ok(const Geom &g, const Taps &t)
 {
     static const bool off = acg_debug_switch("ACG_NO_THINROW"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || !g.thin || g.fold_p) return false;
+    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || !g.thin || g.fold_p || acg_act_kind(g.act) == ACG_ACT_SIGMOID) return false;
     if (g.Cin != 4 || g.Cout != 32 || g.ncols_pad != 32 || g.os != 1 || g.is != 1 || g.oy0 != 0 || g.ox0 != 0 || t.n < 4) return false;
     if (g.stats != nullptr && (g.GH % PT_TH != 0 || g.GW % PT_TW != 0 || g.act != ACG_ACT_NONE)) return false;   // whole 128-pixel tiles
     if (g.ns_part != nullptr && (g.stats != nullptr || g.GH % PT_TH != 0 || g.GW % PT_TW != 0 || g.act != ACG_ACT_NONE || g.ns_x == nullptr ||

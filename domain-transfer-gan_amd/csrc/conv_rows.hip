@@ -357,7 +357,8 @@ static bool rows_slabs(const Taps &t, unsigned long long *slabs)
 bool acg_conv_rows_ok(const Geom &g, const Taps &t)
 {
     static const bool off = acg_debug_switch("ACG_NO_ROWS"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.nphase || g.fold_p) return false;
+    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.nphase || g.fold_p ||
+        acg_act_kind(g.act) == ACG_ACT_SIGMOID) return false;   // (no sigmoid epilogue)
     if (g.stats != nullptr && (g.act != ACG_ACT_NONE || g.stats_chunk0 != 0 || (long long)g.stats_cpi * 128 != (long long)g.GH * g.GW)) return false;
     if (g.ns_part != nullptr && (g.stats != nullptr || g.ns_x == nullptr || g.ns_mask != nullptr || (g.ns_act != ACG_ACT_NONE && g.ns_act != ACG_ACT_RELU) ||
                                  (g.ns_gstride != 0 && g.ns_gstride < 64)))

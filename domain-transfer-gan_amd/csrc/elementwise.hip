@@ -111,7 +111,7 @@ __global__ void act_bwd_kernel(const float *__restrict__ dy, const float *__rest
         f32x4 g = *(const f32x4 *)(dy + i * 4);
         const f32x4 yy = *(const f32x4 *)(y + i * 4);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] *= acg_act_grad_from_y(yy[k], act);
+        for (int k = 0; k < 4; ++k) g[k] *= acg_act_grad_from_y_s(yy[k], act);
         *(f32x4 *)(dx + i * 4) = g;
     }
 }
@@ -312,7 +312,7 @@ __global__ void linear_fwd_kernel(const float *__restrict__ x, const float *__re
     if (o < O) {
         acc = b ? b[o] : 0.f;
         for (int k = 0; k < I; ++k) acc += x[(long long)n * ldx + k] * w[(long long)o * I + k];
-        acc = acg_apply_act(acc, act);
+        acc = acg_apply_act_s(acc, act);
     }
     y[i] = acc;
 }
@@ -338,7 +338,7 @@ __global__ void linear_bwd_kernel(const float *__restrict__ dy, const float *__r
         float acc = 0.f;
 #pragma unroll 8 // independent loads in flight: the rolled loop paid one L2 latency per output channel (19 us for 128)
         for (int o = 0; o < O; ++o) {
-            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y(y[(long long)n * Op + o], act);
+            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y_s(y[(long long)n * Op + o], act);
             acc += g * w[(long long)o * I + i];
         }
         dx[(long long)n * ldx + i] = acc;
@@ -348,7 +348,7 @@ __global__ void linear_bwd_kernel(const float *__restrict__ dy, const float *__r
         float acc = 0.f, bs = 0.f;
 #pragma unroll 8
         for (int n = 0; n < N; ++n) {
-            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y(y[(long long)n * Op + o], act);
+            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y_s(y[(long long)n * Op + o], act);
             acc += g * x[(long long)n * ldx + i];
             bs += g;
         }
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void linear_bwd_dx_kernel(const float *__restr
         const int o1 = (ch + 1) * OC < O ? (ch + 1) * OC : O;
 #pragma unroll 4
         for (int o = ch * OC; o < o1; ++o) {
-            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y(y[(long long)n * Op + o], act);
+            const float g = dy[(long long)n * Op + o] * acg_act_grad_from_y_s(y[(long long)n * Op + o], act);
             acc += g * w[(long long)o * I + i];
         }
     }
@@ -465,7 +465,15 @@ extern "C" int acg_spatial_mean_bwd(const float *dy, float *dx, int N, size_t P,
 }
 
 // ---------------------------------------------------------------- reductions to a device scalar
-// mode: 0 = sum((p-t)^2) ; 1 = sum(|a-b|) ; 2 = sum(p) ; 3 = sum(p^2) (no channel mask)
+// mode: 0 = sum((p-t)^2) ; 1 = sum(|a-b|) ; 2 = sum(p) ; 3 = sum(p^2) (no channel mask) ; 4 = sum of the binary cross
+// entropy of probability p against t (torch's clamp of both logarithms at -100; a NaN probability stays NaN)
+__device__ __forceinline__ float bce_term(float p, float t)
+{
+    float lp = logf(p), lq = log1pf(-p);
+    lp = lp < -100.f ? -100.f : lp;
+    lq = lq < -100.f ? -100.f : lq;
+    return (t - 1.f) * lq - t * lp;
+}
 #define RED_BLOCKS 1024
 template <int MODE>
 __global__ __launch_bounds__(256) void reduce_partial_kernel(const float *__restrict__ a, const float *__restrict__ b,
@@ -480,6 +488,7 @@ __global__ __launch_bounds__(256) void reduce_partial_kernel(const float *__rest
         if (MODE == 0) { const float d = v - target; s += d * d; }
         else if (MODE == 1) s += fabsf(v - b[i]);
         else if (MODE == 2) s += v;
+        else if (MODE == 4) s += bce_term(v, target);
         else s += v * v;
     }
     red[threadIdx.x] = s;
@@ -527,6 +536,12 @@ extern "C" int acg_mse_const_fwd(const float *p, size_t npix, int C, int Cp, flo
     return reduce_launch<0>(p, nullptr, (long long)npix * Cp, C, Cp, target, 1.f / ((float)npix * C), out, ws, ws_bytes,
                             (hipStream_t)stream, "acg_mse_const_fwd");
 }
+extern "C" int acg_bce_const_fwd(const float *p, size_t npix, int C, int Cp, float target, float *out, void *ws,
+                                 size_t ws_bytes, void *stream)
+{
+    return reduce_launch<4>(p, nullptr, (long long)npix * Cp, C, Cp, target, 1.f / ((float)npix * C), out, ws, ws_bytes,
+                            (hipStream_t)stream, "acg_bce_const_fwd");
+}
 extern "C" int acg_l1_fwd(const float *a, const float *b, size_t npix, int C, int Cp, float *out, void *ws,
                           size_t ws_bytes, void *stream)
 {
@@ -557,6 +572,29 @@ extern "C" int acg_mse_const_bwd(const float *p, size_t npix, int C, int Cp, flo
     hipLaunchKernelGGL(mse_const_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, p, total, C, Cp,
                        target, 2.f / ((float)npix * C), gout, dp);
     ACG_CHECK_LAUNCH("mse_const_bwd_kernel");
+    return ACG_OK;
+}
+// torch's binary_cross_entropy backward: gout (p - t) / max(p (1 - p), 1e-12), times 1 / count for the mean
+__global__ void bce_const_bwd_kernel(const float *__restrict__ p, long long total, int C, int Cp, float target,
+                                     float k, const float *__restrict__ gout, float *__restrict__ dp)
+{
+    const float g = gout[0] * k;
+    GRID_STRIDE(i, total) {
+        float v = 0.f;
+        if ((int)(i % Cp) < C) {
+            const float pi = p[i], q = pi * (1.f - pi);
+            v = g * (pi - target) / (q > 1e-12f ? q : 1e-12f);
+        }
+        dp[i] = v;
+    }
+}
+extern "C" int acg_bce_const_bwd(const float *p, size_t npix, int C, int Cp, float target, const float *gout, float *dp,
+                                 void *stream)
+{
+    const long long total = (long long)npix * Cp;
+    hipLaunchKernelGGL(bce_const_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, p, total, C, Cp,
+                       target, 1.f / ((float)npix * C), gout, dp);
+    ACG_CHECK_LAUNCH("bce_const_bwd_kernel");
     return ACG_OK;
 }
 __global__ void l1_bwd_kernel(const float *__restrict__ a, const float *__restrict__ b, long long total, int C, int Cp,

@@ -1,5 +1,5 @@
 // DiscriminatorLatent (networks.py:396-433) as ONE kernel per direction: Linear(I->H) BN1d LReLU(0.2), twice more H->H,
-// then Linear(H->1).  The whole batch (N x H activations) lives in one workgroup's LDS; BatchNorm1d runs in train mode
+// then Linear(H->1) [Sigmoid: use_sigmoid / --no_lsgan, networks.py:420-421].  The whole batch (N x H activations) lives in one workgroup's LDS; BatchNorm1d runs in train mode
 // (batch statistics, biased variance for the normalisation, running buffers updated with the unbiased one, networks.py:407-415).
 // Layer by layer this took 4 linear + 3 x (statistics, final, apply) launches forward and about twice that backward, three
 // times per training step: launch latency only (the arithmetic is 0.4 MFLOP).
@@ -8,6 +8,7 @@
 struct MlpParams {   // device pointers (mirrors acg_latent_mlp_params)
     const float *w[4], *b[4], *gamma[3], *beta[3];
     float *run_mean[3], *run_var[3];
+    int head_act;    // ACG_ACT_NONE or ACG_ACT_SIGMOID
 };
 struct MlpGrads {    // mirrors acg_latent_mlp_grads
     float *dw[4], *db[4], *dgamma[3], *dbeta[3];
@@ -121,15 +122,15 @@ __global__ __launch_bounds__(256) void latent_mlp_fwd_kernel(MlpParams p, const 
         float acc = 0.f;
         for (int k = tid & 15; k < H; k += 16) acc += xs[n * P + k] * p.w[3][k];
         acc += __shfl_xor(acc, 1); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 8);
-        if ((tid & 15) == 0) *(f32x4 *)(out + (long long)n * 4) = (f32x4){acc + p.b[3][0], 0.f, 0.f, 0.f};
+        if ((tid & 15) == 0) *(f32x4 *)(out + (long long)n * 4) = (f32x4){acg_apply_act_s(acc + p.b[3][0], p.head_act), 0.f, 0.f, 0.f};
     }
 }
 
 template <int J>
 __global__ __launch_bounds__(256) void latent_mlp_bwd_kernel(MlpParams p, MlpGrads gr, const float *__restrict__ z, int ldz, int N,
                                                              int I, int H, const float *__restrict__ a_save,
-                                                             const float *__restrict__ stats_save, const float *__restrict__ dout,
-                                                             float *__restrict__ dz, int accumulate)
+                                                             const float *__restrict__ stats_save, const float *__restrict__ out,
+                                                             const float *__restrict__ dout, float *__restrict__ dz, int accumulate)
 {
     extern __shared__ float lds[];
     const MlpLds L(N, H);
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(256) void latent_mlp_bwd_kernel(MlpParams p, MlpGra
     const int tid = threadIdx.x, o = tid % H, n0 = tid / H, nstep = 256 / H, P = H + 1;
     auto put = [&](float *dst, float v) { if (dst) *dst = (accumulate ? *dst : 0.f) + v; };
     const float invN = 1.f / (float)N;
-    // ---- head: p[n] = b4 + h3[n] . w4  (h3 recomputed from the saved pre-norm values of layer 2)
+    // ---- head: p[n] = act(b4 + h3[n] . w4)  (h3 recomputed from the saved pre-norm values of layer 2; the sigmoid's derivative
+    // from the forward's output)
     float g[J];   // gradient w.r.t. the output of the current layer's LeakyReLU, element (n0 + nstep j, o)
     {
         const float *a = a_save + (long long)2 * N * H, *st = stats_save + 2 * 2 * H;
@@ -148,7 +150,8 @@ __global__ __launch_bounds__(256) void latent_mlp_bwd_kernel(MlpParams p, MlpGra
             const int n = n0 + nstep * j;
             g[j] = 0.f;
             if (n < N) {
-                const float d = dout[(long long)n * 4];
+                const float d = p.head_act == ACG_ACT_SIGMOID ? dout[(long long)n * 4] * acg_act_grad_from_y_s(out[(long long)n * 4], ACG_ACT_SIGMOID)
+                                                              : dout[(long long)n * 4];
                 g[j] = d * w4;
                 sw += d * lrelu((a[n * H + o] - mean) * rstd * go + beo);
                 if (o == 0) sb += d;
@@ -271,6 +274,8 @@ static int mlp_check(const MlpParams *p, int N, int I, int H, const char *who)
     ACG_REQUIRE(p != nullptr && acg_latent_mlp_supported(N, I, H),
                 "%s: N=%d I=%d H=%d outside the fused kernel (256 %% H == 0, N * H <= %d; use the layer-by-layer path)", who, N, I, H,
                 256 * MLP_JMAX);
+    ACG_REQUIRE(p->head_act == ACG_ACT_NONE || p->head_act == ACG_ACT_SIGMOID, "%s: head activation %d (NONE or SIGMOID)", who,
+                p->head_act);
     return ACG_OK;
 }
 
@@ -303,13 +308,14 @@ extern "C" int acg_latent_mlp_fwd(const acg_latent_mlp_params *params, const flo
 }
 
 extern "C" int acg_latent_mlp_bwd(const acg_latent_mlp_params *params, const acg_latent_mlp_grads *grads, const float *z, int ldz,
-                                  int N, int I, int H, const float *a_save, const float *stats_save, const float *dout, float *dz,
-                                  int accumulate, void *stream)
+                                  int N, int I, int H, const float *a_save, const float *stats_save, const float *out,
+                                  const float *dout, float *dz, int accumulate, void *stream)
 {
     const MlpParams *p = (const MlpParams *)params;
     int rc = mlp_check(p, N, I, H, "acg_latent_mlp_bwd");
     if (rc) return rc;
     ACG_REQUIRE(grads != nullptr && z != nullptr && a_save != nullptr && stats_save != nullptr && dout != nullptr, "acg_latent_mlp_bwd: null");
+    ACG_REQUIRE(p->head_act != ACG_ACT_SIGMOID || out != nullptr, "acg_latent_mlp_bwd: a sigmoid head needs the forward's output");
     const size_t sh = (size_t)MlpLds(N, H).total * sizeof(float);
     const int J = (N * H + 255) / 256;
 #define MLP_BWD(JJ)                                                                                                              \
@@ -317,7 +323,7 @@ extern "C" int acg_latent_mlp_bwd(const acg_latent_mlp_params *params, const acg
         if (sh > 64 * 1024)                                                                                                      \
             (void)hipFuncSetAttribute((const void *)latent_mlp_bwd_kernel<JJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); \
         hipLaunchKernelGGL(latent_mlp_bwd_kernel<JJ>, dim3(1), dim3(256), sh, (hipStream_t)stream, *p, *(const MlpGrads *)grads, z,  \
-                           ldz, N, I, H, a_save, stats_save, dout, dz, accumulate);                                              \
+                           ldz, N, I, H, a_save, stats_save, out, dout, dz, accumulate);                                              \
     } while (0)
     if (J <= 1) MLP_BWD(1); else if (J <= 2) MLP_BWD(2); else if (J <= 4) MLP_BWD(4); else if (J <= 8) MLP_BWD(8); else MLP_BWD(16);
 #undef MLP_BWD

@@ -667,6 +667,7 @@ extern "C" int acg_norm_apply(const float *x, const float *mean, const float *rs
 {
     int rc = check_norm(G, P, C, "acg_norm_apply");
     if (rc) return rc;
+    ACG_REQUIRE(act != ACG_ACT_SIGMOID, "acg_norm_apply: no sigmoid (a discriminator head has no norm)");
     ACG_REQUIRE(fmt == 0 || ((fmt == 2 || ((fmt == 3 || fmt == 1) && res != nullptr)) && act == ACG_ACT_RELU && C % 8 == 0 && (mask == nullptr || res != nullptr)),
                 "acg_norm_apply: pre-split I/O (fmt %d) is implemented for ReLU: y pre-split (2), y and residual (3), residual only (1)", fmt);
     ACG_REQUIRE(gstride == 0 || (gstride >= C && gstride % 4 == 0), "acg_norm_apply: gstride must be 0 or a row stride >= C");

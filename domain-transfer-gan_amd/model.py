@@ -58,13 +58,26 @@ def kld_std_guss(mu, log_var):
 
 
 def criterion_GAN(pred, target_is_real, use_sigmoid=True):
-    """model.py:56-72.  `pred` is an NCHW / (N,1) tensor (public API form)."""
+    """model.py:56-72.  `pred` is an NCHW / (N,1) tensor (public API form).  The use_sigmoid branch is the reference's,
+    which cannot run (below); --no_lsgan models use criterion_GAN_bce instead."""
     if use_sigmoid:
-        raise NotImplementedError("use_sigmoid (--no_lsgan): the reference's BCE branch builds a Long target and fails "
-                                  "on modern torch (model.py:59-63); only LSGAN is implemented")
+        raise NotImplementedError("use_sigmoid: the reference's BCE branch builds a Long target and fails on modern torch "
+                                  "(model.py:59-63); use criterion_GAN_bce (what --no_lsgan models train with)")
     t = 1.0 if target_is_real else 0.0
     p = pred.reshape(-1, 1).contiguous()
     return ops.MseConst.apply(_pad_cols(p, 4), 1, t)
+
+
+def criterion_GAN_bce(pred, target_is_real):
+    """The vanilla-GAN objective of --no_lsgan (model.py:56-63 with its one bug fixed: the target is FLOAT, the reference's
+    Long target is rejected by F.binary_cross_entropy).  `pred` = sigmoid(head(x)), what a use_sigmoid discriminator
+    returns (NCHW / (N,1)); the loss is F.binary_cross_entropy(pred, full_like(pred, t)), t = 1. or 0.:
+    mean(-(t max(log p, -100) + (1 - t) max(log(1 - p), -100))), gradient g (p - t) / max(p (1 - p), 1e-12) / count.
+    The sigmoid stays a step of its own (fused into the head's epilogue, backward dy y (1 - y)), as in the reference
+    composite: no BCE-with-logits rewrite, whose values differ at saturation."""
+    t = 1.0 if target_is_real else 0.0
+    p = pred.reshape(-1, 1).contiguous()
+    return ops.BceConst.apply(_pad_cols(p, 4), 1, t)
 
 
 def _pad_cols(p, Cp):
@@ -73,9 +86,10 @@ def _pad_cols(p, Cp):
     return out
 
 
-def _gan_loss(pred_c16, target_is_real):
-    """LSGAN on an internal C16 prediction map (1 valid channel)."""
-    return ops.MseConst.apply(pred_c16, 1, 1.0 if target_is_real else 0.0)
+def _gan_loss(pred_c16, target_is_real, bce=False):
+    """The GAN loss on an internal C16 prediction map (1 valid channel): LSGAN, or with bce (--no_lsgan) the binary
+    cross-entropy of criterion_GAN_bce on the sigmoid map."""
+    return (ops.BceConst if bce else ops.MseConst).apply(pred_c16, 1, 1.0 if target_is_real else 0.0)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -313,6 +327,10 @@ class StepGraph(object):
 
 
 class _Base(object):
+    def _gan_loss(self, pred_c16, target_is_real):
+        """the model's criterionGAN on an internal prediction map: LSGAN, or BCE under --no_lsgan"""
+        return _gan_loss(pred_c16, target_is_real, bool(self.opt.use_sigmoid))
+
     def _dev(self):
         return next(self.netG_A_B.parameters()).device
 
@@ -494,7 +512,8 @@ class StochCycleGAN(_Base):
         self.netD_B = networks.define_D_B(input_nc=opt.output_nc, ndf=opt.ndf, which_model_netD=opt.which_model_netD,
                                           norm=opt.norm, use_sigmoid=opt.use_sigmoid, gpu_ids=opt.gpu_ids)
         self._build_optimizers()
-        self.criterionGAN = functools.partial(criterion_GAN, use_sigmoid=opt.use_sigmoid)
+        # --no_lsgan: the reference binds its (broken) BCE branch here; the float-target fix
+        self.criterionGAN = criterion_GAN_bce if opt.use_sigmoid else functools.partial(criterion_GAN, use_sigmoid=False)
         self.criterionCycle = lambda a, b: ops.L1.apply(_as2d(a), _as2d(b), a.shape[1])
         if not testing:
             with open("%s/nets.txt" % opt.expr_dir, 'w') as nets_f:
@@ -530,10 +549,10 @@ class StochCycleGAN(_Base):
         fake_A = self.netG_B_A.forward_nhwc(B)
 
         # ---- D phase (model.py:139-162)
-        p_fA = self.netD_A.forward_nhwc(fake_A.detach()); l_fA = _gan_loss(p_fA, False)
-        p_tA = self.netD_A.forward_nhwc(A); l_tA = _gan_loss(p_tA, True)
-        p_fB = self.netD_B.forward_nhwc(fake_B.detach()); l_fB = _gan_loss(p_fB, False)
-        p_tB = self.netD_B.forward_nhwc(B); l_tB = _gan_loss(p_tB, True)
+        p_fA = self.netD_A.forward_nhwc(fake_A.detach()); l_fA = self._gan_loss(p_fA, False)
+        p_tA = self.netD_A.forward_nhwc(A); l_tA = self._gan_loss(p_tA, True)
+        p_fB = self.netD_B.forward_nhwc(fake_B.detach()); l_fB = self._gan_loss(p_fB, False)
+        p_tB = self.netD_B.forward_nhwc(B); l_tB = self._gan_loss(p_tB, True)
         loss_D_A, loss_D_B = 0.5 * (l_fA + l_tA), 0.5 * (l_fB + l_tB)
         loss_D = loss_D_A + loss_D_B
         self.optimizer_D.zero_grad()
@@ -549,8 +568,8 @@ class StochCycleGAN(_Base):
         ss_D_A, ss_D_B = ss_D_A.clone(), ss_D_B.clone()
         self.f_D_A.set_requires_grad(False); self.f_D_B.set_requires_grad(False)   # D weight grads are not needed
         try:
-            p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = _gan_loss(p_fA, True)
-            p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = _gan_loss(p_fB, True)
+            p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = self._gan_loss(p_fA, True)
+            p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = self._gan_loss(p_fB, True)
             loss_G = loss_G_A + loss_G_B + loss_cycle_A * o.lambda_A + loss_cycle_B * o.lambda_B
             self.optimizer_G.zero_grad()
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_D_B, loss_G_B, loss_cycle_B,
@@ -662,7 +681,8 @@ class AugmentedCycleGAN(_Base):
         self.netD_z_B = networks.define_LAT_D(nlatent=opt.nlatent, ndf=opt.ndf, use_sigmoid=opt.use_sigmoid,
                                               gpu_ids=opt.gpu_ids)
         self._build_optimizers()
-        self.criterionGAN = functools.partial(criterion_GAN, use_sigmoid=opt.use_sigmoid)
+        # --no_lsgan: the reference binds its (broken) BCE branch here; the float-target fix
+        self.criterionGAN = criterion_GAN_bce if opt.use_sigmoid else functools.partial(criterion_GAN, use_sigmoid=False)
         self.criterionCycle = lambda a, b: ops.L1.apply(_as2d(a), _as2d(b), a.shape[1])
         if not testing:
             with open("%s/nets.txt" % opt.expr_dir, 'w') as nets_f:
@@ -714,12 +734,12 @@ class AugmentedCycleGAN(_Base):
             lv_rB = lv_rB * 0.0                                                                 # model.py:419
 
         # ---- D phase (model.py:423-452)
-        p_fA = self.netD_A.forward_nhwc(fake_A.detach()); l_fA = _gan_loss(p_fA, False)
-        p_tA = self.netD_A.forward_nhwc(A); l_tA = _gan_loss(p_tA, True)
-        p_fB = self.netD_B.forward_nhwc(fake_B.detach()); l_fB = _gan_loss(p_fB, False)
-        p_tB = self.netD_B.forward_nhwc(B); l_tB = _gan_loss(p_tB, True)
-        l_pz = _gan_loss(self.netD_z_B.forward_dense(post_z.detach()), False)
-        l_rz = _gan_loss(self.netD_z_B.forward_dense(z), True)
+        p_fA = self.netD_A.forward_nhwc(fake_A.detach()); l_fA = self._gan_loss(p_fA, False)
+        p_tA = self.netD_A.forward_nhwc(A); l_tA = self._gan_loss(p_tA, True)
+        p_fB = self.netD_B.forward_nhwc(fake_B.detach()); l_fB = self._gan_loss(p_fB, False)
+        p_tB = self.netD_B.forward_nhwc(B); l_tB = self._gan_loss(p_tB, True)
+        l_pz = self._gan_loss(self.netD_z_B.forward_dense(post_z.detach()), False)
+        l_rz = self._gan_loss(self.netD_z_B.forward_dense(z), True)
         loss_D_A, loss_D_B, loss_D_z_B = 0.5 * (l_fA + l_tA), 0.5 * (l_fB + l_tB), 0.5 * (l_pz + l_rz)
         loss_D = loss_D_A + loss_D_B
         z_gan = bool(o.z_gan and not o.stoch_enc)
@@ -752,9 +772,9 @@ class AugmentedCycleGAN(_Base):
         for f in flats_D:                                   # D weight gradients are not needed in the G phase
             f.set_requires_grad(False)
         try:
-            p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = _gan_loss(p_fA, True)
-            p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = _gan_loss(p_fB, True)
-            loss_G_z_B = _gan_loss(self.netD_z_B.forward_dense(post_z), True)
+            p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = self._gan_loss(p_fA, True)
+            p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = self._gan_loss(p_fB, True)
+            loss_G_z_B = self._gan_loss(self.netD_z_B.forward_dense(post_z), True)
             loss_G = loss_G_A + loss_G_B + loss_cycle_A * o.lambda_A + loss_cycle_B * o.lambda_B \
                 + loss_cycle_z_B * o.lambda_z_B
             if o.stoch_enc:
@@ -814,8 +834,8 @@ class AugmentedCycleGAN(_Base):
         else:
             post_z = mu
             logvar = logvar * 0.0
-        l_pz = _gan_loss(self.netD_z_B.forward_dense(post_z.detach()), False)
-        l_rz = _gan_loss(self.netD_z_B.forward_dense(z), True)
+        l_pz = self._gan_loss(self.netD_z_B.forward_dense(post_z.detach()), False)
+        l_rz = self._gan_loss(self.netD_z_B.forward_dense(z), True)
         loss_D_z_B = 0.5 * (l_pz + l_rz)
         self.optimizer_D_B.zero_grad()
         ex_D = self._backward(loss_D_z_B, "sup.D", [self.f_D_z_B, self.f_D_B])
@@ -828,7 +848,7 @@ class AugmentedCycleGAN(_Base):
             pred_A = self.netG_B_A.forward_nhwc(B)
             loss_sup_A = ops.L1.apply(pred_A, A, nA)
             loss_sup_B = ops.L1.apply(pred_B, B, nB)
-            loss_G_z_B = _gan_loss(self.netD_z_B.forward_dense(post_z), True)
+            loss_G_z_B = self._gan_loss(self.netD_z_B.forward_dense(post_z), True)
             kld_z_B = kld_std_guss(mu[:, :nl], logvar[:, :nl]).mean(0)
             loss_G = loss_sup_A * o.lambda_sup_A + loss_sup_B * o.lambda_sup_B
             if o.stoch_enc:

@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch.nn.parameter import Parameter
 
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_REFLECT, cpad
+from .ops import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID, PAD_ZERO, PAD_REFLECT, cpad
 
 USE_PYTORCH_IN = False  # modules.py:9
 SYNC_BN = False         # set by model.py from opt.sync_bn: BatchNorm statistics across all data-parallel ranks
@@ -374,7 +374,8 @@ def cond_bank(root, z):
     return z
 
 
-_ACTS = {nn.ReLU: ACT_RELU, nn.LeakyReLU: ACT_LRELU, nn.Tanh: ACT_TANH}
+# nn.Sigmoid: the --no_lsgan discriminator heads (networks.py:293,340,384,421), fused into the head conv / Linear
+_ACTS = {nn.ReLU: ACT_RELU, nn.LeakyReLU: ACT_LRELU, nn.Tanh: ACT_TANH, nn.Sigmoid: ACT_SIGMOID}
 
 
 def _act_of(m):
@@ -441,9 +442,6 @@ def run_sequence(mods, x, C, z=None, res=None, last_block=False):
             if i < n and isinstance(mods[i], (InstanceNorm, CondInstanceNorm, BatchNorm2d)):
                 norm = mods[i]
                 i += 1
-        elif isinstance(m, nn.Sigmoid):
-            raise NotImplementedError("use_sigmoid / --no_lsgan: the reference's BCE branch is broken (model.py:59-63); "
-                                      "only LSGAN is implemented")
         else:
             raise NotImplementedError("run_sequence: unexpected layer %s" % type(m).__name__)
         norm_idx = i - 1
@@ -654,8 +652,6 @@ def run_dense(mods, x):
     while i < n:
         m = mods[i]
         if not isinstance(m, Linear):
-            if isinstance(m, nn.Sigmoid):
-                raise NotImplementedError("use_sigmoid: only LSGAN is implemented")
             raise NotImplementedError("run_dense: unexpected layer %s" % type(m).__name__)
         i += 1
         bn = None

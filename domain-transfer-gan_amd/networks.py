@@ -244,7 +244,7 @@ class DiscriminatorLatent(nn.Module):
         self.model = Sequential(*seq)
 
     def forward_dense(self, z):
-        """z: (N, >=nlatent) -> (N, 4) with column 0 valid"""
+        """z: (N, >=nlatent) -> (N, 4) with column 0 valid (a probability under use_sigmoid)"""
         mods = list(self.model._modules.values())
         fused = self._fused_args(mods, z)
         if fused is not None:
@@ -254,6 +254,9 @@ class DiscriminatorLatent(nn.Module):
     def _fused_args(self, mods, z):
         """the whole chain as one launch per direction (ops.LatentMLPFn) when it is the standard train-mode chain, the batch
         fits one workgroup's LDS and BatchNorm statistics are local to this rank; None otherwise (layer by layer)"""
+        head_act = modules.ACT_NONE
+        if len(mods) == 11 and isinstance(mods[10], nn.Sigmoid):   # use_sigmoid: the head's sigmoid runs inside the kernel
+            head_act, mods = modules.ACT_SIGMOID, mods[:10]
         if len(mods) != 10 or not self.training or modules.sync_bn_active():
             return None
         lins, bns = mods[0:10:3], mods[1:9:3]
@@ -266,7 +269,7 @@ class DiscriminatorLatent(nn.Module):
             return None
         if not ops.latent_mlp_supported(z.shape[0], lins[0].in_features, H):
             return None
-        out = ops.LatentMLPFn.apply(z, bns[0].eps, bns[0].momentum,
+        out = ops.LatentMLPFn.apply(z, bns[0].eps, bns[0].momentum, head_act,
                                     [b.running_mean for b in bns] + [b.running_var for b in bns],
                                     *([m.weight for m in lins] + [m.bias for m in lins] + [b.weight for b in bns]
                                       + [b.bias for b in bns]))

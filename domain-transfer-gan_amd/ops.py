@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_REFLECT, ConvDesc  # noqa: F401
+from ._lib import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID, PAD_ZERO, PAD_REFLECT, ConvDesc  # noqa: F401
 
 _VP = ctypes.c_void_p
 
@@ -1148,14 +1148,15 @@ def latent_mlp_supported(N, I, H):
 
 class LatentMLPFn(torch.autograd.Function):
     """DiscriminatorLatent's whole dense chain (networks.py:396-433) as one launch per direction: three Linear /
-    BatchNorm1d(train) / LeakyReLU(0.2) stages and the Linear head.  `params` = 4 weights, 4 biases, 3 BN weights, 3 BN
-    biases (autograd inputs); `buffers` = 3 running means + 3 running variances, updated in place.  -> (N, 4), column 0
-    valid (the layout LinearFn gives the head)."""
+    BatchNorm1d(train) / LeakyReLU(0.2) stages and the Linear head, followed by a sigmoid when head_act is ACT_SIGMOID
+    (use_sigmoid, networks.py:420-421).  `params` = 4 weights, 4 biases, 3 BN weights, 3 BN biases (autograd inputs);
+    `buffers` = 3 running means + 3 running variances, updated in place.  -> (N, 4), column 0 valid (the layout LinearFn
+    gives the head), columns 1..3 zero."""
 
     NPARAM = 14
 
     @staticmethod
-    def forward(ctx, z, eps, momentum, buffers, *params):
+    def forward(ctx, z, eps, momentum, head_act, buffers, *params):
         z = z.contiguous()
         _check(z, *params)
         _check(*buffers)
@@ -1173,6 +1174,7 @@ class LatentMLPFn(torch.autograd.Function):
         for l in range(3):
             pp.gamma[l], pp.beta[l] = params[8 + l].data_ptr(), params[11 + l].data_ptr()
             pp.run_mean[l], pp.run_var[l] = buffers[l].data_ptr(), buffers[3 + l].data_ptr()
+        pp.head_act = head_act
         a_save = torch.empty((3, N, H), device=z.device, dtype=torch.float32)
         stats = torch.empty((3, 2, H), device=z.device, dtype=torch.float32)
         out = torch.empty((N, 4), device=z.device, dtype=torch.float32)
@@ -1180,13 +1182,14 @@ class LatentMLPFn(torch.autograd.Function):
                   _ptr(stats), _ptr(out), _stream())
         ctx.cfg = (N, ldz, I, H)
         ctx.params = params
-        ctx.save_for_backward(z, a_save, stats, *[p.detach() for p in params])
+        ctx.head_act = head_act
+        ctx.save_for_backward(z, a_save, stats, out if head_act == ACT_SIGMOID else None, *[p.detach() for p in params])
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        z, a_save, stats = ctx.saved_tensors[:3]
-        ws = ctx.saved_tensors[3:]
+        z, a_save, stats, out = ctx.saved_tensors[:4]
+        ws = ctx.saved_tensors[4:]
         N, ldz, I, H = ctx.cfg
         dout = dout.contiguous()
         pp, gg = _lib.LatentMlpParams(), _lib.LatentMlpGrads()
@@ -1194,7 +1197,8 @@ class LatentMLPFn(torch.autograd.Function):
             pp.w[l], pp.b[l] = ws[l].data_ptr(), ws[4 + l].data_ptr()
         for l in range(3):
             pp.gamma[l], pp.beta[l] = ws[8 + l].data_ptr(), ws[11 + l].data_ptr()
-        want = [ctx.needs_input_grad[4 + i] for i in range(LatentMLPFn.NPARAM)]
+        pp.head_act = ctx.head_act
+        want = [ctx.needs_input_grad[5 + i] for i in range(LatentMLPFn.NPARAM)]
         direct = _direct_grad(*ctx.params) if all(want) else None
         if direct is not None:
             grads = direct
@@ -1208,11 +1212,11 @@ class LatentMLPFn(torch.autograd.Function):
             gg.dbeta[l] = grads[11 + l].data_ptr() if grads[11 + l] is not None else None
         dz = torch.zeros_like(z) if ctx.needs_input_grad[0] else None
         _lib.call("acg_latent_mlp_bwd", ctypes.byref(pp), ctypes.byref(gg), _ptr(z), ldz, N, I, H, _ptr(a_save), _ptr(stats),
-                  _ptr(dout), _ptr(dz), 1 if direct is not None else 0, _stream())
+                  _ptr(out), _ptr(dout), _ptr(dz), 1 if direct is not None else 0, _stream())
         if direct is not None:
             _grads_done(*ctx.params)
             grads = [None] * LatentMLPFn.NPARAM
-        return (dz, None, None, None) + tuple(grads)
+        return (dz, None, None, None, None) + tuple(grads)
 
 
 class SpatialMean(torch.autograd.Function):
@@ -1268,6 +1272,34 @@ class MseConst(torch.autograd.Function):
         g = g.contiguous()
         dp = torch.empty_like(p)
         _lib.call("acg_mse_const_bwd", _ptr(p), npix, C, Cp, target, _ptr(g), _ptr(dp), _stream())
+        return dp, None, None
+
+
+class BceConst(torch.autograd.Function):
+    """F.binary_cross_entropy(p, full_like(p, target)) over the C valid channels, p a probability (a sigmoid head): the
+    reference's use_sigmoid branch (model.py:56-63) with a float target in place of its Long one.  Same shape contract as
+    MseConst."""
+
+    @staticmethod
+    def forward(ctx, p, C, target):
+        p = p.contiguous()
+        _check(p)
+        Cp = p.shape[-1]
+        npix = p.numel() // Cp
+        out = torch.empty((), device=p.device, dtype=torch.float32)
+        ws, nb = _red_ws()
+        _lib.call("acg_bce_const_fwd", _ptr(p), npix, C, Cp, float(target), _ptr(out), _ptr(ws), nb, _stream())
+        ctx.cfg = (npix, C, Cp, float(target))
+        ctx.save_for_backward(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        npix, C, Cp, target = ctx.cfg
+        g = g.contiguous()
+        dp = torch.empty_like(p)
+        _lib.call("acg_bce_const_bwd", _ptr(p), npix, C, Cp, target, _ptr(g), _ptr(dp), _stream())
         return dp, None, None
 
 

@@ -57,7 +57,7 @@ _T = [
     ("stoch_enc", "flag", False, "use a stochastic encoder"),
     ("z_gan", ("choice", int, [0, 1]), 1, "use a GAN on z_B"),
     ("enc_A_B", ("choice", int, [0, 1]), 1, "encoder of z_B conditioned on both A and B"),
-    ("no_lsgan", "flag", False, "vanilla GAN (the reference's BCE branch is broken; raises here)"),
+    ("no_lsgan", "flag", False, "vanilla GAN: sigmoid discriminator heads and binary cross-entropy with a float target (the reference's Long target fails)"),
     ("lambda_A", float, 1.0, "weight for cycle loss (A -> B -> A)"),
     ("lambda_B", float, 1.0, "weight for cycle loss (B -> A -> B)"),
     ("lambda_z_B", float, 0.025, "weight for the latent cycle loss"),

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ACG_VERSION 117
+#define ACG_VERSION 118
 
 typedef enum {
     ACG_OK = 0,
@@ -40,7 +40,12 @@ typedef enum {
     ACG_ERR_COMM = -4       /* RCCL unavailable or an RCCL call failed */
 } acg_status;
 
-typedef enum { ACG_ACT_NONE = 0, ACG_ACT_RELU = 1, ACG_ACT_LRELU = 2 /* slope 0.2 */, ACG_ACT_TANH = 3 } acg_act;
+/* ACG_ACT_SIGMOID (--no_lsgan discriminator heads, networks.py:293,340,384,421): a convolution applies it to the REAL output
+ * channels only (acg_conv_desc.Cor, required) and stores exactly 0 in the padded ones (sigmoid(0) = 0.5 would break the
+ * zero-padding invariant); only acg_conv2d_fwd, acg_act_bwd and the dense layers take it. */
+typedef enum {
+    ACG_ACT_NONE = 0, ACG_ACT_RELU = 1, ACG_ACT_LRELU = 2 /* slope 0.2 */, ACG_ACT_TANH = 3, ACG_ACT_SIGMOID = 4
+} acg_act;
 typedef enum { ACG_PAD_ZERO = 0, ACG_PAD_REFLECT = 1 } acg_pad_mode;
 typedef enum { ACG_IMPL_MFMA = 0, ACG_IMPL_DIRECT = 1 } acg_conv_impl;
 typedef enum { ACG_PREC_F32 = 0, ACG_PREC_BF16 = 1, ACG_PREC_BF16X3 = 2 } acg_precision;
@@ -321,6 +326,7 @@ int acg_segments_accumulate(const float *src, const acg_segments *segs, int accu
 typedef struct {
     const float *w[4], *b[4], *gamma[3], *beta[3];
     float *run_mean[3], *run_var[3];
+    int head_act;   /* ACG_ACT_NONE, or ACG_ACT_SIGMOID (use_sigmoid, networks.py:421): out = sigmoid(Linear(H->1)) */
 } acg_latent_mlp_params;
 typedef struct {
     float *dw[4], *db[4], *dgamma[3], *dbeta[3];
@@ -328,9 +334,10 @@ typedef struct {
 int acg_latent_mlp_supported(int N, int I, int H);
 int acg_latent_mlp_fwd(const acg_latent_mlp_params *params, const float *z, int ldz, int N, int I, int H, float eps,
                        float momentum, float *a_save, float *stats_save, float *out, void *stream);
+/* out: the forward's output, read when head_act is ACG_ACT_SIGMOID (dout * out * (1 - out)); may be NULL otherwise */
 int acg_latent_mlp_bwd(const acg_latent_mlp_params *params, const acg_latent_mlp_grads *grads, const float *z, int ldz, int N,
-                       int I, int H, const float *a_save, const float *stats_save, const float *dout, float *dz, int accumulate,
-                       void *stream);
+                       int I, int H, const float *a_save, const float *stats_save, const float *out, const float *dout, float *dz,
+                       int accumulate, void *stream);
 
 /* ---- spatial mean over H*W of a C16 map -> [N][Cp] (LatentEncoder extension for S != 64,
  *      identity at the reference's 1x1 map — networks.py:482) ---- */
@@ -343,6 +350,14 @@ size_t acg_reduce_workspace_bytes(size_t n);
 int acg_mse_const_fwd(const float *p, size_t npix, int C, int Cp, float target, float *out, void *workspace,
                       size_t ws_bytes, void *stream);
 int acg_mse_const_bwd(const float *p, size_t npix, int C, int Cp, float target, const float *gout, float *dp,
+                      void *stream);
+/* out[0] = F.binary_cross_entropy(p, full(target)) = mean(-(t max(log p, -100) + (1 - t) max(log(1 - p), -100))), p a
+ * probability (sigmoid head), target 0 or 1 as a FLOAT (the reference's Long target, model.py:59-63, is rejected by torch).
+ * Same partial-sum tree as acg_mse_const_fwd: deterministic, no atomics.  Backward (torch's formula):
+ * dp = gout (p - t) / max(p (1 - p), 1e-12) / (npix C); padded channels get 0. */
+int acg_bce_const_fwd(const float *p, size_t npix, int C, int Cp, float target, float *out, void *workspace,
+                      size_t ws_bytes, void *stream);
+int acg_bce_const_bwd(const float *p, size_t npix, int C, int Cp, float target, const float *gout, float *dp,
                       void *stream);
 /* out[0] = mean(|a-b|) (F.l1_loss, model.py:391,468,486,494) */
 int acg_l1_fwd(const float *a, const float *b, size_t npix, int C, int Cp, float *out, void *workspace,

@@ -118,7 +118,7 @@ class InjectedDropout(object):
 
 
 # ---------------------------------------------------------------- network-level goldens
-def net_case(name, build, net_name, inputs, seed=0, flavour="rich", buffers=False, cfg=None, drop_seed=None):
+def net_case(name, build, net_name, inputs, seed=0, flavour="rich", buffers=False, cfg=None, drop_seed=None, kind="net"):
     if ONLY and name not in ONLY:
         return
     net = load_recipe(build(), net_name, seed, flavour)
@@ -145,7 +145,7 @@ def net_case(name, build, net_name, inputs, seed=0, flavour="rich", buffers=Fals
         for k, b in net.named_buffers():
             arr["buf/" + k] = b.detach().numpy().copy()
     extra = {} if drop_seed is None else {"drop_seed": drop_seed}
-    save(name, arr, kind="net", net=net_name, seed=seed, flavour=flavour, cfg=cfg or {}, **extra)
+    save(name, arr, kind=kind, net=net_name, seed=seed, flavour=flavour, cfg=cfg or {}, **extra)
 
 
 def make_net_goldens():
@@ -226,17 +226,34 @@ def run_ref_step(m, rec, A, B, z, aug):
         pass
 
 
-def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed=None, drop_seed=None):
+def float_target_bce(pred, target_is_real, use_sigmoid=True):
+    """--no_lsgan fixtures: the reference's criterion_GAN with its use_sigmoid branch fixed — F.binary_cross_entropy against a
+    FLOAT target (the reference builds a Long one, model.py:59-63, which torch rejects).  Installed in place of
+    model.criterion_GAN before the model is built (its functools.partial binds at __init__, model.py:116, 390)."""
+    assert use_sigmoid
+    return torch.nn.functional.binary_cross_entropy(pred, torch.full_like(pred, 1.0 if target_is_real else 0.0))
+
+
+def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed=None, drop_seed=None, kind="step",
+              vis_samples=None):
     """eps_seed: for --stoch_enc cases — the N(0,1) draw inside the reference's gauss_reparametrize
     (`std.data.new(N, 1, nl).normal_()`, model.py:19) is replaced by a fixed, recorded eps (torch.Tensor.normal_ is
-    patched for tensors of exactly that shape while the step runs), so the branch becomes a pure function of the inputs."""
+    patched for tensors of exactly that shape while the step runs), so the branch becomes a pure function of the inputs.
+    opt_kw no_lsgan=True (kind "bce_step"): the reference's nets carry their own nn.Sigmoid heads, the criterion is
+    float_target_bce, and every criterion call's prediction, target and value is recorded (s<k>/gan_pred/<i>, gan_target,
+    gan_values) so that the losses can be re-derived from the D outputs.
+    vis_samples (a count per step, e.g. (2, 1)): keep the fixture small — the inputs are not stored (oracle.recipe.inputs
+    regenerates them from the seed; s<k>/real_A_digest, real_B_digest pin them) and the images only for the first
+    vis_samples[k] samples of step k; losses, gradient norms and the per-tensor digests still cover the whole batch."""
     if ONLY and name not in ONLY:
         return
     opt = ref_opt(**opt_kw)
     rec = Recorder()
     # recorders around the reference's own loss / clip functions
     orig_l1, orig_clip = rmodel.F.l1_loss, torch.nn.utils.clip_grad_norm
-    orig_crit = rmodel.criterion_GAN
+    ref_crit = rmodel.criterion_GAN
+    orig_crit = float_target_bce if opt.no_lsgan else ref_crit
+    gan_io = []
     orig_lpg, orig_normal = rmodel.log_prob_gaussian, torch.Tensor.normal_
     cur_eps = [None]
 
@@ -253,7 +270,8 @@ def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed
         v = orig_l1(a, b, *k, **kw); rec.l1.append(float(v)); return v
 
     def crit(pred, real, use_sigmoid=True):
-        v = orig_crit(pred, real, use_sigmoid=use_sigmoid); rec.gan.append(float(v)); return v
+        v = orig_crit(pred, real, use_sigmoid=use_sigmoid); rec.gan.append(float(v))
+        gan_io.append((pred.detach().numpy().copy(), 1.0 if real else 0.0)); return v
 
     def clip(params, max_norm, *k, **kw):
         v = orig_clip(params, max_norm, *k, **kw); rec.gn.append(float(v)); return v
@@ -287,8 +305,12 @@ def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed
     try:
         for st in range(steps):
             A, B, z = recipe.inputs(seed + st, N, opt.input_nc, opt.output_nc, S, opt.nlatent)
-            arr["s%d/real_A" % st], arr["s%d/real_B" % st], arr["s%d/prior_z_B" % st] = A, B, z
-            for lst in (rec.gan, rec.l1, rec.gn, rec.predA, rec.predB, rec.enc, rec.gAB, rec.gBA, rec.cycz):
+            arr["s%d/prior_z_B" % st] = z
+            if vis_samples is None:
+                arr["s%d/real_A" % st], arr["s%d/real_B" % st] = A, B
+            else:
+                arr["s%d/real_A_digest" % st], arr["s%d/real_B_digest" % st] = digest(A), digest(B)
+            for lst in (rec.gan, rec.l1, rec.gn, rec.predA, rec.predB, rec.enc, rec.gAB, rec.gBA, rec.cycz, gan_io):
                 del lst[:]
             if eps_seed is not None:
                 cur_eps[0] = np.random.RandomState(eps_seed + st).normal(0, 1, (N, 1, opt.nlatent)).astype(np.float32)
@@ -301,6 +323,9 @@ def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed
             # visuals (model.py:524-525 / 199-200): the tensors the reference's own forward calls returned in this step
             arr["s%d/fake_B" % st], arr["s%d/rec_B" % st] = rec.gAB[0], rec.gAB[1]
             arr["s%d/fake_A" % st], arr["s%d/rec_A" % st] = rec.gBA[0], rec.gBA[1]
+            if vis_samples is not None:
+                for k in ("fake_B", "rec_B", "fake_A", "rec_A"):
+                    arr["s%d/%s" % (st, k)] = arr["s%d/%s" % (st, k)][:vis_samples[st]].copy()
             if aug:
                 # call order (model.py:423-464): D_A f/t, D_B f/t, D_z post/prior, G_A, G_B, G_z
                 g = rec.gan
@@ -336,6 +361,11 @@ def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed
                 gn = OrderedDict([("gnorm_G_A_B", rec.gn[2]), ("gnorm_G_B_A", rec.gn[3]),
                                   ("gnorm_D_B", rec.gn[1]), ("gnorm_D_A", rec.gn[0])])
             arr["s%d/losses" % st] = np.array(list(losses.values()), np.float64)
+            if opt.no_lsgan:
+                for i, (pr, t) in enumerate(gan_io):
+                    arr["s%d/gan_pred/%d" % (st, i)] = pr
+                arr["s%d/gan_target" % st] = np.array([t for _, t in gan_io], np.float64)
+                arr["s%d/gan_values" % st] = np.array(rec.gan, np.float64)
             arr["s%d/gnorms" % st] = np.array(list(gn.values()), np.float64)
             loss_keys, gn_keys = list(losses.keys()), list(gn.keys())
             # post-step update digests (post - pre), per tensor, and refresh `pre`
@@ -352,12 +382,14 @@ def step_case(name, aug, opt_kw, N, S, steps=2, seed=0, flavour="rich", eps_seed
                 for k, b in getattr(m, n).named_buffers():
                     arr["final/buf/%s/%s" % (n, k)] = b.detach().numpy().copy()
     finally:
-        rmodel.F.l1_loss, rmodel.criterion_GAN, torch.nn.utils.clip_grad_norm = orig_l1, orig_crit, orig_clip
+        rmodel.F.l1_loss, rmodel.criterion_GAN, torch.nn.utils.clip_grad_norm = orig_l1, ref_crit, orig_clip
         rmodel.log_prob_gaussian = orig_lpg
         if drop is not None:
             drop.__exit__()
     extra = {} if drop_seed is None else {"drop_seed": drop_seed}
-    save(name, arr, kind="step", aug=bool(aug), seed=seed, flavour=flavour, N=N, S=S, steps=steps,
+    if vis_samples is not None:
+        extra["vis_samples"] = list(vis_samples[:steps])
+    save(name, arr, kind=kind, aug=bool(aug), seed=seed, flavour=flavour, N=N, S=S, steps=steps,
          opt={k: v for k, v in opt_kw.items()}, loss_keys=loss_keys, gnorm_keys=gn_keys, **extra)
 
 
@@ -378,9 +410,35 @@ def make_step_goldens():
               flavour="init", drop_seed=55)
 
 
+def make_bce_goldens():
+    """--no_lsgan (vanilla GAN): the reference's nets with use_sigmoid=True and float_target_bce.  Kinds of their own
+    ("bce_net", "bce_step"): the LSGAN-only oracle and the tests that collect "net" / "step" fixtures must not see them."""
+    nc, nl = 3, 4
+    x64 = np.random.RandomState(14).uniform(-1, 1, (2, nc, 64, 64)).astype(np.float32)
+    x40 = np.random.RandomState(15).uniform(-1, 1, (2, nc, 40, 40)).astype(np.float32)
+    net_case("bce_D_B_s40", lambda: rnet.define_D_B(nc, 8, "basic", "instance", use_sigmoid=True), "netD_B", [x40],
+             cfg=dict(input_nc=nc, ndf=8, use_sigmoid=True), kind="bce_net")
+    net_case("bce_D_A_s64", lambda: rnet.define_D_A(nc, 8, "basic", "instance", use_sigmoid=True), "netD_A", [x64],
+             cfg=dict(input_nc=nc, ndf=8, use_sigmoid=True), kind="bce_net")
+    z4 = rnd(17, (4, nl, 1, 1))
+    net_case("bce_D_z_B_n4", lambda: rnet.define_LAT_D(nl, 8, use_sigmoid=True), "netD_z_B", [z4], buffers=True,
+             cfg=dict(nlatent=nl, ndf=8, use_sigmoid=True), kind="bce_net")
+    small = dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4, no_lsgan=True)
+    VIS = (2, 1)   # images kept: two samples at step 0, one after (repository size cap on fixtures)
+    step_case("bce_step_aug_small_s64", True, small, N=4, S=64, steps=2, flavour="rich",
+              kind="bce_step", vis_samples=VIS)
+    step_case("bce_step_aug_small_s64_1step", True, small, N=4, S=64, steps=1, flavour="rich", seed=3,
+              kind="bce_step", vis_samples=VIS)
+    step_case("bce_step_aug_small_s64_init", True, small, N=4, S=64, steps=2, flavour="init",
+              kind="bce_step", vis_samples=VIS)
+    step_case("bce_step_stoch_small_s64", False, dict(small, input_nc=3, output_nc=1), N=2, S=64, steps=2, flavour="rich",
+              kind="bce_step", vis_samples=VIS)
+
+
 if __name__ == "__main__":
     make_net_goldens()
     make_step_goldens()
+    make_bce_goldens()
 
 
 def sup_case(name, opt_kw, N, S, seed=0, flavour="rich"):
