@@ -199,18 +199,9 @@ BCE_RICH_SKIP = (("netG_A_B", "shift_conv"), ("netG_A_B", "scale_conv"))
 
 
 def _bce_check_digests(m, arr, pre, prec, flavour):
-    """test_hip_step's digest check with BCE_RICH_SKIP on 'rich' in both precisions (it selects its skip list for bf16x3 only:
-    f32 on 'rich' is routed through that branch with the f32 tolerances)"""
+    """test_hip_step's digest check with BCE_RICH_SKIP on 'rich' in both precisions"""
     import test_hip_step as S
-    saved_skip, saved_tol = S.RICH_X3_SKIP, S.DIGEST_TOL["bf16x3"]
-    S.RICH_X3_SKIP = BCE_RICH_SKIP
-    try:
-        if prec == "f32" and flavour == "rich":
-            S.DIGEST_TOL["bf16x3"] = S.DIGEST_TOL["f32"]
-            prec = "bf16x3"
-        S._check_digests(m, arr, pre, prec, flavour)
-    finally:
-        S.RICH_X3_SKIP, S.DIGEST_TOL["bf16x3"] = saved_skip, saved_tol
+    S._check_digests(m, arr, pre, prec, flavour, skip=BCE_RICH_SKIP if flavour == "rich" else ())
 
 
 # After the first Adam update of the 'init' fixture the latent encoder's gradient norm is the most sensitive quantity of the

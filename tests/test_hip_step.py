@@ -56,13 +56,13 @@ def test_train_instance_matches_reference_golden(name, prec):
 # fixture flavour.  'init' = the reference's own initialisation statistics (what training starts from): the north-star
 # 1e-3 bar holds in bf16x3.  'rich' = O(1) InstanceNorm gains everywhere, deliberately ill-conditioned
 # (tools/conditioning_probe.py: the EXACT-fp32 path itself moves rec_* by 4e-4..9e-4 under a 4e-6 input perturbation):
-# bf16x3 lands at 1.8-7.9e-4 on the reference goldens (0.8-1.4e-3 in the 6-block oracle case, allowed 3e-3 there).  After an Adam update the fp32 oracle itself is 1.9e-2 from the
+# bf16x3 lands at 1.8-7.9e-4 on the reference goldens (0.7-1.4e-3 in the 6-block oracle case, allowed 2e-3 there).  After an Adam update the fp32 oracle itself is 1.9e-2 from the
 # reference on 'rich' (tests/test_oracle_golden.py).
 # (after the first Adam update the exact-fp32 HIP path sits 8e-3 and bf16x3 2.5e-2 from the reference on the 'init' stoch_enc fixture: Adam turns
 # summation-order noise on ~zero gradients into +-lr moves, and rec_* passes them through two generators)
 # Round 6: the measured step-0 errors are recorded every run (ACG_REC_ERR_LOG; profiles/r06_rec_errors.txt) — 'rich' in bf16x3
 # lands at 1.8e-4 .. 7.9e-4, so the reference goldens are all held to the north-star 1e-3 at step 0 now (the 3e-3 allowance
-# of rounds 2-5 remains only in the build's own 6-block oracle case below, which measures 0.8 / 1.4e-3).
+# of rounds 2-5 is 2e-3 now in the build's own 6-block oracle case below, which measures 7.3e-4 / 7.6e-4).
 REC_TOL = {("f32", "init"): (2e-4, 2e-2), ("f32", "rich"): (3e-4, 4e-2),
            ("bf16x3", "init"): (1e-3, 4e-2), ("bf16x3", "rich"): (1e-3, 6e-2)}
 
@@ -77,32 +77,41 @@ REC_TOL = {("f32", "init"): (2e-4, 2e-2), ("f32", "rich"): (3e-4, 4e-2),
 # ReLU-gated per-sample shifts), all other tensors < 1e-2.  On the deliberately ill-conditioned 'rich' flavour some bf16x3
 # digests are not a pin: switching the InstanceNorm statistics between two equally accurate fp32 methods (both 1e-7 from fp64,
 # test_conv_epilogue_statistics_equal_the_statistics_pass) moves the forward by 3e-5 and the CondInstanceNorm shift / scale
-# convolution gradients by up to 17 % there (tools/debug_stats_ab.py).  Those tensors are SKIPPED BY NAME in bf16x3 on 'rich'
-# (RICH_X3_SKIP: the f32 mode pins them on the same fixtures); every other tensor is held to the bf16x3 tolerance.
+# convolution gradients by up to 17 % there (tools/debug_stats_ab.py).  Those tensors get a bound of their own in bf16x3 on
+# 'rich' (RICH_X3_BOUND; the f32 mode pins them at DIGEST_TOL on the same fixtures); every other tensor is held to the bf16x3
+# tolerance.
 DIGEST_TOL = {"f32": (3e-3, 5e-3), "bf16x3": (2e-2, 2e-2)}
-# (network, substring of the parameter name): the latent-conditioned SHIFT layers (modules.py:111-118: ReLU(1x1 conv(z)),
-# a sum over ReLU-gated per-sample shifts) of the two full-resolution CondInstanceNorms of G_A_B whose planes are largest —
-# the only tensors of the 'rich' fixtures outside the bf16x3 tolerance (measured 3e-2 .. 0.16; all others <= 2e-2)
-RICH_X3_SKIP = (("netG_A_B", "model.2.shift_conv"), ("netG_A_B", "model.14.shift_conv"))
+# (network, parameter name) -> relative bound on both the gradient and the update digests: the latent-conditioned SHIFT layers
+# (modules.py:111-118: ReLU(1x1 conv(z)), a sum over ReLU-gated per-sample shifts) of the two full-resolution CondInstanceNorms
+# of G_A_B whose planes are largest — the only tensors of the 'rich' fixtures outside the bf16x3 tolerance (all others
+# <= 2e-2).  Each bound is about twice the worst digest error measured over the two 'rich' fixtures (step_aug_small_s64,
+# step_stoch_small_s64; printed as `digest_err` every run): model.2 weight 8.1e-3 / 6.6e-2, bias 5.1e-3 / 0.16; model.14
+# bias 1.0e-3 / 3.3e-2.  model.14's weight (9.4e-4 / 8.2e-3) is held to DIGEST_TOL.
+RICH_X3_BOUND = {("netG_A_B", "model.2.shift_conv.0.weight"): 0.13, ("netG_A_B", "model.2.shift_conv.0.bias"): 0.32,
+                 ("netG_A_B", "model.14.shift_conv.0.bias"): 0.07}
 # The --norm batch --use_dropout fixture: BatchNorm gains are ~N(1, 0.02) at initialisation (networks.py:19-21) where the
 # InstanceNorm gains are ~N(0, 0.02), so G_B_A is a high-gain network there although the flavour is 'init', and D_A ends in
 # BatchNorms over 4 samples x (2x2 | 1x1) maps.  tools/step_grad_conditioning.py: the EXACT-fp32 path moves G_B_A's gradients
 # by 2e-4 .. 8e-3 (discretely: one LeakyReLU / ReLU unit on the other side) when its inputs are perturbed by 4e-6, G_A_B's by
 # 2e-5; bf16x3 lands 8e-2 off on the head bias (a sum over all pixels of the image gradient), 2-4e-2 on two more tensors
-# whose digests stay inside the tolerance.  That one tensor is skipped by name in bf16x3; f32 pins it on the same fixture.
-BN_DROPOUT_X3_SKIP = (("netG_B_A", "model.19.bias"),)
+# whose digests stay inside the tolerance.  That one tensor gets a bound of its own in bf16x3, about twice its measured digest
+# error (8.0e-2); f32 pins it at DIGEST_TOL on the same fixture.
+BN_DROPOUT_X3_BOUND = {("netG_B_A", "model.19.bias"): 0.16}
 # Networks whose .grad after the step is comparable: the reference lets loss_G.backward() pile the (unused) G-phase
 # gradients on top of the discriminators' D-phase .grad (model.py:509, no zero_grad for them); the HIP path skips those
 # weight gradients, so the discriminators are pinned by their UPDATE digests (which only see the D-phase gradient).
 GRAD_NETS = ("netG_A_B", "netG_B_A", "netE_B")
 
 
-def _check_digests(m, arr, pre, prec, flavour="init", bn_dropout=False):
+def _check_digests(m, arr, pre, prec, flavour="init", bn_dropout=False, skip=()):
+    """`skip`: (network, substring) pairs left out of the check (test_hip_bce's BCE_RICH_SKIP)"""
     gt, ut = DIGEST_TOL[prec]
-    skip = RICH_X3_SKIP if (prec == "bf16x3" and flavour == "rich") else ()
+    bounds = {}
+    if prec == "bf16x3" and flavour == "rich":
+        bounds.update(RICH_X3_BOUND)
     if prec == "bf16x3" and bn_dropout:
-        skip = skip + BN_DROPOUT_X3_SKIP
-    bad, seen, skipped = [], 0, []
+        bounds.update(BN_DROPOUT_X3_BOUND)
+    bad, seen, skipped, bounded = [], 0, [], []
     for nname, net in m._net_dict().items():
         params = dict(net.named_parameters())
         grads = {k: (p.grad.detach().cpu().numpy() if p.grad is not None else np.zeros(tuple(p.shape), np.float32))
@@ -113,22 +122,32 @@ def _check_digests(m, arr, pre, prec, flavour="init", bn_dropout=False):
             assert key in arr, key
             g = grads[k]
             is_skip = any(nname == sn and sub in k for sn, sub in skip)
+            own = [b for (sn, sub), b in bounds.items() if nname == sn and sub in k]
+            gt_k, ut_k = (own[0], own[0]) if own else (gt, ut)
             if nname in GRAD_NETS:
                 dg, rg = digest(g), arr[key]
                 floor = 3e-5 * gmax * np.array([g.size, np.sqrt(g.size)])    # summation noise on analytically-zero gradients
-                if not np.all(np.abs(dg[1:3] - rg[1:3]) <= gt * np.abs(rg[1:3]) + floor):
-                    (skipped if is_skip else bad).append(("grad", nname, k, float(np.max(np.abs(dg[1:3] - rg[1:3]) / (np.abs(rg[1:3]) + 1e-30)))))
+                e = float(np.max(np.abs(dg[1:3] - rg[1:3]) / (np.abs(rg[1:3]) + 1e-30)))
+                if own and not is_skip:
+                    bounded.append(("grad", nname, k, e, own[0]))
+                if not np.all(np.abs(dg[1:3] - rg[1:3]) <= gt_k * np.abs(rg[1:3]) + floor):
+                    (skipped if is_skip else bad).append(("grad", nname, k, e))
                 seen += 0 if is_skip else 1
             d = digest(p.detach().cpu().numpy().astype(np.float64) - pre[nname][k].astype(np.float64))
             r = arr["s0/upd/%s/%s" % (nname, k)]
             # Adam's g / (|g| + eps) amplifies rounding noise on ~zero gradients to O(lr): well-conditioned tensors only (for
             # the discriminators the criterion uses this side's D-phase gradient, which is what their update was made from)
             if np.min(np.abs(g)) > 1e-5 * gmax and np.min(np.abs(g)) > 1e-6:
-                if not (abs(d[1] - r[1]) <= ut * r[1] + 1e-12 and abs(d[2] - r[2]) <= ut * r[2] + 1e-12):
-                    (skipped if is_skip else bad).append(("upd", nname, k, float(max(abs(d[1] - r[1]) / (r[1] + 1e-30), abs(d[2] - r[2]) / (r[2] + 1e-30)))))
+                e = float(max(abs(d[1] - r[1]) / (r[1] + 1e-30), abs(d[2] - r[2]) / (r[2] + 1e-30)))
+                if own and not is_skip:
+                    bounded.append(("upd", nname, k, e, own[0]))
+                if not (abs(d[1] - r[1]) <= ut_k * r[1] + 1e-12 and abs(d[2] - r[2]) <= ut_k * r[2] + 1e-12):
+                    (skipped if is_skip else bad).append(("upd", nname, k, e))
                 seen += 0 if is_skip else 1
     if skipped:
         print("digests outside the tolerance on tensors skipped by name (%s, %s):" % (prec, flavour), skipped)
+    for kind, nname, k, e, b in bounded:   # the measurement beside the tensor's own bound, every run
+        print("digest_err prec=%s flavour=%s %s %s/%s=%.3e allowed=%.1e" % (prec, flavour, kind, nname, k, e, b))
     assert seen > 50 and not bad, (len(bad), bad)
 
 
@@ -215,9 +234,12 @@ def _check_6_blocks(prec):
         assert rel(n(v1[k]), v0[k]) < vt, k
     # the cycle reconstructions chain two of these high-gain generators: tools/conditioning_probe.py (`step`) shows the
     # EXACT-fp32 path moving rec_A / rec_B by 4e-4 .. 9e-4 when its inputs are perturbed by 4e-6 relative, the
-    # operand rounding of bf16x3 (which lands at 0.8 / 1.4e-3 here; single-pass images at 1.1-1.3e-4)
+    # operand rounding of bf16x3 (which lands at 7.3e-4 / 7.6e-4 here, 0.8 / 1.4e-3 in earlier rounds; single-pass images at
+    # 1.1-1.3e-4)
     for k in ("rec_A", "rec_B"):
-        assert rel(n(v1[k]), v0[k]) < (vt if prec == "f32" else 3e-3), k
+        e, rt = rel(n(v1[k]), v0[k]), (vt if prec == "f32" else 2e-3)
+        print("rec_err case=oracle_6_blocks prec=%s %s=%.3e allowed=%.1e" % (prec, k, e, rt))
+        assert e < rt, (k, e)
     # weights after the step: compare the generators' outputs on a fresh batch
     A2, B2, z2 = recipe.inputs(6, 8, 1, 1, 64, 4)
     from oracle.tape import T
