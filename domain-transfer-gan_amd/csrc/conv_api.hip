@@ -822,6 +822,17 @@ static int check_desc(const acg_conv_desc *d, const char *who)
     return ACG_OK;
 }
 
+// the K x K tap list in kernel order: tap (kh, kw) gathers pixel (base + step kh, base + step kw) relative to the grid position
+static void square_taps(Taps *t, int K, int base, int step)
+{
+    t->n = 0;
+    for (int kh = 0; kh < K; ++kh)
+        for (int kw = 0; kw < K; ++kw) {
+            t->dy[t->n] = (short)(base + step * kh); t->dx[t->n] = (short)(base + step * kw); t->w[t->n] = (short)(kh * K + kw);
+            t->n++;
+        }
+}
+
 static void fwd_geom(const acg_conv_desc *d, Geom *g, Taps *t, int act)
 {
     g->Hin = d->Hi; g->Win = d->Wi; g->Cin = d->Ci;
@@ -832,12 +843,7 @@ static void fwd_geom(const acg_conv_desc *d, Geom *g, Taps *t, int act)
     g->Mtot = (long long)d->N * d->Ho * d->Wo;
     g->thin = thin_in(d) ? 1 : 0;
     g->w_elems = (long long)wf_regular_elems(d->K, d->Ci, d->Co);
-    t->n = 0;
-    for (int kh = 0; kh < d->K; ++kh)
-        for (int kw = 0; kw < d->K; ++kw) {
-            t->dy[t->n] = (short)(kh - d->pad); t->dx[t->n] = (short)(kw - d->pad); t->w[t->n] = (short)(kh * d->K + kw);
-            t->n++;
-        }
+    square_taps(t, d->K, -d->pad, 1);
 }
 
 // Column part of the reflect adjoint for the un-padded data gradient (Geom.unpad): pad column -1 mirrors onto column 1, pad
@@ -911,6 +917,27 @@ __global__ __launch_bounds__(256) void dgrad_colfix_kernel(const char *__restric
 // data gradient (and ConvTranspose forward): gathers from the conv-OUTPUT side tensor `src`
 // (N,Ho,Wo,Co) with packed wb, writes the conv-INPUT side tensor `dst` (N,Hi,Wi,Ci).
 // addend (optional): tensor of dst's shape added to the result; only the frame path below implements it
+static void dgrad_geom(const acg_conv_desc *d, int act, Geom *g)   // the fields both strides share
+{
+    g->Hin = d->Ho; g->Win = d->Wo; g->Cin = d->Co;
+    g->Cout = d->Ci; g->reflect = 0; g->act = act; g->ncols_pad = acg_ncols_pad(d->Ci); g->is = 1;
+    g->thin = (d->stride == 1 && thin_out(d)) ? 1 : 0;
+    g->w_elems = (long long)wb_regular_elems(d->K, d->Ci, d->Co);
+}
+
+// Stride 1: the grid is the padded one (Hi+2p x Wi+2p, folded afterwards) for a reflect-padded layer, else the Hi x Wi input.
+// unpad: the un-padded grid of the pre-split reflect data gradient (Geom.unpad).  Zero padding: dy row = iy + p - kh; reflect
+// (padded grid): dy row = py - kh.  t may be null (the dispatch queries that need only the Geom).
+static void dgrad_s1_geom(const acg_conv_desc *d, int act, bool unpad, Geom *g, Taps *t)
+{
+    dgrad_geom(d, act, g);
+    const int e = d->pad_mode == ACG_PAD_REFLECT && !unpad ? d->pad : 0;
+    g->Hout = d->Hi + 2 * e; g->Wout = d->Wi + 2 * e; g->GH = g->Hout; g->GW = g->Wout;
+    g->os = 1; g->oy0 = 0; g->ox0 = 0;
+    g->Mtot = (long long)d->N * g->GH * g->GW;
+    if (t != nullptr) square_taps(t, d->K, d->pad - e, -1);
+}
+
 static bool dgrad_frame_ok(const acg_conv_desc *d, const Geom &g)
 {
     const int p = d->pad;
@@ -921,8 +948,7 @@ static bool dgrad_frame_ok(const acg_conv_desc *d, const Geom &g)
 // the un-padded grid of the pre-split reflect data gradient (Geom.unpad): 3x3, pad 1, rows that are whole 128-pixel tiles
 static bool dgrad_unpad_ok(const acg_conv_desc *d)
 {
-    static const bool no_unpad = acg_debug_switch("ACG_NO_UNPAD");   // A/B switch
-    return !no_unpad && d->stride == 1 && d->pad_mode == ACG_PAD_REFLECT && d->K == 3 && d->pad == 1 && d->Wi % 128 == 0 &&
+    return d->stride == 1 && d->pad_mode == ACG_PAD_REFLECT && d->K == 3 && d->pad == 1 && d->Wi % 128 == 0 &&
            d->Hi % 32 == 0 && d->Hi >= 64 && d->Co % 128 == 0;
 }
 
@@ -934,14 +960,10 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
 {
     ACG_REQUIRE(act != ACG_ACT_SIGMOID, "dgrad / ConvTranspose2d: no sigmoid epilogue");
     Geom g; Taps t;
-    g.Hin = d->Ho; g.Win = d->Wo; g.Cin = d->Co;
-    g.Cout = d->Ci; g.reflect = 0; g.act = act; g.ncols_pad = acg_ncols_pad(d->Ci); g.is = 1;
-    g.thin = (d->stride == 1 && thin_out(d)) ? 1 : 0;
-    g.w_elems = (long long)wb_regular_elems(d->K, d->Ci, d->Co);
     const int p = d->pad, K = d->K;
     if (d->stride == 1) {
-        const bool refl = d->pad_mode == ACG_PAD_REFLECT && p > 0;
-        const int e = refl ? p : 0; // compute on the padded grid, then fold
+        const bool refl = d->pad_mode == ACG_PAD_REFLECT && p > 0;   // compute on the padded grid, then fold
+        dgrad_s1_geom(d, act, false, &g, &t);
         float *out = dst;
         if (refl) {
             const size_t need = (size_t)d->N * (d->Hi + 2 * p) * (d->Wi + 2 * p) * d->Ci * sizeof(float);
@@ -952,17 +974,10 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
             ACG_REQUIRE(bias == nullptr && act == ACG_ACT_NONE, "dgrad: reflect with epilogue unsupported");
             out = (float *)ws;
         }
-        g.Hout = d->Hi + 2 * e; g.Wout = d->Wi + 2 * e; g.GH = g.Hout; g.GW = g.Wout;
-        g.os = 1; g.oy0 = 0; g.ox0 = 0;
-        g.Mtot = (long long)d->N * g.GH * g.GW;
         // Pre-split operands, 3x3, pad 1, rows that are whole tiles: the un-padded grid (Geom.unpad) — 3 % fewer tiles than the
         // padded grid, one row segment per tile, and the fold pass over the frame goes away
         if (refl && in_s16 && dgrad_unpad_ok(d) && dgrad_frame_ok(d, g)) {
-            g.Hout = d->Hi; g.Wout = d->Wi; g.GH = d->Hi; g.GW = d->Wi;
-            g.Mtot = (long long)d->N * g.GH * g.GW;
-            t.n = 0;
-            for (int kh = 0; kh < K; ++kh)
-                for (int kw = 0; kw < K; ++kw) { t.dy[t.n] = (short)(p - kh); t.dx[t.n] = (short)(p - kw); t.w[t.n] = (short)(kh * K + kw); t.n++; }
+            dgrad_s1_geom(d, act, true, &g, &t);
             ACG_REQUIRE(acg_igemm_x3_pre_ok(g, t) && (relu_s16 == 0 || out_s16) && (out_s16 == 0 || addend == nullptr) &&
                         (relu_src == nullptr || relu_s16 == out_s16) && d->Co % 128 == 0,
                         "dgrad: unsupported pre-split combination (query acg_conv2d_s16_supported)");
@@ -981,14 +996,6 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
         }
         ACG_REQUIRE((ns == nullptr || (!refl && !in_s16 && !out_s16 && addend == nullptr && relu_src == nullptr)) && relu_mask == nullptr,
                     "dgrad: norm sums / a sign bitmask as the ReLU source need the un-padded pre-split path or the row pipeline (query acg_conv2d_bwd_data_s16_sums_supported / acg_conv2d_bwd_data_sums_supported)");
-        t.n = 0;
-        // zero pad: dy row = iy + p - kh ; reflect (padded grid): dy row = py - kh
-        const int base = refl ? 0 : p;
-        for (int kh = 0; kh < K; ++kh)
-            for (int kw = 0; kw < K; ++kw) {
-                t.dy[t.n] = (short)(base - kh); t.dx[t.n] = (short)(base - kw); t.w[t.n] = (short)(kh * K + kw);
-                t.n++;
-            }
         // the wave-specialised kernel stores the pixels nothing is mirrored onto straight into dst: only the frame is folded
         const bool frame = refl && dgrad_frame_ok(d, g);
         ACG_REQUIRE((addend == nullptr && relu_src == nullptr) || frame,
@@ -1033,6 +1040,7 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
     ACG_REQUIRE(d->pad_mode == ACG_PAD_ZERO, "dgrad: stride 2 needs zero padding");
     ACG_REQUIRE(addend == nullptr && relu_src == nullptr && relu_mask == nullptr && !in_s16 && !out_s16, "dgrad: stride 2 takes no fused side inputs");
     ACG_REQUIRE(ns == nullptr || acg_conv2d_bwd_data_sums_supported(d), "dgrad: norm sums on this stride-2 geometry (query acg_conv2d_bwd_data_sums_supported)");
+    dgrad_geom(d, act, &g);
     g.Hout = d->Hi; g.Wout = d->Wi; g.os = 2;
     auto phase_taps = [&](int py, int px, Taps &tt, int base) {
         int n = 0;
@@ -1050,10 +1058,9 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
     // One launch for the four phases where the generic bf16 tile runs them anyway: even output sizes (equal phase grids of
     // whole 128-pixel tiles), at most 16 taps per phase.  The phases of a tile read the same rows of `src`: side by side on
     // one XCD they fetch them from HBM once (four launches: 2.0x the algorithmic traffic, profiles/r02_a_layer_traffic).
-    static const bool no_phased = acg_debug_switch("ACG_NO_PHASED");   // A/B switch
     g.GH = d->Hi / 2; g.GW = d->Wi / 2; g.oy0 = 0; g.ox0 = 0;
     g.Mtot = (long long)d->N * g.GH * g.GW;
-    if (!no_phased && d->Hi % 2 == 0 && d->Wi % 2 == 0 && g.Mtot % 128 == 0 && (K + 1) / 2 * ((K + 1) / 2) <= 16 &&
+    if (d->Hi % 2 == 0 && d->Wi % 2 == 0 && g.Mtot % 128 == 0 && (K + 1) / 2 * ((K + 1) / 2) <= 16 &&
         g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && !thin_in_valu_dgrad(d) && !thin_out(d) &&
         !acg_igemm_uses_ws(g)) {
         t.n = 64;
@@ -1138,10 +1145,9 @@ extern "C" int acg_conv2d_fwd_stats_supported(const acg_conv_desc *d)
     if (d == nullptr || g_acg_precision == ACG_PREC_F32 || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
     // the C4 image -> 32 channel stem (conv_thinrow_x3): statistics over its 8 x 16 pixel tiles
     if (thin_in(d) && d->Ci == 4 && d->Co == 32 && d->stride == 1 && d->K <= 7 && g_acg_precision == ACG_PREC_BF16X3 && d->Ho % 8 == 0 &&
-        d->Wo % 16 == 0 && !acg_debug_switch("ACG_NO_THINROW"))
+        d->Wo % 16 == 0)
         return 1;
     if (thin_in(d) || thin_out(d) || d->Co < 32 || d->Ci % 16 != 0) return 0;    // MFMA tiles of the bf16 kernels only
-    if (d->Co < 128 && acg_debug_switch("ACG_NO_GENERIC_STATS")) return 0;   // A/B switch: statistics pass for the narrow layers
     return ((long long)d->Ho * d->Wo) % 128 == 0 ? 1 : 0;
 }
 
@@ -1164,7 +1170,6 @@ extern "C" int acg_conv_transpose2d_fwd_stats_supported(const acg_conv_desc *d)
 {
     if (d == nullptr || g_acg_precision == ACG_PREC_F32 || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
     if (d->stride != 2 || thin_in(d) || thin_out(d) || d->Ci < 32 || d->Co % 16 != 0 || d->Ci >= 128) return 0;
-    if (acg_debug_switch("ACG_NO_GENERIC_STATS")) return 0;
     if (d->Hi % 2 || d->Wi % 2) return 0;
     return ((long long)(d->Hi / 2) * (d->Wi / 2)) % 128 == 0 ? 1 : 0;
 }
@@ -1198,7 +1203,7 @@ extern "C" int acg_conv2d_bwd_data_add_supported(const acg_conv_desc *d)
 {
     if (d == nullptr || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
     Geom g;
-    g.Cin = d->Co; g.Cout = d->Ci; g.thin = (d->stride == 1 && thin_out(d)) ? 1 : 0;
+    dgrad_s1_geom(d, ACG_ACT_NONE, false, &g, nullptr);
     return dgrad_frame_ok(d, g) ? 1 : 0;
 }
 
@@ -1226,25 +1231,22 @@ extern "C" int acg_conv2d_bwd_data_relu(const acg_conv_desc *d, const float *dy,
 // An S16 tensor has the shape and byte size of its fp32 NHWC twin; per pixel and 8-channel group it holds 16 bytes of bf16
 // hi followed by 16 bytes of bf16 lo (x = hi + lo up to 2^-17 |x|: exactly the operand the bf16x3 convolutions consume).
 // Replaces the per-launch split of `modules.py:205-227`'s activations inside the convolution loaders.
-static bool acg_wgrad_krow_s16_ok(const acg_conv_desc *d) // the conditions under which wgrad_plan sizes the kernel-row split
+// the kernel-row weight gradients (conv_wgrad_tr.hip) of the stride-1 3x3 layers: 128-multiple channels (the one the
+// pre-split operands need), and the 32 <-> 64 channel variant
+static bool wgrad_krow(const acg_conv_desc *d)
 {
-    return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !thin_in(d) && d->K == 3 && d->stride == 1 &&
-           d->pad == 1 && d->Hi == d->Ho && d->Wi == d->Wo && d->Wo % 32 == 0 && d->Ci % 128 == 0 && d->Co % 128 == 0 &&
-           !acg_debug_switch("ACG_NO_KROW");
+    return !thin_in(d) && acg_wgrad_krow_shape_ok(d->K, d->stride, d->pad, d->Hi, d->Wi, d->Ho, d->Wo, d->Ci, d->Co);
+}
+static bool wgrad_krow_s(const acg_conv_desc *d)
+{
+    return !thin_in(d) && acg_wgrad_krow_s_shape_ok(d->K, d->stride, d->pad, d->Hi, d->Wi, d->Ho, d->Wo, d->Ci, d->Co);
 }
 
 static bool s16_dgrad_geom_ok(const acg_conv_desc *d)
 {
     if (d->stride != 1 || d->pad_mode != ACG_PAD_REFLECT || d->pad <= 0) return false;
     Geom g; Taps t;
-    g.Hin = d->Ho; g.Win = d->Wo; g.Cin = d->Co; g.Cout = d->Ci; g.reflect = 0; g.act = 0; g.ncols_pad = acg_ncols_pad(d->Ci);
-    g.is = 1; g.thin = (d->stride == 1 && thin_out(d)) ? 1 : 0;
-    const int p = d->pad, K = d->K;
-    g.Hout = d->Hi + 2 * p; g.Wout = d->Wi + 2 * p; g.GH = g.Hout; g.GW = g.Wout; g.os = 1; g.oy0 = 0; g.ox0 = 0;
-    g.Mtot = (long long)d->N * g.GH * g.GW;
-    t.n = 0;
-    for (int kh = 0; kh < K; ++kh)
-        for (int kw = 0; kw < K; ++kw) { t.dy[t.n] = (short)(-kh); t.dx[t.n] = (short)(-kw); t.w[t.n] = (short)(kh * K + kw); t.n++; }
+    dgrad_s1_geom(d, ACG_ACT_NONE, false, &g, &t);
     return dgrad_frame_ok(d, g) && acg_igemm_x3_pre_ok(g, t);
 }
 
@@ -1255,7 +1257,7 @@ extern "C" int acg_conv2d_s16_supported(const acg_conv_desc *d)
     Geom g; Taps t;
     fwd_geom(d, &g, &t, 0);
     if (!acg_igemm_x3_pre_ok(g, t) || !s16_dgrad_geom_ok(d)) return 0;
-    return acg_wgrad_krow_s16_ok(d) ? 1 : 0;
+    return wgrad_krow(d) ? 1 : 0;
 }
 
 extern "C" int acg_conv2d_fwd_s16(const acg_conv_desc *d, const void *x, const float *wf, const float *bias, void *y, int act,
@@ -1338,23 +1340,22 @@ extern "C" int acg_conv2d_bwd_data_s16_sums(const acg_conv_desc *d, const void *
 // pre-split kernel's (where a workgroup owns several chunks its sums sit in the first, zeros in the others)
 extern "C" int acg_conv2d_bwd_data_sums_supported(const acg_conv_desc *d)
 {
-    if (d == nullptr || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || acg_debug_switch("ACG_NO_ROWS")) return 0;
+    if (d == nullptr || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
     if (check_desc(d, "acg_conv2d_bwd_data_sums_supported") != ACG_OK) return 0;
-    static const bool no_tile_sums = acg_debug_switch("ACG_NO_TILE_SUMS");   // A/B switch: the three producers of round 6
     // the four-phase tile of the stride-2 3x3 data gradient (igemm_conv_ph4<SUMS>): 64 input channels of the convolution, phase
     // grid rows that are whole 128-pixel tiles
-    if (!no_tile_sums && !acg_debug_switch("ACG_NO_PH4_SUMS") && d->K == 3 && d->stride == 2 && d->pad == 1 && d->pad_mode != ACG_PAD_REFLECT && d->Ci == 64 &&
-        d->Co % 32 == 0 && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo && d->Wo % 128 == 0 && !acg_debug_switch("ACG_NO_PH4") && !acg_debug_switch("ACG_NO_PHASED"))
+    if (d->K == 3 && d->stride == 2 && d->pad == 1 && d->pad_mode != ACG_PAD_REFLECT && d->Ci == 64 &&
+        d->Co % 32 == 0 && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo && d->Wo % 128 == 0)
         return 1;
     // the 7x7 (K <= 7) stride-1 zero-padded layer with a C4 image on its output side (the head, networks.py:187-188):
     // conv_thinrow_x3's whole 8 x 16 tiles
-    if (!no_tile_sums && d->stride == 1 && d->pad_mode != ACG_PAD_REFLECT && thin_out(d) && d->Co == 4 && d->Ci == 32 && d->K >= 2 && d->K <= 7 &&
-        d->Hi == d->Ho && d->Wi == d->Wo && d->Hi % 8 == 0 && d->Wi % 16 == 0 && !thin_in_valu_dgrad(d) && !acg_debug_switch("ACG_NO_THINROW"))
+    if (d->stride == 1 && d->pad_mode != ACG_PAD_REFLECT && thin_out(d) && d->Co == 4 && d->Ci == 32 && d->K >= 2 && d->K <= 7 &&
+        d->Hi == d->Ho && d->Wi == d->Wo && d->Hi % 8 == 0 && d->Wi % 16 == 0 && !thin_in_valu_dgrad(d))
         return 1;
     // the generic 128-pixel tile on the data gradient of the zero-padded 3x3 stride-1 32 -> 64 layer (networks.py:164: 64 gathered,
     // 32 written channels — the mirror shape the row pipeline does not take): row-patch tiles, i.e. rows of whole 128-pixel tiles
-    if (!no_tile_sums && d->K == 3 && d->stride == 1 && d->pad == 1 && d->pad_mode != ACG_PAD_REFLECT && d->Ci == 32 && d->Co == 64 &&
-        d->Hi == d->Ho && d->Wi == d->Wo && d->Wi % 128 == 0 && !acg_debug_switch("ACG_NO_RP"))
+    if (d->K == 3 && d->stride == 1 && d->pad == 1 && d->pad_mode != ACG_PAD_REFLECT && d->Ci == 32 && d->Co == 64 &&
+        d->Hi == d->Ho && d->Wi == d->Wo && d->Wi % 128 == 0)
         return 1;
     return d->K == 3 && d->stride == 1 && d->pad == 1 && d->pad_mode != ACG_PAD_REFLECT && d->Co == 32 && d->Ci == 64 && d->Hi == d->Ho &&
            d->Wi == d->Wo && d->Wi % 128 == 0 ? 1 : 0;
@@ -1376,22 +1377,21 @@ extern "C" int acg_conv2d_bwd_weight_s16(const acg_conv_desc *d, const void *x, 
 // split-K plan shared by the workspace query and the launch
 static bool wgrad_thin(const acg_conv_desc *d) { return thin_in(d); }
 // the persistent patch kernel of the 7x7 image layers (conv_wgrad_thin.hip): workgroups = partial slabs, or 0 where the layer
-// does not take it (same conditions as acg_wgrad_thin_patch_ok, on the descriptor)
+// does not take it
 static int wgrad_thin_patch_splits(const acg_conv_desc *d)
 {
-    if (g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || d->stride != 1 || d->K < 2 || d->K > 7 ||
-        d->Hi != d->Ho || d->Wi != d->Wo || acg_debug_switch("ACG_NO_WGRAD_THIN_PATCH"))
-        return 0;
-    const bool stem = thin_in(d) && d->Ci == 4 && d->Co == 32;
-    const bool head = thin_out(d) && d->Co == 4 && d->Ci == 32 && !(d->pad_mode == ACG_PAD_REFLECT && d->pad > 0);
+    const bool stem = thin_in(d) && acg_wgrad_thin_patch_shape_ok(d->K, d->stride, d->Hi, d->Wi, d->Ho, d->Wo, d->Ci, d->Co);
+    const bool head = thin_out(d) && !(d->pad_mode == ACG_PAD_REFLECT && d->pad > 0) &&
+                      acg_wgrad_thin_patch_shape_ok(d->K, d->stride, d->Ho, d->Wo, d->Hi, d->Wi, d->Co, d->Ci);
     if (!stem && !head) return 0;
     const long long ntiles = (long long)d->N * ((d->Ho + 7) / 8) * ((d->Wo + 15) / 16);
     return (int)(ntiles < 768 ? ntiles : 768);
 }
 
-static void wgrad_plan(const acg_conv_desc *d, int Cx, int Cg, long long Mtot, int *CiP, int *CoP, int *nsplit,
-                       long long *mps)
+static void wgrad_plan(const acg_conv_desc *d, int *CiP, int *CoP, int *nsplit, long long *mps)
 {
+    const int Cx = d->Ci, Cg = d->Co;
+    const long long Mtot = (long long)d->N * d->Ho * d->Wo;
     int bci, bco;
     acg_wgrad_tiles(Cx, Cg, &bci, &bco, wgrad_thin(d) ? 0 : d->K * d->K);
     *CiP = (Cx + bci - 1) / bci * bci;
@@ -1410,18 +1410,13 @@ static void wgrad_plan(const acg_conv_desc *d, int Cx, int Cg, long long Mtot, i
     long long target = (g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA && ((bci == 128 && bco == 128) || nt == 3) && !wgrad_thin(d)) ? 512 : 1024;
     long long nblk = base;
     int gran = KP;
-    // kernel-row weight gradient (conv_wgrad_tr.hip, same conditions as acg_wgrad_krow_ok): three taps per workgroup, one
-    // 512-thread workgroup per CU -> one residency wave of 256
-    static const bool no_krow = acg_debug_switch("ACG_NO_KROW");
-    if (!no_krow && g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !wgrad_thin(d) && d->K == 3 &&
-        d->stride == 1 && d->pad == 1 && d->Hi == d->Ho && d->Wi == d->Wo && d->Wo % 32 == 0 && Cx % 128 == 0 && Cg % 128 == 0) {
+    // kernel-row weight gradient: three taps per workgroup, one 512-thread workgroup per CU -> one residency wave of 256
+    if (wgrad_krow(d)) {
         nblk = 3LL * (*CiP / 128) * (*CoP / 128);
         target = 256;
         gran = 32; // its stage is a 32-pixel run: splits this fine fill 255 of the 256 CUs at batch 32 (256-pixel splits: 246)
-    } else if (!no_krow && g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !wgrad_thin(d) && d->K == 3 &&
-               d->stride == 1 && d->pad == 1 && d->Hi == d->Ho && d->Wi == d->Wo && d->Wo % 128 == 0 &&
-               ((Cx == 32 && Cg == 64) || (Cx == 64 && Cg == 32))) {
-        nblk = 3; // the 32 <-> 64 channel variant (acg_wgrad_krow_s_ok): 256 threads, two workgroups per CU
+    } else if (wgrad_krow_s(d)) {
+        nblk = 3; // the 32 <-> 64 channel variant: 256 threads, two workgroups per CU
         target = 512;
         gran = 128;
     }
@@ -1447,23 +1442,43 @@ static void wgrad_plan(const acg_conv_desc *d, int Cx, int Cg, long long Mtot, i
     *mps = per;
 }
 
-static size_t wgrad_ws_bytes(const acg_conv_desc *d, int Cx, int Cg, long long Mtot)
+// wgrad_thin_out's split plan (<= 512 splits, or one slab per workgroup of the patch kernel).  slabs: what the workspace
+// query reserves, at least nsplit
+struct ThinOutPlan {
+    int CiP, CoP, nsplit;
+    long long per, slabs;
+};
+static ThinOutPlan wgrad_thin_out_plan(const acg_conv_desc *d)
+{
+    ThinOutPlan p;
+    p.CiP = 32 * ((d->K * d->K + 7) / 8);
+    p.CoP = (d->Ci + 31) / 32 * 32;
+    const long long M = (long long)d->N * d->Hi * d->Wi;
+    long long ns = 1536 / ((long long)(p.CiP / 32) * (p.CoP / 32)), cap = M / 1024;
+    if (ns > cap) ns = cap;
+    if (ns > 512) ns = 512;
+    if (ns < 1) ns = 1;
+    p.per = (M + ns - 1) / ns;
+    p.per = (p.per + 255) / 256 * 256;
+    p.nsplit = (int)((M + p.per - 1) / p.per);
+    const int patch = wgrad_thin_patch_splits(d);
+    if (patch > 0) p.nsplit = patch;
+    p.slabs = (patch > ns ? patch : ns) + 1;
+    return p;
+}
+
+static size_t wgrad_ws_bytes(const acg_conv_desc *d)
 {
     int CiP, CoP, ns; long long mps;
-    wgrad_plan(d, Cx, Cg, Mtot, &CiP, &CoP, &ns, &mps);
+    wgrad_plan(d, &CiP, &CoP, &ns, &mps);
     const size_t part = (size_t)ns * d->K * d->K * CiP * CoP * sizeof(float);
     const int Cmax = d->Ci > d->Co ? d->Ci : d->Co;
     const long long Mbig = (long long)d->N * (d->Hi > d->Ho ? d->Hi : d->Ho) * (d->Wi > d->Wo ? d->Wi : d->Wo);
     const size_t bias_part = (size_t)ns * 2 * (CiP > CoP ? CiP : CoP) * sizeof(float);   // x-side sums: `stride` slots per split
     size_t total = acg_round_up(part, 256) + acg_round_up(colsum_ws_bytes(Mbig, Cmax) + bias_part, 256);
-    if (thin_out(d) && d->stride == 1) { // wgrad_thin_out's partial buffer (its own split plan, <= 512 splits)
-        const long long Mx = (long long)d->N * d->Hi * d->Wi;
-        long long ns2 = 1536 / ((long long)((d->K * d->K + 7) / 8) * ((d->Ci + 31) / 32)), cap = Mx / 1024;
-        if (ns2 > cap) ns2 = cap;
-        if (ns2 > 512) ns2 = 512;
-        if (ns2 < 1) ns2 = 1;
-        if (wgrad_thin_patch_splits(d) > ns2) ns2 = wgrad_thin_patch_splits(d);
-        const size_t t2 = (size_t)(ns2 + 1) * 32 * ((d->K * d->K + 7) / 8) * ((d->Ci + 31) / 32 * 32) * sizeof(float);
+    if (thin_out(d) && d->stride == 1) { // wgrad_thin_out's partial buffer
+        const ThinOutPlan p = wgrad_thin_out_plan(d);
+        const size_t t2 = (size_t)p.slabs * p.CiP * p.CoP * sizeof(float);
         if (t2 > total) total = t2;
     }
     return total;
@@ -1473,8 +1488,7 @@ extern "C" size_t acg_conv2d_bwd_weight_workspace_bytes(const acg_conv_desc *d)
 {
     if (d == nullptr) return 0;
     // covers both orientations (Conv2d and ConvTranspose2d use of the same descriptor)
-    const size_t a = wgrad_ws_bytes(d, d->Ci, d->Co, (long long)d->N * d->Ho * d->Wo);
-    return a;
+    return wgrad_ws_bytes(d);
 }
 
 // x_side: conv-input-side tensor (N,Hi,Wi,Ci); g_side: conv-output-side tensor (N,Ho,Wo,Co)
@@ -1496,7 +1510,7 @@ static int wgrad_common(const acg_conv_desc *d, const float *x_side, const float
     g.is = d->stride; g.reflect = d->pad_mode == ACG_PAD_REFLECT;
     g.thin = (thin_conv && wgrad_thin(d)) ? 1 : 0;
     g.Mtot = (long long)d->N * d->Ho * d->Wo;
-    wgrad_plan(d, d->Ci, d->Co, g.Mtot, &g.CiP, &g.CoP, &g.nsplit, &g.m_per_split);
+    wgrad_plan(d, &g.CiP, &g.CoP, &g.nsplit, &g.m_per_split);
     const int ntb = g.thin ? 1 : t.n;
     const size_t need = (size_t)g.nsplit * ntb * g.CiP * g.CoP * sizeof(float);
     if (ws == nullptr || ws_bytes < need) {
@@ -1507,7 +1521,7 @@ static int wgrad_common(const acg_conv_desc *d, const float *x_side, const float
     g.bias_part = (float *)((char *)ws + acg_round_up(need, 256));
     int rc;
     if (s16) {
-        ACG_REQUIRE(acg_wgrad_krow_s16_ok(d) && g.CiP == d->Ci && g.CoP == d->Co && g.m_per_split % 32 == 0 && g.bias_from != 2,
+        ACG_REQUIRE(wgrad_krow(d) && g.CiP == d->Ci && g.CoP == d->Co && g.m_per_split % 32 == 0 && g.bias_from != 2,
                     "wgrad: pre-split operands need the kernel-row geometry (query acg_conv2d_s16_supported)");
         rc = acg_wgrad_krow_s16_launch(x_side, g_side, (float *)ws, g, st);
     } else {
@@ -1535,26 +1549,13 @@ static int wgrad_thin_out(const acg_conv_desc *d, const float *x, const float *d
                           size_t ws_bytes, hipStream_t st, int accumulate)
 {
     WGeom g; Taps t;
-    const int K = d->K, p = d->pad;
-    t.n = 0;
-    for (int kh = 0; kh < K; ++kh)
-        for (int kw = 0; kw < K; ++kw) { t.dy[t.n] = (short)(p - kh); t.dx[t.n] = (short)(p - kw); t.w[t.n] = (short)(kh * K + kw); t.n++; }
+    square_taps(&t, d->K, d->pad, -1);
     g.Hin = d->Ho; g.Win = d->Wo; g.Cin = d->Co;      // gathered side: dy
     g.Hg = d->Hi; g.Wg = d->Wi; g.Cg = d->Ci;         // plain rows: x
     g.is = 1; g.reflect = 0; g.thin = 1; g.bias_from = 0; g.bias_part = nullptr;
     g.Mtot = (long long)d->N * d->Hi * d->Wi;
-    g.CiP = 32 * ((K * K + 7) / 8);
-    g.CoP = (d->Ci + 31) / 32 * 32;
-    const long long base = (long long)(g.CiP / 32) * (g.CoP / 32);
-    long long ns = 1536 / base, cap = g.Mtot / 1024;
-    if (ns > cap) ns = cap;
-    if (ns > 512) ns = 512;
-    if (ns < 1) ns = 1;
-    long long per = (g.Mtot + ns - 1) / ns;
-    per = (per + 255) / 256 * 256;
-    g.nsplit = (int)((g.Mtot + per - 1) / per);
-    g.m_per_split = per;
-    if (wgrad_thin_patch_splits(d) > 0) g.nsplit = wgrad_thin_patch_splits(d);   // one slab per persistent workgroup
+    const ThinOutPlan p = wgrad_thin_out_plan(d);
+    g.CiP = p.CiP; g.CoP = p.CoP; g.nsplit = p.nsplit; g.m_per_split = p.per;
     const size_t need = (size_t)g.nsplit * g.CiP * g.CoP * sizeof(float);
     if (ws == nullptr || ws_bytes < need) {
         acg_set_error("acg_conv2d_bwd_weight(thin out): workspace %zu < %zu", ws_bytes, need);
@@ -1575,7 +1576,7 @@ static int wgrad_thin_out(const acg_conv_desc *d, const float *x, const float *d
 static float *colsum_area(const acg_conv_desc *d, void *ws, size_t ws_bytes, size_t *avail)
 {
     int CiP, CoP, ns; long long mps;
-    wgrad_plan(d, d->Ci, d->Co, (long long)d->N * d->Ho * d->Wo, &CiP, &CoP, &ns, &mps);
+    wgrad_plan(d, &CiP, &CoP, &ns, &mps);
     const size_t part = acg_round_up((size_t)ns * d->K * d->K * CiP * CoP * sizeof(float), 256);
     *avail = ws_bytes > part ? ws_bytes - part : 0;
     return (float *)((char *)ws + part);

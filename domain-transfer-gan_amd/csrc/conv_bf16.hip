@@ -420,11 +420,7 @@ __global__ __launch_bounds__(256) void igemm_conv_bf16(const float *__restrict__
                 const int co = n0 + wn * TN + j * 32 + (lane & 31);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-#ifdef ACG_ABL_NOSTORE   // diagnostic build: keep the arithmetic alive, store (almost) nothing
-                    const bool ok = rel[q] != ~0u && co < g.Cout && acc[i][j][4 * r4 + q] == 12345.678f;
-#else
                     const bool ok = rel[q] != ~0u && co < g.Cout;
-#endif
                     const float v = acc[i][j][4 * r4 + q]; // (a bit cast of the vector-element lvalue itself reads element 0)
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, acg_masked_off(rel[q] + (unsigned)co * 4u, ok), 0, 0);
                 }
@@ -478,8 +474,7 @@ static bool rp_groups(const Geom &g, Taps &t)
 // does this launch go to the wave-specialised bf16x3 kernel (conv_x3.hip)?  128-column tiles, 32-channel stages
 bool acg_igemm_uses_ws(const Geom &g)
 {
-    static const bool no_ws = acg_debug_switch("ACG_NO_WS"); // A/B switch
-    return !no_ws && g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && g.Cout >= 128 &&
+    return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && g.Cout >= 128 &&
            g.Cin % 32 == 0 && acg_act_kind(g.act) != ACG_ACT_SIGMOID;   // (no sigmoid epilogue: the generic tile takes it)
 }
 
@@ -512,7 +507,7 @@ int acg_igemm_bf16_launch(const float *in, const void *wp, const float *bias, fl
                          g0.os == 1 && ((long long)g0.GH * g0.GW) % 128 == 0 && g0.ns_x != nullptr && g0.ns_mean != nullptr && g0.ns_rstd != nullptr &&
                          g0.ns_mask == nullptr && (g0.ns_act == ACG_ACT_NONE || (g0.ns_act == ACG_ACT_RELU && g0.ns_gamma != nullptr && g0.ns_beta != nullptr)) &&
                          (g0.ns_gstride == 0 || g0.ns_gstride >= g0.Cout) && !acg_conv_patchn_ok(g0, t) && !acg_conv_patch16_ok(g0, t) &&
-                         bn == 32 && g0.Cin % 32 == 0 && !g0.reflect && !acg_debug_switch("ACG_NO_RP") && [&]() { Taps tq = t; return rp_groups(g, tq); }();
+                         bn == 32 && g0.Cin % 32 == 0 && !g0.reflect && [&]() { Taps tq = t; return rp_groups(g, tq); }();
     ACG_REQUIRE(g0.ns_part == nullptr || (split && !acg_igemm_uses_ws(g0) && (acg_conv_rows_ok(g0, t) || ns_tile)),
                 "igemm_conv_bf16: norm-backward sums requested on a geometry neither the row pipeline nor the generic tile takes");
     if (acg_igemm_uses_ws(g0)) {
@@ -523,17 +518,15 @@ int acg_igemm_bf16_launch(const float *in, const void *wp, const float *bias, fl
     if (split && acg_conv_rows_ok(g0, t)) return acg_conv_rows_launch(in, wp, bias, out, g0, t, n_w_elems, st);   // persistent row pipeline
     if (split && acg_conv_patchn_ok(g0, t))   // C4 output: the N-packed weights sit behind the regular hi + lo images
         return acg_conv_patchn_launch(in, (const __bf16 *)wp + 2 * n_w_elems, bias, out, g0, t, st);
-    static const bool no_patch = acg_debug_switch("ACG_NO_PATCH"); // A/B switch
-    if (!no_patch && acg_conv_patch16_ok(g0, t)) {
+    if (acg_conv_patch16_ok(g0, t)) {
         ACG_REQUIRE(g0.stats == nullptr, "conv_patch16: no statistics epilogue");
         return acg_conv_patch16_launch(in, wp, bias, out, g0, t, n_w_elems, st);
     }
     ACG_REQUIRE(g0.stats == nullptr || (((long long)g0.GH * g0.GW) % 128 == 0 && g0.act == ACG_ACT_NONE && g0.Mtot % 128 == 0),
                 "igemm_conv_bf16: per-tile statistics need whole 128-pixel tiles per image and no activation");
     ACG_REQUIRE(g0.fold_p == 0, "igemm_conv_bf16: the fold bypass is implemented by the wave-specialised kernel only");
-    static const bool no_rp = acg_debug_switch("ACG_NO_RP"); // A/B switch
     Taps tr = t;
-    if (!no_rp && split && rp_groups(g, tr)) {
+    if (split && rp_groups(g, tr)) {
         if (g.reflect) launch_bf16_kc<32, true, true, true>(bn, grid, st, in, w, bias, out, g, tr, inb, wb, wlo);
         else launch_bf16_kc<32, false, true, true>(bn, grid, st, in, w, bias, out, g, tr, inb, wb, wlo);
         ACG_CHECK_LAUNCH("igemm_conv_bf16 (row patch)");

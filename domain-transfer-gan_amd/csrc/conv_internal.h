@@ -126,11 +126,6 @@ bool acg_igemm_uses_ws(const Geom &g);
 bool acg_igemm_x3_pre_ok(const Geom &g, const Taps &t);
 int acg_igemm_x3_pre_launch(const void *in, const void *wp, const float *bias, float *out, const Geom &g, const Taps &t,
                             long long n_w_elems, hipStream_t st, float *stats = nullptr);
-// conv_x3_pp.hip: its persistent form (one workgroup per CU walks over its tiles; the epilogue of a tile is drained by two
-// dedicated waves during the next tile's loop)
-bool acg_igemm_x3_pp_ok(const Geom &g, const Taps &t);
-int acg_igemm_x3_pp_launch(const void *in, const void *wp, const float *bias, float *out, const Geom &g, const Taps &t,
-                           long long n_w_elems, hipStream_t st, float *stats = nullptr);
 bool acg_conv_patch16_ok(const Geom &g, const Taps &t);
 int acg_conv_patch16_launch(const float *in, const void *wp, const float *bias, float *out, const Geom &g, const Taps &t,
                             long long n_w_elems, hipStream_t st);
@@ -151,12 +146,17 @@ int acg_igemm_bf16_launch(const float *in, const void *wp, const float *bias, fl
                           int bn, long long n_w_elems, hipStream_t st);
 int acg_wgrad_bf16_launch(const float *x, const float *dy, float *part, const WGeom &g, const Taps &t, int bci, int bco,
                           hipStream_t st);
-// conv_wgrad_tr.hip: one kernel row per workgroup (stride-1 3x3, 128-multiple channels, bf16x3)
+// conv_wgrad_tr.hip: one kernel row per workgroup (stride-1 3x3, 128-multiple channels, bf16x3).  The *_shape_ok predicates
+// take the convolution's shape (x side Hi x Wi x Cx, gradient side Ho x Wo x Cg): the split plan (wgrad_plan, conv_api.hip)
+// asks them, the WGeom-level *_ok predicates build on them
+bool acg_wgrad_krow_shape_ok(int K, int stride, int pad, int Hi, int Wi, int Ho, int Wo, int Cx, int Cg);
 bool acg_wgrad_krow_ok(const WGeom &g, const Taps &t);
 int acg_wgrad_krow_launch(const float *x, const float *dy, float *part, const WGeom &g, hipStream_t st);
 int acg_wgrad_krow_s16_launch(const void *x, const void *dy, float *part, const WGeom &g, hipStream_t st); // pre-split operands
+bool acg_wgrad_krow_s_shape_ok(int K, int stride, int pad, int Hi, int Wi, int Ho, int Wo, int Cx, int Cg);
 bool acg_wgrad_krow_s_ok(const WGeom &g, const Taps &t);   // its 32 <-> 64 channel, 128-pixel-run variant
 // conv_wgrad_thin.hip: the 7x7 image layers (C4 tensor on one side, 32 channels on the other), persistent over 8 x 16 tiles
+bool acg_wgrad_thin_patch_shape_ok(int K, int stride, int Hthin, int Wthin, int Hwide, int Wwide, int Cthin, int Cwide);
 bool acg_wgrad_thin_patch_ok(const WGeom &g, const Taps &t, int *K, int *flip);
 int acg_wgrad_thin_patch_tiles(const WGeom &g);
 int acg_wgrad_thin_patch_launch(const float *thin, const float *wide, float *part, const WGeom &g, const Taps &t, hipStream_t st);

@@ -300,8 +300,7 @@ static bool patchn_window(const Taps &t, int *ymin, int *xmin, int *KH, int *KW)
 
 bool acg_conv_patchn_ok(const Geom &g, const Taps &t)
 {
-    static const bool off = acg_debug_switch("ACG_NO_PATCHN"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.fold_p || g.stats) return false;
+    if (g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.fold_p || g.stats) return false;
     if (g.Cin != 32 || g.Cout != 4 || g.os != 1 || g.is != 1 || g.oy0 != 0 || g.ox0 != 0 || t.n < 4) return false;
     int a, b, kh, kw;
     if (!patchn_window(t, &a, &b, &kh, &kw)) return false;
@@ -557,8 +556,7 @@ __global__ __launch_bounds__(256) void conv_thinrow_x3(const float *__restrict__
 
 bool acg_conv_thinrow_ok(const Geom &g, const Taps &t)
 {
-    static const bool off = acg_debug_switch("ACG_NO_THINROW"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || !g.thin || g.fold_p || acg_act_kind(g.act) == ACG_ACT_SIGMOID) return false;
+    if (g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || !g.thin || g.fold_p || acg_act_kind(g.act) == ACG_ACT_SIGMOID) return false;
     if (g.Cin != 4 || g.Cout != 32 || g.ncols_pad != 32 || g.os != 1 || g.is != 1 || g.oy0 != 0 || g.ox0 != 0 || t.n < 4) return false;
     if (g.stats != nullptr && (g.GH % PT_TH != 0 || g.GW % PT_TW != 0 || g.act != ACG_ACT_NONE)) return false;   // whole 128-pixel tiles
     if (g.ns_part != nullptr && (g.stats != nullptr || g.GH % PT_TH != 0 || g.GW % PT_TW != 0 || g.act != ACG_ACT_NONE || g.ns_x == nullptr ||

@@ -394,8 +394,7 @@ bool acg_ph4_plan(const Taps &t, const int nt[4], Taps *out)
 // g: the phased Geom of conv_api.hip (GH x GW = the phase grid, os = 2); tp: a plan of acg_ph4_plan
 bool acg_igemm_ph4_ok(const Geom &g)
 {
-    static const bool off = acg_debug_switch("ACG_NO_PH4"); // A/B switch
-    return !off && g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && g.is == 1 && g.os == 2 &&
+    return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && !g.thin && g.is == 1 && g.os == 2 &&
            g.GW % BM == 0 && g.Mtot % BM == 0 && g.Cin % KC == 0 && g.ncols_pad == 64 && g.Hout == 2 * g.GH && g.Wout == 2 * g.GW &&
            !g.reflect;
 }

@@ -17,7 +17,6 @@
 #include "common.h"
 #include "conv_internal.h"
 #include <type_traits>
-#include <cstdlib>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -40,7 +39,7 @@ typedef __attribute__((address_space(3))) char lds_char;
 
 __global__ __launch_bounds__(768) void conv_rows_x3(const float *__restrict__ in, const __bf16 *__restrict__ wp,
                                                     const float *__restrict__ bias, float *__restrict__ out, Geom g,
-                                                    unsigned long long slabs, unsigned in_bytes, long long w_lo_elems, int R, int cpb, int abl)
+                                                    unsigned long long slabs, unsigned in_bytes, long long w_lo_elems, int R, int cpb)
 {
     __shared__ __attribute__((aligned(256))) char lds[RW_LDS];
     __shared__ __attribute__((aligned(16))) float ptab[64 * 4];   // norm sums: (mean, rstd, gamma, beta) of the 64 channels of image n
@@ -56,7 +55,6 @@ __global__ __launch_bounds__(768) void conv_rows_x3(const float *__restrict__ in
     int rows = H - y0;
     rows = rows < R ? rows : R;           // output rows of this workgroup (> 0: the launcher sizes cpb that way)
     auto row_barrier = [&]() {
-        if (abl & 8) return;   // (timing ablation: no row barriers — wrong results)
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS traffic is done; vector memory stays in flight
         __builtin_amdgcn_s_barrier();
@@ -96,7 +94,6 @@ __global__ __launch_bounds__(768) void conv_rows_x3(const float *__restrict__ in
             constexpr int P = decltype(PC)::value;
             const int iy = y0 + i;
             const bool rowok = (unsigned)iy < (unsigned)H && i <= rows;
-            if (abl & 2) return;
 #pragma unroll
             for (int k = 0; k < RW_UPT; ++k) {
                 if (k == RW_UPT - 1 && pt + 256 * k >= RW_UNITS) continue;   // (wave-uniform for whole waves past the end)
@@ -109,7 +106,6 @@ __global__ __launch_bounds__(768) void conv_rows_x3(const float *__restrict__ in
         auto store_row = [&](int i, auto PC) {   // ... split and stored into ring slot (i + 1) & 3
             constexpr int P = decltype(PC)::value;
             char *slot = Al + ((i + 1) & (RW_NSLOT - 1)) * RW_SLOT;
-            if (abl & 2) return;
 #pragma unroll
             for (int k = 0; k < RW_UPT; ++k) {
                 if (pt + 256 * k >= RW_UNITS) continue;
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(768) void conv_rows_x3(const float *__restrict__ in
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = acg_apply_act(v[r], act);
                 }
-                if (!(abl & 1)) *(f32x4 *)(orow + pb * 16 * 64 + cb * 16) = v;
+                *(f32x4 *)(orow + pb * 16 * 64 + cb * 16) = v;
             }
         row_barrier();
     };
@@ -356,8 +352,7 @@ static bool rows_slabs(const Taps &t, unsigned long long *slabs)
 
 bool acg_conv_rows_ok(const Geom &g, const Taps &t)
 {
-    static const bool off = acg_debug_switch("ACG_NO_ROWS"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.nphase || g.fold_p ||
+    if (g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || g.thin || g.nphase || g.fold_p ||
         acg_act_kind(g.act) == ACG_ACT_SIGMOID) return false;   // (no sigmoid epilogue)
     if (g.stats != nullptr && (g.act != ACG_ACT_NONE || g.stats_chunk0 != 0 || (long long)g.stats_cpi * 128 != (long long)g.GH * g.GW)) return false;
     if (g.ns_part != nullptr && (g.stats != nullptr || g.ns_x == nullptr || g.ns_mask != nullptr || (g.ns_act != ACG_ACT_NONE && g.ns_act != ACG_ACT_RELU) ||
@@ -386,9 +381,8 @@ int acg_conv_rows_launch(const float *in, const void *wp, const float *bias, flo
     const int R = (int)((g.GH + cpb - 1) / cpb);
     cpb = (g.GH + R - 1) / R;
     const long long blocks = nimg * bands * cpb;
-    static const int abl = getenv("ACG_ROWS_ABL") && acg_debug_switch("ACG_ROWS_ABL") ? atoi(getenv("ACG_ROWS_ABL")) : 0;   // timing ablations
     hipLaunchKernelGGL(conv_rows_x3, dim3((unsigned)blocks), dim3(768), 0, st, in, (const __bf16 *)wp, bias, out, g, slabs,
-                       (unsigned)in_bytes, n_w_elems, R, (int)cpb, abl);
+                       (unsigned)in_bytes, n_w_elems, R, (int)cpb);
     ACG_CHECK_LAUNCH("conv_rows_x3");
     acg_note_kernel("conv_rows_x3<32,64> (%d rows per workgroup)", R);
     return ACG_OK;

@@ -259,8 +259,7 @@ __global__ __launch_bounds__(256) void wgrad_f32(const float *__restrict__ x, co
 // 3x3 layers (stride-2 downsample / ConvTranspose, networks.py:168, 178) take a 64 x 128 tile and a whole kernel row
 int acg_wgrad_taps_per_wg(int Ci, int Co, int ntaps, int thin)
 {
-    static const bool off = acg_debug_switch("ACG_NO_WGRAD_NT"); // A/B switch
-    return (!off && !thin && g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA && ntaps == 9 && Ci == 64 &&
+    return (!thin && g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA && ntaps == 9 && Ci == 64 &&
             Co >= 128 && Co % 128 == 0) ? 3 : 1;
 }
 
@@ -300,7 +299,7 @@ int acg_wgrad_launch(const float *x, const float *dy, float *part, const WGeom &
         hipLaunchKernelGGL((wgrad_f32<32, 64, 1, 2, 2, 64>), grid, block, 0, st, x, dy, part, g, t, xb, db);
     else if (bci == 64 && bco == 32)
         hipLaunchKernelGGL((wgrad_f32<64, 32, 2, 1, 2, 64>), grid, block, 0, st, x, dy, part, g, t, xb, db);
-    else if (g.thin && g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA && !acg_debug_switch("ACG_NO_THIN_X3"))
+    else if (g.thin && g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA)
         hipLaunchKernelGGL((wgrad_f32<32, 32, 1, 1, 4, 128, true>), grid, block, 0, st, x, dy, part, g, t, xb, db);
     else
         hipLaunchKernelGGL((wgrad_f32<32, 32, 1, 1, 4, 128>), grid, block, 0, st, x, dy, part, g, t, xb, db);

@@ -301,8 +301,7 @@ __global__ __launch_bounds__(512) void wgrad_x3_krowg(const float *__restrict__ 
 // 3x3 at stride 2 with 64 input channels
 bool acg_wgrad_krowg_shape_ok(int K, int stride, int pad, int reflect, int Wi, int Wo, int Cx, int Cg)
 {
-    static const bool off = acg_debug_switch("ACG_NO_KROWG"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA) return false;
+    if (g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA) return false;
     if (pad != 1 || reflect || Wo < 16 || (Wo % KP != 0 && Wo % KP < 16) || Cg % BC != 0) return false;
     if ((Wo - 1) * stride + K - 2 > Wi) return false;   // the last tap's column stays inside the padded row (a valid convolution)
     if (K == 4) return (stride == 1 && Cx % BC == 0) || (stride == 2 && (Cx % BC == 0 || Cx == 64));
@@ -327,10 +326,8 @@ int acg_wgrad_krowg_launch(const float *x, const float *dy, float *part, const W
     const long long nimg = g.Mtot / ((long long)g.Hg * g.Wg);
     const long long xbytes = nimg * g.Hin * g.Win * g.Cin * 4, dbytes = g.Mtot * g.Cg * 4;
     ACG_REQUIRE(xbytes < (1LL << 32) && dbytes < (1LL << 32), "wgrad_x3_krowg: operand exceeds the 4 GiB buffer-addressing limit");
-    static const bool pf2 = acg_debug_switch("ACG_KROWG_PF2"); // A/B switch
 #define KROWG(NT, IS, BCI) hipLaunchKernelGGL((wgrad_x3_krowg<NT, IS, BCI, (BCI == 64 ? 2 : 1)>), dim3(blocks), dim3(512), 0, st, x, dy, part, g, (unsigned)xbytes, (unsigned)dbytes)
-    if (K == 4 && g.is == 1 && pf2) hipLaunchKernelGGL((wgrad_x3_krowg<4, 1, 128, 2>), dim3(blocks), dim3(512), 0, st, x, dy, part, g, (unsigned)xbytes, (unsigned)dbytes);
-    else if (K == 4 && g.is == 1) KROWG(4, 1, 128);
+    if (K == 4 && g.is == 1) KROWG(4, 1, 128);
     else if (K == 4 && bci == 128) KROWG(4, 2, 128);
     else if (K == 4) KROWG(4, 2, 64);
     else KROWG(3, 2, 64);

@@ -183,16 +183,20 @@ __global__ __launch_bounds__(256) void wgrad_thin_patch_x3(const float *__restri
     if (bias_wave && lane < 32) g.bias_part[(long long)blockIdx.x * g.CoP + lane] = accb[0];
 }
 
-// K x K window (K <= 7), stride 1, thin tensor C4, wide tensor 32 channels; the tap list in kernel order (forward: dy = kh -
-// pad; mirrored: dy = pad - kh)
+// K x K window (2 <= K <= 7), stride 1, same-size maps, thin tensor C4 (Hthin x Wthin), wide tensor 32 channels
+bool acg_wgrad_thin_patch_shape_ok(int K, int stride, int Hthin, int Wthin, int Hwide, int Wwide, int Cthin, int Cwide)
+{
+    return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && stride == 1 && K >= 2 && K <= 7 &&
+           Hthin == Hwide && Wthin == Wwide && Cthin == 4 && Cwide == 32;
+}
+
+// ... with the tap list in kernel order (forward: dy = kh - pad; mirrored: dy = pad - kh)
 bool acg_wgrad_thin_patch_ok(const WGeom &g, const Taps &t, int *Kout, int *flip)
 {
-    static const bool off = acg_debug_switch("ACG_NO_WGRAD_THIN_PATCH"); // A/B switch
-    if (off || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA || !g.thin || g.is != 1) return false;
-    if (g.Cin != 4 || g.Cg != 32 || g.CoP != 32 || g.Hin != g.Hg || g.Win != g.Wg || g.bias_from == 2) return false;
     int K = 1;
     while (K * K < t.n) ++K;
-    if (K * K != t.n || K < 2 || K > 7 || g.CiP < 4 * K * K) return false;
+    if (!g.thin || K * K != t.n || !acg_wgrad_thin_patch_shape_ok(K, g.is, g.Hin, g.Win, g.Hg, g.Wg, g.Cin, g.Cg)) return false;
+    if (g.CoP != 32 || g.bias_from == 2 || g.CiP < 4 * K * K) return false;
     bool fwd = true, bwd = true;
     for (int i = 0; i < t.n; ++i) {
         const int kh = i / K, kw = i - kh * K;

@@ -306,10 +306,8 @@ igemm_conv_x3_pre(const char *__restrict__ in, const __bf16 *__restrict__ wp, co
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-#ifndef ACG_ABL_HIONLY   // (timing-only ablation: one MFMA per product; the lo fragments are not even read then)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], b[j], acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], bl[j], acc[i][j], 0, 0, 0);
-#endif
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
             }
     };
@@ -683,7 +681,6 @@ int acg_igemm_x3_pre_launch(const void *in, const void *wp, const float *bias, f
 {
     Geom g = g0;
     g.thin = 0;
-    if (acg_igemm_x3_pp_ok(g, t)) return acg_igemm_x3_pp_launch(in, wp, bias, out, g, t, n_w_elems, st, stats);   // the persistent form
     int kdim = 0, dxmin = 0, kstep = 1;
     ACG_REQUIRE(acg_igemm_x3_pre_ok(g, t) && pre_rowp(g, t, &kdim, &dxmin, &kstep), "igemm_conv_x3_pre: unsupported geometry");
     dim3 grid(acg_cdiv(g.Mtot, BM) * (g.ncols_pad / BN));

@@ -32,11 +32,6 @@ void acg_note_kernel(const char *fmt, ...)
     va_end(ap);
 }
 extern "C" const char *acg_last_kernel(void) { return g_kern; }
-bool acg_debug_switch(const char *name)
-{
-    static const bool enabled = getenv("ACG_DEBUG_SWITCHES") != nullptr;
-    return enabled && getenv(name) != nullptr;
-}
 extern "C" int acg_version(void) { return ACG_VERSION; }
 
 // bench.py's timing hook: an event the NEXT weight-gradient entry point of this thread records on its stream between its

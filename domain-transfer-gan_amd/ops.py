@@ -8,7 +8,6 @@ carried as torch tensors of shape (N, H, W, Cp) — or (N, Cp) for latent / MLP 
 There is no CPU path: tensors must live on a ROCm device and the library must load.
 """
 import ctypes
-import os
 
 import torch
 
@@ -58,12 +57,6 @@ def _check(*ts):
 
 
 _WS = {}
-
-
-def _debug_switch(name):
-    """A/B switches (ACGAN_NO_*: run the un-fused / previous path, for interleaved timings on one GPU box and for the
-    bit-identity tests of the fusions).  Development aids: honoured only when ACGAN_DEBUG_SWITCHES is set."""
-    return os.environ.get("ACGAN_DEBUG_SWITCHES") is not None and os.environ.get(name) is not None
 
 
 def workspace(nbytes, slot=0):
@@ -309,7 +302,7 @@ def conv_desc(N, Hi, Wi, Ci, Co, K, stride, pad, pad_mode, Cir=0, Cor=0):
 
 
 STATS_ROWS = 128
-CONV_STATS_ENABLED = not _debug_switch("ACGAN_NO_CONV_STATS")  # A/B switch
+CONV_STATS_ENABLED = True  # False: the unfused path (the tests' reference)
 
 
 class ConvStats(object):
@@ -340,7 +333,7 @@ class SkipGrad(object):
             return dskip, None
         if dy is None or dy.data_ptr() != dskip.data_ptr() or dy.shape != dskip.shape:
             raise _lib.AcgError("the un-materialised skip gradient of a residual block was altered on its way to the block's "
-                                "first convolution (tensor hook / extra consumer of the skip tensor); set ACGAN_NO_LAZY_DRES=1")
+                                "first convolution (tensor hook / extra consumer of the skip tensor); set ops.LAZY_DRES = False")
         return dskip, mask
 
 
@@ -349,7 +342,7 @@ class SkipGrad(object):
 # (accumulate=1) instead of returning a fresh tensor for autograd's AccumulateGrad to add with one more kernel per parameter
 # (564 five-microsecond launches per training step).  The Function then returns None for that parameter, so the
 # post-accumulate hooks of the data-parallel exchange (dist.hook_params) are fired by hand.
-DIRECT_GRAD = not _debug_switch("ACGAN_NO_DIRECT_GRAD")   # A/B switch
+DIRECT_GRAD = True   # False: the unfused path (the tests' reference)
 
 
 def _direct_grad(*params):
@@ -376,7 +369,7 @@ def _grads_done(*params):
                 h(p)
 
 
-LAZY_DRES = not _debug_switch("ACGAN_NO_LAZY_DRES")   # A/B switch (SkipGrad)
+LAZY_DRES = True   # False: the unfused path (the tests' reference; SkipGrad)
 
 
 class NormSums(object):
@@ -403,7 +396,7 @@ class NormSums(object):
         return d
 
 
-NORM_SUMS = not _debug_switch("ACGAN_NO_NORM_SUMS")   # A/B switch
+NORM_SUMS = True   # False: the unfused path (the tests' reference)
 NORM_SUMS_USED = 0   # norm backward passes that took their sums from a data-gradient epilogue (tests read it)
 # Which fused paths the step actually took (bench.py prints them per step as `fused_paths`, so a fusion that a torch-side
 # change — a hook, a clone, a shape — silently turned off shows in the bench line): launches per key since the last clear()
@@ -426,15 +419,15 @@ class ReluLink(object):
         self.mask = None   # sign bitmask of the ReLU output where the producing convolution stored one (pre-split trunk)
 
 
-RELU_LINK = not _debug_switch("ACGAN_NO_RELU_LINK")   # A/B switch
-RELU_MASK = not _debug_switch("ACGAN_NO_RELU_MASK")   # A/B switch: the link carries a sign bitmask instead of the activation
+RELU_LINK = True   # False: the unfused path (the tests' reference)
+RELU_MASK = True   # False: the unfused path (the tests' reference); True: the link carries a sign bitmask instead of the activation
 
 
 # Pre-split ("S16") activation storage of the residual trunk (include/acgan_hip.h, acg_s16_encode): an S16 tensor is carried
 # as an fp32-typed torch tensor of the same shape whose BYTES are (bf16 hi, bf16 lo) groups, tagged `_acg_s16`; only the
 # Functions below read or write it, and every one of them knows from its forward-time plan which of its tensors are S16
 # (autograd only ever hands such a gradient from the one Function that wrote it to the one that reads it).
-S16_ENABLED = not _debug_switch("ACGAN_NO_S16")   # A/B switch
+S16_ENABLED = True   # False: the unfused path (the tests' reference)
 
 
 def is_s16(t):
@@ -776,7 +769,7 @@ class ConvTranspose2dFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # normalisation (+ fused activation / residual)
 # ----------------------------------------------------------------------------------------------
-NORM_SIGN_MASK = not _debug_switch("ACGAN_NO_NORM_MASK")   # A/B switch
+NORM_SIGN_MASK = True   # False: the unfused path (the tests' reference)
 
 
 class NormAct(torch.autograd.Function):
@@ -1070,7 +1063,7 @@ class LinearFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-COND_BANK = not _debug_switch("ACGAN_NO_COND_BANK")   # A/B switch
+COND_BANK = True   # False: the unfused path (the tests' reference)
 
 
 class CondBankFn(torch.autograd.Function):
@@ -1139,7 +1132,7 @@ class CondBankFn(torch.autograd.Function):
         return (dz, None) + tuple(pg)
 
 
-LATENT_MLP = not _debug_switch("ACGAN_NO_LATENT_MLP")   # A/B switch
+LATENT_MLP = True   # False: the unfused path (the tests' reference)
 
 
 def latent_mlp_supported(N, I, H):

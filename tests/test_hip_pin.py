@@ -158,7 +158,7 @@ class _MaskTap(object):
 def _hip_relu_patterns(kind, net, xt, zt):
     """the activation patterns of the five ReLU layers as the HIP forward produced them: the net run piece by piece (stem +
     norm + ReLU, then per block its inner conv (+ CondIN) + ReLU and the block itself), outputs > 0.  Pieces run alone take
-    the same kernels' arithmetic (tools/s16_check.py, tools/pp_check.py: fused and unfused outputs agree bit for bit)."""
+    the same kernels' arithmetic (tools/s16_check.py, DESIGN_LOG.md R5.1: fused and unfused outputs agree bit for bit)."""
     from dtgan_amd import modules as M
     from hip_util import n
     mods = list(net._modules.values())
@@ -299,7 +299,7 @@ def test_trunk_at_bench_geometry_matches_the_oracle(kind, prec):
         assert "acg_conv2d_fwd_s16" in ents and "acg_conv2d_bwd_weight_s16" in ents and "acg_conv2d_bwd_data_s16_sums" in ents, ents
         if kind == "plain":
             assert "acg_conv2d_fwd_s16_mask" in ents and "acg_conv2d_bwd_data_s16_mask" in ents, ents
-        # (igemm_conv_x3_pre; its opt-in persistent form igemm_conv_x3_pp has its own test, tests/test_hip_parked.py)
+        # (igemm_conv_x3_pre; its persistent form igemm_conv_x3_pp was measured slower and removed, DESIGN_LOG.md R5.1)
         assert any(k.startswith("igemm_conv_x3_pre<REFLECT=1") for k in kerns), kerns
         assert any("SUMS" in k for k in kerns), kerns
         assert "wgrad_x3_krow_s16" in kerns, kerns

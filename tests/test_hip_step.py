@@ -77,7 +77,7 @@ REC_TOL = {("f32", "init"): (2e-4, 2e-2), ("f32", "rich"): (3e-4, 4e-2),
 # ReLU-gated per-sample shifts), all other tensors < 1e-2.  On the deliberately ill-conditioned 'rich' flavour some bf16x3
 # digests are not a pin: switching the InstanceNorm statistics between two equally accurate fp32 methods (both 1e-7 from fp64,
 # test_conv_epilogue_statistics_equal_the_statistics_pass) moves the forward by 3e-5 and the CondInstanceNorm shift / scale
-# convolution gradients by up to 17 % there (tools/debug_stats_ab.py).  Those tensors get a bound of their own in bf16x3 on
+# convolution gradients by up to 17 % there (measured with the statistics A/B switches of DESIGN_LOG.md §5).  Those tensors get a bound of their own in bf16x3 on
 # 'rich' (RICH_X3_BOUND; the f32 mode pins them at DIGEST_TOL on the same fixtures); every other tensor is held to the bf16x3
 # tolerance.
 DIGEST_TOL = {"f32": (3e-3, 5e-3), "bf16x3": (2e-2, 2e-2)}

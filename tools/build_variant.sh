@@ -10,7 +10,7 @@ SRC=domain-transfer-gan_amd/csrc
 OBJ=build/obj_$NAME
 mkdir -p $OBJ
 SRCS=$(sed -n 's/^SRCS *:= *//p' $SRC/Makefile)
-DEPS="$SRC/common.h $SRC/conv_internal.h $SRC/conv_wgrad_tr_s16.inc include/acgan_hip.h"
+DEPS="$SRC/common.h $SRC/conv_internal.h include/acgan_hip.h"
 if [ "$(cat $OBJ/.flags 2>/dev/null)" != "$*" ]; then rm -f $OBJ/*.o; echo "$*" > $OBJ/.flags; fi
 pids=()
 for f in $SRCS; do

@@ -97,7 +97,7 @@ def run(N, H, W, C, time_it, iters):
 
     # whole-row tiles (W % 128 == 0): the pre-split data gradient runs on the un-padded grid with summed weight slabs for the
     # mirrored rows and a separate column term — the same sums in another order, no longer bit-identical
-    unpad = W % 128 == 0 and H % 32 == 0 and H >= 64 and not os.environ.get("ACG_NO_UNPAD")
+    unpad = W % 128 == 0 and H % 32 == 0 and H >= 64
     dg_ref(); dg_s16()
     ok &= check("dgrad (fp32 out)", dx1, dx0, exact=not unpad, tol=2e-5)
     mask = None
