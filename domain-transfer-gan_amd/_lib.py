@@ -15,6 +15,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 IMPL_MFMA, IMPL_DIRECT = 0, 1
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
+NLL_LAPLACE, NLL_GAUSSIAN = 0, 1
 
 c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
@@ -144,6 +145,11 @@ SIGNATURES = {
     "acg_l1_bwd": (c_int, [_P, _P, c_size_t, c_int, c_int, _P, _P, _P, _P]),
     "acg_mean_fwd": (c_int, [_P, c_size_t, c_int, c_int, _P, _P, c_size_t, _P]),
     "acg_sumsq": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P]),
+    "acg_pixel_nll_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "acg_pixel_nll_fwd": (c_int, [c_int, _P, _P, _P, c_int, c_size_t, c_int, c_int, _P, _P, c_size_t, _P]),
+    "acg_pixel_nll_bwd": (c_int, [c_int, _P, _P, _P, c_int, c_size_t, c_int, c_int, _P, _P, _P, _P]),
+    "acg_latent_bound_step": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
+                                      _P]),
     "acg_comm_unique_id": (c_int, [_P]),
     "acg_comm_init": (c_int, [ctypes.POINTER(c_void_p), _P, c_int, c_int]),
     "acg_comm_allreduce_mean": (c_int, [_P, _P, c_size_t, _P]),

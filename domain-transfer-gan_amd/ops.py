@@ -1324,6 +1324,71 @@ class L1(torch.autograd.Function):
         return da, db, None
 
 
+def l1_into(a, b, C, out):
+    """out[()] = F.l1_loss(a, b) over the C valid channels, written into a given device scalar (no grad)."""
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    _check(a, b, out)
+    Cp = a.shape[-1]
+    ws, nb = _red_ws()
+    _lib.call("acg_l1_fwd", _ptr(a), _ptr(b), a.numel() // Cp, C, Cp, _ptr(out), _ptr(ws), nb, _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# the variational bound of the evaluator (evaluate.py, test.py)
+# ----------------------------------------------------------------------------------------------
+NLL_KINDS = {"laplace": _lib.NLL_LAPLACE, "gaussian": _lib.NLL_GAUSSIAN}
+
+
+class PixelNLL(torch.autograd.Function):
+    """-sum over pixels and the C valid channels of log_prob_laplace / log_prob_gaussian(x, mu, logvar) per sample
+    (model.py:24-34, summed as evaluate.py:94-95 does): x, mu (N, H, W, Cp) image tensors, logvar ONE (1, H, W, Cp) plane
+    broadcast over the batch -> (N,).  Gradients reach mu and logvar; x is data."""
+
+    @staticmethod
+    def forward(ctx, x, mu, logvar, C, kind="laplace"):
+        x, mu, logvar = x.contiguous(), mu.contiguous(), logvar.contiguous()
+        _check(x, mu, logvar)
+        N, Cp = mu.shape[0], mu.shape[-1]
+        npix = mu.numel() // (N * Cp)
+        if x.shape != mu.shape or logvar.numel() != npix * Cp or logvar.shape[-1] != Cp:
+            raise _lib.AcgError("PixelNLL: x %s, mu %s and the logvar plane %s disagree" % (tuple(x.shape), tuple(mu.shape),
+                                                                                       tuple(logvar.shape)))
+        out = torch.empty((N,), device=mu.device, dtype=torch.float32)
+        nb = _lib.query("acg_pixel_nll_workspace_bytes", N, npix)
+        ws = workspace(nb, slot=1)
+        _lib.call("acg_pixel_nll_fwd", NLL_KINDS[kind], _ptr(x), _ptr(mu), _ptr(logvar), N, npix, C, Cp, _ptr(out), _ptr(ws), nb,
+                  _stream())
+        ctx.cfg = (NLL_KINDS[kind], N, npix, C, Cp)
+        ctx.save_for_backward(x, mu, logvar)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mu, logvar = ctx.saved_tensors
+        kind, N, npix, C, Cp = ctx.cfg
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("PixelNLL: no gradient w.r.t. the data x")
+        g = g.contiguous()
+        dmu = torch.empty_like(mu) if ctx.needs_input_grad[1] else None
+        dlv = torch.empty_like(logvar) if ctx.needs_input_grad[2] else None
+        if dmu is not None or dlv is not None:
+            _lib.call("acg_pixel_nll_bwd", kind, _ptr(x), _ptr(mu), _ptr(logvar), N, npix, C, Cp, _ptr(g), _ptr(dmu), _ptr(dlv),
+                      _stream())
+        return None, dmu, dlv, None, None
+
+
+def latent_bound_step(mu, logvar, sq_mu, sq_logvar, eps, dz, nll, npx, lr, trace_row=None, eps_next=None, z_next=None,
+                      alpha=0.99, rms_eps=1e-8):
+    """acg_latent_bound_step: one iterate's latent tail of the bound on (N, L) tensors — KLD, the trace row (mean bound,
+    mean KLD, bits per pixel), the gradient of the mean bound through the clamp of the reparametrisation, torch's RMSprop
+    on (mu, logvar) in place and the next code z_next from eps_next.  dz None: only z_next from the current parameters."""
+    _check(mu, logvar, sq_mu, sq_logvar, eps, dz, nll, trace_row, eps_next, z_next)
+    N, L = mu.shape
+    _lib.call("acg_latent_bound_step", N, L, int(npx), _ptr(mu), _ptr(logvar), _ptr(sq_mu), _ptr(sq_logvar), _ptr(eps), _ptr(dz),
+              _ptr(nll), float(lr), float(alpha), float(rms_eps), _ptr(trace_row), _ptr(eps_next), _ptr(z_next), _stream())
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

@@ -126,7 +126,9 @@ class TrainOptions(object):
 
 
 class TestOptions(object):
-    """options.py:134-143"""
+    """options.py:134-143 (the options of dtgan_amd.test).  Additions: the metric `mvgauss` (the reference's
+    compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
+    500) and --gpu_ids (test.py:214 hard-codes [0])."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -134,7 +136,9 @@ class TestOptions(object):
         self.parser.add_argument('--res_dir', type=str, default='test_res')
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
-        self.parser.add_argument('--metric', required=True, type=str, choices=['bpp', 'mse', 'visual', 'noise_sens'])
+        self.parser.add_argument('--metric', required=True, type=str, choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss'])
+        self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
+        self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
 
     def parse(self, argv=None):
         return self.parser.parse_args(argv)

@@ -368,6 +368,38 @@ int acg_l1_bwd(const float *a, const float *b, size_t npix, int C, int Cp, const
 int acg_mean_fwd(const float *x, size_t npix, int C, int Cp, float *out, void *workspace, size_t ws_bytes,
                  void *stream);
 
+/* ---- the variational bound of the offline evaluator (evaluate.py:93-122 — also run by train.py every epoch —,
+ *      test.py:137-175 train_logvar / the MVGauss baseline, test.py:111-121 eval_bpp_MVGauss_B) ----
+ * x, mu: (N, npix, Cp) NHWC image tensors (C4 for the networks' images), C channels valid, Cp a multiple of 4, 16-byte
+ * aligned; logvar: ONE (npix, Cp) plane broadcast over the batch.
+ * acg_pixel_nll_fwd: out[n] = -sum over pixels and valid channels of log p(x | mu, logvar) — ACG_NLL_LAPLACE
+ * 0.5 lv + |x - mu| / exp(0.5 lv) + log 2 (log_prob_laplace, model.py:24-28), ACG_NLL_GAUSSIAN
+ * 0.5 lv + (x - mu)^2 / (2 exp(lv)) + 0.5 log 2 pi (log_prob_gaussian, model.py:31-34).  Per-block partials in the workspace
+ * (acg_pixel_nll_workspace_bytes), folded in a fixed order: deterministic, no atomics.
+ * acg_pixel_nll_bwd: gradients of sum_n g[n] out[n] (g: N device floats).  dmu (N, npix, Cp) per element, one launch as wide
+ * as the tensor; dlogvar (npix, Cp) summed over the batch by one thread per pixel walking n in order, a launch of its own only
+ * when asked for.  Either may be NULL; padded channels get exactly 0;
+ * the Laplace gradient takes sign(0) = 0 (torch's abs backward). */
+typedef enum { ACG_NLL_LAPLACE = 0, ACG_NLL_GAUSSIAN = 1 } acg_nll_kind;
+size_t acg_pixel_nll_workspace_bytes(int N, size_t npix);
+int acg_pixel_nll_fwd(int kind, const float *x, const float *mu, const float *logvar, int N, size_t npix, int C, int Cp,
+                      float *out, void *workspace, size_t ws_bytes, void *stream);
+int acg_pixel_nll_bwd(int kind, const float *x, const float *mu, const float *logvar, int N, size_t npix, int C, int Cp,
+                      const float *g, float *dmu, float *dlogvar, void *stream);
+/* One iterate's latent tail of the bound (evaluate.py:93-122), one workgroup, on (N, L) row-major tensors:
+ *  1-2. kld[n] of the current (mu, logvar) (kld_std_guss, model.py:45-53); trace_row[0..2] = mean over n of
+ *       nll[n] + kld[n] + npx log 127.5, mean kld, and that bound / (npx log 2) (bits per pixel).  nll: acg_pixel_nll_fwd's out.
+ *  3. the gradients of that mean bound w.r.t. mu and logvar: dz is d mean_n(nll[n]) / dz for z = clamp(eps exp(0.5 logvar) + mu,
+ *     -4, 4) (gauss_reparametrize, model.py:15-22; eps: the draw z was made with), passed where -4 <= pre-clamp <= 4 inclusive
+ *     (torch's clamp backward), plus the KLD's term / N.
+ *  4. torch.optim.RMSprop (no momentum, not centred) on mu and logvar in place; sq_mu / sq_logvar: its square averages, held by
+ *     the caller (zeros before the first step).
+ *  5. z_next = clamp(eps_next exp(0.5 logvar) + mu, -4, 4) from the updated parameters (eps_next and z_next both NULL: none).
+ * dz NULL: steps 1-4 are skipped (the first iterate's code from the initial parameters).  trace_row may be NULL. */
+int acg_latent_bound_step(int N, int L, int npx, float *mu, float *logvar, float *sq_mu, float *sq_logvar, const float *eps,
+                          const float *dz, const float *nll, float lr, float alpha, float rms_eps, float *trace_row,
+                          const float *eps_next, float *z_next, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);

@@ -504,16 +504,21 @@ def make_init_fixture(seed=1234):
     save("init_seeded", arr, kind="init", seed=seed)
 
 
-def eval_case(name, opt_kw, N, S, steps=3, seed=0, flavour="rich"):
+def eval_case(name, opt_kw, N, S, steps=3, seed=0, flavour="rich", aug=True, compute_l1=False, digests=False):
     """Evaluation numbers (evaluate.py:10-19 eval_mse_A, evaluate.py:39-148 variational_ubo).  evaluate.py itself is
     Python 2 and hard-codes .cuda(), so it cannot be imported here; the harness walks through its algorithm with the
     reference's OWN model (predict_A / predict_B / predict_enc_params) and model.py helpers (gauss_reparametrize,
     log_prob_laplace, kld_std_guss) on the CPU, with the two random draws — the dequantisation noise and the
-    reparametrisation noise of every iterate — fixed and recorded."""
+    reparametrisation noise of every iterate — fixed and recorded.  aug=False: StochCycleGAN (no encoder: mu starts at 0);
+    compute_l1: the L1 column of evaluate.py:75-80, 126-131 (B against its reconstruction from mu, or the iterate's own
+    prediction under --stoch_enc) is recorded as a fourth trace column."""
     import math
+    if ONLY and name not in ONLY:
+        return
     opt = ref_opt(**opt_kw)
-    m = rmodel.AugmentedCycleGAN(opt, testing=True)
-    for n in ["netG_A_B", "netG_B_A", "netD_A", "netD_B", "netE_B", "netD_z_B"]:
+    m = (rmodel.AugmentedCycleGAN if aug else rmodel.StochCycleGAN)(opt, testing=True)
+    nets = ["netG_A_B", "netG_B_A", "netD_A", "netD_B"] + (["netE_B", "netD_z_B"] if aug else [])
+    for n in nets:
         load_recipe(getattr(m, n), n, seed, flavour)
     A, B, _ = recipe.inputs(seed + 50, N, opt.input_nc, opt.output_nc, S, opt.nlatent)
     rs = np.random.RandomState(seed + 51)
@@ -530,11 +535,13 @@ def eval_case(name, opt_kw, N, S, steps=3, seed=0, flavour="rich"):
     torch.Tensor.normal_ = normal_
     try:
         npx = opt.output_nc * S * S                                                     # 64*64*3 in evaluate.py:104
-        params = m.predict_enc_params(tA, tB)                                           # evaluate.py:56-62
-        mu = params[0].detach().clone().requires_grad_(True)
+        mu = torch.zeros(N, opt.nlatent).requires_grad_(True)                          # evaluate.py:48-52
         logvar = torch.full((N, opt.nlatent), math.log(0.01)).requires_grad_(True)
-        if len(params) == 2:
-            logvar = params[1].detach().clone().requires_grad_(True)
+        if hasattr(m, 'netE_B'):
+            params = m.predict_enc_params(tA, tB)                                       # evaluate.py:56-62
+            mu = params[0].detach().clone().requires_grad_(True)
+            if len(params) == 2:
+                logvar = params[1].detach().clone().requires_grad_(True)
         logvar_B = torch.full((1, opt.output_nc, S, S), math.log(0.01))
         it = torch.optim.RMSprop([mu, logvar], lr=1e-2)                                 # evaluate.py:65
         rB = tB + torch.from_numpy(dequant)
@@ -547,6 +554,10 @@ def eval_case(name, opt_kw, N, S, steps=3, seed=0, flavour="rich"):
             kld = rmodel.kld_std_guss(mu, logvar)
             ubo = (-log_prob + kld) + npx * math.log(127.5)
             trace.append([float(ubo.mean(0)), float(kld.mean(0)), float(ubo.mean(0)) / (npx * math.log(2.))])
+            if compute_l1:                                                              # evaluate.py:75-80, 126-131
+                with torch.no_grad():
+                    rec_B = fake_B if opt.stoch_enc else m.predict_B(tA, mu.detach().view(N, opt.nlatent, 1, 1))
+                    trace[-1].append(float(torch.nn.functional.l1_loss(rB, rec_B)))
             it.zero_grad()
             ubo.mean(0).backward()
             it.step()
@@ -555,9 +566,167 @@ def eval_case(name, opt_kw, N, S, steps=3, seed=0, flavour="rich"):
             fake_B = m.predict_B(tA, z_B)
     finally:
         torch.Tensor.normal_ = orig_normal
-    save(name, dict(real_A=A, real_B=B, dequant=dequant, eps=eps, mse_A=np.array(mse_A), trace=np.array(trace, np.float64),
-                    mu_final=mu.detach().numpy().copy(), logvar_final=logvar.detach().numpy().copy()),
-         kind="eval", seed=seed, flavour=flavour, N=N, S=S, steps=steps, opt=dict(opt_kw))
+    arrays = dict(real_A=A, real_B=B, dequant=dequant, eps=eps, mse_A=np.array(mse_A), trace=np.array(trace, np.float64),
+                  mu_final=mu.detach().numpy().copy(), logvar_final=logvar.detach().numpy().copy())
+    if digests:
+        arrays.update({"digest/" + k: digest(arrays[k]) for k in ("trace", "mu_final", "logvar_final")})
+    save(name, arrays,
+         kind="eval", seed=seed, flavour=flavour, N=N, S=S, steps=steps, opt=dict(opt_kw), aug=aug, compute_l1=compute_l1)
+
+
+def make_eval_goldens():
+    """the offline evaluator's variants of the bound (dtgan_amd.test / evaluate.variational_ubo): an encoder that also gives
+    logvar (--stoch_enc), a model without an encoder (StochCycleGAN: mu starts at 0) and the L1 column of compute_l1"""
+    small = dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4)
+    eval_case("eval_aug_small_s64_stoch_enc", dict(small, stoch_enc=True), N=4, S=64, steps=4, digests=True)
+    eval_case("eval_stoch_small_s64", small, N=3, S=64, steps=4, aug=False, digests=True)
+    eval_case("eval_aug_small_s64_l1", small, N=4, S=64, steps=3, compute_l1=True, digests=True)
+    trainlogvar_case("trainlogvar_aug_small_s64", small, N=3, S=64, batches=2)
+    mvgauss_case("mvgauss_s64", N=4, S=64, batches=3)
+    noisesens_case("noisesens_aug_small_s64", small, N=3, S=64)
+
+
+class FixedNormal(object):
+    """While active, torch.Tensor.normal_(mean, std) on a tensor of shape `shape` writes mean + std * draws[k] for its k-th such
+    call (draws: standard normals) instead of drawing from torch's generator — torch is patched, never the reference's source.
+    Other shapes draw as usual."""
+
+    def __init__(self, shape, draws):
+        self.shape, self.draws, self.k = tuple(shape), draws, 0
+
+    def __enter__(self):
+        self.orig = torch.Tensor.normal_
+        me = self
+
+        def normal_(t, mean=0., std=1., *a, **kw):
+            if tuple(t.shape) != me.shape:
+                return me.orig(t, mean, std, *a, **kw)
+            t.copy_(torch.from_numpy(me.draws[me.k]).to(t.dtype) * std + mean)
+            me.k += 1
+            return t
+        torch.Tensor.normal_ = normal_
+        return self
+
+    def __exit__(self, *a):
+        torch.Tensor.normal_ = self.orig
+
+
+def _ref_model(opt_kw, seed, flavour, aug=True):
+    opt = ref_opt(**opt_kw)
+    m = (rmodel.AugmentedCycleGAN if aug else rmodel.StochCycleGAN)(opt, testing=True)
+    for n in ["netG_A_B", "netG_B_A", "netD_A", "netD_B"] + (["netE_B", "netD_z_B"] if aug else []):
+        load_recipe(getattr(m, n), n, seed, flavour)
+    return opt, m
+
+
+def driver_draws(kind, seed, N, S, nl=4, batches=1):
+    """The inputs and random draws of the offline evaluator's fixtures, regenerated from their seeds on every box (the
+    fixtures hold only the outputs and digests of these): B images, dequantisation noise, reparametrisation / perturbation
+    normals.  Mirrored by tests/test_hip_eval_goldens.py."""
+    _, B, _ = recipe.inputs(seed + 60, N * batches, 3, 3, S, nl)
+    rs = np.random.RandomState(seed + 61)
+    out = dict(B=B)
+    if kind in ("trainlogvar", "mvgauss"):
+        out["dequant"] = rs.uniform(0, 1. / 127.5, (batches, N, 3, S, S)).astype(np.float32)
+    if kind == "trainlogvar":
+        out["eps"] = rs.normal(0, 1, (batches, N, 1, nl)).astype(np.float32)
+    if kind == "mvgauss":
+        _, out["B_test"], _ = recipe.inputs(seed + 62, N * batches, 3, 3, S, nl)
+    if kind == "noisesens":
+        out["noise"] = rs.normal(0, 1, (8, N, 3, S, S)).astype(np.float32)
+    return out
+
+
+def trainlogvar_case(name, opt_kw, N, S, batches=2, seed=0, flavour="rich"):
+    """test.py:156-196 train_logvar (Python 2, imports a missing module: walked here with the reference's model and model.py
+    helpers, as eval_case does): RMSprop on logvar_B, one update per batch of B -> A -> B through the encoder's code, with
+    the dequantisation noise and the reparametrisation draw of every batch fixed.  Records (ubo, kld, bpp) per batch and the
+    final logvar_B."""
+    import math
+    if ONLY and name not in ONLY:
+        return
+    opt, m = _ref_model(opt_kw, seed, flavour)
+    nl = opt.nlatent
+    d = driver_draws("trainlogvar", seed, N, S, nl, batches)
+    npx = 3 * S * S
+    logvar_B = torch.full((1, 3, S, S), math.log(0.01)).requires_grad_(True)
+    it = torch.optim.RMSprop([logvar_B], lr=1e-2)
+    trace = []
+    for k in range(batches):
+        real_B = torch.from_numpy(d["B"][k * N:(k + 1) * N]) + torch.from_numpy(d["dequant"][k])
+        enc_mu = torch.zeros(N, nl)
+        enc_logvar = torch.full((N, nl), math.log(0.01))
+        fake_A = m.predict_A(real_B)
+        params = m.predict_enc_params(fake_A, real_B)
+        enc_mu = params[0].detach()
+        if len(params) == 2:
+            enc_logvar = params[1].detach()
+        with FixedNormal((N, 1, nl), d["eps"][k:k + 1]):
+            z_B = rmodel.gauss_reparametrize(enc_mu, enc_logvar)
+        fake_B = m.predict_B(fake_A, z_B)
+        log_prob = rmodel.log_prob_laplace(real_B, fake_B, logvar_B).view(N, -1).sum(1)
+        kld = rmodel.kld_std_guss(enc_mu, enc_logvar)
+        ubo = (-log_prob + kld) + npx * math.log(127.5)
+        trace.append([float(ubo.mean(0)), float(kld.mean(0)), float(ubo.mean(0)) / (npx * math.log(2.))])
+        it.zero_grad()
+        ubo.mean(0).backward()
+        it.step()
+    lv = logvar_B.detach().numpy().copy()
+    save(name, {"trace": np.array(trace, np.float64), "logvar_B": lv, "digest/trace": digest(trace), "digest/logvar_B": digest(lv),
+                "digest/dequant": digest(d["dequant"]), "digest/eps": digest(d["eps"])},
+         kind="trainlogvar", seed=seed, flavour=flavour, N=N, S=S, batches=batches, opt=dict(opt_kw))
+
+
+def mvgauss_case(name, N, S, batches=3, seed=0):
+    """test.py:109-141 train_MVGauss_B + eval_bpp_MVGauss_B (walked with the reference's log_prob_gaussian): the per-pixel
+    mean of the training batches' means, the mean of their mean squared deviations, then the bpp of every dequantised test
+    batch under N(mean, var + 1e-5) and the reference's mean over the batch means."""
+    import math
+    if ONLY and name not in ONLY:
+        return
+    d = driver_draws("mvgauss", seed, N, S, 4, batches)
+    train = [torch.from_numpy(d["B"][k * N:(k + 1) * N]) for k in range(batches)]
+    b_mean = 0
+    for real_B in train:
+        b_mean = b_mean + real_B.mean(0, keepdim=True)
+    b_mean = b_mean / batches
+    b_var = 0
+    for real_B in train:
+        b_var = b_var + ((real_B - b_mean) ** 2).mean(0, keepdim=True)
+    b_var = b_var / batches
+    logvar = torch.log(b_var + 1e-5)
+    npx = 3 * S * S
+    bpp = []
+    for k in range(batches):
+        real_B = torch.from_numpy(d["B_test"][k * N:(k + 1) * N]) + torch.from_numpy(d["dequant"][k])
+        nll = -rmodel.log_prob_gaussian(real_B, b_mean, logvar)
+        nll = nll.view(real_B.size(0), -1).sum(1) + npx * math.log(127.5)
+        bpp.append(float(nll.mean(0)) / (npx * math.log(2)))
+    mean, var = b_mean.numpy().copy(), b_var.numpy().copy()
+    save(name, {"mean": mean, "var": var, "bpp_batches": np.array(bpp), "bpp": np.array(np.mean(bpp)),
+                "digest/mean": digest(mean), "digest/var": digest(var), "digest/dequant": digest(d["dequant"])},
+         kind="mvgauss", seed=seed, N=N, S=S, batches=batches)
+
+
+def noisesens_case(name, opt_kw, N, S, seed=0, flavour="rich"):
+    """test.py:97-107 sensitivity_to_edge_noise through the reference model's own generate_noisy_cycle (model.py:626-645),
+    with the perturbation of fake_A fixed: the k-th normal_(0, std / 127.5) on fake_A's shape becomes std / 127.5 * noise[k].
+    Records mean |B - rec_B| per sample at the eight noise levels (the reference divides by 64*64*3 = C*H*W here)."""
+    if ONLY and name not in ONLY:
+        return
+    opt, m = _ref_model(opt_kw, seed, flavour)
+    d = driver_draws("noisesens", seed, N, S, opt.nlatent)
+    real_B = torch.from_numpy(d["B"])
+    res = []
+    with FixedNormal((N, 3, S, S), d["noise"]) as fx, torch.no_grad():
+        for std in (0, 0.1, 0.2, 0.5, 1, 2, 3, 5):
+            rec_B = m.generate_noisy_cycle(real_B, std)
+            s = torch.abs(real_B - rec_B).sum(3).sum(2).sum(1) / (3 * S * S)
+            res.append(s.numpy().tolist())
+        assert fx.k == 8, fx.k
+    res = np.array(res)
+    save(name, {"noise_sens": res, "digest/noise_sens": digest(res), "digest/noise": digest(d["noise"])},
+         kind="noisesens", seed=seed, flavour=flavour, N=N, S=S, opt=dict(opt_kw))
 
 
 def _py3_source(path):
@@ -624,9 +793,12 @@ def data_case(name="data_pipeline"):
     save(name, arr, kind="data")
 
 
+if __name__ == "__main__" and ONLY:
+    make_eval_goldens()
 if __name__ == "__main__" and not ONLY:
     make_key_fixture()
     make_init_fixture()
     eval_case("eval_aug_small_s64", dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4), N=4, S=64)
+    make_eval_goldens()
     data_case()
     sup_case("sup_aug_small_s64", dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4), N=4, S=64)
