@@ -112,7 +112,7 @@ class DevicePrefetcher(object):
         for v in out.values():
             if torch.is_tensor(v):
                 v.record_stream(torch.cuda.current_stream())
-        self.stream.synchronize()       # the pinned buffers are about to be refilled
+        ev.synchronize()                # the pinned buffers are about to be refilled: their copy (all this stream holds) is done
         self._stage()
         return out
 

@@ -215,9 +215,13 @@ class DeferredStep(object):
     def __init__(self, pending, host, event):
         self._pending, self._host, self._event, self._out = pending, host, event, None
 
+    def wait(self):
+        """block the host until the step (and its scalars' copy) has completed on the device"""
+        self._event.synchronize()
+
     def result(self):
         if self._out is None:
-            self._event.synchronize()
+            self.wait()
             self._out = self._pending.finish(OrderedDict(zip(self._pending.names, self._host.tolist())))
         return self._out
 
@@ -227,12 +231,17 @@ class StepGraph(object):
     library's ctypes launches go to the capturing stream like torch's own kernels).  What a replay cannot take from the
     host is kept on the device: the inputs (static buffers copied into), the Adam step number (FusedAdam.t_dev, read by
     acg_clip_adam_multi) and the reported scalars (one .tolist() after the replay).  The learning rates are launch
-    arguments: a change re-captures."""
+    arguments: a change re-captures.  `step` names the model's step method: `_train_instance` (default) or
+    `_supervised_train_instance` (the paired step, a second instance with its own warm-up, key, inputs and scratch).  Every
+    instance checks the packed weights it was captured with before each of its replays."""
     WARMUP = 2
 
-    def __init__(self, model):
+    def __init__(self, model, step="_train_instance"):
         self.model, self.graph, self.key, self.calls, self.ws, self.packed = model, None, None, 0, None, None
+        self.step = step
         self.defer_scalars = False
+        self.captures = 0      # completed captures (a re-capture after a learning-rate change counts again)
+        self.stepped = None    # the optimisers whose Adam step the captured step takes (the paired step leaves D_A alone)
 
     def _key(self, a, b, z):
         m = self.model
@@ -276,8 +285,9 @@ class StepGraph(object):
         gc.disable()
         try:
             with torch.cuda.graph(graph), _in_train_step():
-                pending = m._train_instance(*inputs)
+                pending = getattr(m, self.step)(*inputs)
             graph_ws = ops._WS
+            stepped = [opt for opt, t in zip(opts, t_before) if opt.t != t]
         finally:
             if gc_was_on:
                 gc.enable()
@@ -288,7 +298,9 @@ class StepGraph(object):
                 opt.dev_step = False
         # only a capture that completed is kept: a failed one leaves no half-built graph behind for the next call to replay
         self.graph, self.key, self.inputs, self.pending, self.ws = graph, key, inputs, pending, graph_ws
+        self.stepped = stepped
         self.packed = [packed_of(net) for net in m._nets()]     # (strong references: the graph holds their device pointers)
+        self.captures += 1
 
     def __call__(self, real_A, real_B, prior_z_B):
         m = self.model
@@ -296,8 +308,7 @@ class StepGraph(object):
         self.calls += 1
         if self.calls <= self.WARMUP:                 # lazily built state (packed weights, workspaces) settles eagerly
             with _in_train_step():
-                return m._train_instance(real_A, real_B, prior_z_B)
-        opts = list(m._optimizers().values())
+                return getattr(m, self.step)(real_A, real_B, prior_z_B)
         if self.graph is not None and key == self.key:
             # the layers must still hold the packed weights the graph was captured with (a checkpoint load, a precision switch or
             # mark_dirty() in between replaces them): otherwise capture again
@@ -305,14 +316,16 @@ class StepGraph(object):
             if any(a is not b for pa, pb in zip(now, self.packed) for a, b in zip(pa, pb)):
                 self.graph = None
         if self.graph is None or key != self.key:
+            if self.graph is not None and self.defer_scalars:
+                torch.cuda.current_stream().synchronize()   # earlier replays of the graph dropped here may still be running
             self.graph = self.key = None
             self._capture(key, real_A, real_B, prior_z_B)
         for dst, src in zip(self.inputs, (real_A, real_B, prior_z_B)):
             dst.copy_(src)
-        for opt in opts:
+        for opt in self.stepped:
             opt.t_dev.fill_(opt.t)
         self.graph.replay()
-        for opt in opts:
+        for opt in self.stepped:
             opt.t += 1
         deferred = None
         if self.defer_scalars:   # the scalars leave for pinned memory behind the replay; nobody waits here
@@ -380,6 +393,7 @@ class _Base(object):
 
     _capturing = False
     _step_graph = None
+    _sup_step_graph = None
 
     def _report(self, vals, finish):
         """finish(vals) builds what the step returns from the host-side scalars; deferred while a graph is being captured"""
@@ -395,10 +409,15 @@ class _Base(object):
         bound either way.  The first calls run eagerly (warm-up), the tensors in the returned `visuals` are overwritten by the
         next call, and the data-parallel exchange keeps the eager path.  defer_scalars: a replayed step returns a DeferredStep
         (`.result()` gives the usual tuple) instead of waiting for its scalars — the host then enqueues the next step while
-        this one runs."""
+        this one runs.  A model with a paired step (AugmentedCycleGAN.supervised_train_instance) replays that one from a
+        second graph (`_sup_step_graph`) in the same way."""
         self._step_graph = StepGraph(self) if on else None
-        if self._step_graph is not None:
-            self._step_graph.defer_scalars = bool(defer_scalars)
+        self._sup_step_graph = None
+        if on and hasattr(self, "_supervised_train_instance"):
+            self._sup_step_graph = StepGraph(self, "_supervised_train_instance")
+        for sg in (self._step_graph, self._sup_step_graph):
+            if sg is not None:
+                sg.defer_scalars = bool(defer_scalars)
 
     # ---- forward-only helpers shared by both models (model.py:210-280, 606-733): compositions of the two generators.
     # Subclass hooks: _z (noise transform), _cycle_code (the latent the B -> A -> B cycle is closed with).
@@ -820,6 +839,8 @@ class AugmentedCycleGAN(_Base):
 
     def supervised_train_instance(self, real_A, real_B, prior_z_B):
         """model.py:541-604 (paired step; off by default, --supervised)"""
+        if self._sup_step_graph is not None and not acg_dist.exchange_on():
+            return self._sup_step_graph(real_A, real_B, prior_z_B)
         with _in_train_step():
             return self._supervised_train_instance(real_A, real_B, prior_z_B)
 
@@ -867,9 +888,12 @@ class AugmentedCycleGAN(_Base):
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
         names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B', 'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
         vals = self._scalars(ex_G, self.f_E_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_E, ss_D_z])
-        for k in names[4:]:
-            vals[k] = math.sqrt(max(vals[k], 0.0))
-        return vals                                                                             # model.py:596-604
+
+        def finish(vals):
+            for k in names[4:]:
+                vals[k] = math.sqrt(max(vals[k], 0.0))
+            return vals                                                                         # model.py:596-604
+        return self._report(vals, finish)
 
     # ---- hooks of the shared forward-only helpers (_Base) + the encoder-specific ones (model.py:606-733) ----
     _noise_before_code = True

@@ -1,6 +1,7 @@
 """Command-line options — Py3 counterpart of /root/reference/augmented_cyclegan/options.py (which is Python 2:
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
-(options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist."""
+(options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
+--step_graph, --defer_scalars."""
 import argparse
 import os
 import pickle
@@ -76,8 +77,12 @@ _T = [
      "and the parity tests run), f32 (exact products, 2.4x slower)"),
     ("synthetic", int, 0, "use N synthetic U(-1,1) samples per split instead of --dataroot"),
     ("sync_bn", "flag", False, "data parallel: BatchNorm (E_B, D_z_B) statistics across all ranks"),
-    ("step_graph", "flag", False, "replay the training step as one captured HIP graph (launch-bound sizes: small images / "
-                                  "batches; single GPU)"),
+    ("step_graph", "flag", False, "replay the training step (and, with --supervised, the paired step from a second graph) as "
+                                  "one captured HIP graph (launch-bound sizes: small images / batches; single GPU: under the "
+                                  "data-parallel exchange both steps run eagerly)"),
+    ("defer_scalars", "flag", False, "with --step_graph: a replayed step hands its losses back later, read only on --print_freq "
+                                     "/ --display_freq steps, so the host enqueues the next step while this one runs (at most "
+                                     "2 in flight); the logged numbers are those of --step_graph alone"),
     ("eval_steps", int, 50, "variational-bound steps per epoch (train.py:285 uses 50)"),
 ]
 
@@ -104,6 +109,8 @@ class TrainOptions(object):
         opt = self.opt = self.parser.parse_args(argv)
         if opt.dataroot is None and not opt.synthetic:
             self.parser.error("--dataroot is required (or --synthetic N)")
+        if opt.defer_scalars and not opt.step_graph:
+            self.parser.error("--defer_scalars requires --step_graph")
         opt.gpu_ids = [i for i in (int(tok) for tok in opt.gpu_ids.split(",")) if i >= 0]      # options.py:92-97
         if opt.gpu_ids and torch.cuda.is_available():
             local = int(os.environ.get("LOCAL_RANK", opt.gpu_ids[0]))

@@ -21,7 +21,7 @@ import torch
 from . import dist as D, ops
 from .dataloader import AlignedIterator, DevicePrefetcher, UnalignedIterator, load_numpy_data, synthetic_data
 from .evaluate import eval_mse_A, eval_ubo_B, one_to_three_channels
-from .model import AugmentedCycleGAN, StochCycleGAN
+from .model import AugmentedCycleGAN, DeferredStep, StochCycleGAN
 from .options import TrainOptions, create_sub_dirs
 
 
@@ -99,6 +99,38 @@ def _cuda(t, on):
     return t.cuda() if on else t
 
 
+# --defer_scalars: at most this many replayed steps are in flight when the next one is enqueued
+RUN_AHEAD = 2
+
+
+class PinnedUploads(object):
+    """Host -> device uploads that do not make the host wait for the compute stream (a pageable .cuda() copy does): each
+    tensor is staged in one of a small ring of pinned buffers per (name, shape) and sent with non_blocking=True.  A buffer
+    is overwritten only after the event of the copy that last read it has completed; with RUN_AHEAD steps in flight, three
+    buffers per name never wait on a step still running."""
+    SLOTS = 3
+
+    def __init__(self, device):
+        self.device, self.rings = device, {}
+
+    def __call__(self, name, t):
+        ring = self.rings.get((name, tuple(t.shape)))
+        if ring is None:
+            ring = self.rings[(name, tuple(t.shape))] = dict(
+                bufs=[torch.empty(t.shape, dtype=t.dtype).pin_memory() for _ in range(self.SLOTS)],
+                events=[None] * self.SLOTS, next=0)
+        i = ring['next']
+        ring['next'] = (i + 1) % self.SLOTS
+        if ring['events'][i] is not None:
+            ring['events'][i].synchronize()     # that buffer's previous copy has left host memory
+        buf = ring['bufs'][i]
+        buf.copy_(t)
+        out = buf.to(self.device, non_blocking=True)
+        ev = ring['events'][i] = torch.cuda.Event()
+        ev.record()
+        return out
+
+
 class Trainer(object):
     """One training run: data -> model -> epochs of train_instance (+ optional paired step) -> per-epoch checkpoint,
     evaluation, best-model tracking and LR decay.  Rank 0 owns all files; every rank trains on its shard of each batch."""
@@ -159,8 +191,10 @@ class Trainer(object):
             raise NotImplementedError('Specified model is not implemented.')
         self.log("model [%s] was created (conv arithmetic: %s, %d rank%s)"
                  % (self.model.__class__.__name__, ops.get_precision(), self.ws, "" if self.ws == 1 else "s"))
-        if getattr(o, "step_graph", False) and not getattr(o, "supervised", False):
-            self.model.enable_step_graph()            # ignored while the data-parallel exchange is on (model.train_instance)
+        self.defer = bool(getattr(o, "defer_scalars", False))
+        if getattr(o, "step_graph", False):           # both steps (unsupervised and paired) replay from graphs; ignored while
+            self.model.enable_step_graph(defer_scalars=self.defer)   # the data-parallel exchange is on (model.train_instance)
+        self.upload = PinnedUploads(torch.device("cuda")) if self.defer and self.gpu else None
         if o.continue_train:
             chk = os.path.join(o.expr_dir, o.which_epoch)
             self.model.load(chk)
@@ -204,9 +238,18 @@ class Trainer(object):
         src = Sharded(self.train_it)
         return DevicePrefetcher(src) if self.gpu else src
 
+    def _to_device(self, name, t):
+        if self.upload is not None:
+            return self.upload(name, t)
+        return _cuda(t, self.gpu)
+
     def train_epoch(self, epoch):
+        """one pass over the training batches.  Under --defer_scalars a replayed step returns a model.DeferredStep: its
+        numbers are read (.result()) only on a step that logs or visualises, before the next step is enqueued (its visuals
+        are the graph's static buffers), and at most RUN_AHEAD steps are in flight."""
         o, m = self.opt, self.model
         seen = 0
+        in_flight = []
         for data in self._train_batches():
             real_A, real_B = data['A'], data['B']
             nA, nB = data['n']
@@ -215,14 +258,23 @@ class Trainer(object):
             prior_z_B = torch.empty((nA, o.nlatent, 1, 1)).normal_(0, 1)                 # on the host, train.py:193
             self.total_steps += o.batchSize
             seen += o.batchSize
-            prior_z_B = _cuda(self._shard(prior_z_B), self.gpu)
+            if len(in_flight) >= RUN_AHEAD:
+                in_flight.pop(0).wait()
+            prior_z_B = self._to_device('prior_z_B', self._shard(prior_z_B))
             out = m.train_instance(real_A, real_B, prior_z_B)
             sup_losses = None
             if self.sup_it is not None:
                 sd = next(self.sup_it)
-                sA, sB = _cuda(self._shard(sd['A']), self.gpu), _cuda(self._shard(sd['B']), self.gpu)
+                sA, sB = self._to_device('sup_A', self._shard(sd['A'])), self._to_device('sup_B', self._shard(sd['B']))
                 sup_losses = m.supervised_train_instance(sA, sB, prior_z_B[:sA.size(0)])
-            if self.total_steps % o.display_freq == 0 and self.rank == 0:
+            last = sup_losses if sup_losses is not None else out
+            if isinstance(last, DeferredStep):     # completes after everything this iteration enqueued
+                in_flight.append(last)
+            display = self.total_steps % o.display_freq == 0 and self.rank == 0
+            if display or self.total_steps % o.print_freq == 0:
+                out = out.result() if isinstance(out, DeferredStep) else out
+                sup_losses = sup_losses.result() if isinstance(sup_losses, DeferredStep) else sup_losses
+            if display:
                 self._visualize(real_A, out[1], epoch, seen // o.batchSize)
             if self.total_steps % o.print_freq == 0:
                 t = (time.time() - self.tick) / o.batchSize                            # seconds per image, train.py:243
