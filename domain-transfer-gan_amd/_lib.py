@@ -150,6 +150,9 @@ SIGNATURES = {
     "acg_pixel_nll_bwd": (c_int, [c_int, _P, _P, _P, c_int, c_size_t, c_int, c_int, _P, _P, _P, _P]),
     "acg_latent_bound_step": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
                                       _P]),
+    "acg_ensemble_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "acg_ensemble_stats": (c_int, [_P, _P, c_int, c_int, c_size_t, c_int, c_int, ctypes.POINTER(c_float), c_int, _P, _P, _P, _P,
+                                   _P, _P, _P, c_size_t, _P]),
     "acg_comm_unique_id": (c_int, [_P]),
     "acg_comm_init": (c_int, [ctypes.POINTER(c_void_p), _P, c_int, c_int]),
     "acg_comm_allreduce_mean": (c_int, [_P, _P, c_size_t, _P]),

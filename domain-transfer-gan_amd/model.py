@@ -22,7 +22,7 @@ import torch
 
 from . import dist as acg_dist
 from . import networks, ops
-from .modules import as_latent, mark_dirty, packed_of, repack
+from .modules import _starts_with_conv, as_latent, mark_dirty, packed_of, repack
 from .ops import cpad
 
 
@@ -441,6 +441,60 @@ class _Base(object):
         """each A against multi_prior_z_B.size(0) / |A| consecutive codes (train.py:66)"""
         return self.predict_B(_each_n_times(real_A, multi_prior_z_B.size(0) // real_A.size(0)), multi_prior_z_B)
 
+    def translate_ensemble(self, real_A, n_samples, z=None, real_B=None, quantiles=(0.05, 0.5, 0.95), chunk=None):
+        """The distribution of A -> B: n_samples translations of every input, summarised per pixel on the device.
+        z: (N*n_samples, nlatent, 1, 1) codes in generate_multi's order (input n takes rows n*M .. n*M + M - 1; default N(0, 1)
+        from torch's generator), passed through _z (cycle_gan: a degenerate ensemble).  The generator runs in eval state
+        under no_grad on groups of whole inputs of at most `chunk` images (default: ensemble_chunk), each group followed by
+        one acg_ensemble_stats launch into slices of the outputs.  Returns device tensors: mean, std (N, C, H, W) and
+        quantiles (N, nq, C, H, W); with real_B also the per-input crps, crps_fair (NaN for one sample), mse_mean, spread,
+        coverage (N,), rank_hist (N, M + 1) and crps_map (N, C, H, W).  Nothing is read back to the host."""
+        M = int(n_samples)
+        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+            raise ValueError("translate_ensemble: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        q = ops.check_quantiles(quantiles)
+        N, _, H, W = real_A.shape
+        C = self.opt.output_nc
+        if z is None:
+            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
+        if z.size(0) != N * M:
+            raise ValueError("translate_ensemble: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
+        if real_B is not None and (real_B.size(0), real_B.size(1)) != (N, C):
+            raise ValueError("translate_ensemble: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
+        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
+        per = chunk // M
+        if per < 1:
+            raise ValueError("translate_ensemble: a group of %d images cannot hold one input's %d samples" % (chunk, M))
+        G = self.netG_A_B
+        out = ops.ensemble_outputs(N, M, C, H, W, len(q), real_B is not None, real_A.device)
+        modes = [(m, m.training) for m in G.modules()]
+        G.eval()
+        try:
+            with torch.no_grad():
+                img_in = _starts_with_conv(G.model)
+                for g0 in range(0, N, per):
+                    n = min(per, N - g0)
+                    a = real_A[g0:g0 + n]
+                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
+                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
+                    tgt = None
+                    if real_B is not None:
+                        tgt = ops.ToNHWC.apply(real_B[g0:g0 + n], members.shape[-1] == ops.cimg(C))
+                    ops.ensemble_stats(members, tgt, M, C, q, out={k: v[g0:g0 + n] for k, v in out.items()})
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        if real_B is None:
+            return out
+        sums, cells = out.pop("sums"), float(C * H * W)
+        e1, e2 = sums[:, 0], sums[:, 1]
+        out["crps"] = (e1 - e2 / 2) / cells
+        out["crps_fair"] = (e1 - e2 * (M / (2. * (M - 1)))) / cells if M > 1 else torch.full_like(e1, float("nan"))
+        out["mse_mean"] = sums[:, 2] / cells
+        out["spread"] = torch.sqrt(sums[:, 3] / cells)
+        out["coverage"] = sums[:, 4] / cells
+        return out
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)
@@ -497,6 +551,14 @@ def _in_train_step():
         yield
     finally:
         modules.IN_TRAIN_STEP = prev
+
+
+def ensemble_chunk(ngf, H, W):
+    """the largest number of images one generator pass may hold: its widest full-resolution tensor (2*ngf channels, stored
+    as cpad) must stay under the 4 GiB operand limit of every launcher — 255 images at 256 x 256 and 63 at
+    512 x 512 with ngf 32"""
+    per_image = H * W * ops.cpad(2 * ngf) * 4
+    return max(((1 << 32) - 1) // per_image, 1)
 
 
 def _each_n_times(x, n):

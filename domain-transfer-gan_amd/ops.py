@@ -1389,6 +1389,60 @@ def latent_bound_step(mu, logvar, sq_mu, sq_logvar, eps, dz, nll, npx, lr, trace
               _ptr(nll), float(lr), float(alpha), float(rms_eps), _ptr(trace_row), _ptr(eps_next), _ptr(z_next), _stream())
 
 
+# ----------------------------------------------------------------------------------------------
+# ensemble statistics of M translations per input (model.translate_ensemble, test.py --metric ensemble)
+# ----------------------------------------------------------------------------------------------
+ENSEMBLE_MAX_M, ENSEMBLE_MAX_Q = 64, 8
+
+
+def check_quantiles(quantiles):
+    """-> the levels as a tuple of floats; ValueError unless 1..8 levels, sorted, inside [0, 1]"""
+    q = tuple(float(v) for v in quantiles)
+    if not 1 <= len(q) <= ENSEMBLE_MAX_Q:
+        raise ValueError("need 1 to %d quantile levels (got %d)" % (ENSEMBLE_MAX_Q, len(q)))
+    if any(not 0.0 <= v <= 1.0 for v in q) or any(b < a for a, b in zip(q, q[1:])):
+        raise ValueError("quantile levels must be sorted inside [0, 1] (got %s)" % (q,))
+    return q
+
+
+def ensemble_outputs(N, M, C, H, W, nq, scored, device):
+    """the device tensors acg_ensemble_stats writes for N inputs of M members: mean, std (N, C, H, W), quantiles
+    (N, nq, C, H, W) and, when scored, crps_map (N, C, H, W), sums (N, 6) and rank_hist (N, M + 1, int32)"""
+    f = dict(device=device, dtype=torch.float32)
+    out = dict(mean=torch.empty((N, C, H, W), **f), std=torch.empty((N, C, H, W), **f),
+               quantiles=torch.empty((N, nq, C, H, W), **f))
+    if scored:
+        out.update(crps_map=torch.empty((N, C, H, W), **f), sums=torch.empty((N, 6), **f),
+                   rank_hist=torch.empty((N, M + 1), device=device, dtype=torch.int32))
+    return out
+
+
+def ensemble_stats(members_nhwc, target_nhwc, M, C, quantiles, out=None):
+    """acg_ensemble_stats: members (N*M, H, W, Cp) NHWC, member m of input n at row n*M + m; target (N, H, W, Cp) or None.
+    -> dict of device tensors (ensemble_outputs; `out`: such a dict to write instead, e.g. slices of larger ones).  One
+    launch (plus its fold with a target), nothing read back to the host."""
+    x = members_nhwc.contiguous()
+    y = None if target_nhwc is None else target_nhwc.contiguous()
+    _check(x, y)
+    q = check_quantiles(quantiles)
+    NM, H, W, Cp = x.shape
+    if M < 1 or NM % M:
+        raise _lib.AcgError("ensemble_stats: %d member rows are not a multiple of M=%d" % (NM, M))
+    N, npix = NM // M, H * W
+    if y is not None and tuple(y.shape) != (N, H, W, Cp):
+        raise _lib.AcgError("ensemble_stats: target %s does not pair with members %s" % (tuple(y.shape), tuple(x.shape)))
+    if out is None:
+        out = ensemble_outputs(N, M, C, H, W, len(q), y is not None, x.device)
+    nb = _lib.query("acg_ensemble_workspace_bytes", N, npix) if y is not None else 0
+    ws = workspace(nb, slot=1) if y is not None else None
+    levels = (ctypes.c_float * len(q))(*q)
+    hist = out.get("rank_hist")
+    _lib.call("acg_ensemble_stats", _ptr(x), _ptr(y), N, int(M), npix, int(C), Cp, levels, len(q), _ptr(out.get("mean")),
+              _ptr(out.get("std")), _ptr(out.get("quantiles")), _ptr(out.get("crps_map")), _ptr(out.get("sums")), _ptr(hist),
+              _ptr(ws), nb, _stream())
+    return out
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -10,6 +10,11 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
   visual      cycle / multi / cycle-B-multi / multi-cycle (/ inference) grids of every dev batch of 10
   noise_sens  |B - rec_B| per sample after perturbing fake_A with eight noise levels -> <res_dir>/noise_sens.npy
   mvgauss     the multivariate-Gaussian baseline bpp (compute_bpp_MVGauss_B, test.py:123-134; new as a --metric)
+  ensemble    (new) the stochastic direction scored as a distribution: --n_samples translations A -> B of every dev and test
+              input (model.translate_ensemble), per input the CRPS, its fair form, the MSE of the ensemble mean, the spread
+              and the coverage of the outer --quantiles band against the paired B, and the rank histogram of B among the
+              members -> <res_dir>/ensemble.npz, and grids of A, B, mean, std and the outer quantiles for the first dev batch
+              of 10 (ensemble_0.png)
 
 Deviations from the reference:
   * the pixel count is C*H*W of the data, not the hard-coded 64*64*3;
@@ -229,6 +234,39 @@ def train_logvar(dataset, model, epochs=1, use_gpu=True, dequant_seq=None, eps_s
     return logvar_B
 
 
+ENSEMBLE_SCORES = ('crps', 'crps_fair', 'mse_mean', 'spread', 'coverage')
+
+
+def eval_ensemble_B(dataset, model, n_samples, quantiles, use_gpu=True):
+    """the per-input ensemble scores of A -> B on an aligned split (model.translate_ensemble, one read of the numbers per
+    batch) -> ({score: (N,) array for every input}, rank histogram pooled over the split (n_samples + 1,))"""
+    per, hist = {k: [] for k in ENSEMBLE_SCORES}, np.zeros(n_samples + 1, dtype=np.int64)
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        r = model.translate_ensemble(real_A, n_samples, real_B=real_B, quantiles=quantiles)
+        host = torch.cat([torch.stack([r[k] for k in ENSEMBLE_SCORES], 1).double(), r['rank_hist'].double()], 1).cpu().numpy()
+        for i, k in enumerate(ENSEMBLE_SCORES):
+            per[k].append(host[:, i])
+        hist += host[:, len(ENSEMBLE_SCORES):].sum(0).astype(np.int64)
+    return {k: np.concatenate(v) for k, v in per.items()}, hist
+
+
+def visualize_ensemble(opt, real_A, real_B, model, name):
+    """rows A, B, ensemble mean, std (scaled to the image range by the grid's largest value), lowest and highest quantile;
+    one column per input"""
+    r = model.translate_ensemble(real_A, opt.n_samples, quantiles=opt.quantiles)
+    std = r['std']
+    std = std * (2. / max(float(std.max()), 1e-12)) - 1.
+    rows = [real_A, real_B, r['mean'], std, r['quantiles'][:, 0], r['quantiles'][:, -1]]
+    _grid(torch.cat([one_to_three_channels(x.detach().cpu()) for x in rows], 0), os.path.join(opt.res_dir, name), real_A.size(0))
+
+
+def _pooled_spread(spread):
+    return float(np.sqrt(np.mean(np.square(spread))))
+
+
 def _build(opt):
     if opt.model == 'stoch_cycle_gan':
         return StochCycleGAN(opt, testing=True), False
@@ -253,7 +291,7 @@ def test_model(argv=None):
     opt = argparse.Namespace(**vars(args))
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
-    for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps'):
+    for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -319,6 +357,20 @@ def test_model(argv=None):
     elif opt.metric == 'mvgauss':
         full_train = UnalignedIterator(trainA, trainB, batch_size=cap(len(trainA), 200))
         print("MVGauss BPP: %.4f" % compute_bpp_MVGauss_B(full_train, test_dataset))
+    elif opt.metric == 'ensemble':
+        torch.manual_seed(opt.seed)          # the codes of dev, then test, follow from the evaluator's seed alone
+        dev, dev_hist = eval_ensemble_B(dev_dataset, model, opt.n_samples, opt.quantiles)
+        test, test_hist = eval_ensemble_B(test_dataset, model, opt.n_samples, opt.quantiles)
+        arrays = dict(n_samples=np.int64(opt.n_samples), quantiles=np.array(opt.quantiles, dtype=np.float64),
+                      dev_rank_hist=dev_hist, test_rank_hist=test_hist)
+        for split, scores in (('dev', dev), ('test', test)):
+            arrays.update(('%s_%s' % (split, k), v) for k, v in scores.items())
+        np.savez(os.path.join(opt.res_dir, 'ensemble.npz'), **arrays)
+        vis = next(iter(AlignedIterator(devA, devB, batch_size=cap(len(devA), 10))))
+        visualize_ensemble(opt, vis['A'].cuda(), vis['B'].cuda(), model, 'ensemble_0.png')
+        print("DEV_CRPS_B: %.4f, TEST_CRPS_B: %.4f, TEST_MSE_MEAN_B: %.4f, TEST_SPREAD_B: %.4f, TEST_COVERAGE_B: %.4f"
+              % (dev['crps'].mean(), test['crps'].mean(), test['mse_mean'].mean(), _pooled_spread(test['spread']),
+                 test['coverage'].mean()))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

@@ -400,6 +400,23 @@ int acg_latent_bound_step(int N, int L, int npx, float *mu, float *logvar, float
                           const float *dz, const float *nll, float lr, float alpha, float rms_eps, float *trace_row,
                           const float *eps_next, float *z_next, void *stream);
 
+/* ---- ensemble statistics of M translations per input (model.translate_ensemble, test.py --metric ensemble) ----
+ * x: members (N*M, npix, Cp) NHWC fp32, member m of input n at row n*M + m; y: the paired target (N, npix, Cp) or NULL.
+ * Cp is the stored width (4 for C4 images, else a multiple of 16), C <= Cp valid channels; padded channels are ignored.
+ * q: nq quantile levels in HOST memory (read before the launch, passed by value), sorted inside [0, 1].  1 <= M <= 64,
+ * 1 <= nq <= 8.  Per cell (input, pixel, channel), members sorted x_(1..M):
+ *   mean, stdev (unbiased, 0 when M = 1): (N, C, npix) NCHW;  quant: numpy's linear rule, (N, nq, C, npix);
+ *   crps_map: E1 - E2/2 with E1 = mean |x_i - y|, E2 = mean over pairs |x_i - x_j| (sorted form), (N, C, npix), needs y;
+ *   sums (N, 6): per input over its C*npix cells sum E1, sum E2, sum (mean - y)^2, sum stdev^2, count of cells with the lowest
+ *     quantile <= y <= the highest, the cell count; needs y;
+ *   rank_hist (N, M + 1): cells per rank #{x_i < y} + floor(#{x_i = y} / 2); needs y.
+ * Every output may be NULL.  The float sums fold per-block partials of the workspace (acg_ensemble_workspace_bytes; needed
+ * only with y) in a fixed order: deterministic, no float atomics. */
+size_t acg_ensemble_workspace_bytes(int N, size_t npix);
+int acg_ensemble_stats(const float *x, const float *y, int N, int M, size_t npix, int C, int Cp, const float *q, int nq,
+                       float *mean, float *stdev, float *quant, float *crps_map, float *sums, unsigned *rank_hist,
+                       void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
