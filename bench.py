@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/sec of the Augmented CycleGAN step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|5] [--full]
 
 N > 1: when RANK is not in the environment this process is only a LAUNCHER — before touching the GPU it starts N fresh
 child processes of this same file (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), one rank per
@@ -24,7 +24,12 @@ losses and Adam are fp32 throughout; the convolution products run on the matrix 
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel: the 3x3 reflect-pad 128->128 resblock convolution forward),
 `roofline_hbm` (the stride-2 64->128 downsample convolution forward, HBM-bound) — both timed live with HIP events on the
-launch stream, kernel names read back from the dispatcher — and `cpu_baseline` (the oracle "port" on the host cores).
+launch stream inside the timed steps, kernel names read back from the dispatcher.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+`--full` also runs the measurements that take runs of their own, behind the timed region:
+  roofline.peak_sustained  the library's register-only MFMA loop on this device (bf16x3 only; null in a plain run);
+  cpu_baseline             the oracle "port" on the host cores, in fresh child processes (one GPU; not with --no-cpu-baseline).
 """
 import argparse
 import json
@@ -73,7 +78,10 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--blocks", type=int, default=None)
     ap.add_argument("--nc", type=int, default=None, help="image channels of both domains")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the live sustained-MFMA probe and the CPU "
+                         "baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-step-graph", action="store_true",
                     help="enqueue every step kernel by kernel.  Default on ONE GPU: the step is replayed as one captured HIP graph "
                          "(model.enable_step_graph, train.py --step_graph: the same launches without ~1 400 launch boundaries, "
@@ -352,7 +360,7 @@ def main():
     # (In front of the timed region its 150 ms at full matrix power cost the step 3 %: 145.8 against 141.6 ms, every trunk
     # kernel 3-4 % slower — the chip starts the timed steps at a lower clock.)
     sustained = None
-    if a.precision == "bf16x3" and rank == 0:
+    if a.full and a.precision == "bf16x3" and rank == 0:
         import ctypes
         from dtgan_amd import _lib
         scratch = torch.empty(512 * 1024, device=dev)
@@ -486,7 +494,7 @@ def main():
     }
     out["fused_paths"] = {"per_step": fused_paths, "note": "launches per training step that took each fused path (ops.FUSED); "
                           "config 3 expects 70 norm_bwd_sums_from_dgrad (54 trunk + 16 full-resolution layers), 72 wgrad_s16, 18 relu bitmask links"}
-    if ws == 1 and not a.no_cpu_baseline:
+    if ws == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a, [x for x in argv if x != "--no-cpu-baseline"])
     print(json.dumps(out), flush=True)
 

@@ -1,7 +1,7 @@
 """GPU: `bench.py` as the driver runs it — the contract line of a SMALL workload (same code path as the headline: the step
 replayed as a captured HIP graph, every N-th timed step enqueued eagerly with the HIP-event brackets of the roofline block) and
 of the plain eager procedure, in fresh child processes.  Both must report the same loss (same kernels, same inputs), the
-roofline blocks, the fused-path counts and the measurement hooks' fields.
+roofline blocks, the fused-path counts and the measurement hooks' fields (`--full`); a plain run leaves out what `--full` adds.
 
 What is timed replaces /root/reference/augmented_cyclegan/train.py:190-245 (the reference's loop around
 `model.train_instance`, which reports seconds per image)."""
@@ -18,9 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--steps", "7", "--batch", "2", "--size", "128", "--blocks", "2", "--no-cpu-baseline", "--timer-every", "3"]
 
 
-def _bench(*extra):
+def _bench(*extra, args=ARGS):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + ARGS + list(extra), env=env, cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + list(extra), env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -30,8 +30,8 @@ def _bench(*extra):
 
 def test_bench_line_graph_replay_and_eager_agree():
     # the graph path runs two untimed steps behind its capture (the third call): 3 warm-up calls = 5 steps in front of the timed ones
-    g, err = _bench("--warmup", "3")
-    e, _ = _bench("--warmup", "5", "--no-step-graph")
+    g, err = _bench("--warmup", "3", "--full")
+    e, _ = _bench("--warmup", "5", "--no-step-graph", "--full")
     assert "capture failed" not in err
     for d in (g, e):
         for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -50,6 +50,20 @@ def test_bench_line_graph_replay_and_eager_agree():
         assert d["fused_paths"]["per_step"]["wgrad_s16"] == 16.0
     assert "captured HIP graph" in g["config"]["launch"] and e["config"]["launch"] == "eager"
     assert g["config"]["loss_G_A"] == e["config"]["loss_G_A"]      # the replay runs the same launches on the same inputs
+
+
+def test_plain_bench_line_leaves_out_what_full_adds():
+    """Without --full the run times the steps and prints the line: no live MFMA probe, no CPU baseline (here even without
+    --no-cpu-baseline), the roofline blocks still read from the event brackets of the timed steps."""
+    d, err = _bench("--warmup", "3", args=[x for x in ARGS if x != "--no-cpu-baseline"])
+    assert "capture failed" not in err
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "roofline_hbm", "fused_paths"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 3 and abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 0.02 * d["value"]
+    assert "cpu_baseline" not in d
+    r = d["roofline"]
+    assert r["peak_sustained"] is None and r["frac_of_sustained"] is None and r["peak_sustained_source"] is None
+    assert r["launches_timed"] == 3 * 16 and 0.0 < r["frac"] < 1.0
 
 
 def test_bench_dump_outputs_repeat_for_the_same_arguments(tmp_path):

@@ -237,6 +237,15 @@ def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
         bench.parse_args(["--steps", "0"])
 
 
+def test_bench_full_is_off_by_default():
+    """A plain `bench.py` run measures the headline alone; `--full` adds the runs of their own (MFMA probe, CPU baseline),
+    which --no-cpu-baseline still trims."""
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert a.full is True and a.no_cpu_baseline is True
+
+
 _WORKER8 = """
 import os, sys
 sys.path.insert(0, %(root)r)

@@ -1,16 +1,19 @@
 #!/bin/bash
-# final measurement pass of a round (GPU box).  usage: tools/gpu_final.sh <tag> bench|profile
-#   bench:   bench lines of configs 3 (default line, with cpu_baseline), 2, 5 and config 3 in exact fp32
+# final measurement pass of a round (GPU box).  usage: tools/gpu_final.sh <tag> bench|profile [dir]
+#   bench:   bench.py --full lines of configs 3 (default line, with cpu_baseline), 2, 5 and config 3 in exact fp32, written
+#            to <dir> (default bench_out/) as <tag>_bench_*.json with their stderr beside them
 #   profile: per-kernel statistics + per-shape table of the step, HBM traffic of the dominant kernel, layer table (all rows)
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 TAG=${1:-r04}
 if [ "$2" = "bench" ]; then
-  timeout -k 10 700 python bench.py > gpurun_out/${TAG}_bench_cfg3.json 2> gpurun_out/${TAG}_bench_cfg3.err || exit 1
-  cut -c1-400 gpurun_out/${TAG}_bench_cfg3.json
-  timeout -k 10 300 python bench.py --config 2 --no-cpu-baseline > gpurun_out/${TAG}_bench_cfg2.json 2> gpurun_out/${TAG}_bench_cfg2.err || exit 1
-  timeout -k 10 300 python bench.py --config 5 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench_cfg5.json 2> gpurun_out/${TAG}_bench_cfg5.err || exit 1
-  timeout -k 10 300 python bench.py --precision f32 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench_cfg3_f32.json 2> gpurun_out/${TAG}_bench_cfg3_f32.err || exit 1
+  OUT=${3:-bench_out}
+  mkdir -p $OUT
+  timeout -k 10 700 python bench.py --full > $OUT/${TAG}_bench_cfg3.json 2> $OUT/${TAG}_bench_cfg3.err || exit 1
+  cut -c1-400 $OUT/${TAG}_bench_cfg3.json
+  timeout -k 10 300 python bench.py --full --config 2 --no-cpu-baseline > $OUT/${TAG}_bench_cfg2.json 2> $OUT/${TAG}_bench_cfg2.err || exit 1
+  timeout -k 10 300 python bench.py --full --config 5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_cfg5.json 2> $OUT/${TAG}_bench_cfg5.err || exit 1
+  timeout -k 10 300 python bench.py --full --precision f32 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_cfg3_f32.json 2> $OUT/${TAG}_bench_cfg3_f32.err || exit 1
   exit 0
 fi
 bash tools/profile_stats.sh bf16x3 $TAG > gpurun_out/${TAG}_stats.log 2>&1 || exit 1
