@@ -1,0 +1,415 @@
+// Radially averaged power spectra of square fields (model.translate_spectrum, test.py --metric spectrum): per field of one
+// channel of one image, S x S real pixels, P = |fft2(x)|^2 / S^2 averaged over rings of integer wavenumber 0 .. S/2.
+// There is no reference call site: the reference has no spectral code; tests/spectrum_ref.py states the definition.
+//
+// A batched real 2-D FFT in fp32 with the power and the ring sums fused behind it, no vendor FFT:
+//   rows     two real rows per complex transform (z = row 2r + i row 2r+1), radix-2 Stockham autosort in LDS (every stage reads
+//            unit-stride and writes runs of the stage's width: no bit-reversal gather, no stride-2^k access), then the two rows'
+//            half spectra are untangled.  Columns kx = 0 and kx = S/2 of a real row are real, so they travel packed in one
+//            complex column (re: kx = 0, im: kx = S/2): the half spectrum is exactly S x S/2 complex, the field's own bytes.
+//   columns  the same Stockham stages down the columns of a [ky][kx] tile with the lanes along kx, so every LDS access is
+//            unit-stride across the wave and the twiddle is a broadcast.
+//   power    w |F|^2 / S^2 per cell, w = 2 for 0 < kx < S/2 (the Hermitian twin lies in the same ring), 1 for kx = 0 and S/2,
+//            whose packed column is untangled here.
+//   rings    ring b holds the cells with b (b - 1) < fx^2 + fy^2 <= b (b + 1) (integers: sqrt(s) rounded to nearest).  One
+//            work item per (ring, sign of fy) enumerates its cells row by row from the integer rule and sums them in double in
+//            that fixed order, and counts them; psd[b] = (sum+ + sum-) / count.  No float atomics: two runs give the same bits,
+//            and the arithmetic does not depend on the input's layout.
+// S <= 128: one workgroup per field does all of it in LDS and writes nothing but psd.  Above, a row pass writes the packed half
+// spectrum to the workspace and a column pass (one workgroup per field, tile after tile of columns) reads it back and bins.
+// Twiddles: sincospif on exact arguments, one table per stage laid out by butterfly index (unit-stride reads).
+#include <math.h>
+#include <stdint.h>
+#include "common.h"
+
+#define SPEC_TILE 4096                   // complex elements of one LDS buffer of the two-pass kernels (32 KiB)
+#define SPEC_MIN_S 16
+#define SPEC_MAX_S 1024
+#define SPEC_ONE_WG_MAX_S 128            // the half spectrum of a field fits one workgroup's LDS up to here
+
+// threads of a workgroup: the one-workgroup kernel by the butterflies of a stage (S^2 / 4) and, at S = 128, by its being alone on
+// the CU (129 KiB of LDS); the two passes share a CU two workgroups at a time (66-72 KiB of LDS each): 16 waves of the row pass,
+// all 32 of the column pass, whose one workgroup per field is a serial chain of tiles and wants the widest workgroup
+__host__ __device__ constexpr int spec_field_threads(int S) { return S <= 16 ? 64 : S <= 64 ? 256 : 1024; }
+#define SPEC_ROWS_THREADS 512
+#define SPEC_COLS_THREADS 1024
+
+enum { SPEC_SCALAR = 0, SPEC_PLANAR = 1, SPEC_C4 = 2 };   // how a field's pixels are loaded
+
+// tw[Ns + k] = exp(-i pi k / Ns), 0 <= k < Ns, Ns = 1, 2, .. S/2: stage Ns reads tw[Ns + (j mod Ns)]
+template <int S>
+__device__ __forceinline__ void spec_twiddles(float2 *tw)
+{
+    for (int m = threadIdx.x + 1; m < S; m += blockDim.x) {
+        const int Ns = 1 << (31 - __clz(m)), k = m - Ns;
+        float s, c;
+        sincospif(-(float)k / (float)Ns, &s, &c);
+        tw[m] = make_float2(c, s);
+    }
+}
+
+__device__ __forceinline__ void spec_butterfly(float2 u, float2 v, float2 w, float2 &p, float2 &m)
+{
+    const float2 wv = make_float2(w.x * v.x - w.y * v.y, w.x * v.y + w.y * v.x);
+    p = make_float2(u.x + wv.x, u.y + wv.y);
+    m = make_float2(u.x - wv.x, u.y - wv.y);
+}
+
+// NSEQ transforms of length S along the contiguous index, layout [seq][S]; returns the buffer that holds the result
+template <int S, int NSEQ>
+__device__ __forceinline__ float2 *spec_fft_rows(float2 *a, float2 *b, const float2 *tw)
+{
+    for (int Ns = 1; Ns < S; Ns <<= 1) {
+        for (int t = threadIdx.x; t < NSEQ * (S / 2); t += blockDim.x) {
+            const int q = t / (S / 2), j = t & (S / 2 - 1), k = j & (Ns - 1), j0 = 2 * j - k;
+            const float2 *in = a + q * S;
+            float2 *out = b + q * S;
+            float2 p, m;
+            spec_butterfly(in[j], in[j + S / 2], tw[Ns + k], p, m);
+            if (Ns == 1) {
+                *reinterpret_cast<float4 *>(out + j0) = make_float4(p.x, p.y, m.x, m.y);   // neighbours: one 16-byte store
+            } else {
+                out[j0] = p;
+                out[j0 + Ns] = m;
+            }
+        }
+        __syncthreads();
+        float2 *t2 = a;
+        a = b;
+        b = t2;
+    }
+    return a;
+}
+
+// KT transforms of length S down the rows of a [S][KT] tile, the lanes along the KT columns
+template <int S, int KT>
+__device__ __forceinline__ float2 *spec_fft_cols(float2 *a, float2 *b, const float2 *tw)
+{
+    for (int Ns = 1; Ns < S; Ns <<= 1) {
+        for (int t = threadIdx.x; t < (S / 2) * KT; t += blockDim.x) {
+            const int j = t / KT, c = t & (KT - 1), k = j & (Ns - 1), j0 = 2 * j - k;
+            float2 p, m;
+            spec_butterfly(a[j * KT + c], a[(j + S / 2) * KT + c], tw[Ns + k], p, m);
+            b[j0 * KT + c] = p;
+            b[(j0 + Ns) * KT + c] = m;
+        }
+        __syncthreads();
+        float2 *t2 = a;
+        a = b;
+        b = t2;
+    }
+    return a;
+}
+
+__device__ __forceinline__ float spec_pick(float4 v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
+// z[q][w] = x[2 (rp0 + q)][w] + i x[2 (rp0 + q) + 1][w] for NRP row pairs; four pixels of both rows per work item.
+// xf: the field's first pixel (SPEC_C4: the image's, the channel picked from each pixel's 16 bytes).
+template <int S, int NRP>
+__device__ __forceinline__ void spec_load_rows(const float *__restrict__ xf, int pix_stride, int mode, int c, int rp0, float2 *z)
+{
+    for (int t = threadIdx.x; t < NRP * (S / 4); t += blockDim.x) {
+        const int q = t / (S / 4), w = (t & (S / 4 - 1)) * 4;
+        const long long p0 = (long long)(2 * (rp0 + q)) * S + w, p1 = p0 + S;
+        float4 r0, r1;
+        if (mode == SPEC_PLANAR) {
+            r0 = *reinterpret_cast<const float4 *>(xf + p0);
+            r1 = *reinterpret_cast<const float4 *>(xf + p1);
+        } else if (mode == SPEC_C4) {
+            const float4 *x4 = reinterpret_cast<const float4 *>(xf);
+            r0 = make_float4(spec_pick(x4[p0], c), spec_pick(x4[p0 + 1], c), spec_pick(x4[p0 + 2], c), spec_pick(x4[p0 + 3], c));
+            r1 = make_float4(spec_pick(x4[p1], c), spec_pick(x4[p1 + 1], c), spec_pick(x4[p1 + 2], c), spec_pick(x4[p1 + 3], c));
+        } else {
+            r0 = make_float4(xf[p0 * pix_stride], xf[(p0 + 1) * pix_stride], xf[(p0 + 2) * pix_stride], xf[(p0 + 3) * pix_stride]);
+            r1 = make_float4(xf[p1 * pix_stride], xf[(p1 + 1) * pix_stride], xf[(p1 + 2) * pix_stride], xf[(p1 + 3) * pix_stride]);
+        }
+        float4 *dst = reinterpret_cast<float4 *>(z + q * S + w);
+        dst[0] = make_float4(r0.x, r1.x, r0.y, r1.y);
+        dst[1] = make_float4(r0.z, r1.z, r0.w, r1.w);
+    }
+}
+
+// The spectra of the two real rows of z = a + i b at column k of the packed half spectrum (k < S/2):
+// A = (Z[k] + conj Z[S-k]) / 2, B = (Z[k] - conj Z[S-k]) / 2i; k = 0 carries (A[0], A[S/2]) and (B[0], B[S/2]), all real.
+template <int S>
+__device__ __forceinline__ void spec_untangle(const float2 *z, int k, float2 &ha, float2 &hb)
+{
+    if (k == 0) {
+        const float2 z0 = z[0], zn = z[S / 2];
+        ha = make_float2(z0.x, zn.x);
+        hb = make_float2(z0.y, zn.y);
+    } else {
+        const float2 u = z[k], v = z[S - k];
+        ha = make_float2(0.5f * (u.x + v.x), 0.5f * (u.y - v.y));
+        hb = make_float2(0.5f * (u.y + v.y), 0.5f * (v.x - u.x));
+    }
+}
+
+// NRP transformed row pairs z[q][S] -> rows 2q, 2q + 1 of h (row stride S/2 complex; LDS or global), two columns per store
+template <int S, int NRP>
+__device__ __forceinline__ void spec_untangle_rows(const float2 *z, float2 *h)
+{
+    for (int t = threadIdx.x; t < NRP * (S / 4); t += blockDim.x) {
+        const int q = t / (S / 4), k = (t & (S / 4 - 1)) * 2;
+        float2 a0, b0, a1, b1;
+        spec_untangle<S>(z + q * S, k, a0, b0);
+        spec_untangle<S>(z + q * S, k + 1, a1, b1);
+        *reinterpret_cast<float4 *>(h + (long long)(2 * q) * (S / 2) + k) = make_float4(a0.x, a0.y, a1.x, a1.y);
+        *reinterpret_cast<float4 *>(h + (long long)(2 * q + 1) * (S / 2) + k) = make_float4(b0.x, b0.y, b1.x, b1.y);
+    }
+}
+
+// The weighted power of a transformed [S][KT] tile of columns kx0 .. kx0 + KT - 1 -> pw[S][KT]; the tile of kx0 = 0 untangles
+// the packed column into pw[ky][0] (kx = 0) and pn[ky] (kx = S/2), both of weight 1
+template <int S, int KT>
+__device__ __forceinline__ void spec_power(const float2 *f, int kx0, float *pw, float *pn)
+{
+    const float inv = 1.f / ((float)S * (float)S);
+    for (int t = threadIdx.x; t < S * KT; t += blockDim.x) {
+        const int ky = t / KT, c = t & (KT - 1);
+        const float2 u = f[t];
+        if (kx0 + c == 0) {
+            const float2 v = f[((S - ky) & (S - 1)) * KT];
+            const float dr = u.x + v.x, di = u.y - v.y, nr = u.x - v.x, ni = u.y + v.y;
+            pw[t] = (dr * dr + di * di) * (0.25f * inv);
+            pn[ky] = (nr * nr + ni * ni) * (0.25f * inv);
+        } else {
+            pw[t] = (u.x * u.x + u.y * u.y) * (2.f * inv);
+        }
+    }
+}
+
+__device__ __forceinline__ int spec_isqrt(int n)                  // floor(sqrt(n)), n >= 0
+{
+    int r = (int)sqrtf((float)n);
+    while (r * r > n) --r;
+    while ((r + 1) * (r + 1) <= n) ++r;
+    return r;
+}
+__device__ __forceinline__ int spec_isqrt_ceil(int n) { return n <= 0 ? 0 : spec_isqrt(n - 1) + 1; }
+
+// Ring b, rows of one sign of fy (neg: fy < 0; fy = 0 goes with the positive side), inside the tile's columns: the row range and
+// each row's column range follow from b (b - 1) < fx^2 + fy^2 <= b (b + 1); cells are added row by row, left to right.
+template <int S, int KT>
+__device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const float *pw, const float *pn, double &acc, int &cnt)
+{
+    constexpr int H = S / 2;
+    const int kx1 = kx0 + KT - 1;
+    if (b == 0) {
+        if (!neg && kx0 == 0) {
+            acc += (double)pw[0];
+            cnt += 1;
+        }
+        return;
+    }
+    const int up = b * (b + 1), lo = b * (b - 1) + 1;
+    if (up >= kx0 * kx0) {
+        const int ymax = min(spec_isqrt(up - kx0 * kx0), neg ? H : H - 1);
+        const int ymin = max(spec_isqrt_ceil(lo - kx1 * kx1), neg ? 1 : 0);
+        for (int y = ymin; y <= ymax; ++y) {
+            const int ky = neg ? S - y : y;
+            const int xh = min(spec_isqrt(up - y * y), kx1), xl = max(spec_isqrt_ceil(lo - y * y), kx0);
+            for (int x = xl; x <= xh; ++x) {
+                acc += (double)pw[ky * KT + (x - kx0)];
+                cnt += x == 0 ? 1 : 2;
+            }
+        }
+    }
+    if (b == H && kx0 == 0) {                                     // the column fx = -S/2: H^2 + fy^2 <= H (H + 1)
+        const int ylast = spec_isqrt(H);
+        for (int y = neg ? 1 : 0; y <= ylast; ++y) {
+            acc += (double)pn[neg ? S - y : y];
+            cnt += 1;
+        }
+    }
+}
+
+template <int S, int T>                  // T: threads of the workgroup
+struct SpecBins {
+    static constexpr int NB = S / 2 + 1;
+    static constexpr int NI = (2 * NB + T - 1) / T;    // (ring, sign) items per thread
+    double acc[NI];
+    int cnt[NI];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            acc[i] = 0.0;
+            cnt[i] = 0;
+        }
+    }
+    template <int KT>
+    __device__ __forceinline__ void add_tile(int kx0, const float *pw, const float *pn)
+    {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int it = threadIdx.x + i * T;
+            if (it < 2 * NB) spec_bin_item<S, KT>(it >> 1, it & 1, kx0, pw, pn, acc[i], cnt[i]);
+        }
+    }
+    // psd[b] = (sum of the positive side + sum of the negative side) / cells; lds: 2 NB doubles and 2 NB ints, free to overwrite
+    __device__ __forceinline__ void store(void *lds, float *__restrict__ psd)
+    {
+        double *fin = reinterpret_cast<double *>(lds);
+        int *fcnt = reinterpret_cast<int *>(fin + 2 * NB);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int it = threadIdx.x + i * T;
+            if (it < 2 * NB) {
+                fin[it] = acc[i];
+                fcnt[it] = cnt[i];
+            }
+        }
+        __syncthreads();
+        for (int b = threadIdx.x; b < NB; b += blockDim.x)
+            psd[b] = (float)((fin[2 * b] + fin[2 * b + 1]) / (double)(fcnt[2 * b] + fcnt[2 * b + 1]));
+    }
+};
+
+__device__ __forceinline__ const float *spec_field(const float *x, int f, int C, long long row_stride, long long chan_stride,
+                                                   int mode, int &c)
+{
+    const int row = f / C;
+    c = f - row * C;
+    return x + (long long)row * row_stride + (mode == SPEC_C4 ? 0 : (long long)c * chan_stride);
+}
+
+// S <= 128: one workgroup per field; nothing but psd is written
+template <int S>
+__global__ __launch_bounds__(spec_field_threads(S)) void spectrum_field_kernel(const float *__restrict__ x, int C, long long row_stride,
+                                                                      int pix_stride, long long chan_stride, int mode,
+                                                                      float *__restrict__ psd)
+{
+    constexpr int H = S / 2;
+    __shared__ __attribute__((aligned(16))) float2 buf0[H * S];
+    __shared__ __attribute__((aligned(16))) float2 buf1[H * S];
+    __shared__ float2 tw[S];
+    int c;
+    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
+    spec_twiddles<S>(tw);
+    spec_load_rows<S, H>(xf, pix_stride, mode, c, 0, buf0);
+    __syncthreads();
+    float2 *z = spec_fft_rows<S, H>(buf0, buf1, tw);
+    float2 *h = z == buf0 ? buf1 : buf0;
+    spec_untangle_rows<S, H>(z, h);                                // [ky][S/2]: the column tile of the whole field
+    __syncthreads();
+    float2 *f = spec_fft_cols<S, H>(h, z, tw);
+    float *pw = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pw + S * H;
+    spec_power<S, H>(f, 0, pw, pn);
+    __syncthreads();
+    SpecBins<S, spec_field_threads(S)> bins;
+    bins.clear();
+    bins.template add_tile<H>(0, pw, pn);
+    bins.store(f, psd + (long long)blockIdx.x * SpecBins<S, spec_field_threads(S)>::NB);
+}
+
+// S > 128, first pass: SPEC_TILE / S row pairs of one field per workgroup -> their rows of the packed half spectrum
+template <int S>
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(const float *__restrict__ x, int C, long long row_stride,
+                                                                     int pix_stride, long long chan_stride, int mode,
+                                                                     float2 *__restrict__ half)
+{
+    constexpr int NRP = SPEC_TILE / S;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    int c;
+    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
+    const int rp0 = blockIdx.y * NRP;
+    spec_twiddles<S>(tw);
+    spec_load_rows<S, NRP>(xf, pix_stride, mode, c, rp0, buf0);
+    __syncthreads();
+    const float2 *z = spec_fft_rows<S, NRP>(buf0, buf1, tw);
+    spec_untangle_rows<S, NRP>(z, half + ((long long)blockIdx.x * S + 2 * rp0) * (S / 2));
+}
+
+// S > 128, second pass: one workgroup per field walks its half spectrum in tiles of SPEC_TILE / S columns
+template <int S>
+__global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const float2 *__restrict__ half, float *__restrict__ psd)
+{
+    constexpr int KT = SPEC_TILE / S, H = S / 2;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    const float2 *hf = half + (long long)blockIdx.x * S * H;
+    spec_twiddles<S>(tw);
+    SpecBins<S, SPEC_COLS_THREADS> bins;
+    bins.clear();
+    float2 *f = buf0;
+    for (int kx0 = 0; kx0 < H; kx0 += KT) {
+        for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+            const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+            *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * H + kx0 + cc);
+        }
+        __syncthreads();
+        f = spec_fft_cols<S, KT>(buf0, buf1, tw);
+        float *pw = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pw + SPEC_TILE;
+        spec_power<S, KT>(f, kx0, pw, pn);
+        __syncthreads();
+        bins.template add_tile<KT>(kx0, pw, pn);
+        __syncthreads();                                           // pw may be buf0, which the next tile's load overwrites
+    }
+    bins.store(f, psd + (long long)blockIdx.x * SpecBins<S, SPEC_COLS_THREADS>::NB);
+}
+
+static bool spec_size_ok(int S) { return S >= SPEC_MIN_S && S <= SPEC_MAX_S && (S & (S - 1)) == 0; }
+
+extern "C" size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S)
+{
+    if (rows < 1 || C < 1 || !spec_size_ok(S) || S <= SPEC_ONE_WG_MAX_S) return 0;
+    return (size_t)rows * (size_t)C * (size_t)S * (size_t)(S / 2) * sizeof(float2);
+}
+
+template <int S>
+static void spec_launch(hipStream_t st, const float *x, int fields, int C, long long row_stride, int pix_stride,
+                        long long chan_stride, int mode, float *psd, float2 *half)
+{
+    if constexpr (S <= SPEC_ONE_WG_MAX_S) {
+        hipLaunchKernelGGL(spectrum_field_kernel<S>, dim3(fields), dim3(spec_field_threads(S)), 0, st, x, C, row_stride, pix_stride,
+                           chan_stride, mode, psd);
+        acg_note_kernel("spectrum_field<%d>", S);
+    } else {
+        hipLaunchKernelGGL(spectrum_rows_kernel<S>, dim3(fields, (S / 2) / (SPEC_TILE / S)), dim3(SPEC_ROWS_THREADS), 0, st, x, C,
+                           row_stride, pix_stride, chan_stride, mode, half);
+        hipLaunchKernelGGL(spectrum_cols_kernel<S>, dim3(fields), dim3(SPEC_COLS_THREADS), 0, st, (const float2 *)half, psd);
+        acg_note_kernel("spectrum_rows<%d> + spectrum_cols<%d>", S, S);
+    }
+}
+
+extern "C" int acg_radial_spectrum(const float *x, int rows, int C, int S, long long row_stride, int pix_stride,
+                                   long long chan_stride, float *psd, void *ws, size_t ws_bytes, void *stream)
+{
+    ACG_REQUIRE(x != nullptr && psd != nullptr, "acg_radial_spectrum: null tensor");
+    ACG_REQUIRE(spec_size_ok(S), "acg_radial_spectrum: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
+                SPEC_MAX_S, S);
+    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_radial_spectrum: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_radial_spectrum: too many fields (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
+                "acg_radial_spectrum: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride,
+                chan_stride);
+    const size_t need = acg_radial_spectrum_workspace_bytes(rows, C, S);
+    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
+        acg_set_error("acg_radial_spectrum: workspace too small (%zu < %zu)", ws_bytes, need);
+        return ACG_ERR_WORKSPACE;
+    }
+    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_radial_spectrum: the workspace must be 16-byte aligned");
+    // 16-byte loads where the layout allows them: four pixels of a planar row, or a C4 pixel's channels
+    const bool aligned = (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
+    int mode = SPEC_SCALAR;
+    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) mode = SPEC_PLANAR;
+    else if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) mode = SPEC_C4;
+    hipStream_t st = (hipStream_t)stream;
+    const int fields = rows * C;
+    float2 *half = (float2 *)ws;
+    switch (S) {
+    case 16: spec_launch<16>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    case 32: spec_launch<32>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    case 64: spec_launch<64>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    case 128: spec_launch<128>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    case 256: spec_launch<256>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    case 512: spec_launch<512>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    default: spec_launch<1024>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
+    }
+    ACG_CHECK_LAUNCH("acg_radial_spectrum");
+    return ACG_OK;
+}

@@ -495,6 +495,52 @@ class _Base(object):
         out["coverage"] = sums[:, 4] / cells
         return out
 
+    def translate_spectrum(self, real_A, n_samples, z=None, real_B=None, chunk=None):
+        """The variance of A -> B at every spatial scale: the radially averaged power spectrum (ops.radial_spectrum) of each
+        of n_samples translations of every input and of their per-pixel mean.  z, chunk, the eval state and the grouping are
+        translate_ensemble's.  Per group: generator -> members (NHWC) -> their spectra; acg_ensemble_stats for the mean map
+        alone -> its spectrum.  Returns device tensors: members (N, M, C, nb), ens_mean (N, C, nb) and with real_B also
+        target (N, C, nb), nb = S/2 + 1.  Nothing is read back to the host."""
+        M = int(n_samples)
+        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+            raise ValueError("translate_spectrum: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        N, _, H, W = real_A.shape
+        C = self.opt.output_nc
+        nb = ops._spectrum_size(H, W) // 2 + 1
+        if z is None:
+            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
+        if z.size(0) != N * M:
+            raise ValueError("translate_spectrum: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
+        if real_B is not None and (real_B.size(0), real_B.size(1)) != (N, C):
+            raise ValueError("translate_spectrum: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
+        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
+        per = chunk // M
+        if per < 1:
+            raise ValueError("translate_spectrum: a group of %d images cannot hold one input's %d samples" % (chunk, M))
+        G = self.netG_A_B
+        f = dict(device=real_A.device, dtype=torch.float32)
+        out = dict(members=torch.empty((N, M, C, nb), **f), ens_mean=torch.empty((N, C, nb), **f))
+        modes = [(m, m.training) for m in G.modules()]
+        G.eval()
+        try:
+            with torch.no_grad():
+                img_in = _starts_with_conv(G.model)
+                for g0 in range(0, N, per):
+                    n = min(per, N - g0)
+                    a = real_A[g0:g0 + n]
+                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
+                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
+                    ops.radial_spectrum(members, C, "nhwc", out=out["members"][g0:g0 + n].view(n * M, C, nb))
+                    mean = torch.empty((n, C, H, W), **f)
+                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
+                    ops.radial_spectrum(mean, C, "nchw", out=out["ens_mean"][g0:g0 + n])
+                if real_B is not None:
+                    out["target"] = ops.radial_spectrum(real_B, C, "nchw")
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        return out
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)

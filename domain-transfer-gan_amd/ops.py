@@ -1443,6 +1443,62 @@ def ensemble_stats(members_nhwc, target_nhwc, M, C, quantiles, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum)
+# ----------------------------------------------------------------------------------------------
+SPECTRUM_MIN_S, SPECTRUM_MAX_S = 16, 1024
+
+
+def _spectrum_size(H, W):
+    if H != W or not SPECTRUM_MIN_S <= H <= SPECTRUM_MAX_S or H & (H - 1):
+        raise _lib.AcgError("radial_spectrum: fields must be S x S with S a power of two in %d..%d (got %d x %d)"
+                            % (SPECTRUM_MIN_S, SPECTRUM_MAX_S, H, W))
+    return int(H)
+
+
+def spectrum_bins(S):
+    """the cells of every ring of an S x S plane -> (S/2 + 1,) int64 on the host: the bin of signed integer wavenumbers
+    (fx, fy) with s = fx^2 + fy^2 is 0 for s = 0, else the largest b with b (b - 1) < s; the corners beyond S/2 are dropped"""
+    import numpy as np
+    S = _spectrum_size(S, S)
+    f = np.arange(S, dtype=np.int64)
+    f = np.where(f < S // 2, f, f - S)
+    s = (f[:, None] ** 2 + f[None, :] ** 2).ravel()
+    b = np.floor(np.sqrt(s.astype(np.float64))).astype(np.int64)
+    b += (b * (b + 1) < s)                                         # the integer rule settles what the float root leaves open
+    b -= (b * (b - 1) >= s) & (s > 0)
+    return np.bincount(b[b <= S // 2], minlength=S // 2 + 1).astype(np.int64)
+
+
+def radial_spectrum(x, C, layout, out=None):
+    """acg_radial_spectrum of the C valid channels of every row of x -> (rows, C, S/2 + 1) float32 on the device.  layout
+    "nhwc": x (rows, S, S, Cp) as forward_nhwc / ToNHWC give it (padded channels never reach a result); "nchw": x (rows, C, S, S).
+    One launch up to S = 128, a row and a column pass above; nothing is read back to the host."""
+    x = x.contiguous()
+    _check(x, out)
+    if x.dim() != 4 or layout not in ("nhwc", "nchw"):
+        raise _lib.AcgError("radial_spectrum: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (tuple(x.shape), layout))
+    C = int(C)
+    if layout == "nhwc":
+        rows, H, W, Cp = x.shape
+        strides = (H * W * Cp, Cp, 1)
+    else:
+        rows, Cp, H, W = x.shape
+        strides = (Cp * H * W, 1, H * W)
+    S = _spectrum_size(H, W)
+    if not 1 <= C <= Cp or rows < 1:
+        raise _lib.AcgError("radial_spectrum: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (Cp, rows, C))
+    nb = S // 2 + 1
+    if out is None:
+        out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, C, nb):
+        raise _lib.AcgError("radial_spectrum: out %s is not (%d, %d, %d)" % (tuple(out.shape), rows, C, nb))
+    nbytes = _lib.query("acg_radial_spectrum_workspace_bytes", rows, C, S)
+    ws = workspace(nbytes, slot=2) if nbytes else None
+    _lib.call("acg_radial_spectrum", _ptr(x), rows, C, S, strides[0], strides[1], strides[2], _ptr(out), _ptr(ws), nbytes, _stream())
+    return out
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

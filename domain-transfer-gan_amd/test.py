@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -15,6 +15,12 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               and the coverage of the outer --quantiles band against the paired B, and the rank histogram of B among the
               members -> <res_dir>/ensemble.npz, and grids of A, B, mean, std and the outer quantiles for the first dev batch
               of 10 (ensemble_0.png)
+  spectrum    (new) the variance at every spatial scale: the radially averaged power spectrum (F = fft2 of a channel, |F|^2 / S^2
+              averaged over rings of integer wavenumber 0 .. S/2; a HIP FFT, ops.radial_spectrum) of --n_samples translations
+              A -> B of every dev and test input and of their per-pixel mean (model.translate_spectrum) against the real B, and
+              of B -> A against the real A; split-mean spectra per channel and log-spectral distances in dB over bins
+              1 .. S/2 (LSD = sqrt(mean_b (10 log10(p_b / q_b))^2), spectra clamped at 1e-30, the mean over channels), computed
+              on the host in float64 -> <res_dir>/spectrum.npz.  Square fields, S a power of two in 16 .. 1024.  No plot
 
 Deviations from the reference:
   * the pixel count is C*H*W of the data, not the hard-coded 64*64*3;
@@ -263,6 +269,45 @@ def visualize_ensemble(opt, real_A, real_B, model, name):
     _grid(torch.cat([one_to_three_channels(x.detach().cpu()) for x in rows], 0), os.path.join(opt.res_dir, name), real_A.size(0))
 
 
+def log_spectral_distance(p, q):
+    """(..., C, nb) spectra -> (...,) float64: sqrt(mean over bins 1 .. S/2 of (10 log10(p / q))^2) in dB, both clamped at
+    1e-30, averaged over the channels"""
+    p = np.maximum(np.asarray(p, dtype=np.float64)[..., 1:], 1e-30)
+    q = np.maximum(np.asarray(q, dtype=np.float64)[..., 1:], 1e-30)
+    return np.sqrt(np.mean((10.0 * np.log10(p / q)) ** 2, axis=-1)).mean(axis=-1)
+
+
+def eval_spectrum(dataset, model, n_samples, use_gpu=True):
+    """radially averaged power spectra on an aligned split, one read of the bin arrays per batch.  A -> B: n_samples members
+    per input and their ensemble mean (model.translate_spectrum) against the real B; B -> A: predict_A against the real A.
+    -> dict: psd_real_B, psd_members_B (over inputs and members), psd_ens_mean_B, psd_real_A, psd_fake_A: split means, (C, nb)
+    float64; lsd_B, lsd_mean_B, lsd_A: the distances of those means; lsd_B_per_input (N,): every input's member-mean
+    spectrum against its own paired B"""
+    keys = ('members', 'ens_mean', 'target', 'real_A', 'fake_A')
+    parts = {k: [] for k in keys}
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        r = model.translate_spectrum(real_A, n_samples, real_B=real_B)
+        with torch.no_grad():
+            r['fake_A'] = ops.radial_spectrum(model.predict_A(real_B), real_A.size(1), "nchw")
+        r['real_A'] = ops.radial_spectrum(real_A, real_A.size(1), "nchw")
+        host = torch.cat([r[k].reshape(-1) for k in keys]).cpu().numpy().astype(np.float64)
+        o = 0
+        for k in keys:
+            parts[k].append(host[o:o + r[k].numel()].reshape(tuple(r[k].shape)))
+            o += r[k].numel()
+    p = {k: np.concatenate(v) for k, v in parts.items()}
+    res = dict(psd_real_B=p['target'].mean(0), psd_members_B=p['members'].mean((0, 1)), psd_ens_mean_B=p['ens_mean'].mean(0),
+               psd_real_A=p['real_A'].mean(0), psd_fake_A=p['fake_A'].mean(0))
+    res['lsd_B'] = float(log_spectral_distance(res['psd_members_B'], res['psd_real_B']))
+    res['lsd_mean_B'] = float(log_spectral_distance(res['psd_ens_mean_B'], res['psd_real_B']))
+    res['lsd_A'] = float(log_spectral_distance(res['psd_fake_A'], res['psd_real_A']))
+    res['lsd_B_per_input'] = log_spectral_distance(p['members'].mean(1), p['target'])
+    return res
+
+
 def _pooled_spread(spread):
     return float(np.sqrt(np.mean(np.square(spread))))
 
@@ -371,6 +416,16 @@ def test_model(argv=None):
         print("DEV_CRPS_B: %.4f, TEST_CRPS_B: %.4f, TEST_MSE_MEAN_B: %.4f, TEST_SPREAD_B: %.4f, TEST_COVERAGE_B: %.4f"
               % (dev['crps'].mean(), test['crps'].mean(), test['mse_mean'].mean(), _pooled_spread(test['spread']),
                  test['coverage'].mean()))
+    elif opt.metric == 'spectrum':
+        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
+        dev = eval_spectrum(dev_dataset, model, opt.n_samples)
+        test = eval_spectrum(test_dataset, model, opt.n_samples)
+        arrays = dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1]))
+        for split, res in (('dev', dev), ('test', test)):
+            arrays.update(('%s_%s' % (split, k), np.asarray(v, dtype=np.float64)) for k, v in res.items())
+        np.savez(os.path.join(opt.res_dir, 'spectrum.npz'), **arrays)
+        print("DEV_LSD_B: %.4f, TEST_LSD_B: %.4f, TEST_LSD_MEAN_B: %.4f, TEST_LSD_A: %.4f"
+              % (dev['lsd_B'], test['lsd_B'], test['lsd_mean_B'], test['lsd_A']))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

@@ -417,6 +417,21 @@ int acg_ensemble_stats(const float *x, const float *y, int N, int M, size_t npix
                        float *mean, float *stdev, float *quant, float *crps_map, float *sums, unsigned *rank_hist,
                        void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum; no reference call site: the
+ *      reference has no spectral code, tests/spectrum_ref.py states the definition) ----
+ * x: rows x C real fields of S x S fp32 pixels; pixel (h, w) of channel c of row r is x[r row_stride + c chan_stride +
+ * (h S + w) pix_stride] (strides in floats): NHWC with Cp stored channels is (S S Cp, Cp, 1) - padded channels are never
+ * read into a result - and planar NCHW is (C S S, 1, S S).  S: a power of two, 16 .. 1024; anything else is refused before a
+ * launch.  Per field F = fft2(x) (unnormalised, no taper, no mean removal), P = |F|^2 / S^2; with signed integer wavenumbers
+ * (fx, fy) and s = fx^2 + fy^2 the cell's bin is 0 for s = 0, else the largest b with b (b - 1) < s (sqrt(s) rounded to
+ * nearest); psd (rows, C, S/2 + 1): the mean of P over the cells of bins 0 .. S/2, the corners beyond are dropped.
+ * fp32 transform, ring sums in double in a fixed order: deterministic, no float atomics, the same bits for every layout.
+ * S <= 128 needs no workspace (one workgroup per field, nothing but psd is written); above, the workspace
+ * (acg_radial_spectrum_workspace_bytes, 16-byte aligned) holds the half spectrum between the row and the column pass. */
+size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S);
+int acg_radial_spectrum(const float *x, int rows, int C, int S, long long row_stride, int pix_stride, long long chan_stride,
+                        float *psd, void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
