@@ -3,11 +3,12 @@
 
 Every layer class keeps the torch.nn parameter layout (OIHW weights, etc.) so reference
 checkpoints load unchanged; `forward` on NCHW tensors is provided for drop-in use of a single
-module, while the networks run the fused NHWC pipeline in `run_sequence` below (conv + bias +
+module, while the networks run the fused NHWC pipeline of `plan_sequence` / `_run_stages` below (conv + bias +
 activation in one kernel; norm + activation (+ residual add) in one pass).
 """
 import functools  # noqa: F401  (kept: reference modules export it implicitly via networks)
 
+import collections
 import ctypes
 
 import torch
@@ -107,21 +108,10 @@ class Conv2d(nn.Conv2d, _Cached):
     def packed(self):
         return self._cached(lambda: ops.PackedConv(self.weight, self.bias, cpad(self.in_channels), cpad(self.out_channels)))
 
-    def forward_nhwc(self, x, act=ACT_NONE, reflect_pad=0, want_stats=None, want_identity=False, link_out=None,
-                     link_in=None, skip_grad=None, s16=None, norm_sums=None):
-        if reflect_pad:
-            pad, mode = reflect_pad, PAD_REFLECT
-        else:
-            pad, mode = self.padding[0], PAD_ZERO
+    def forward_nhwc(self, x, act=ACT_NONE, reflect_pad=0, fusion=None):
+        pad, mode = (reflect_pad, PAD_REFLECT) if reflect_pad else (self.padding[0], PAD_ZERO)
         x = restore_width(x, self.packed().Cis)
-        out = ops.Conv2dFn.apply(x, self.weight, self.bias, self.packed(), self.stride[0], pad, mode, act, want_stats,
-                                 want_identity, link_out, link_in, skip_grad, s16, norm_sums)
-        if s16 is not None and s16.x:   # tag what left the convolution pre-split: its output (conv + ReLU) and the alias of x
-            if want_identity:
-                ops.tag_s16(out[1])
-            if s16.y:
-                ops.tag_s16(out[0] if want_identity else out)
-        return out
+        return ops.Conv2dFn.apply(x, self.weight, self.bias, self.packed(), self.stride[0], pad, mode, act, fusion)
 
     def dgrad_sums_ok(self, x):
         """does this (zero-padded) convolution's data gradient, for an NHWC input of x's shape, emit the backward sums of a norm
@@ -233,6 +223,40 @@ class Linear(nn.Linear):
         return self.forward_act(input)
 
 
+class _Planned(object):
+    """Mixin of the layer containers: the layer plan of the children, parsed once and again when a child is replaced.  A
+    plain attribute: state_dict, repr and modules() do not see it."""
+    _acg_plan = None
+
+    def _planned(self):   # -> (the module list the plan describes, its parser)
+        return tuple(self._modules.values()), plan_sequence
+
+    def layer_plan(self):
+        mods, parse = self._planned()
+        if self._acg_plan is None or self._acg_plan[0] != mods:   # (modules compare by identity)
+            self._acg_plan = (mods, parse(mods))
+        return self._acg_plan[1]
+
+
+class _PlannedSequence(_Planned):
+    def run_nhwc(self, x, C, z=None):
+        """the children on an NHWC C16 tensor of C real channels (z: the latent) -> (tensor, real channel count)"""
+        return _run_stages(self.layer_plan(), x, C, z)
+
+
+class _PlannedBlock(_Planned):
+    """Mixin of the residual blocks: out = ReLU(x + conv_block(x)) (modules.py:185-188, 232-235)"""
+
+    def _planned(self):
+        return tuple(self.conv_block._modules.values()), plan_block
+
+    def s16_ok(self, x):
+        return _block_s16_ok(self, x)
+
+    def forward_nhwc(self, x, z=None, last=False):
+        return _run_block(self, x, z, last)
+
+
 ######################################################################
 # Superclass of all Modules that take two inputs  (modules.py:15-17)
 ######################################################################
@@ -253,7 +277,7 @@ class MergeModule(TwoInputModule):
         return self.module2.forward(self.module1.forward(input1), input2)
 
 
-class TwoInputSequential(nn.Sequential, TwoInputModule):
+class TwoInputSequential(nn.Sequential, TwoInputModule, _PlannedSequence):
     """nn.Sequential that threads `input2` to every TwoInputModule child (modules.py:44-56)."""
 
     def __init__(self, *args):
@@ -261,17 +285,14 @@ class TwoInputSequential(nn.Sequential, TwoInputModule):
 
     def forward(self, input1, input2):
         x = ops.ToNHWC.apply(input1, _starts_with_conv(self))
-        y, C = run_sequence(list(self._modules.values()), x, input1.shape[1], cond_bank(self, as_latent(input2)))
+        y, C = self.run_nhwc(x, input1.shape[1], cond_bank(self, as_latent(input2)))
         return ops.ToNCHW.apply(y, C)
 
 
 def _starts_with_conv(seq):
     """does the layer list take its input straight into a Conv2d (then an image input may be stored C4, ops.cimg)?"""
-    for m in seq._modules.values():
-        if isinstance(m, nn.ReflectionPad2d):
-            continue
-        return isinstance(m, Conv2d) or (isinstance(m, MergeModule) and isinstance(m.module1, Conv2d))
-    return False
+    first = seq.layer_plan()[:1]
+    return bool(first) and isinstance(first[0], ConvStage) and isinstance(first[0].conv, Conv2d)
 
 
 def as_latent(z):
@@ -387,148 +408,162 @@ def _act_of(m):
     return None
 
 
-def run_sequence(mods, x, C, z=None, res=None, last_block=False):
-    """Interpret a reference-style layer list on an NHWC C16 tensor with peephole fusion:
-         [ReflectionPad2d] Conv2d|ConvTranspose2d|MergeModule(conv, CondIN) [norm] [activation]
-    `res`: residual input folded into the LAST norm of the list together with a ReLU
-    (ResnetBlock / CINResnetBlock: out = ReLU(x + conv_block(x)), modules.py:185-188, 232-235); `last_block`: no block
-    follows this one, so a pre-split block writes its output fp32 (what the layer behind the trunk reads).
-    Returns (tensor, real channel count)."""
-    i, n = 0, len(mods)
-    last_norm = max([k for k, m in enumerate(mods) if isinstance(m, (InstanceNorm, CondInstanceNorm, BatchNorm2d))
-                     or (isinstance(m, MergeModule))] + [-1]) if res is not None else -1
-    reflect = 0
-    skip_routed = False
-    relu_link = None   # set by a conv+ReLU whose output goes straight into the next convolution (ops.ReluLink)
-    skip_grad = None   # ops.SkipGrad slot shared by the block's first convolution and its last norm
-    # Pre-split ("S16") storage of the residual trunk (ops.S16Plan): the norm in front of the first block writes its
-    # output pre-split when that block can take it, every tensor a 3x3 trunk convolution reads stays pre-split from there
-    # (block outputs, conv + ReLU outputs, the gradients the norms and the fused data gradients write), and the first
-    # last block writes its output fp32 for the layer behind it (a block that cannot know it is last — called on its own —
-    # leaves a pre-split tensor, decoded here).  s16 = this list is the inside of such a block.
-    s16 = res is not None and ops.is_s16(x)
-    nconv = 0
-    # ops.NormSums: a norm whose pre-split output goes to ONE trunk convolution (inside a block: the next convolution of the
-    # list; a block's output or the norm in front of the first block: the next block's first convolution, whose data gradient
-    # already includes the skip gradient) shares a slot with it — the slot travels on the tensor between blocks
-    ns_prev = getattr(x, "_acg_ns", None) if s16 else None
-    while i < n:
+_INSTANCE_NORMS = (InstanceNorm, CondInstanceNorm)   # the norms that take a ConvStats / NormSums slot and write pre-split
+
+# One `[ReflectionPad2d] Conv2d|ConvTranspose2d|MergeModule(conv, CondIN) [norm] [activation] [Dropout]` group of a layer list.
+# reflect: pad width (0: the convolution's zero padding); act: ACT_* code; dropout: the nn.Dropout or None (--use_dropout:
+# behind the first ReLU of a residual block, modules.py:167-168, 214-215); and what stands behind the group:
+#   relu_feeds_conv: a conv + ReLU without a norm whose next convolution, an optional ReflectionPad2d in between, is a Conv2d
+#                    (that one's data gradient can apply this ReLU's mask: ops.ReluLink)
+#   next_conv:       the Conv2d that is the very next module, else None (its data gradient can leave the norm's ops.NormSums)
+#   next_block:      the residual block that is the very next module, else None (the norm may write pre-split for it)
+ConvStage = collections.namedtuple("ConvStage", "reflect conv norm act dropout relu_feeds_conv next_conv next_block")
+BlockStage = collections.namedtuple("BlockStage", "block last")   # a residual block; last: no block follows it
+
+
+def plan_sequence(mods):
+    """Parse a reference-style layer list into a tuple of ConvStage / BlockStage records.  Structure only, from the modules
+    alone: no tensor, no ops.* switch, no train / eval mode.  A list the executors cannot run raises NotImplementedError;
+    that includes an nn.Dropout anywhere but directly behind a convolution group (no network here builds one)."""
+    mods, blocks = list(mods) + [None, None], (ResnetBlock, CINResnetBlock)
+    stages, reflect, i = [], 0, 0
+    while mods[i] is not None:
         m = mods[i]
+        i += 1
         if isinstance(m, nn.ReflectionPad2d):
             reflect = m.padding[0]
-            i += 1
-            continue
-        if isinstance(m, nn.Dropout):   # --use_dropout: behind the first ReLU of a residual block (modules.py:167-168, 214-215)
-            if m.training and m.p > 0.0:
-                if ops.is_s16(x):
-                    raise NotImplementedError("dropout on a pre-split tensor")
-                x = ops.DropoutFn.apply(x, C, m.p)
-            i += 1
-            continue
-        if isinstance(m, (ResnetBlock, CINResnetBlock)):
-            x = m.forward_nhwc(x, z, last=not (i + 1 < n and isinstance(mods[i + 1], (ResnetBlock, CINResnetBlock))))
-            ns_prev = None   # (the slot of the norm in front of the trunk belongs to the first block's first convolution)
-            i += 1
-            continue
-        if res is None and ops.is_s16(x):
-            x = ops.S16Decode.apply(x)
-        conv, norm, stats = None, None, None
-        if isinstance(m, MergeModule):
-            conv, norm = m.module1, m.module2
-            i += 1
-        elif isinstance(m, (Conv2d, ConvTranspose2d)):
-            conv = m
-            i += 1
-            if i < n and isinstance(mods[i], (InstanceNorm, CondInstanceNorm, BatchNorm2d)):
-                norm = mods[i]
-                i += 1
+        elif isinstance(m, blocks):
+            stages.append(BlockStage(m, not isinstance(mods[i], blocks)))
         else:
-            raise NotImplementedError("run_sequence: unexpected layer %s" % type(m).__name__)
-        norm_idx = i - 1
-        act = ACT_NONE
-        if i < n and _act_of(mods[i]) is not None:
-            act = _act_of(mods[i])
-            i += 1
-        # convolution (activation fused only when no norm follows)
-        cact = act if norm is None else ACT_NONE
-        if isinstance(conv, ConvTranspose2d):
-            if reflect:
+            if isinstance(m, MergeModule):
+                conv, norm = m.module1, m.module2
+            elif isinstance(m, (Conv2d, ConvTranspose2d)):
+                conv, norm = m, None
+                if isinstance(mods[i], _INSTANCE_NORMS + (BatchNorm2d,)):
+                    norm, i = mods[i], i + 1
+            else:
+                raise NotImplementedError("run_sequence: unexpected layer %s" % type(m).__name__)
+            if reflect and isinstance(conv, ConvTranspose2d):
                 raise NotImplementedError("reflection pad before ConvTranspose2d")
-            stats = ops.ConvStats() if isinstance(norm, (InstanceNorm, CondInstanceNorm)) else None
+            act = ACT_NONE
+            if _act_of(mods[i]) is not None:
+                act, i = _act_of(mods[i]), i + 1
+            nxt = mods[i]
+            after_pad = mods[i + 1] if isinstance(nxt, nn.ReflectionPad2d) else nxt
+            stages.append(ConvStage(reflect, conv, norm, act, nxt if isinstance(nxt, nn.Dropout) else None,
+                                    norm is None and act == ACT_RELU and isinstance(after_pad, Conv2d),
+                                    nxt if isinstance(nxt, Conv2d) else None, nxt if isinstance(nxt, blocks) else None))
+            reflect = 0
+            if isinstance(nxt, nn.Dropout):
+                i += 1
+    return tuple(stages)
+
+
+def plan_block(mods):
+    """plan_sequence of the inside of a residual block, checked to be the two stages the block executor names directly:
+    [pad] conv [norm] [act] [Dropout], [pad] conv norm — the second norm takes the residual and the block's ReLU."""
+    stages = plan_sequence(mods)
+    if len(stages) != 2 or not all(isinstance(st, ConvStage) and isinstance(st.conv, Conv2d) for st in stages):
+        raise NotImplementedError("residual block: expected [pad] conv [norm] [act] [Dropout], [pad] conv norm")
+    if stages[1].norm is None or stages[1].act != ACT_NONE or stages[1].dropout is not None:
+        raise NotImplementedError("residual fusion expects the block to end with its norm")
+    if isinstance(stages[1].norm, CondInstanceNorm):
+        raise NotImplementedError("residual after CondInstanceNorm")
+    return stages
+
+
+def _norm_act(norm, x, z, act, stats, emit=False, s16=False, sums=False, res=None, lazy_dres=None):
+    """the norm (+ activation, + residual) of a stage.  stats: the ConvStats slot the convolution in front got; emit / s16: output
+    / incoming gradient pre-split; sums: share an ops.NormSums slot with the ONE convolution that reads the output (`_acg_ns`)"""
+    if not isinstance(norm, _INSTANCE_NORMS):   # BatchNorm2d (--norm batch; E_B always)
+        return norm.forward_act(x, act, res)
+    part = stats.part if stats is not None else None
+    ns = ops.NormSums() if sums else None
+    if isinstance(norm, CondInstanceNorm):
+        x = norm.forward_act(x, z, act, part, emit, s16, ns)
+    else:
+        x = norm.forward_act(x, act, res, lazy_dres, part, emit, s16, ns)
+    if ns is not None:
+        x._acg_ns = ns
+    return x
+
+
+def _drop(dropout, x, C):
+    if dropout is not None and dropout.training and dropout.p > 0.0:
+        if ops.is_s16(x):
+            raise NotImplementedError("dropout on a pre-split tensor")
+        x = ops.DropoutFn.apply(x, C, dropout.p)
+    return x
+
+
+def _run_stages(plan, x, C, z=None):
+    """Run the plan of a plain layer list (generator, discriminator, encoder) on an NHWC C16 tensor of C real channels ->
+    (tensor, real channel count).  Pre-split ("S16") trunk (ops.S16Plan): the norm in front of the first block writes pre-split
+    when that block can take it, the blocks keep it so, and the last one writes fp32 (what a block called on its own, which
+    cannot know it is last, leaves pre-split is decoded here)."""
+    link = None   # ops.ReluLink of a conv + ReLU whose output goes straight into the next stage's convolution
+    for st in plan:
+        if isinstance(st, BlockStage):
+            x = st.block.forward_nhwc(x, z, last=st.last)
+            continue
+        if ops.is_s16(x):
+            x = ops.S16Decode.apply(x)
+        conv, norm, instance = st.conv, st.norm, isinstance(st.norm, _INSTANCE_NORMS)
+        stats = ops.ConvStats() if instance else None   # the norm can take its statistics from the convolution's epilogue
+        cact = st.act if norm is None else ACT_NONE     # (activation fused into the convolution only when no norm follows)
+        if isinstance(conv, ConvTranspose2d):
             x = conv.forward_nhwc(x, cact, stats)
-        else:  # an (Cond)InstanceNorm right behind the conv can take its statistics from the conv epilogue
-            skip_here = res is not None and not skip_routed and x is res  # the block's FIRST convolution
-            link_in, relu_link = relu_link, None
-            link_out = None
-            if cact == ACT_RELU:  # pad-conv-ReLU-pad-conv: the next convolution's data gradient applies this ReLU's mask
-                k = i + 1 if (i < n and isinstance(mods[i], nn.ReflectionPad2d)) else i
-                if k < n and isinstance(mods[k], Conv2d):
-                    link_out = relu_link = ops.ReluLink()
-            stats = ops.ConvStats() if isinstance(norm, (InstanceNorm, CondInstanceNorm)) else None
-            if skip_here:
-                skip_grad = ops.SkipGrad()
-            plan = None
-            if s16:
-                # first convolution: writes pre-split iff it is a conv + ReLU (then its dy arrives pre-split and masked from the
-                # next convolution's data gradient), dx fp32 + skip gradient; second: dy pre-split from the block-output norm,
-                # dx pre-split with the first one's ReLU mask where that link exists (else fp32 for the norm in between)
-                plan = ops.S16Plan(x=True, y=(cact == ACT_RELU and link_out is not None), gy=norm is not None,
-                                   dx=(nconv > 0 and link_in is not None))
-                if nconv == 0 and not skip_here:
-                    raise NotImplementedError("pre-split trunk: the block's first layer must be its first convolution")
-            nconv += 1
-            # (outside the trunk: a norm + ReLU whose output goes to this convolution alone left its slot on the tensor — taken
-            # where the data gradient runs on the row pipeline, acg_conv2d_bwd_data_sums_supported)
-            if plan is None and res is None and ns_prev is None:
-                ns_prev = getattr(x, "_acg_ns", None)
-            ns_conv, ns_prev = (ns_prev if ((plan is not None and (skip_here or nconv > 1)) or (plan is None and res is None)) else None), None
-            x = conv.forward_nhwc(x, cact, reflect, stats, skip_here, link_out, link_in, skip_grad if skip_here else None, plan,
-                                  ns_conv)
-            if skip_here:  # the skip connection continues from the conv's identity output: its gradient is added
-                x, res = x  # inside that conv's data-gradient epilogue
-                skip_routed = True
-        reflect = 0
+        else:   # (norm_sums: a norm whose output goes to this convolution alone left its slot on the tensor)
+            link_in, link = link, (ops.ReluLink() if st.relu_feeds_conv else None)
+            fusion = ops.ConvFusion(stats, link_out=link, link_in=link_in, norm_sums=getattr(x, "_acg_ns", None))
+            x = conv.forward_nhwc(x, cact, st.reflect, fusion)
         C = conv.out_channels
         if norm is not None:
-            fuse_res = res is not None and norm_idx == last_norm
-            if fuse_res and act != ACT_NONE:
-                raise NotImplementedError("residual fusion expects the block to end with its norm")
-            # pre-split output: inside a pre-split block always (its consumer is a trunk convolution or the next block);
-            # outside, when the next module is a block that can take it
-            emit = s16 and not (fuse_res and last_block)
-            if not s16 and res is None and act == ACT_RELU and i < n and isinstance(mods[i], (ResnetBlock, CINResnetBlock)) \
-                    and isinstance(norm, (InstanceNorm, CondInstanceNorm)):
-                emit = mods[i].s16_ok(x)
-            # outside the trunk: the next layer is a zero-padded convolution whose data gradient (the gradient w.r.t. this norm's
-            # output) can leave the norm's backward sums (ops.NormSums on fp32 tensors)
-            rows_ns = (not s16 and res is None and not emit and ops.NORM_SUMS and act in (ACT_NONE, ACT_RELU) and i < n
-                       and isinstance(mods[i], Conv2d) and isinstance(norm, (InstanceNorm, CondInstanceNorm))
-                       and mods[i].dgrad_sums_ok(x))
-            if isinstance(norm, CondInstanceNorm):
-                if fuse_res:
-                    raise NotImplementedError("residual after CondInstanceNorm")
-                if s16 and act != ACT_RELU:
-                    raise NotImplementedError("pre-split trunk: CondInstanceNorm without ReLU")
-                ns_prev = ops.NormSums() if (emit or rows_ns) else None
-                x = norm.forward_act(x, z, act, stats.part if stats is not None else None, emit, s16, ns_prev)
-                if ns_prev is not None:
-                    x._acg_ns = ns_prev
-            elif isinstance(norm, InstanceNorm):
-                # skip_routed: `res` is the identity output of the block's first convolution, i.e. its gradient goes to that
-                # convolution's data-gradient epilogue and nowhere else -> it may stay un-materialised (ops.NormAct lazy_dres)
-                if s16 and not (fuse_res and skip_routed):
-                    raise NotImplementedError("pre-split trunk: InstanceNorm that is not the block output")
-                ns_prev = ops.NormSums() if (emit or rows_ns) else None
-                x = norm.forward_act(x, ACT_RELU if fuse_res else act, res if fuse_res else None,
-                                     skip_grad if (fuse_res and skip_routed) else None, stats.part if stats is not None else None,
-                                     emit, s16, ns_prev)
-                if ns_prev is not None:
-                    x._acg_ns = ns_prev
-            else:   # BatchNorm2d (--norm batch; E_B always): a block-output norm takes the residual + ReLU in its apply pass
-                x = norm.forward_act(x, ACT_RELU if fuse_res else act, res if fuse_res else None)
-    if res is None and ops.is_s16(x):   # the list ended with a block
+            # pre-split output when the next module is a block that can take it; else, when it is a zero-padded convolution
+            # whose data gradient runs on the row pipeline, that gradient can leave this norm's backward sums
+            emit = st.act == ACT_RELU and st.next_block is not None and instance and st.next_block.s16_ok(x)
+            rows_ns = (not emit and ops.NORM_SUMS and st.act in (ACT_NONE, ACT_RELU) and st.next_conv is not None
+                       and instance and st.next_conv.dgrad_sums_ok(x))
+            x = _norm_act(norm, x, z, st.act, stats, emit, False, emit or rows_ns)
+        x = _drop(st.dropout, x, C)
+    if ops.is_s16(x):   # the list ended with a block
         x = ops.S16Decode.apply(x)
     return x, C
+
+
+def _run_block(block, x, z, last):
+    """out = ReLU(x + conv_block(x)) of a residual block (plan_block).  A pre-split input (ops.is_s16) keeps every tensor a
+    3x3 trunk convolution reads pre-split: the conv + ReLU output, the block output unless `last` (no block follows: the
+    layer behind the trunk reads fp32), and the gradients the norms and the fused data gradients write."""
+    st1, st2 = block.layer_plan()
+    s16 = ops.is_s16(x)
+    # first convolution: its identity output continues the skip connection, so the skip gradient is added in its data gradient's
+    # epilogue, un-materialised through the SkipGrad slot shared with the output norm.  Pre-split, it writes pre-split iff it is a
+    # conv + ReLU (its dy then arrives pre-split, masked by the second one's data gradient) and holds the NormSums slot x carries.
+    norm, skip_grad = st1.norm, ops.SkipGrad()
+    stats = ops.ConvStats() if isinstance(norm, _INSTANCE_NORMS) else None
+    link = ops.ReluLink() if st1.relu_feeds_conv else None
+    split = ops.S16Plan(x=True, y=link is not None, gy=norm is not None, dx=False) if s16 else None
+    fusion = ops.ConvFusion(stats, True, link, None, skip_grad, split, getattr(x, "_acg_ns", None) if s16 else None)
+    x, res = st1.conv.forward_nhwc(x, st1.act if norm is None else ACT_NONE, st1.reflect, fusion)
+    if s16:   # tag what left the convolution pre-split: the alias of x and, for a conv + ReLU, its output
+        res, x = ops.tag_s16(res), (ops.tag_s16(x) if split.y else x)
+    if norm is not None:
+        if s16 and isinstance(norm, CondInstanceNorm) and st1.act != ACT_RELU:
+            raise NotImplementedError("pre-split trunk: CondInstanceNorm without ReLU")
+        if s16 and isinstance(norm, InstanceNorm):
+            raise NotImplementedError("pre-split trunk: InstanceNorm that is not the block output")
+        x = _norm_act(norm, x, z, st1.act, stats, s16, s16, s16)
+    x = _drop(st1.dropout, x, st1.conv.out_channels)
+    # second convolution: dy pre-split from the output norm, dx pre-split with the first one's ReLU mask where that link
+    # exists (else fp32 for the norm in between, whose NormSums slot it then holds)
+    stats = ops.ConvStats() if isinstance(st2.norm, _INSTANCE_NORMS) else None
+    split = ops.S16Plan(x=True, y=False, gy=True, dx=link is not None) if s16 else None
+    fusion = ops.ConvFusion(stats, link_in=link, s16=split, norm_sums=getattr(x, "_acg_ns", None) if s16 else None)
+    x = st2.conv.forward_nhwc(x, ACT_NONE, st2.reflect, fusion)
+    # output norm: residual + ReLU in its apply pass; pre-split, with a NormSums slot for the next block's first convolution
+    emit = s16 and not last
+    return _norm_act(st2.norm, x, z, ACT_RELU, stats, emit, s16, emit, res, skip_grad)
 
 
 def _block_s16_ok(block, x):
@@ -537,14 +572,10 @@ def _block_s16_ok(block, x):
     key = (tuple(x.shape), ops.CONFIG_EPOCH, ops.S16_ENABLED)
     cache = block.__dict__.setdefault("_acg_s16_ok", {})
     if key not in cache:
-        mods = list(block.conv_block._modules.values())
-        convs = [m.module1 if isinstance(m, MergeModule) else m for m in mods if isinstance(m, (Conv2d, MergeModule))]
-        pads = [m for m in mods if isinstance(m, nn.ReflectionPad2d)]
+        stages = block.layer_plan()
         N, H, W, C = x.shape
-        ok = (len(convs) == 2 and len(pads) == 2 and all(p.padding[0] == 1 for p in pads)
-              and not any(isinstance(m, nn.Dropout) for m in mods)
-              and all(c.kernel_size[0] == 3 and c.stride[0] == 1 and c.padding[0] == 0 and c.in_channels == C
-                      and c.out_channels == C for c in convs)
+        ok = (all(st.reflect == 1 and st.dropout is None and st.conv.kernel_size[0] == 3 and st.conv.stride[0] == 1
+                  and st.conv.padding[0] == 0 and st.conv.in_channels == C and st.conv.out_channels == C for st in stages)
               and ops.conv_s16_supported(N, H, W, C, 3, 1, PAD_REFLECT))
         cache[key] = bool(ok)
     return cache[key]
@@ -576,7 +607,7 @@ def _dropout(use_dropout):
 ######################################################################
 # CINResnetBlock  (modules.py:139-188)
 ######################################################################
-class CINResnetBlock(TwoInputModule):
+class CINResnetBlock(TwoInputModule, _PlannedBlock):
     def __init__(self, x_dim, z_dim, padding_type, norm_layer, use_dropout, use_bias):
         super(CINResnetBlock, self).__init__()
         self.conv_block = self.build_conv_block(x_dim, z_dim, padding_type, norm_layer, use_dropout, use_bias)
@@ -595,13 +626,6 @@ class CINResnetBlock(TwoInputModule):
                   [conv(), InstanceNorm2d(x_dim, affine=True)]]
         return TwoInputSequential(*[m for st in stages for m in _pad_front(padding_type) + st])
 
-    def s16_ok(self, x):
-        return _block_s16_ok(self, x)
-
-    def forward_nhwc(self, x, z, last=False):
-        y, _ = run_sequence(list(self.conv_block._modules.values()), x, None, z, res=x, last_block=last)
-        return y
-
     def forward(self, x, noise):
         C = x.shape[1]
         return ops.ToNCHW.apply(self.forward_nhwc(ops.ToNHWC.apply(x), as_latent(noise)), C)
@@ -610,7 +634,7 @@ class CINResnetBlock(TwoInputModule):
 ######################################################################
 # ResnetBlock  (modules.py:193-235): pad-conv-ReLU-pad-conv-IN ; ReLU(x + out)
 ######################################################################
-class ResnetBlock(nn.Module):
+class ResnetBlock(nn.Module, _PlannedBlock):
     def __init__(self, dim, padding_type, norm_layer, use_dropout, use_bias):
         super(ResnetBlock, self).__init__()
         self.conv_block = self.build_conv_block(dim, padding_type, norm_layer, use_dropout, use_bias)
@@ -623,26 +647,19 @@ class ResnetBlock(nn.Module):
                   [conv(), norm_layer(dim)]]
         return Sequential(*[m for st in stages for m in _pad_front(padding_type) + st])
 
-    def s16_ok(self, x):
-        return _block_s16_ok(self, x)
-
-    def forward_nhwc(self, x, z=None, last=False):
-        y, _ = run_sequence(list(self.conv_block._modules.values()), x, None, None, res=x, last_block=last)
-        return y
-
     def forward(self, x):
         C = x.shape[1]
         return ops.ToNCHW.apply(self.forward_nhwc(ops.ToNHWC.apply(x)), C)
 
 
-class Sequential(nn.Sequential):
+class Sequential(nn.Sequential, _PlannedSequence):
     """nn.Sequential whose forward (NCHW in / NCHW out) runs the fused HIP pipeline."""
 
     def forward(self, input):
         if input.dim() == 2:
             return run_dense(list(self._modules.values()), input)
         x = ops.ToNHWC.apply(input, _starts_with_conv(self))
-        y, C = run_sequence(list(self._modules.values()), x, input.shape[1])
+        y, C = self.run_nhwc(x, input.shape[1])
         return ops.ToNCHW.apply(y, C)
 
 

@@ -19,8 +19,8 @@ import torch.nn as nn
 
 from . import modules, ops
 from .modules import (ResnetBlock, CondInstanceNorm, TwoInputSequential, CINResnetBlock, InstanceNorm2d,  # noqa: F401
-                      Conv2d, ConvTranspose2d, BatchNorm2d, BatchNorm1d, Linear, Sequential, run_sequence,
-                      run_dense, as_latent, mark_dirty, cond_bank)
+                      Conv2d, ConvTranspose2d, BatchNorm2d, BatchNorm1d, Linear, Sequential, run_dense, as_latent, mark_dirty,
+                      cond_bank)
 
 
 ###############################################################################
@@ -157,7 +157,7 @@ class CINResnetGenerator(nn.Module):
 
     def forward_nhwc(self, x, z):
         """x: NHWC C16, z: (N, >=nlatent) -> NHWC C16 (output_nc valid channels)"""
-        return run_sequence(list(self.model._modules.values()), x, self.input_nc, cond_bank(self.model, z))[0]
+        return self.model.run_nhwc(x, self.input_nc, cond_bank(self.model, z))[0]
 
     def forward(self, input, noise):
         return self.model(input, noise)
@@ -177,7 +177,7 @@ class ResnetGenerator(nn.Module):
         self.model = Sequential(*_generator_layers(norm_layer, input_nc, output_nc, ngf, n_blocks, block))
 
     def forward_nhwc(self, x):
-        return run_sequence(list(self.model._modules.values()), x, self.input_nc)[0]
+        return self.model.run_nhwc(x, self.input_nc)[0]
 
     def forward(self, input):
         return self.model(input)
@@ -201,7 +201,7 @@ def _patch_discriminator(input_nc, ndf, norm_layer, use_sigmoid, specs, head):
 
 class _ImageD(nn.Module):
     def forward_nhwc(self, x):
-        return run_sequence(list(self.model._modules.values()), x, None)[0]
+        return self.model.run_nhwc(x, None)[0]
 
     def forward(self, input):
         return self.model(input)
@@ -302,7 +302,7 @@ class LatentEncoder(nn.Module):
 
     def forward_nhwc(self, x):
         """x: NHWC C16 -> (mu, logvar), each (N, cpad(nlatent)) with nlatent valid columns"""
-        h = run_sequence(list(self.conv_modules._modules.values()), x, None)[0]
+        h = self.conv_modules.run_nhwc(x, None)[0]
         return ops.SpatialMean.apply(self.enc_mu.forward_nhwc(h)), ops.SpatialMean.apply(self.enc_logvar.forward_nhwc(h))
 
     def forward(self, input):

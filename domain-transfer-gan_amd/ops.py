@@ -7,6 +7,7 @@ carried as torch tensors of shape (N, H, W, Cp) — or (N, Cp) for latent / MLP 
 
 There is no CPU path: tensors must live on a ROCm device and the library must load.
 """
+import collections
 import ctypes
 
 import torch
@@ -306,7 +307,7 @@ CONV_STATS_ENABLED = True  # False: the unfused path (the tests' reference)
 
 
 class ConvStats(object):
-    """Slot the caller hands to a convolution AND to the (Cond)InstanceNorm behind it (modules.run_sequence): where the
+    """Slot the caller hands to a convolution AND to the (Cond)InstanceNorm behind it (modules._run_stages / _run_block): where the
     kernel supports it the convolution's epilogue emits the norm's per-tile statistics (acg_conv2d_fwd_stats) and leaves
     them here: `part` [N][Ho*Wo/STATS_ROWS][2][Co] (mean, M2 per 128-pixel tile), else None."""
 
@@ -373,7 +374,7 @@ LAZY_DRES = True   # False: the unfused path (the tests' reference; SkipGrad)
 
 
 class NormSums(object):
-    """Slot shared by a (Cond)InstanceNorm and THE convolution that consumes its output (modules.run_sequence): the
+    """Slot shared by a (Cond)InstanceNorm and THE convolution that consumes its output (modules._run_stages / _run_block): the
     convolution's data gradient is the gradient w.r.t. the norm's output, and where its kernel supports it
     (acg_conv2d_bwd_data_s16_sums) the epilogue leaves the first pass of the norm's backward — per-tile sums of gy and
     gy * xhat — in `part`, so the norm's backward skips its own pass over dy and x.  The norm fills what the kernel needs at
@@ -485,17 +486,43 @@ class S16Encode(torch.autograd.Function):
         return g
 
 
+# What a Conv2d shares with its neighbours (None in place of the record = a plain convolution): the slots documented at
+# ConvStats (want_stats), SkipGrad, ReluLink (link_out / link_in), S16Plan (s16) and NormSums.  want_identity: also return x
+# itself as a second output; a ResnetBlock feeds that alias to its skip connection, so the skip gradient arrives at the
+# convolution and is added inside the data-gradient epilogue (acg_conv2d_bwd_data_add) instead of by an autograd accumulation.
+ConvFusion = collections.namedtuple("ConvFusion", "want_stats want_identity link_out link_in skip_grad s16 norm_sums",
+                                    defaults=(None, False, None, None, None, None, None))
+
+
+def _weight_grad(ctx, entry, x, g, nbias, st, timed=True):
+    """the weight (and bias, `nbias` long) gradient of a convolution Function through library entry point `entry`: added
+    straight into .grad where the parameters take that (-> None, None), else returned as fresh tensors"""
+    d, pk = ctx.d, ctx.packed
+    direct = _direct_grad(ctx.wparam, ctx.bparam)
+    if direct is not None:
+        dw, db = direct
+    else:
+        dw = torch.empty((pk.Or, pk.Ir, pk.K, pk.K), device=x.device, dtype=torch.float32)
+        db = torch.empty(nbias, device=x.device, dtype=torch.float32) if ctx.has_bias else None
+    nb = _lib.query("acg_conv2d_bwd_weight_workspace_bytes", ctypes.byref(d))
+    ws = workspace(nb)
+    span = ConvTimer.span("wgrad", d) if timed else None
+    _lib.call(entry, ctypes.byref(d), _ptr(x), _ptr(g), _ptr(dw), _ptr(db), pk.Or, pk.Ir, _ptr(ws), nb,
+              1 if direct is not None else 0, st)
+    if timed:
+        span.done()
+    if direct is None:
+        return dw, db
+    _grads_done(ctx.wparam, ctx.bparam)
+    return None, None
+
+
 class Conv2dFn(torch.autograd.Function):
-    """nn.Conv2d (+ preceding ReflectionPad2d) + bias + fused activation.  want_stats (a ConvStats slot or None): the
-    caller runs an (Cond)InstanceNorm on the output next — where the kernel supports it the epilogue emits that norm's
-    per-tile partial statistics, saving the norm one read of the tensor.  want_identity: also return x itself as a second
-    output; a ResnetBlock feeds that alias to its skip connection, so the skip gradient arrives HERE and is added
-    inside the data-gradient epilogue (acg_conv2d_bwd_data_add) instead of by a separate autograd accumulation;
-    skip_grad (a SkipGrad slot or None) lets that gradient arrive un-materialised.  link_out / link_in: ReluLink."""
+    """nn.Conv2d (+ preceding ReflectionPad2d) + bias + fused activation; `fusion`: a ConvFusion or None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, packed, stride, pad, pad_mode, act, want_stats=None, want_identity=False,
-                link_out=None, link_in=None, skip_grad=None, s16=None, norm_sums=None):
+    def forward(ctx, x, weight, bias, packed, stride, pad, pad_mode, act, fusion=None):
+        want_stats, want_identity, link_out, link_in, skip_grad, s16, norm_sums = fusion or ConvFusion()
         x = x.contiguous()
         _check(x)
         N, Hi, Wi, Ci = x.shape
@@ -602,103 +629,70 @@ class Conv2dFn(torch.autograd.Function):
                     dx = dx + dskip
             span.done()
         if ctx.needs_input_grad[1]:
-            direct = _direct_grad(ctx.wparam, ctx.bparam)
-            if direct is not None:
-                dw, db = direct
+            dw, db = _weight_grad(ctx, "acg_conv2d_bwd_weight", x, g, pk.Or, st)
+        return dx, dw, db, None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_s16(ctx, x, dy, dskip):
+        """Conv2dFn.backward on pre-split operands: x and dy are S16 (dy comes from the norm behind this convolution, or — for
+        a conv + ReLU — from the next convolution's data gradient, which already applied the ReLU mask)."""
+        d, pk, p = ctx.d, ctx.packed, ctx.s16
+        st = _stream()
+        if p.y:
+            if ctx.link_out is None or not ctx.link_out.done:
+                raise _lib.AcgError("pre-split trunk: the gradient of a conv + ReLU output must come from the next convolution's "
+                                    "fused data gradient")
+            ctx.link_out.done = False
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            nb = _lib.query("acg_conv2d_bwd_data_workspace_bytes", ctypes.byref(d))
+            ws = workspace(nb) if nb else None
+            ns = ctx.norm_sums if not p.dx else None
+            if ns is not None and not (ns.x is not None and tuple(ns.x.shape) == tuple(dx.shape) and
+                                       _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d))):
+                ns = None
+            span = ConvTimer.span("dgrad_sums" if ns is not None else "dgrad", d)
+            if p.dx:     # the gradient w.r.t. the pre-activation of the conv + ReLU in front, pre-split for its own backward
+                if dskip is not None or ctx.link_in is None:
+                    raise _lib.AcgError("pre-split trunk: unexpected skip gradient / missing ReLU link")
+                if ctx.link_in.mask is not None and ctx.link_in.mask.numel() == (x.numel() + 31) // 32 and \
+                        _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d)):
+                    _fused("dgrad_s16_relu_bitmask")
+                    _lib.call("acg_conv2d_bwd_data_s16_mask", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb,
+                              _ptr(ctx.link_in.mask), st)
+                else:
+                    _fused("dgrad_s16_relu_src")
+                    _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, None, None,
+                              _ptr(x), 1, st)
+                ctx.link_in.done = True
             else:
-                dw = torch.empty((pk.Or, pk.Ir, pk.K, pk.K), device=x.device, dtype=torch.float32)
-                db = torch.empty(pk.Or, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-            nb = _lib.query("acg_conv2d_bwd_weight_workspace_bytes", ctypes.byref(d))
-            ws = workspace(nb)
-            span = ConvTimer.span("wgrad", d)
-            _lib.call("acg_conv2d_bwd_weight", ctypes.byref(d), _ptr(x), _ptr(g), _ptr(dw), _ptr(db), pk.Or, pk.Ir, _ptr(ws),
-                      nb, 1 if direct is not None else 0, st)
+                smask = None
+                if dskip is not None:
+                    dskip = dskip.contiguous()
+                    if ctx.skip_grad is not None:
+                        dskip, smask = ctx.skip_grad.take(dskip)
+                if ns is not None:
+                    # dx is the gradient w.r.t. the output of the norm in front: its backward sums leave with the tiles
+                    part = torch.empty((d.N, (d.Hi * d.Wi) // STATS_ROWS, 2, d.Ci), device=dx.device, dtype=torch.float32)
+                    desc = ns.desc(part)
+                    _fused("dgrad_s16_norm_sums")
+                    if smask is not None:
+                        _fused("dgrad_s16_lazy_skip")
+                    _lib.call("acg_conv2d_bwd_data_s16_sums", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
+                              _ptr(smask), ctypes.byref(desc), st)
+                    ns.part, ns.dx = part, dx
+                else:
+                    _fused("dgrad_s16_plain")
+                    if smask is not None:
+                        _fused("dgrad_s16_lazy_skip")
+                    _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
+                              _ptr(smask), None, 0, st)
             span.done()
-            if direct is not None:
-                dw = db = None
-                _grads_done(ctx.wparam, ctx.bparam)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
-
-
-def _conv_backward_s16(ctx, x, dy, dskip):
-    """Conv2dFn.backward on pre-split operands: x and dy are S16 (dy comes from the norm behind this convolution, or — for
-    a conv + ReLU — from the next convolution's data gradient, which already applied the ReLU mask)."""
-    d, pk, p = ctx.d, ctx.packed, ctx.s16
-    st = _stream()
-    if p.y:
-        if ctx.link_out is None or not ctx.link_out.done:
-            raise _lib.AcgError("pre-split trunk: the gradient of a conv + ReLU output must come from the next convolution's "
-                                "fused data gradient")
-        ctx.link_out.done = False
-    dx = None
-    if ctx.needs_input_grad[0]:
-        dx = torch.empty_like(x)
-        nb = _lib.query("acg_conv2d_bwd_data_workspace_bytes", ctypes.byref(d))
-        ws = workspace(nb) if nb else None
-        ns = ctx.norm_sums if not p.dx else None
-        if ns is not None and not (ns.x is not None and tuple(ns.x.shape) == tuple(dx.shape) and
-                                   _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d))):
-            ns = None
-        span = ConvTimer.span("dgrad_sums" if ns is not None else "dgrad", d)
-        if p.dx:     # the gradient w.r.t. the pre-activation of the conv + ReLU in front, pre-split for its own backward
-            if dskip is not None or ctx.link_in is None:
-                raise _lib.AcgError("pre-split trunk: unexpected skip gradient / missing ReLU link")
-            if ctx.link_in.mask is not None and ctx.link_in.mask.numel() == (x.numel() + 31) // 32 and \
-                    _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d)):
-                _fused("dgrad_s16_relu_bitmask")
-                _lib.call("acg_conv2d_bwd_data_s16_mask", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb,
-                          _ptr(ctx.link_in.mask), st)
-            else:
-                _fused("dgrad_s16_relu_src")
-                _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, None, None,
-                          _ptr(x), 1, st)
-            ctx.link_in.done = True
-        else:
-            smask = None
-            if dskip is not None:
-                dskip = dskip.contiguous()
-                if ctx.skip_grad is not None:
-                    dskip, smask = ctx.skip_grad.take(dskip)
-            if ns is not None:
-                # dx is the gradient w.r.t. the output of the norm in front: its backward sums leave with the tiles
-                part = torch.empty((d.N, (d.Hi * d.Wi) // STATS_ROWS, 2, d.Ci), device=dx.device, dtype=torch.float32)
-                desc = ns.desc(part)
-                _fused("dgrad_s16_norm_sums")
-                if smask is not None:
-                    _fused("dgrad_s16_lazy_skip")
-                _lib.call("acg_conv2d_bwd_data_s16_sums", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
-                          _ptr(smask), ctypes.byref(desc), st)
-                ns.part, ns.dx = part, dx
-            else:
-                _fused("dgrad_s16_plain")
-                if smask is not None:
-                    _fused("dgrad_s16_lazy_skip")
-                _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
-                          _ptr(smask), None, 0, st)
-        span.done()
-    if ctx.needs_input_grad[1]:
-        direct = _direct_grad(ctx.wparam, ctx.bparam)
-        if direct is not None:
-            dw, db = direct
-        else:
-            dw = torch.empty((pk.Or, pk.Ir, pk.K, pk.K), device=x.device, dtype=torch.float32)
-            db = torch.empty(pk.Or, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-        nb = _lib.query("acg_conv2d_bwd_weight_workspace_bytes", ctypes.byref(d))
-        ws = workspace(nb)
-        span = ConvTimer.span("wgrad", d)
-        _fused("wgrad_s16")
-        _lib.call("acg_conv2d_bwd_weight_s16", ctypes.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), pk.Or, pk.Ir, _ptr(ws),
-                  nb, 1 if direct is not None else 0, st)
-        span.done()
-        if direct is not None:
-            dw = db = None
-            _grads_done(ctx.wparam, ctx.bparam)
-    else:
-        dw = db = None
-    return (dx, dw, db) + (None,) * 12
-
-
-Conv2dFn._backward_s16 = staticmethod(_conv_backward_s16)
+        if ctx.needs_input_grad[1]:
+            _fused("wgrad_s16")
+            dw, db = _weight_grad(ctx, "acg_conv2d_bwd_weight_s16", x, dy, pk.Or, st)
+        return dx, dw, db, None, None, None, None, None, None
 
 
 class ConvTranspose2dFn(torch.autograd.Function):
@@ -750,19 +744,7 @@ class ConvTranspose2dFn(torch.autograd.Function):
             dx = torch.empty_like(x)
             _lib.call("acg_conv_transpose2d_bwd_data", ctypes.byref(d), _ptr(g), _ptr(pk.wf), _ptr(dx), st)
         if ctx.needs_input_grad[1]:
-            direct = _direct_grad(ctx.wparam, ctx.bparam)
-            if direct is not None:
-                dw, db = direct
-            else:
-                dw = torch.empty((pk.Or, pk.Ir, pk.K, pk.K), device=x.device, dtype=torch.float32)
-                db = torch.empty(pk.Ir, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-            nb = _lib.query("acg_conv2d_bwd_weight_workspace_bytes", ctypes.byref(d))
-            ws = workspace(nb)
-            _lib.call("acg_conv_transpose2d_bwd_weight", ctypes.byref(d), _ptr(x), _ptr(g), _ptr(dw), _ptr(db), pk.Or,
-                      pk.Ir, _ptr(ws), nb, 1 if direct is not None else 0, st)
-            if direct is not None:
-                dw = db = None
-                _grads_done(ctx.wparam, ctx.bparam)
+            dw, db = _weight_grad(ctx, "acg_conv_transpose2d_bwd_weight", x, g, pk.Ir, st, timed=False)
         return dx, dw, db, None, None, None, None, None, None
 
 

@@ -20,22 +20,24 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--blocks", type=int, default=9)
     ap.add_argument("--precision", default="bf16x3")
+    ap.add_argument("--nc", type=int, default=3, help="image channels")
     a = ap.parse_args()
+    a.sync_bn = False   # (bench.make_opt reads it)
     from dtgan_amd import model as M, ops
     ops.set_precision(a.precision)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     model = M.AugmentedCycleGAN(bench.make_opt(a, 0), testing=True)
     N, S = a.batch, a.size
-    A = torch.rand((N, 3, S, S), device=dev) * 2 - 1
-    B = torch.rand((N, 3, S, S), device=dev) * 2 - 1
+    A = torch.rand((N, a.nc, S, S), device=dev) * 2 - 1
+    B = torch.rand((N, a.nc, S, S), device=dev) * 2 - 1
     marks = {}
-    orig = M._finish_scalars
+    orig = model._scalars
 
-    def probe(names, tensors):
+    def probe(*args, **kw):   # the whole step is enqueued when it gathers its scalars for the one device->host copy
         marks["enq"] = time.perf_counter()
-        return orig(names, tensors)
-    M._finish_scalars = probe
+        return orig(*args, **kw)
+    model._scalars = probe
     for i in range(a.steps + 2):
         z = torch.randn((N, 16, 1, 1), device=dev)
         torch.cuda.synchronize()
