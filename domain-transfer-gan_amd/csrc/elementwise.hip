@@ -232,13 +232,18 @@ __global__ __launch_bounds__(256) void minmax_scale_kernel(const float *__restri
     __syncthreads();
     mn = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
     mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-    const float inv = mx > mn ? 2.f / (mx - mn) : 0.f;
+    // on quarters: max - min of a plane that holds both infinities (+-FLT_MAX after the clamp) overflows fp32, and the scaled
+    // plane was NaN at the infinities and -1 everywhere else.  0.25 is a power of two, so every other plane keeps its bits
+    // as long as 0.25 v, 0.25 min and 0.25 (max - min) are normal numbers (magnitudes near FLT_MIN lose bits to the subnormal
+    // range): 0.25 v - 0.25 min = 0.25 (v - min) and 2 / (0.25 (max - min)) = 4 * 2 / (max - min) exactly.
+    const float qmn = 0.25f * mn, qw = 0.25f * mx - qmn;
+    const float inv = mx > mn ? 2.f / qw : 0.f;
     float *dst = out + ((long long)n * C + c) * HW;
     for (long long i = threadIdx.x; i < HW; i += 256) {
         float v = src[i * Craw];
         v = (v != v) ? 0.f : v;
         v = fminf(fmaxf(v, -3.4028234664e38f), 3.4028234664e38f);
-        dst[i] = mx > mn ? -1.f + (v - mn) * inv : 0.f;
+        dst[i] = mx > mn ? -1.f + (0.25f * v - qmn) * inv : 0.f;
     }
 }
 extern "C" int acg_minmax_scale_nhwc_to_nchw(const float *raw, float *out, int N, int H, int W, int Craw, int C, void *stream)

@@ -49,8 +49,14 @@ __global__ __launch_bounds__(256) void norm_stats_partial(const float *__restric
     if (cnt > 0.f) {
         mean = s1 / cnt;
         m2 = s2 - s1 * mean;
+        // a group of at most rows_par pixels: every thread holds ONE row, which has no spread.  s2 - s1 * mean is then the
+        // rounding error of x * x that the fused multiply-add leaves (up to 6e-8 x^2), nothing else goes into the merge, and a
+        // channel whose variance is of the order of eps took it for variance: rstd off by 0.5 % at P = 1, 2e-4 at P = 2.
+        // (In a larger group the single rows of a short last chunk stay as they are: their error is that of every other
+        // partial sum, and the statistics of every P > rows_par keep their bits.)
+        const bool single = P <= rows_par;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) m2[k] = m2[k] < 0.f ? 0.f : m2[k];
+        for (int k = 0; k < 4; ++k) m2[k] = (m2[k] < 0.f || single) ? 0.f : m2[k];
     }
     *(f32x4 *)&sm[threadIdx.x * 4] = mean;
     *(f32x4 *)&sq[threadIdx.x * 4] = m2;
@@ -519,11 +525,15 @@ static void launch_norm_apply(dim3 grid, hipStream_t st, const float *x, const f
                               int C, int act, unsigned *mask, int fmt)
 {
 #define LA(A, R, K, F) hipLaunchKernelGGL((norm_apply_kernel<A, R, K, F>), grid, dim3(256), 0, st, x, mean, rstd, gamma, beta, gstride, res, y, P, C, mask)
-    if (fmt) { // pre-split I/O: the combinations the residual trunk uses (ReLU; residual + bitmask, or neither)
+    if (fmt) { // pre-split I/O (ReLU): every combination acg_norm_apply lets through
         if (res && mask && fmt == 3) LA(ACG_ACT_RELU, true, true, 3);
         else if (res && fmt == 3) LA(ACG_ACT_RELU, true, false, 3);
         else if (res && mask && fmt == 1) LA(ACG_ACT_RELU, true, true, 1);   // the LAST block of a trunk: residual pre-split, y fp32
         else if (res && fmt == 1) LA(ACG_ACT_RELU, true, false, 1);
+        // fmt 2 with an fp32 residual (ops.NormAct when the residual is not tagged pre-split): these two were missing and the
+        // call fell through to the instance below, which neither adds the residual nor writes the bitmask, and returned 0
+        else if (res && mask) LA(ACG_ACT_RELU, true, true, 2);
+        else if (res) LA(ACG_ACT_RELU, true, false, 2);
         else LA(ACG_ACT_RELU, false, false, 2);
         return;
     }

@@ -246,7 +246,22 @@ int acg_norm_stats_from_partials(const float *part, int G, size_t P, int C, int 
 /* BatchNorm eval mode: mean/rstd (length Cp) from the running buffers (length C) */
 int acg_bn_eval_stats(const float *run_mean, const float *run_var, int C, int Cp, float eps, float *mean, float *rstd,
                       void *stream);
-/* y = act((x-mean)*rstd*gamma + beta [+ res]); gamma/beta indexed [g*gstride + c] (gstride 0 or C) */
+/* y = act((x-mean)*rstd*gamma + beta [+ res]); gamma/beta indexed [g*gstride + c]: gstride 0 (shared), C, or any row stride
+ * >= C that is a multiple of 4 (a column block of a wider [G][gstride] matrix).
+ * Every norm entry point rejects (-1 and acg_last_error, nothing is launched) C % 4 != 0, C > 1024 (one workgroup row of
+ * 256 float4), G > 65535 and G, P or C of 0.  On top of that:
+ *   acg_norm_stats / acg_norm_stats_from_partials: unbiased != 0 with P < 2; acg_norm_stats: running statistics with G != 1.
+ *   acg_norm_apply: a gstride below C or not a multiple of 4; ACG_ACT_SIGMOID; fmt != 0 with anything but ReLU or with
+ *     C % 8 != 0; fmt 1 / 3 without res; sign_mask without res, with an activation other than ReLU / LeakyReLU, or with
+ *     P*C/4 % 8 != 0 (just outside: P = 63, C = 16).  fmt 2 takes an fp32 res (and a sign_mask) like fmt 0.
+ *   acg_norm_bwd / acg_norm_bwd_partials: tanh / sigmoid (no norm of the networks is followed by one); dx_s16 with dres,
+ *     with an activation other than ReLU, with C % 8 != 0 or with y given and no sign_mask; accumulate with gstride != 0;
+ *     nparam outside 0..C; a gstride below C or not a multiple of 4; an activation with neither y, sign_mask nor beta;
+ *     sign_mask with P*C/4 % 8 != 0; acg_norm_bwd_partials without partials.  unbiased == 1 with P < 2 is NOT checked
+ *     here (the statistics call before it refuses it).
+ *   acg_norm_bwd_sums / acg_norm_bwd_apply (the SyncBN halves): an activation without y; acg_norm_bwd_sums a short
+ *     workspace (-2).  They do NOT reject tanh (it is dispatched: 1 - y^2), take ACG_ACT_SIGMOID for no activation,
+ *     and do not check Ptot. */
 int acg_norm_apply(const float *x, const float *mean, const float *rstd, const float *gamma, const float *beta,
                    int gstride, const float *res, float *y, unsigned *sign_mask, int G, size_t P, int C, int act, int fmt,
                    void *stream);
