@@ -413,3 +413,307 @@ extern "C" int acg_radial_spectrum(const float *x, int rows, int C, int S, long 
     ACG_CHECK_LAUNCH("acg_radial_spectrum");
     return ACG_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The data gradient (ops.RadialSpectrum.backward, ops.spectral_loss): for a cotangent g[b] per field and ring,
+// gx = d sum_b g[b] psd[b] / dx = 2 Re ifft2(w F), w[ky, kx] = g[bin] / count[bin] (0 beyond ring S/2), ifft2 normalised by
+// 1 / S^2.  w F is Hermitian, so ifft2(w F) = fft2(conj(w F)) / S^2 is real: the inverse runs on the forward's Stockham stages
+// and twiddle tables, and every step stays inside the packed half spectrum:
+//   scale    G = conj(w F) per cell, w recomputed from the integer ring rule; 2 / S^2 is folded into the ring weights (a power
+//            of two: exact).  The packed column (kx = 0 and S/2, each Hermitian in ky) is untangled, scaled and re-tangled:
+//            its column transform is then real + i real, the packed form of two real row coefficients again.
+//   columns  the forward's column stages on G.
+//   rows     row y of the result is Hermitian in kx; rows 2q and 2q + 1 are re-tangled into one complex row (the inverse of
+//            spec_untangle), one complex transform gives row 2q in the real and row 2q + 1 in the imaginary part.
+// The cells of a ring are counted from the integer rule by a launch of their own into the head of the workspace (integer
+// atomics in LDS only).  No float atomics; the arithmetic does not depend on the layout.  NHWC: the workgroups of channel 0
+// also write the zeros of the padded channels C .. Cp - 1.
+// S <= 128: one workgroup per field (forward, scale, inverse, store in the forward's two LDS buffers).  Above: the forward's
+// row pass, a column pass per tile (transform, scale, transform, written back in place) and an inverse row pass.
+#define SPEC_COUNT_THREADS 256
+
+__host__ __device__ constexpr size_t spec_counts_bytes(int S) { return ((size_t)(S / 2 + 1) * sizeof(int) + 15) / 16 * 16; }
+
+// cnt[b]: the cells (fx, fy) in [-S/2, S/2 - 1]^2 of ring b; one workgroup per ring, the rows fy over its work items
+__global__ __launch_bounds__(SPEC_COUNT_THREADS) void spectrum_ring_counts_kernel(int S, int *__restrict__ cnt)
+{
+    __shared__ int total;
+    const int b = blockIdx.x, H = S / 2;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    int n = 0;
+    if (b == 0) {
+        n = threadIdx.x == 0 ? 1 : 0;
+    } else {
+        const int up = b * (b + 1), lo = b * (b - 1) + 1;
+        for (int y = threadIdx.x; y < S; y += blockDim.x) {
+            const int fy = y < H ? y : y - S, hi = up - fy * fy;
+            if (hi < 0) continue;
+            const int xh = spec_isqrt(hi), xl = spec_isqrt_ceil(lo - fy * fy);
+            n += max(0, min(xh, H - 1) - xl + 1);                   // 0 <= fx <= S/2 - 1
+            n += max(0, min(xh, H) - max(xl, 1) + 1);               // -S/2 <= fx < 0
+        }
+    }
+    if (n) atomicAdd(&total, n);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[b] = total;
+}
+
+// gw[b] = g[b] (2 / S^2) / count[b]: the weight of every cell of ring b, the factor 2 and ifft2's 1 / S^2 included
+template <int S>
+__device__ __forceinline__ void spec_ring_weights(const float *__restrict__ g, const int *__restrict__ cnt, float *gw)
+{
+    const float k = 2.f / ((float)S * (float)S);
+    for (int b = threadIdx.x; b <= S / 2; b += blockDim.x) gw[b] = g[b] * k / (float)cnt[b];
+}
+
+// the weight of the cell of signed wavenumbers (fx, fy): its ring by the integer rule, 0 beyond ring S/2
+template <int S>
+__device__ __forceinline__ float spec_cell_weight(const float *gw, int fx, int fy)
+{
+    const int s = fx * fx + fy * fy;
+    int b = spec_isqrt(s);
+    if (b * (b + 1) < s) ++b;
+    return b <= S / 2 ? gw[b] : 0.f;
+}
+
+// A transformed [S][KT] tile of columns kx0 .. kx0 + KT - 1, in place: f <- conj(w f); the tile of kx0 = 0 untangles its
+// packed column into kx = 0 and kx = S/2, scales both and packs conj(w0 F0) + i conj(wn Fn)
+template <int S, int KT>
+__device__ __forceinline__ void spec_scale_conj(float2 *f, int kx0, const float *gw)
+{
+    constexpr int H = S / 2;
+    for (int t = threadIdx.x; t < S * KT; t += blockDim.x) {
+        const int ky = t / KT, c = t & (KT - 1), fy = ky < H ? ky : ky - S;
+        if (kx0 + c == 0) {
+            if (ky > H) continue;                                   // the work item of ky writes S - ky as well
+            const int kz = (S - ky) & (S - 1);
+            const float2 u = f[t], v = f[kz * KT];
+            const float ar = 0.5f * (u.x + v.x), ai = 0.5f * (u.y - v.y), br = 0.5f * (u.y + v.y), bi = 0.5f * (v.x - u.x);
+            const float wa = spec_cell_weight<S>(gw, 0, fy), wb = spec_cell_weight<S>(gw, H, fy);
+            f[t] = make_float2(wa * ar + wb * bi, wb * br - wa * ai);
+            if (kz != ky) f[kz * KT] = make_float2(wa * ar - wb * bi, wb * br + wa * ai);
+        } else {
+            const float w = spec_cell_weight<S>(gw, kx0 + c, fy);
+            const float2 u = f[t];
+            f[t] = make_float2(w * u.x, -w * u.y);
+        }
+    }
+}
+
+// Rows 2q, 2q + 1 of the packed half spectrum h (row stride S/2 complex; LDS or global), each Hermitian in kx, -> the complex
+// rows z[q][S] = row 2q + i row 2q+1 for NRP row pairs: the inverse of spec_untangle_rows
+template <int S, int NRP>
+__device__ __forceinline__ void spec_tangle_rows(const float2 *h, float2 *z)
+{
+    constexpr int H = S / 2;
+    for (int t = threadIdx.x; t < NRP * H; t += blockDim.x) {
+        const int q = t / H, k = t & (H - 1);
+        const float2 a = h[(long long)(2 * q) * H + k], b = h[(long long)(2 * q + 1) * H + k];
+        float2 *zq = z + q * S;
+        if (k == 0) {
+            zq[0] = make_float2(a.x, b.x);
+            zq[H] = make_float2(a.y, b.y);
+        } else {
+            zq[k] = make_float2(a.x - b.y, a.y + b.x);
+            zq[S - k] = make_float2(a.x + b.y, b.x - a.y);
+        }
+    }
+}
+
+// z[q][w] = row 2 (rp0 + q) + i row 2 (rp0 + q) + 1 -> gx, in x's layout; gf: the field's first pixel, gi: its image's.
+// The work items of channel 0 (zero_ch > 0) also clear channels zero_from .. zero_from + zero_ch - 1 of their pixels.
+template <int S, int NRP>
+__device__ __forceinline__ void spec_store_rows(const float2 *z, float *__restrict__ gf, float *__restrict__ gi, int pix_stride,
+                                                long long chan_stride, bool planar, int rp0, int zero_from, int zero_ch)
+{
+    for (int t = threadIdx.x; t < NRP * (S / 4); t += blockDim.x) {
+        const int q = t / (S / 4), w = (t & (S / 4 - 1)) * 4;
+        const long long p0 = (long long)(2 * (rp0 + q)) * S + w, p1 = p0 + S;
+        const float4 lo = *reinterpret_cast<const float4 *>(z + q * S + w), hi = *reinterpret_cast<const float4 *>(z + q * S + w + 2);
+        const float r0[4] = {lo.x, lo.z, hi.x, hi.z}, r1[4] = {lo.y, lo.w, hi.y, hi.w};
+        if (planar) {
+            *reinterpret_cast<float4 *>(gf + p0) = make_float4(r0[0], r0[1], r0[2], r0[3]);
+            *reinterpret_cast<float4 *>(gf + p1) = make_float4(r1[0], r1[1], r1[2], r1[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                gf[(p0 + i) * pix_stride] = r0[i];
+                gf[(p1 + i) * pix_stride] = r1[i];
+            }
+        }
+        for (int cc = zero_from; cc < zero_from + zero_ch; ++cc) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                gi[(p0 + i) * pix_stride + cc * chan_stride] = 0.f;
+                gi[(p1 + i) * pix_stride + cc * chan_stride] = 0.f;
+            }
+        }
+    }
+}
+
+// what a workgroup needs to place its field's gradient: the field's first pixel, its image's, and the padded channels it clears
+struct SpecDst {
+    float *gf, *gi;
+    int zero_from, zero_ch;
+};
+__device__ __forceinline__ SpecDst spec_dst(float *gx, int f, int C, int Cp, long long row_stride, long long chan_stride)
+{
+    const int row = f / C, c = f - row * C;
+    SpecDst d;
+    d.gi = gx + (long long)row * row_stride;
+    d.gf = d.gi + (long long)c * chan_stride;
+    d.zero_from = C;
+    d.zero_ch = c == 0 ? Cp - C : 0;
+    return d;
+}
+
+// S <= 128: one workgroup per field
+template <int S>
+__global__ __launch_bounds__(spec_field_threads(S)) void spectrum_bwd_field_kernel(const float *__restrict__ x, const float *__restrict__ g,
+                                                                          const int *__restrict__ cnt, int C, int Cp,
+                                                                          long long row_stride, int pix_stride,
+                                                                          long long chan_stride, int mode, float *__restrict__ gx)
+{
+    constexpr int H = S / 2;
+    __shared__ __attribute__((aligned(16))) float2 buf0[H * S];
+    __shared__ __attribute__((aligned(16))) float2 buf1[H * S];
+    __shared__ float2 tw[S];
+    __shared__ float gw[H + 1];
+    int c;
+    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
+    spec_twiddles<S>(tw);
+    spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
+    spec_load_rows<S, H>(xf, pix_stride, mode, c, 0, buf0);
+    __syncthreads();
+    float2 *z = spec_fft_rows<S, H>(buf0, buf1, tw);
+    float2 *h = z == buf0 ? buf1 : buf0;
+    spec_untangle_rows<S, H>(z, h);
+    __syncthreads();
+    float2 *f = spec_fft_cols<S, H>(h, z, tw);
+    spec_scale_conj<S, H>(f, 0, gw);
+    __syncthreads();
+    float2 *o = f == buf0 ? buf1 : buf0;
+    float2 *t = spec_fft_cols<S, H>(f, o, tw);                     // [y][S/2]: every row's half spectrum
+    o = t == buf0 ? buf1 : buf0;
+    spec_tangle_rows<S, H>(t, o);
+    __syncthreads();
+    const float2 *r = spec_fft_rows<S, H>(o, t, tw);
+    const SpecDst d = spec_dst(gx, blockIdx.x, C, Cp, row_stride, chan_stride);
+    spec_store_rows<S, H>(r, d.gf, d.gi, pix_stride, chan_stride, mode == SPEC_PLANAR, 0, d.zero_from, d.zero_ch);
+}
+
+// S > 128, second pass: one workgroup per tile of SPEC_TILE / S columns of a field's half spectrum, in place
+template <int S>
+__global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_bwd_cols_kernel(float2 *__restrict__ half, const float *__restrict__ g,
+                                                                         const int *__restrict__ cnt)
+{
+    constexpr int KT = SPEC_TILE / S, H = S / 2;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    __shared__ float gw[H + 1];
+    const int kx0 = blockIdx.y * KT;
+    float2 *hf = half + (long long)blockIdx.x * S * H + kx0;
+    spec_twiddles<S>(tw);
+    spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
+    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+        *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * H + cc);
+    }
+    __syncthreads();
+    float2 *f = spec_fft_cols<S, KT>(buf0, buf1, tw);
+    spec_scale_conj<S, KT>(f, kx0, gw);
+    __syncthreads();
+    const float2 *r = spec_fft_cols<S, KT>(f, f == buf0 ? buf1 : buf0, tw);
+    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+        *reinterpret_cast<float4 *>(hf + (long long)ky * H + cc) = *reinterpret_cast<const float4 *>(r + ky * KT + cc);
+    }
+}
+
+// S > 128, third pass: SPEC_TILE / S row pairs of one field per workgroup, half spectra -> the real rows of gx
+template <int S>
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(const float2 *__restrict__ half, int C, int Cp,
+                                                                         long long row_stride, int pix_stride,
+                                                                         long long chan_stride, int mode, float *__restrict__ gx)
+{
+    constexpr int NRP = SPEC_TILE / S;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    const int rp0 = blockIdx.y * NRP;
+    spec_twiddles<S>(tw);
+    spec_tangle_rows<S, NRP>(half + ((long long)blockIdx.x * S + 2 * rp0) * (S / 2), buf0);
+    __syncthreads();
+    const float2 *r = spec_fft_rows<S, NRP>(buf0, buf1, tw);
+    const SpecDst d = spec_dst(gx, blockIdx.x, C, Cp, row_stride, chan_stride);
+    spec_store_rows<S, NRP>(r, d.gf, d.gi, pix_stride, chan_stride, mode == SPEC_PLANAR, rp0, d.zero_from, d.zero_ch);
+}
+
+extern "C" size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S)
+{
+    if (rows < 1 || C < 1 || !spec_size_ok(S)) return 0;
+    return spec_counts_bytes(S) + acg_radial_spectrum_workspace_bytes(rows, C, S);
+}
+
+template <int S>
+static void spec_bwd_launch(hipStream_t st, const float *x, const float *g, int fields, int C, int Cp, long long row_stride,
+                            int pix_stride, long long chan_stride, int mode, float *gx, int *cnt, float2 *half)
+{
+    hipLaunchKernelGGL(spectrum_ring_counts_kernel, dim3(S / 2 + 1), dim3(SPEC_COUNT_THREADS), 0, st, S, cnt);
+    if constexpr (S <= SPEC_ONE_WG_MAX_S) {
+        hipLaunchKernelGGL(spectrum_bwd_field_kernel<S>, dim3(fields), dim3(spec_field_threads(S)), 0, st, x, g, (const int *)cnt, C,
+                           Cp, row_stride, pix_stride, chan_stride, mode, gx);
+        acg_note_kernel("spectrum_bwd_field<%d>", S);
+    } else {
+        constexpr int TILES = (S / 2) / (SPEC_TILE / S);
+        hipLaunchKernelGGL(spectrum_rows_kernel<S>, dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, x, C, row_stride, pix_stride,
+                           chan_stride, mode, half);
+        hipLaunchKernelGGL(spectrum_bwd_cols_kernel<S>, dim3(fields, TILES), dim3(SPEC_COLS_THREADS), 0, st, half, g,
+                           (const int *)cnt);
+        hipLaunchKernelGGL(spectrum_bwd_rows_kernel<S>, dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, (const float2 *)half, C,
+                           Cp, row_stride, pix_stride, chan_stride, mode, gx);
+        acg_note_kernel("spectrum_rows<%d> + spectrum_bwd_cols<%d> + spectrum_bwd_rows<%d>", S, S, S);
+    }
+}
+
+extern "C" int acg_radial_spectrum_bwd(const float *x, const float *g, int rows, int C, int Cp, int S, long long row_stride,
+                                       int pix_stride, long long chan_stride, float *gx, void *ws, size_t ws_bytes, void *stream)
+{
+    ACG_REQUIRE(x != nullptr && g != nullptr && gx != nullptr, "acg_radial_spectrum_bwd: null tensor");
+    ACG_REQUIRE(spec_size_ok(S), "acg_radial_spectrum_bwd: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
+                SPEC_MAX_S, S);
+    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_radial_spectrum_bwd: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE(Cp >= C, "acg_radial_spectrum_bwd: the stored channels cannot be fewer than the valid ones (C=%d, Cp=%d)", C, Cp);
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_radial_spectrum_bwd: too many fields (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
+                "acg_radial_spectrum_bwd: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride,
+                chan_stride);
+    ACG_REQUIRE(x != gx, "acg_radial_spectrum_bwd: gx must not alias x");
+    const size_t need = acg_radial_spectrum_bwd_workspace_bytes(rows, C, S);
+    if (ws == nullptr || ws_bytes < need) {
+        acg_set_error("acg_radial_spectrum_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
+        return ACG_ERR_WORKSPACE;
+    }
+    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_radial_spectrum_bwd: the workspace must be 16-byte aligned");
+    const bool aligned = (uintptr_t)x % 16 == 0 && (uintptr_t)gx % 16 == 0 && row_stride % 4 == 0;
+    int mode = SPEC_SCALAR;
+    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) mode = SPEC_PLANAR;
+    else if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) mode = SPEC_C4;
+    hipStream_t st = (hipStream_t)stream;
+    const int fields = rows * C;
+    int *cnt = (int *)ws;
+    float2 *half = (float2 *)((char *)ws + spec_counts_bytes(S));
+    switch (S) {
+    case 16: spec_bwd_launch<16>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    case 32: spec_bwd_launch<32>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    case 64: spec_bwd_launch<64>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    case 128: spec_bwd_launch<128>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    case 256: spec_bwd_launch<256>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    case 512: spec_bwd_launch<512>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    default: spec_bwd_launch<1024>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
+    }
+    ACG_CHECK_LAUNCH("acg_radial_spectrum_bwd");
+    return ACG_OK;
+}

@@ -249,7 +249,8 @@ class StepGraph(object):
         # everything a captured launch bakes in as an argument: shapes, learning rates, train/eval mode, the kernel
         # configuration (precision / implementation switch) and the scalar options of the step
         baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
-                                                        "lambda_sup_B", "stoch_enc", "z_gan", "beta1"))
+                                                        "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
+                                                        "lambda_spec_B"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -346,6 +347,32 @@ class _Base(object):
 
     def _dev(self):
         return next(self.netG_A_B.parameters()).device
+
+    def _spec_lambdas(self):
+        """(lambda_spec_A, lambda_spec_B); 0 for options written before the spectral loss existed (opt.pkl)"""
+        o = self.opt
+        return float(getattr(o, 'lambda_spec_A', 0.0) or 0.0), float(getattr(o, 'lambda_spec_B', 0.0) or 0.0)
+
+    def _spectral_terms(self, fake_A, A, fake_B, B):
+        """The spectral loss of the first-pass outputs against the real batches (ops.spectral_loss on the internal NHWC
+        tensors; unpaired: batch-mean spectra): None when both weights are 0 (the default: no launch is issued), else
+        (Spec_A, Spec_B, weighted sum for loss_G).  A term of weight 0 is a monitor without gradient."""
+        lam_A, lam_B = self._spec_lambdas()
+        if lam_A <= 0 and lam_B <= 0:
+            return None
+
+        def term(fake, real, C, lam):
+            if lam > 0:
+                return ops.spectral_loss(fake, real, C, "nhwc")
+            with torch.no_grad():
+                return ops.spectral_loss(fake.detach(), real, C, "nhwc")
+        spec_A = term(fake_A, A, self.opt.input_nc, lam_A)
+        spec_B = term(fake_B, B, self.opt.output_nc, lam_B)
+        add = None
+        for v, lam in ((spec_A, lam_A), (spec_B, lam_B)):
+            if lam > 0:
+                add = v * lam if add is None else add + v * lam
+        return spec_A, spec_B, add
 
     def _nchw(self, x, C):
         return ops.ToNCHW.apply(x, C).detach()
@@ -698,26 +725,32 @@ class StochCycleGAN(_Base):
             p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = self._gan_loss(p_fA, True)
             p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = self._gan_loss(p_fB, True)
             loss_G = loss_G_A + loss_G_B + loss_cycle_A * o.lambda_A + loss_cycle_B * o.lambda_B
+            spec = self._spectral_terms(fake_A, A, fake_B, B)
+            if spec is not None:
+                loss_G = loss_G + spec[2]
             self.optimizer_G.zero_grad()
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_D_B, loss_G_B, loss_cycle_B,
                     m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
+            if spec is not None:
+                sums += [spec[0], spec[1]]
             ex_G = self._backward(loss_G, "stoch.G", [self.f_G_B_A, self.f_G_A_B], tail=(self.f_G_A_B, sums))
         finally:
             self.f_D_A.set_requires_grad(True); self.f_D_B.set_requires_grad(True)
         self._wait(ex_G, self.f_G_A_B, self.f_G_B_A)
         ss_G_A_B, ss_G_B_A = self.optimizer_G.clip_and_step(o.max_gnorm)
 
-        names = ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B',
-                 'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
+        n_loss = len(sums)
+        names = ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + \
+                ['Spec_A', 'Spec_B'][:n_loss - 10] + ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_D_B, ss_D_A])
         visuals = OrderedDict([('real_A', real_A.detach()), ('fake_B', self._nchw(fake_B, nB)),
                                ('rec_A', self._nchw(rec_A, nA)), ('real_B', real_B.detach()),
                                ('fake_A', self._nchw(fake_A, nA)), ('rec_B', self._nchw(rec_B, nB))])
 
         def finish(vals):
-            losses = OrderedDict((k, vals[k]) for k in names[:10])                               # model.py:193-196
+            losses = OrderedDict((k, vals[k]) for k in names[:n_loss])                           # model.py:193-196
             if o.monitor_gnorm:
-                gnorms = OrderedDict((k, math.sqrt(max(vals[k], 0.0))) for k in names[10:])      # model.py:202-205
+                gnorms = OrderedDict((k, math.sqrt(max(vals[k], 0.0))) for k in names[n_loss:])  # model.py:202-205
                 return losses, visuals, gnorms
             return losses, visuals
         return self._report(vals, finish)
@@ -908,10 +941,15 @@ class AugmentedCycleGAN(_Base):
                 loss_G = loss_G + kld_z_B * o.lambda_z_B
             if z_gan:
                 loss_G = loss_G + loss_G_z_B
+            spec = self._spectral_terms(fake_A, A, fake_B, B)
+            if spec is not None:
+                loss_G = loss_G + spec[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             mu_v, lv_v = mu_rB.detach()[:, :nl], lv_rB.detach()[:, :nl]
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_cycle_z_B, kld_z_B, loss_D_B, loss_G_B, loss_cycle_B,
                     loss_D_z_B, m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
+            if spec is not None:
+                sums += [spec[0], spec[1]]
             mins, maxs = [mu_v.min(), lv_v.min()], [mu_v.max(), lv_v.max()]
             # completion order of the G backward: E_B (its first call is the last of the three first-pass networks to have
             # been built), then G_B_A, then G_A_B — which therefore carries the scalar tail
@@ -925,8 +963,9 @@ class AugmentedCycleGAN(_Base):
         self._wait(ex_G, self.f_G_A_B, self.f_E_B)
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
 
+        n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B',
-                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B',
+                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + ['Spec_A', 'Spec_B'][:n_loss - 13] + [
                  'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_B', 'gnorm_D_z_B', 'gnorm_D_A',
                  'mu_min', 'logvar_min', 'mu_max', 'logvar_max']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, mins, maxs,
@@ -936,9 +975,9 @@ class AugmentedCycleGAN(_Base):
                                ('fake_A', self._nchw(fake_A, nA)), ('rec_B', self._nchw(rec_B, nB))])
 
         def finish(vals):
-            losses = OrderedDict((k, vals[k]) for k in names[:13])                              # model.py:518-523
+            losses = OrderedDict((k, vals[k]) for k in names[:n_loss])                          # model.py:518-523
             if o.monitor_gnorm:
-                gnorms = OrderedDict((k, math.sqrt(max(vals[k], 0.0))) for k in names[13:19])   # model.py:527-533
+                gnorms = OrderedDict((k, math.sqrt(max(vals[k], 0.0))) for k in names[n_loss:n_loss + 6])   # model.py:527-533
                 for k in ('mu_min', 'mu_max', 'logvar_min', 'logvar_max'):
                     gnorms[k] = vals[k]
                 return losses, visuals, gnorms

@@ -1426,7 +1426,7 @@ def ensemble_stats(members_nhwc, target_nhwc, M, C, quantiles, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
-# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum)
+# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum) and the spectral loss on them
 # ----------------------------------------------------------------------------------------------
 SPECTRUM_MIN_S, SPECTRUM_MAX_S = 16, 1024
 
@@ -1452,14 +1452,10 @@ def spectrum_bins(S):
     return np.bincount(b[b <= S // 2], minlength=S // 2 + 1).astype(np.int64)
 
 
-def radial_spectrum(x, C, layout, out=None):
-    """acg_radial_spectrum of the C valid channels of every row of x -> (rows, C, S/2 + 1) float32 on the device.  layout
-    "nhwc": x (rows, S, S, Cp) as forward_nhwc / ToNHWC give it (padded channels never reach a result); "nchw": x (rows, C, S, S).
-    One launch up to S = 128, a row and a column pass above; nothing is read back to the host."""
-    x = x.contiguous()
-    _check(x, out)
+def _spectrum_args(x, C, layout, what):
+    """(rows, C, Cp, S, (row, pixel, channel) strides in floats) of a contiguous tensor in the layout"""
     if x.dim() != 4 or layout not in ("nhwc", "nchw"):
-        raise _lib.AcgError("radial_spectrum: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (tuple(x.shape), layout))
+        raise _lib.AcgError("%s: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (what, tuple(x.shape), layout))
     C = int(C)
     if layout == "nhwc":
         rows, H, W, Cp = x.shape
@@ -1469,7 +1465,14 @@ def radial_spectrum(x, C, layout, out=None):
         strides = (Cp * H * W, 1, H * W)
     S = _spectrum_size(H, W)
     if not 1 <= C <= Cp or rows < 1:
-        raise _lib.AcgError("radial_spectrum: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (Cp, rows, C))
+        raise _lib.AcgError("%s: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (what, Cp, rows, C))
+    return rows, C, Cp, S, strides
+
+
+def _radial_spectrum(x, C, layout, out=None):
+    x = x.contiguous()
+    _check(x, out)
+    rows, C, Cp, S, strides = _spectrum_args(x, C, layout, "radial_spectrum")
     nb = S // 2 + 1
     if out is None:
         out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
@@ -1479,6 +1482,63 @@ def radial_spectrum(x, C, layout, out=None):
     ws = workspace(nbytes, slot=2) if nbytes else None
     _lib.call("acg_radial_spectrum", _ptr(x), rows, C, S, strides[0], strides[1], strides[2], _ptr(out), _ptr(ws), nbytes, _stream())
     return out
+
+
+def radial_spectrum_bwd(x, g, C, layout):
+    """acg_radial_spectrum_bwd: the gradient of sum(g * radial_spectrum(x)) with respect to x, in x's layout; g (rows, C,
+    S/2 + 1).  NHWC: the padded channels are written as 0.  One launch (and the ring counts') up to S = 128, three above."""
+    x, g = x.contiguous(), g.contiguous()
+    _check(x, g)
+    rows, C, Cp, S, strides = _spectrum_args(x, C, layout, "radial_spectrum_bwd")
+    if tuple(g.shape) != (rows, C, S // 2 + 1):
+        raise _lib.AcgError("radial_spectrum_bwd: the cotangent %s is not (%d, %d, %d)" % (tuple(g.shape), rows, C, S // 2 + 1))
+    gx = torch.empty_like(x)
+    nbytes = _lib.query("acg_radial_spectrum_bwd_workspace_bytes", rows, C, S)
+    ws = workspace(nbytes, slot=2)
+    _lib.call("acg_radial_spectrum_bwd", _ptr(x), _ptr(g), rows, C, Cp if layout == "nhwc" else C, S, strides[0], strides[1],
+              strides[2], _ptr(gx), _ptr(ws), nbytes, _stream())
+    return gx
+
+
+class RadialSpectrum(torch.autograd.Function):
+    """radial_spectrum with its data gradient: forward acg_radial_spectrum, backward acg_radial_spectrum_bwd
+    (gx = 2 Re ifft2(w fft2(x)), w the cotangent of a cell's ring over the ring's cell count)."""
+
+    @staticmethod
+    def forward(ctx, x, C, layout):
+        x = x.contiguous()
+        ctx.cfg = (int(C), layout)
+        ctx.save_for_backward(x)
+        return _radial_spectrum(x, C, layout)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        C, layout = ctx.cfg
+        return radial_spectrum_bwd(x, g, C, layout), None, None
+
+
+def radial_spectrum(x, C, layout, out=None):
+    """acg_radial_spectrum of the C valid channels of every row of x -> (rows, C, S/2 + 1) float32 on the device.  layout
+    "nhwc": x (rows, S, S, Cp) as forward_nhwc / ToNHWC give it (padded channels never reach a result); "nchw": x (rows, C, S, S).
+    One launch up to S = 128, a row and a column pass above; nothing is read back to the host.  Differentiable in x
+    (RadialSpectrum) when x requires grad, gradients are enabled and no `out` is given."""
+    if out is None and torch.is_grad_enabled() and x.requires_grad:
+        return RadialSpectrum.apply(x, C, layout)
+    return _radial_spectrum(x, C, layout, out)
+
+
+def spectral_loss(x, y, C, layout, eps=1e-6):
+    """The squared log-spectral distance (in nepers) of the batch-mean spectra of x and y -> device scalar, differentiable in
+    x: p = radial_spectrum(x).mean(0), q the same of y (detached); mean over the C channels and bins 1 .. S/2 of
+    (ln(p + eps) - ln(q + eps))^2.  Bin 0 (the mean) takes no part, as in test.log_spectral_distance.  eps belongs to the
+    definition: above the forward's absolute floor in an empty bin (~2.8e-7 for fields in [-1, 1]), below any populated bin.
+    x and y need not pair (nor hold the same number of rows)."""
+    p = radial_spectrum(x, C, layout).mean(0)
+    with torch.no_grad():
+        q = _radial_spectrum(y.detach(), C, layout).mean(0)
+    d = torch.log(p[:, 1:] + eps) - torch.log(q[:, 1:] + eps)
+    return (d * d).mean()
 
 
 def mean_valid(x, C, out=None):

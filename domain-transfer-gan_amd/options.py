@@ -1,7 +1,7 @@
 """Command-line options — Py3 counterpart of /root/reference/augmented_cyclegan/options.py (which is Python 2:
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
 (options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
---step_graph, --defer_scalars."""
+--step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B."""
 import argparse
 import os
 import pickle
@@ -84,6 +84,10 @@ _T = [
                                      "/ --display_freq steps, so the host enqueues the next step while this one runs (at most "
                                      "2 in flight); the logged numbers are those of --step_graph alone"),
     ("eval_steps", int, 50, "variational-bound steps per epoch (train.py:285 uses 50)"),
+    ("lambda_spec_A", float, 0.0, "weight of the spectral loss on fake_A against the real A: the squared log distance of the "
+                                  "batch-mean radially averaged power spectra (ops.spectral_loss); 0: off; needs --grid_size "
+                                  "a power of two in 16..1024"),
+    ("lambda_spec_B", float, 0.0, "the same on fake_B against the real B"),
 ]
 
 
@@ -111,6 +115,10 @@ class TrainOptions(object):
             self.parser.error("--dataroot is required (or --synthetic N)")
         if opt.defer_scalars and not opt.step_graph:
             self.parser.error("--defer_scalars requires --step_graph")
+        g = opt.grid_size
+        if (opt.lambda_spec_A > 0 or opt.lambda_spec_B > 0) and (not 16 <= g <= 1024 or g & (g - 1)):
+            self.parser.error("--lambda_spec_A / --lambda_spec_B: the spectral loss needs fields of S x S with S a power of two "
+                              "in 16..1024 (--grid_size %d)" % g)
         opt.gpu_ids = [i for i in (int(tok) for tok in opt.gpu_ids.split(",")) if i >= 0]      # options.py:92-97
         if opt.gpu_ids and torch.cuda.is_available():
             local = int(os.environ.get("LOCAL_RANK", opt.gpu_ids[0]))

@@ -446,6 +446,18 @@ int acg_ensemble_stats(const float *x, const float *y, int N, int M, size_t npix
 size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S);
 int acg_radial_spectrum(const float *x, int rows, int C, int S, long long row_stride, int pix_stride, long long chan_stride,
                         float *psd, void *workspace, size_t ws_bytes, void *stream);
+/* The data gradient of the above (ops.RadialSpectrum, ops.spectral_loss): g (rows, C, S/2 + 1) is the cotangent of psd,
+ * gx = d sum_b g[b] psd[b] / dx = 2 Re ifft2(w F) per field, w[ky, kx] = g[bin] / count[bin] by the same integer ring rule
+ * (0 in the dropped corners), ifft2 normalised by 1 / S^2.  x, its strides, S and the refusals are the forward's; gx has the
+ * layout of x and must not alias it.  Cp: the channels stored per pixel of gx, channels C .. Cp - 1 are written as 0 (NHWC:
+ * Cp = pix_stride; planar: Cp = C).  The inverse transform is the forward's Stockham stages on conj(w F), all inside the
+ * packed half spectrum; the ring cell counts come from the integer rule (a launch of their own into the head of the
+ * workspace).  Deterministic, no float atomics, the same bits for every layout.  S <= 128: one workgroup per field; above:
+ * the forward's row pass, a column pass per tile and an inverse row pass through the half spectrum in the workspace
+ * (acg_radial_spectrum_bwd_workspace_bytes, never 0, 16-byte aligned). */
+size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S);
+int acg_radial_spectrum_bwd(const float *x, const float *g, int rows, int C, int Cp, int S, long long row_stride,
+                            int pix_stride, long long chan_stride, float *gx, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */

@@ -16,6 +16,20 @@ float64 reference on exactly the inputs and sizes of tests/test_hip_spectrum.py;
 with |psd - ref| <= tau sqrt(ref E) + tau^2 E in every bin.  The test's constant is 4 x the overall value.
 
     python tools/spectrum_bench.py --cpu-tolerance
+
+--cpu-grad-tolerance, the same for the data gradient (tests/test_hip_spectrum_grad.py): 2 Re ifft2(w fft2(x)) with torch.fft
+in float32 on the CPU against tests/spectrum_grad_ref.py in float64 over that test's sizes, fields and cotangents; the error
+of a field is max |gx - ref| / (2 max_b |g[b] / count[b]| rms(x)).  Then ops.spectral_loss's value and input gradient
+formed in float32 the same way (ring sums in float64, as the kernel forms them; torch's autograd) on that test's batches.
+The test's constants are 4 x the overall values.
+
+    python tools/spectrum_bench.py --cpu-grad-tolerance
+
+--backward: microseconds per field of acg_radial_spectrum_bwd beside the forward's at 128 x 128 x 3 x 32, 256 x 256 x 3 x 32
+and 512 x 512 x 1 x 32 (C4 NHWC, what the training step hands it), each over the HBM floor of one read of x and one write of
+gx (padded channels included).  One JSON line per case.
+
+    python tools/spectrum_bench.py --backward [--reps 20] [--bwd-cases 128x3:32,256x3:32,512x1:32]
 """
 import argparse
 import json
@@ -48,6 +62,95 @@ def cpu_tolerance():
                           test_constant_4x=float("%.4e" % (4 * worst)))), flush=True)
 
 
+def cpu_grad_tolerance(loss_only=False):
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import spectrum_grad_ref as G
+    import spectrum_ref as R
+    worst = 0.0
+    for S in (() if loss_only else R.FIELD_SIZES):
+        per = {}
+        for kind in R.FIELD_KINDS:
+            x = R.make_fields(kind, S)
+            F = torch.fft.fft2(torch.from_numpy(x))                     # complex64 on the CPU
+            for ck in G.COTANGENT_KINDS:
+                g = G.cotangents(ck, S, x.shape[:2])
+                w = torch.from_numpy(G.cell_weights(S, g).astype(np.float32))
+                gx = 2.0 * torch.fft.ifft2(w * F).real
+                err = float(G.vjp_error(gx.numpy(), G.rapsd_vjp(x, g), g, x).max())
+                per[kind] = max(per.get(kind, 0.0), err)
+        worst = max(worst, max(per.values()))
+        print(json.dumps(dict(tool="spectrum_bench", mode="cpu-grad-tolerance", S=S,
+                              err={k: float("%.3e" % v) for k, v in per.items()})), flush=True)
+    if not loss_only:
+        print(json.dumps(dict(tool="spectrum_bench", mode="cpu-grad-tolerance", err_overall=float("%.4e" % worst),
+                              test_constant_4x=float("%.4e" % (4 * worst)))), flush=True)
+    # the loss itself in float32 (transform, power, logs; the ring sums in float64 as the forward kernel forms them) with
+    # torch's autograd behind it, on the batches of the test of ops.spectral_loss
+    worst_v = worst_g = 0.0
+    for S in G.LOSS_SIZES:
+        for kind in G.LOSS_KINDS:
+            x, y = G.loss_batches(kind, S)
+            ref, dref, g = G.spectral_loss_and_grad(x, y)
+            b = torch.from_numpy(R.bin_index(S).ravel())
+            keep, cnt = b <= S // 2, torch.from_numpy(R.bin_counts(S)).double()
+
+            def mean_psd(t):
+                F = torch.fft.fft2(t)
+                P = ((F.real ** 2 + F.imag ** 2) / float(S * S)).reshape(t.shape[:2] + (S * S,))
+                sums = torch.zeros(t.shape[:2] + (S // 2 + 1,), dtype=torch.float64).index_add(-1, b[keep], P.double()[..., keep])
+                return (sums / cnt).float().mean(0)
+            xt = torch.from_numpy(x).requires_grad_()
+            d = torch.log(mean_psd(xt)[:, 1:] + 1e-6) - torch.log(mean_psd(torch.from_numpy(y))[:, 1:] + 1e-6)
+            loss = (d * d).mean()
+            loss.backward()
+            ev = abs(float(loss.detach()) - ref) / ref
+            eg = float(G.vjp_error(xt.grad.numpy(), dref, np.broadcast_to(g, (x.shape[0],) + g.shape), x).max())
+            worst_v, worst_g = max(worst_v, ev), max(worst_g, eg)
+            print(json.dumps(dict(tool="spectrum_bench", mode="cpu-grad-tolerance", loss=kind, S=S, value=float("%.6g" % ref),
+                                  value_rel_err=float("%.3e" % ev), grad_err=float("%.3e" % eg))), flush=True)
+    print(json.dumps(dict(tool="spectrum_bench", mode="cpu-grad-tolerance", loss_value_rel_err_overall=float("%.4e" % worst_v),
+                          loss_grad_err_overall=float("%.4e" % worst_g), value_constant_4x=float("%.4e" % (4 * worst_v)),
+                          grad_constant_4x=float("%.4e" % (4 * worst_g)))), flush=True)
+
+
+def backward_bench(a):
+    import torch
+    import dtgan_amd  # noqa: F401
+    from dtgan_amd import _lib, ops
+    if not torch.cuda.is_available():
+        raise SystemExit("spectrum_bench needs a GPU (or --cpu-tolerance / --cpu-grad-tolerance)")
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for case in a.bwd_cases.split(","):
+        geo, rows = case.split(":")
+        S, C = (int(v) for v in geo.split("x"))
+        rows, Cp = int(rows), 4
+        x = torch.rand(rows, S, S, Cp, device="cuda", generator=gen) * 2 - 1
+        g = torch.randn(rows, C, S // 2 + 1, device="cuda", generator=gen)
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.reps + 1)]
+            ev[0].record()
+            for i in range(a.reps):
+                fn()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps))
+            return ms[len(ms) // 2]
+        with torch.no_grad():
+            fwd_ms = timed(lambda: ops.radial_spectrum(x, C, "nhwc"))
+            fwd_kernel = _lib.query("acg_last_kernel").decode()
+            bwd_ms = timed(lambda: ops.radial_spectrum_bwd(x, g, C, "nhwc"))
+        fields, floor_s = rows * C, 2 * x.numel() * 4 / HBM
+        print(json.dumps(dict(tool="spectrum_bench", mode="backward", S=S, C=C, Cp=Cp, rows=rows, reps=a.reps,
+                              fwd_kernel=fwd_kernel, bwd_kernel=_lib.query("acg_last_kernel").decode(),
+                              fwd_us_per_field=round(fwd_ms * 1e3 / fields, 2), bwd_us_per_field=round(bwd_ms * 1e3 / fields, 2),
+                              bwd_over_fwd=round(bwd_ms / fwd_ms, 2), hbm_floor_us_per_field=round(floor_s * 1e6 / fields, 3),
+                              bwd_x_hbm_floor=round(bwd_ms * 1e-3 / floor_s, 1))), flush=True)
+
+
 def spectrum_bytes(rows, S, C, Cp):
     read = rows * S * S * Cp * 4                                        # the members, padded channels included
     half = rows * C * S * (S // 2) * 8 if S > 128 else 0                # the packed half spectrum, written and read once
@@ -57,13 +160,22 @@ def spectrum_bytes(rows, S, C, Cp):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu-tolerance", action="store_true")
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cpu-grad-tolerance", action="store_true")
+    ap.add_argument("--backward", action="store_true")
+    ap.add_argument("--bwd-cases", default="128x3:32,256x3:32,512x1:32")
+    ap.add_argument("--reps", type=int, default=None, help="default 3, with --backward 20")
     ap.add_argument("--precision", default="bf16x3")
     ap.add_argument("--N", type=int, default=200)
     ap.add_argument("--cases", default="256x3:16,512x1:16,64x3:16")
     a = ap.parse_args()
     if a.cpu_tolerance:
         return cpu_tolerance()
+    if a.cpu_grad_tolerance:
+        return cpu_grad_tolerance()
+    if a.reps is None:
+        a.reps = 20 if a.backward else 3
+    if a.backward:
+        return backward_bench(a)
     import torch
     import dtgan_amd  # noqa: F401
     from dtgan_amd import _lib, ops
