@@ -145,17 +145,17 @@ __device__ __forceinline__ void spec_untangle(const float2 *z, int k, float2 &ha
     }
 }
 
-// NRP transformed row pairs z[q][S] -> rows 2q, 2q + 1 of h (row stride S/2 complex; LDS or global), two columns per store
+// NRP transformed row pairs z[q][S] -> rows 2q, 2q + 1 of h (row stride ld complex; LDS or global), two columns per store
 template <int S, int NRP>
-__device__ __forceinline__ void spec_untangle_rows(const float2 *z, float2 *h)
+__device__ __forceinline__ void spec_untangle_rows(const float2 *z, float2 *h, int ld = S / 2)
 {
     for (int t = threadIdx.x; t < NRP * (S / 4); t += blockDim.x) {
         const int q = t / (S / 4), k = (t & (S / 4 - 1)) * 2;
         float2 a0, b0, a1, b1;
         spec_untangle<S>(z + q * S, k, a0, b0);
         spec_untangle<S>(z + q * S, k + 1, a1, b1);
-        *reinterpret_cast<float4 *>(h + (long long)(2 * q) * (S / 2) + k) = make_float4(a0.x, a0.y, a1.x, a1.y);
-        *reinterpret_cast<float4 *>(h + (long long)(2 * q + 1) * (S / 2) + k) = make_float4(b0.x, b0.y, b1.x, b1.y);
+        *reinterpret_cast<float4 *>(h + (long long)(2 * q) * ld + k) = make_float4(a0.x, a0.y, a1.x, a1.y);
+        *reinterpret_cast<float4 *>(h + (long long)(2 * q + 1) * ld + k) = make_float4(b0.x, b0.y, b1.x, b1.y);
     }
 }
 
@@ -189,15 +189,16 @@ __device__ __forceinline__ int spec_isqrt(int n)                  // floor(sqrt(
 __device__ __forceinline__ int spec_isqrt_ceil(int n) { return n <= 0 ? 0 : spec_isqrt(n - 1) + 1; }
 
 // Ring b, rows of one sign of fy (neg: fy < 0; fy = 0 goes with the positive side), inside the tile's columns: the row range and
-// each row's column range follow from b (b - 1) < fx^2 + fy^2 <= b (b + 1); cells are added row by row, left to right.
-template <int S, int KT>
-__device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const float *pw, const float *pn, double &acc, int &cnt)
+// each row's column range follow from b (b - 1) < fx^2 + fy^2 <= b (b + 1); the cells are visited row by row, left to right:
+// cell(ky * KT + kx - kx0) for 0 <= kx < S/2, nyq(ky) for the column fx = -S/2
+template <int S, int KT, class Cell, class Nyq>
+__device__ __forceinline__ void spec_ring_cells(int b, bool neg, int kx0, int &cnt, Cell cell, Nyq nyq)
 {
     constexpr int H = S / 2;
     const int kx1 = kx0 + KT - 1;
     if (b == 0) {
         if (!neg && kx0 == 0) {
-            acc += (double)pw[0];
+            cell(0);
             cnt += 1;
         }
         return;
@@ -210,7 +211,7 @@ __device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const fl
             const int ky = neg ? S - y : y;
             const int xh = min(spec_isqrt(up - y * y), kx1), xl = max(spec_isqrt_ceil(lo - y * y), kx0);
             for (int x = xl; x <= xh; ++x) {
-                acc += (double)pw[ky * KT + (x - kx0)];
+                cell(ky * KT + (x - kx0));
                 cnt += x == 0 ? 1 : 2;
             }
         }
@@ -218,10 +219,16 @@ __device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const fl
     if (b == H && kx0 == 0) {                                     // the column fx = -S/2: H^2 + fy^2 <= H (H + 1)
         const int ylast = spec_isqrt(H);
         for (int y = neg ? 1 : 0; y <= ylast; ++y) {
-            acc += (double)pn[neg ? S - y : y];
+            nyq(neg ? S - y : y);
             cnt += 1;
         }
     }
+}
+
+template <int S, int KT>
+__device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const float *pw, const float *pn, double &acc, int &cnt)
+{
+    spec_ring_cells<S, KT>(b, neg, kx0, cnt, [&](int i) { acc += (double)pw[i]; }, [&](int ky) { acc += (double)pn[ky]; });
 }
 
 template <int S, int T>                  // T: threads of the workgroup
@@ -354,6 +361,15 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const 
 
 static bool spec_size_ok(int S) { return S >= SPEC_MIN_S && S <= SPEC_MAX_S && (S & (S - 1)) == 0; }
 
+// 16-byte loads where the layout allows them: four pixels of a planar row, or a C4 pixel's channels
+static int spec_load_mode(const float *x, int C, long long row_stride, int pix_stride, long long chan_stride)
+{
+    const bool aligned = (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
+    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) return SPEC_PLANAR;
+    if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) return SPEC_C4;
+    return SPEC_SCALAR;
+}
+
 extern "C" size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S)
 {
     if (rows < 1 || C < 1 || !spec_size_ok(S) || S <= SPEC_ONE_WG_MAX_S) return 0;
@@ -393,11 +409,7 @@ extern "C" int acg_radial_spectrum(const float *x, int rows, int C, int S, long 
         return ACG_ERR_WORKSPACE;
     }
     ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_radial_spectrum: the workspace must be 16-byte aligned");
-    // 16-byte loads where the layout allows them: four pixels of a planar row, or a C4 pixel's channels
-    const bool aligned = (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
-    int mode = SPEC_SCALAR;
-    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) mode = SPEC_PLANAR;
-    else if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) mode = SPEC_C4;
+    const int mode = spec_load_mode(x, C, row_stride, pix_stride, chan_stride);
     hipStream_t st = (hipStream_t)stream;
     const int fields = rows * C;
     float2 *half = (float2 *)ws;
@@ -715,5 +727,281 @@ extern "C" int acg_radial_spectrum_bwd(const float *x, const float *g, int rows,
     default: spec_bwd_launch<1024>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
     }
     ACG_CHECK_LAUNCH("acg_radial_spectrum_bwd");
+    return ACG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Paired cross-spectra (ops.cross_spectrum, model.translate_coherence, test.py --metric coherence): per pair of fields x, y
+// and ring, the means of Pxx = |X|^2 / S^2, Pyy = |Y|^2 / S^2 and the co-spectrum Cxy = Re(X conj Y) / S^2.  The quadrature part
+// Im(X conj Y) sums to 0 over every ring of two real fields (the twin cell holds the conjugate product) and is no output.
+// The two fields share every pass, but never a complex transform: tangled as z = x + i y, the rounding of the stronger field
+// would leak into the weaker one's spectrum at the stronger one's scale (a generator against a truth 1000 times fainter).
+//   rows     each field as in the forward (rows 2r and 2r + 1 of ONE field per complex transform), untangled into a [ky][S]
+//            tile: X's packed half spectrum in columns 0 .. S/2 - 1, Y's behind.
+//   columns  the forward's column stages on that tile (above S = 64: S/2 columns of it at a time, half of them X's, half Y's).
+//   products w |X|^2, w |Y|^2, w Re(X conj Y), each / S^2, per cell into three planes, w as in spec_power; the packed column
+//            (kx = 0 and S/2) is untangled for both fields before their product is taken.  Of the column kx = S/2 only the rows
+//            |fy| < cross_nyq(S) / 2 are kept: a ring reaches no further (fy^2 <= S/2).
+//   rings    the forward's enumeration and order, three double sums per (ring, sign of fy).  No float atomics.
+// A pair holds two half spectra, 64 KiB of LDS in two buffers at S = 64: one workgroup per pair up to there (two share a CU),
+// above a row pass and a column pass (one workgroup per pair) through a workspace of S x S complex per pair.
+#define CROSS_ONE_WG_MAX_S 64
+// slots of the kept rows of the column kx = S/2: row fy in slot fy & (slots - 1); fy^2 <= S/2 <= 512 lies well inside
+__host__ __device__ constexpr int cross_nyq(int S) { return S < 64 ? S : 64; }
+
+// threads of the one-workgroup kernel: a stage has S^2 / 2 butterflies
+__host__ __device__ constexpr int cross_field_threads(int S) { return S <= 16 ? 64 : S <= 32 ? 256 : 512; }
+
+// A transformed [S][2 KH] tile, X's columns kx0 .. kx0 + KH - 1 in front and Y's behind -> pl[3][S][KH]: the weighted Pxx, Pyy,
+// Cxy of every cell; the tile of kx0 = 0 untangles both packed columns into kx = 0 (pl[.][ky][0]) and kx = S/2 (pn[3][cross_nyq(S)])
+template <int S, int KH>
+__device__ __forceinline__ void cross_products(const float2 *f, int kx0, float *pl, float *pn)
+{
+    constexpr int KT = 2 * KH, H = S / 2, NQ = cross_nyq(S);
+    const float inv = 1.f / ((float)S * (float)S);
+    for (int t = threadIdx.x; t < S * KH; t += blockDim.x) {
+        const int ky = t / KH, c = t & (KH - 1);
+        const float2 u = f[ky * KT + c], v = f[ky * KT + KH + c];
+        if (kx0 + c == 0) {
+            const int kz = (S - ky) & (S - 1), fy = ky < H ? ky : ky - S;
+            const float2 u2 = f[kz * KT], v2 = f[kz * KT + KH];
+            const float xdr = u.x + u2.x, xdi = u.y - u2.y, xnr = u.x - u2.x, xni = u.y + u2.y;
+            const float ydr = v.x + v2.x, ydi = v.y - v2.y, ynr = v.x - v2.x, yni = v.y + v2.y;
+            pl[t] = (xdr * xdr + xdi * xdi) * (0.25f * inv);
+            pl[S * KH + t] = (ydr * ydr + ydi * ydi) * (0.25f * inv);
+            pl[2 * S * KH + t] = (xdr * ydr + xdi * ydi) * (0.25f * inv);
+            if (fy > -NQ / 2 && fy < NQ / 2) {
+                const int slot = fy & (NQ - 1);
+                pn[slot] = (xnr * xnr + xni * xni) * (0.25f * inv);
+                pn[NQ + slot] = (ynr * ynr + yni * yni) * (0.25f * inv);
+                pn[2 * NQ + slot] = (xnr * ynr + xni * yni) * (0.25f * inv);
+            }
+        } else {
+            pl[t] = (u.x * u.x + u.y * u.y) * (2.f * inv);
+            pl[S * KH + t] = (v.x * v.x + v.y * v.y) * (2.f * inv);
+            pl[2 * S * KH + t] = (u.x * v.x + u.y * v.y) * (2.f * inv);
+        }
+    }
+}
+
+template <int S, int T>                  // SpecBins with the three sums of a pair; T: threads of the workgroup
+struct CrossBins {
+    static constexpr int NB = S / 2 + 1;
+    static constexpr int NI = (2 * NB + T - 1) / T;
+    static constexpr size_t LDS_BYTES = 2 * NB * (3 * sizeof(double) + sizeof(int));
+    double acc[NI][3];
+    int cnt[NI];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
+            cnt[i] = 0;
+        }
+    }
+    template <int KH>
+    __device__ __forceinline__ void add_tile(int kx0, const float *pl, const float *pn)
+    {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int it = threadIdx.x + i * T;
+            if (it >= 2 * NB) continue;
+            double &a0 = acc[i][0], &a1 = acc[i][1], &a2 = acc[i][2];
+            spec_ring_cells<S, KH>(
+                it >> 1, it & 1, kx0, cnt[i],
+                [&](int c) {
+                    a0 += (double)pl[c];
+                    a1 += (double)pl[S * KH + c];
+                    a2 += (double)pl[2 * S * KH + c];
+                },
+                [&](int ky) {
+                    const int slot = (ky < S / 2 ? ky : ky - S) & (cross_nyq(S) - 1);
+                    a0 += (double)pn[slot];
+                    a1 += (double)pn[cross_nyq(S) + slot];
+                    a2 += (double)pn[2 * cross_nyq(S) + slot];
+                });
+        }
+    }
+    // out[k][b] = (sum+ + sum-) / cells for k = Pxx, Pyy, Cxy; lds: LDS_BYTES, free to overwrite
+    __device__ __forceinline__ void store(void *lds, float *__restrict__ out)
+    {
+        double *fin = reinterpret_cast<double *>(lds);
+        int *fcnt = reinterpret_cast<int *>(fin + 6 * NB);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int it = threadIdx.x + i * T;
+            if (it < 2 * NB) {
+                fin[3 * it] = acc[i][0];
+                fin[3 * it + 1] = acc[i][1];
+                fin[3 * it + 2] = acc[i][2];
+                fcnt[it] = cnt[i];
+            }
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < 3 * NB; t += blockDim.x) {
+            const int k = t / NB, b = t - k * NB;
+            out[t] = (float)((fin[6 * b + k] + fin[6 * b + 3 + k]) / (double)(fcnt[2 * b] + fcnt[2 * b + 1]));
+        }
+    }
+};
+
+// where a workgroup's pair reads its two fields: pair p is channel c of row r of x against channel c of row r / x_per_y of y
+struct CrossSrc {
+    const float *x, *y;
+    long long x_row, x_chan, y_row, y_chan;
+    int x_pix, y_pix, x_mode, y_mode, x_per_y, C;
+};
+__device__ __forceinline__ void cross_fields(const CrossSrc &s, int p, const float *&xf, int &cx, const float *&yf, int &cy)
+{
+    const int row = p / s.C, c = p - row * s.C;
+    xf = spec_field(s.x, p, s.C, s.x_row, s.x_chan, s.x_mode, cx);
+    yf = spec_field(s.y, (row / s.x_per_y) * s.C + c, s.C, s.y_row, s.y_chan, s.y_mode, cy);
+}
+
+// S <= 64: one workgroup per pair; nothing but out is written
+template <int S>
+__global__ __launch_bounds__(cross_field_threads(S)) void cross_spectrum_field_kernel(CrossSrc src, float *__restrict__ out)
+{
+    constexpr int H = S / 2, T = cross_field_threads(S);
+    __shared__ __attribute__((aligned(16))) float2 buf0[S * S];
+    __shared__ __attribute__((aligned(16))) float2 buf1[S * S];
+    __shared__ float2 tw[S];
+    static_assert(3 * (S * H + cross_nyq(S)) * sizeof(float) <= sizeof(buf0) && CrossBins<S, T>::LDS_BYTES <= sizeof(buf0), "LDS");
+    const float *xf, *yf;
+    int cx, cy;
+    cross_fields(src, blockIdx.x, xf, cx, yf, cy);
+    spec_twiddles<S>(tw);
+    spec_load_rows<S, H>(xf, src.x_pix, src.x_mode, cx, 0, buf0);
+    spec_load_rows<S, H>(yf, src.y_pix, src.y_mode, cy, 0, buf0 + H * S);
+    __syncthreads();
+    float2 *z = spec_fft_rows<S, S>(buf0, buf1, tw);               // x's S/2 row pairs, then y's
+    float2 *h = z == buf0 ? buf1 : buf0;
+    spec_untangle_rows<S, H>(z, h, S);                             // [ky][S]: X's half spectrum | Y's
+    spec_untangle_rows<S, H>(z + H * S, h + H, S);
+    __syncthreads();
+    float2 *f = spec_fft_cols<S, S>(h, z, tw);
+    float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + 3 * S * H;
+    cross_products<S, H>(f, 0, pl, pn);
+    __syncthreads();
+    CrossBins<S, T> bins;
+    bins.clear();
+    bins.template add_tile<H>(0, pl, pn);
+    bins.store(f, out + (long long)blockIdx.x * 3 * CrossBins<S, T>::NB);
+}
+
+// S > 64, first pass: SPEC_TILE / S row pairs of one field of a pair per workgroup (blockIdx.y: x's tiles, then y's) -> their
+// rows of that field's side of the pair's [ky][S] tile in the workspace
+template <int S>
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void cross_spectrum_rows_kernel(CrossSrc src, float2 *__restrict__ half)
+{
+    constexpr int NRP = SPEC_TILE / S, TILES = (S / 2) / NRP;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    const float *xf, *yf;
+    int cx, cy;
+    cross_fields(src, blockIdx.x, xf, cx, yf, cy);
+    const bool of_y = blockIdx.y >= TILES;
+    const int rp0 = (blockIdx.y - (of_y ? TILES : 0)) * NRP;
+    spec_twiddles<S>(tw);
+    if (of_y) spec_load_rows<S, NRP>(yf, src.y_pix, src.y_mode, cy, rp0, buf0);
+    else spec_load_rows<S, NRP>(xf, src.x_pix, src.x_mode, cx, rp0, buf0);
+    __syncthreads();
+    const float2 *z = spec_fft_rows<S, NRP>(buf0, buf1, tw);
+    spec_untangle_rows<S, NRP>(z, half + ((long long)blockIdx.x * S + 2 * rp0) * S + (of_y ? S / 2 : 0), S);
+}
+
+// S > 64, second pass: one workgroup per pair walks both half spectra in tiles of SPEC_TILE / (2 S) columns of each
+template <int S>
+__global__ __launch_bounds__(SPEC_COLS_THREADS) void cross_spectrum_cols_kernel(const float2 *__restrict__ half, float *__restrict__ out)
+{
+    constexpr int KT = SPEC_TILE / S, KH = KT / 2, H = S / 2;
+    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
+    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
+    __shared__ float2 tw[S];
+    static_assert(KH >= 2 && 3 * (S * KH + cross_nyq(S)) * sizeof(float) <= sizeof(buf0) &&
+                      CrossBins<S, SPEC_COLS_THREADS>::LDS_BYTES <= sizeof(buf0), "LDS");
+    const float2 *hf = half + (long long)blockIdx.x * S * S;
+    spec_twiddles<S>(tw);
+    CrossBins<S, SPEC_COLS_THREADS> bins;
+    bins.clear();
+    float2 *f = buf0;
+    for (int kx0 = 0; kx0 < H; kx0 += KH) {
+        for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+            const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+            const int col = cc < KH ? kx0 + cc : H + kx0 + cc - KH;  // X's columns, then Y's
+            *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * S + col);
+        }
+        __syncthreads();
+        f = spec_fft_cols<S, KT>(buf0, buf1, tw);
+        float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + 3 * S * KH;
+        cross_products<S, KH>(f, kx0, pl, pn);
+        __syncthreads();
+        bins.template add_tile<KH>(kx0, pl, pn);
+        __syncthreads();                                           // pl may be buf0, which the next tile's load overwrites
+    }
+    bins.store(f, out + (long long)blockIdx.x * 3 * CrossBins<S, SPEC_COLS_THREADS>::NB);
+}
+
+extern "C" size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S)
+{
+    if (rows < 1 || C < 1 || !spec_size_ok(S) || S <= CROSS_ONE_WG_MAX_S) return 0;
+    return (size_t)rows * (size_t)C * (size_t)S * (size_t)S * sizeof(float2);
+}
+
+template <int S>
+static void cross_launch(hipStream_t st, const CrossSrc &src, int pairs, float *out, float2 *half)
+{
+    if constexpr (S <= CROSS_ONE_WG_MAX_S) {
+        hipLaunchKernelGGL(cross_spectrum_field_kernel<S>, dim3(pairs), dim3(cross_field_threads(S)), 0, st, src, out);
+        acg_note_kernel("cross_spectrum_field<%d>", S);
+    } else {
+        hipLaunchKernelGGL(cross_spectrum_rows_kernel<S>, dim3(pairs, S / (SPEC_TILE / S)), dim3(SPEC_ROWS_THREADS), 0, st, src, half);  // x's and y's tiles
+        hipLaunchKernelGGL(cross_spectrum_cols_kernel<S>, dim3(pairs), dim3(SPEC_COLS_THREADS), 0, st, (const float2 *)half, out);
+        acg_note_kernel("cross_spectrum_rows<%d> + cross_spectrum_cols<%d>", S, S);
+    }
+}
+
+extern "C" int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int S, long long x_row_stride,
+                                  int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                                  long long y_chan_stride, float *out, void *ws, size_t ws_bytes, void *stream)
+{
+    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_cross_spectrum: null tensor");
+    ACG_REQUIRE(spec_size_ok(S), "acg_cross_spectrum: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
+                SPEC_MAX_S, S);
+    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_cross_spectrum: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_cross_spectrum: too many pairs (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
+                    y_chan_stride >= 1,
+                "acg_cross_spectrum: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, "
+                "channel %lld)", x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
+    ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0,
+                "acg_cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)", rows, x_per_y);
+    const size_t need = acg_cross_spectrum_workspace_bytes(rows, C, S);
+    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
+        acg_set_error("acg_cross_spectrum: workspace too small (%zu < %zu)", ws_bytes, need);
+        return ACG_ERR_WORKSPACE;
+    }
+    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_cross_spectrum: the workspace must be 16-byte aligned");
+    CrossSrc src;
+    src.x = x, src.y = y;
+    src.x_row = x_row_stride, src.x_chan = x_chan_stride, src.y_row = y_row_stride, src.y_chan = y_chan_stride;
+    src.x_pix = x_pix_stride, src.y_pix = y_pix_stride;
+    src.x_mode = spec_load_mode(x, C, x_row_stride, x_pix_stride, x_chan_stride);
+    src.y_mode = spec_load_mode(y, C, y_row_stride, y_pix_stride, y_chan_stride);
+    src.x_per_y = x_per_y, src.C = C;
+    hipStream_t st = (hipStream_t)stream;
+    const int pairs = rows * C;
+    float2 *half = (float2 *)ws;
+    switch (S) {
+    case 16: cross_launch<16>(st, src, pairs, out, half); break;
+    case 32: cross_launch<32>(st, src, pairs, out, half); break;
+    case 64: cross_launch<64>(st, src, pairs, out, half); break;
+    case 128: cross_launch<128>(st, src, pairs, out, half); break;
+    case 256: cross_launch<256>(st, src, pairs, out, half); break;
+    case 512: cross_launch<512>(st, src, pairs, out, half); break;
+    default: cross_launch<1024>(st, src, pairs, out, half); break;
+    }
+    ACG_CHECK_LAUNCH("acg_cross_spectrum");
     return ACG_OK;
 }

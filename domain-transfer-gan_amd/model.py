@@ -568,6 +568,53 @@ class _Base(object):
                 m.training = mode
         return out
 
+    def translate_coherence(self, real_A, n_samples, real_B, z=None, chunk=None):
+        """Whether the variance of A -> B is in the right place: the paired cross-spectra (ops.cross_spectrum: per ring the
+        means of Pxx, Pyy and the co-spectrum Cxy, x the translation, y the paired real_B) of each of n_samples translations
+        of every input and of their per-pixel mean.  z, chunk, the eval state, the grouping and the refusals are
+        translate_spectrum's.  Per group: generator -> members (NHWC) -> their cross-spectra against the group's real_B rows
+        (one truth per M members); acg_ensemble_stats for the mean map alone -> its cross-spectra.  Returns device tensors:
+        members (N, M, C, 3, nb) and ens_mean (N, C, 3, nb), nb = S/2 + 1, to be summed over a set of pairs and handed to
+        ops.coherence_summary.  Nothing is read back to the host."""
+        M = int(n_samples)
+        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+            raise ValueError("translate_coherence: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        N, _, H, W = real_A.shape
+        C = self.opt.output_nc
+        nb = ops._spectrum_size(H, W) // 2 + 1
+        if z is None:
+            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
+        if z.size(0) != N * M:
+            raise ValueError("translate_coherence: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
+        if real_B.dim() != 4 or (real_B.size(0), real_B.size(1)) != (N, C):
+            raise ValueError("translate_coherence: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
+        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
+        per = chunk // M
+        if per < 1:
+            raise ValueError("translate_coherence: a group of %d images cannot hold one input's %d samples" % (chunk, M))
+        G = self.netG_A_B
+        f = dict(device=real_A.device, dtype=torch.float32)
+        out = dict(members=torch.empty((N, M, C, 3, nb), **f), ens_mean=torch.empty((N, C, 3, nb), **f))
+        real_B = real_B.detach().contiguous()
+        modes = [(m, m.training) for m in G.modules()]
+        G.eval()
+        try:
+            with torch.no_grad():
+                img_in = _starts_with_conv(G.model)
+                for g0 in range(0, N, per):
+                    n = min(per, N - g0)
+                    a, b = real_A[g0:g0 + n], real_B[g0:g0 + n]
+                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
+                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
+                    ops.cross_spectrum(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 3, nb))
+                    mean = torch.empty((n, C, H, W), **f)
+                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
+                    ops.cross_spectrum(mean, b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        return out
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)

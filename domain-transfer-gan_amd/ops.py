@@ -1426,7 +1426,8 @@ def ensemble_stats(members_nhwc, target_nhwc, M, C, quantiles, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
-# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum) and the spectral loss on them
+# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum), the spectral loss on them and the
+# paired cross-spectra (model.translate_coherence, test.py --metric coherence)
 # ----------------------------------------------------------------------------------------------
 SPECTRUM_MIN_S, SPECTRUM_MAX_S = 16, 1024
 
@@ -1539,6 +1540,60 @@ def spectral_loss(x, y, C, layout, eps=1e-6):
         q = _radial_spectrum(y.detach(), C, layout).mean(0)
     d = torch.log(p[:, 1:] + eps) - torch.log(q[:, 1:] + eps)
     return (d * d).mean()
+
+
+def cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
+    """acg_cross_spectrum: the paired cross-spectra of the C valid channels of x and y -> (rows, C, 3, S/2 + 1) float32 on the
+    device holding, per ring, the means of Pxx = |X|^2 / S^2, Pyy = |Y|^2 / S^2 and the co-spectrum Cxy = Re(X conj Y) / S^2
+    in that order (X = fft2(x), Y = fft2(y); the rings of radial_spectrum).  Row r of x pairs with row r / x_per_y of y: the
+    x_per_y members of an ensemble share one truth.  Each operand has its own layout ("nhwc" or "nchw", as radial_spectrum
+    takes them).  One launch up to S = 64, a row and a column pass above; nothing is read back to the host.  Not
+    differentiable."""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    rows, C, _, S, sx = _spectrum_args(x, C, layout_x, "cross_spectrum")
+    rows_y, _, _, Sy, sy = _spectrum_args(y, C, layout_y, "cross_spectrum")
+    x_per_y = int(x_per_y)
+    if x_per_y < 1 or rows % x_per_y:
+        raise _lib.AcgError("cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)" % (rows, x_per_y))
+    if Sy != S or rows_y * x_per_y != rows:
+        raise _lib.AcgError("cross_spectrum: %d rows of %d x %d do not pair with %d rows of %d x %d at x_per_y=%d"
+                            % (rows, S, S, rows_y, Sy, Sy, x_per_y))
+    nb = S // 2 + 1
+    if out is not None and tuple(out.shape) != (rows, C, 3, nb):
+        raise _lib.AcgError("cross_spectrum: out %s is not (%d, %d, 3, %d)" % (tuple(out.shape), rows, C, nb))
+    _check(x, y, out)                                              # after the refusals that need no device
+    if out is None:
+        out = torch.empty((rows, C, 3, nb), device=x.device, dtype=torch.float32)
+    nbytes = _lib.query("acg_cross_spectrum_workspace_bytes", rows, C, S)
+    ws = workspace(nbytes, slot=2) if nbytes else None
+    _lib.call("acg_cross_spectrum", _ptr(x), _ptr(y), rows, x_per_y, C, S, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(out),
+              _ptr(ws), nbytes, _stream())
+    return out
+
+
+def coherence_summary(sums):
+    """(..., 3, nb) triples (pxx, pyy, cxy) summed over a set of pairs -> dict of float64 arrays on the host:
+      coh   (..., nb)  the spectral coherence (sum cxy)^2 / (sum pxx sum pyy), in [0, 1] by Cauchy-Schwarz, 0 where the
+                       denominator is 0;
+      r     (..., nb)  the signed correlation sum cxy / sqrt(sum pxx sum pyy), 0 where the denominator is 0;
+      perr  (..., nb)  the error spectrum pxx + pyy - 2 cxy: the radial spectrum of x - y (the summed one, as the triples are);
+      k_eff (...)      int64, the effective resolution: the smallest bin b >= 1 with coh[b] < 0.5, nb if there is none.
+    The sums matter: the ring-wise coherence of ONE pair is noisy where a ring has few cells (independent fields reach 0.3-0.6
+    in bins 1-3), so a metric pools the triples over its split before it divides."""
+    import numpy as np
+    t = np.asarray(sums, dtype=np.float64)
+    if t.ndim < 2 or t.shape[-2] != 3:
+        raise ValueError("coherence_summary: need (..., 3, nb) triples (got %s)" % (t.shape,))
+    pxx, pyy, cxy = t[..., 0, :], t[..., 1, :], t[..., 2, :]
+    den = pxx * pyy
+    ok = den > 0
+    safe = np.where(ok, den, 1.0)
+    coh = np.where(ok, np.minimum(cxy * cxy / safe, 1.0), 0.0)
+    r = np.where(ok, np.clip(cxy / np.sqrt(safe), -1.0, 1.0), 0.0)
+    nb = t.shape[-1]
+    low = coh[..., 1:] < 0.5
+    k_eff = np.where(low.any(-1), low.argmax(-1) + 1, nb).astype(np.int64)
+    return dict(coh=coh, r=r, perr=pxx + pyy - 2.0 * cxy, k_eff=k_eff)
 
 
 def mean_valid(x, C, out=None):

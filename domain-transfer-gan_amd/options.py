@@ -144,7 +144,7 @@ class TestOptions(object):
     """options.py:134-143 (the options of dtgan_amd.test).  Additions: the metric `mvgauss` (the reference's
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
-    `spectrum` (it reuses --n_samples)."""
+    `spectrum` and the metric `coherence` (both reuse --n_samples)."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -153,10 +153,10 @@ class TestOptions(object):
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
-                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum'])
+                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
 

@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -21,6 +21,14 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               of B -> A against the real A; split-mean spectra per channel and log-spectral distances in dB over bins
               1 .. S/2 (LSD = sqrt(mean_b (10 log10(p_b / q_b))^2), spectra clamped at 1e-30, the mean over channels), computed
               on the host in float64 -> <res_dir>/spectrum.npz.  Square fields, S a power of two in 16 .. 1024.  No plot
+  coherence   (new) whether that variance is in the right place: on the aligned dev and test pairs the cross-spectrum of
+              prediction x and truth y per ring (Pxx, Pyy and the co-spectrum Cxy = Re(X conj Y) / S^2; ops.cross_spectrum, one
+              transform for both fields) of --n_samples translations A -> B and of their per-pixel mean
+              (model.translate_coherence) against the paired B, and of B -> A against the paired A.  The triples are summed
+              over the split, then (ops.coherence_summary, float64 on the host) the coherence Cxy^2 / (Pxx Pyy), the signed
+              correlation, the error spectrum Pxx + Pyy - 2 Cxy (the MSE split by scale) and the effective resolution k_eff:
+              the first ring whose coherence falls below 0.5 (S/2 + 1: none does), printed as its mean over the channels ->
+              <res_dir>/coherence.npz.  Sizes as for spectrum.  No plot
 
 Deviations from the reference:
   * the pixel count is C*H*W of the data, not the hard-coded 64*64*3;
@@ -308,6 +316,41 @@ def eval_spectrum(dataset, model, n_samples, use_gpu=True):
     return res
 
 
+COHERENCE_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
+
+
+def eval_coherence(dataset, model, n_samples, use_gpu=True):
+    """paired cross-spectra on an aligned split, one read of the bin arrays per batch.  A -> B: n_samples members per input
+    and their ensemble mean (model.translate_coherence) against the paired real B; B -> A: predict_A against the paired real
+    A.  The (pxx, pyy, cxy) triples of every comparison are summed over the split (over the members too) before anything is
+    divided: one pair's ring-wise coherence is noisy where a ring has few cells.  -> dict, per comparison k of
+    COHERENCE_PAIRS: sums_k (C, 3, nb) float64 and coh_k, r_k, perr_k (C, nb), k_eff_k (C,) of ops.coherence_summary; perr_k
+    is the mean error spectrum per pair (the summed one over the number of pairs)"""
+    sums = {k: 0.0 for k in COHERENCE_PAIRS}
+    pairs = {k: 0 for k in COHERENCE_PAIRS}
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        r = model.translate_coherence(real_A, n_samples, real_B)
+        with torch.no_grad():
+            fake_A = ops.cross_spectrum(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw")
+        parts = (r['members'].flatten(0, 1), r['ens_mean'], fake_A)
+        host = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy().astype(np.float64)
+        o = 0
+        for k, t in zip(COHERENCE_PAIRS, parts):
+            sums[k] = sums[k] + host[o:o + t.numel()].reshape(tuple(t.shape)).sum(0)
+            pairs[k] += t.size(0)
+            o += t.numel()
+    res = {}
+    for k in COHERENCE_PAIRS:
+        res['sums_' + k] = sums[k]
+        summary = ops.coherence_summary(sums[k])
+        summary['perr'] = summary['perr'] / pairs[k]
+        res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
+    return res
+
+
 def _pooled_spread(spread):
     return float(np.sqrt(np.mean(np.square(spread))))
 
@@ -426,6 +469,17 @@ def test_model(argv=None):
         np.savez(os.path.join(opt.res_dir, 'spectrum.npz'), **arrays)
         print("DEV_LSD_B: %.4f, TEST_LSD_B: %.4f, TEST_LSD_MEAN_B: %.4f, TEST_LSD_A: %.4f"
               % (dev['lsd_B'], test['lsd_B'], test['lsd_mean_B'], test['lsd_A']))
+    elif opt.metric == 'coherence':
+        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
+        dev = eval_coherence(dev_dataset, model, opt.n_samples)
+        test = eval_coherence(test_dataset, model, opt.n_samples)
+        arrays = dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1]))
+        for split, res in (('dev', dev), ('test', test)):
+            arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
+        np.savez(os.path.join(opt.res_dir, 'coherence.npz'), **arrays)
+        print("DEV_KEFF_B: %.4f, TEST_KEFF_B: %.4f, TEST_KEFF_MEAN_B: %.4f, TEST_KEFF_A: %.4f, TEST_COH_B: %.4f"
+              % (dev['k_eff_members_B'].mean(), test['k_eff_members_B'].mean(), test['k_eff_ens_mean_B'].mean(),
+                 test['k_eff_fake_A'].mean(), test['coh_members_B'][:, 1:].mean()))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

@@ -458,6 +458,21 @@ int acg_radial_spectrum(const float *x, int rows, int C, int S, long long row_st
 size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S);
 int acg_radial_spectrum_bwd(const float *x, const float *g, int rows, int C, int Cp, int S, long long row_stride,
                             int pix_stride, long long chan_stride, float *gx, void *workspace, size_t ws_bytes, void *stream);
+/* Paired cross-spectra (ops.cross_spectrum, model.translate_coherence, test.py --metric coherence; tests/cross_spectrum_ref.py
+ * states the definition): row r of x pairs with row r / x_per_y of y, channel by channel (x_per_y ensemble members share one
+ * truth; rows % x_per_y must be 0).  With X = fft2(x), Y = fft2(y) as above, out (rows, C, 3, S/2 + 1) holds the ring means of
+ * Pxx = |X|^2 / S^2, Pyy = |Y|^2 / S^2 and the co-spectrum Cxy = Re(X conj Y) / S^2, in that order, by the ring rule of
+ * acg_radial_spectrum.  The quadrature part Im(X conj Y) sums to 0 over every ring of two real fields and is no output.  Each
+ * operand has its own strides (their meaning, S and the refusals are acg_radial_spectrum's); padded channels are never read
+ * into a result.  Each field is transformed as acg_radial_spectrum transforms it (the two never share a complex transform:
+ * a faint field keeps its own accuracy beside a strong one); the products are formed per cell.  fp32 transform, ring sums in double
+ * in a fixed order: deterministic, no float atomics, the same bits for every layout.  S <= 64 needs no workspace (one
+ * workgroup per pair); above, the workspace (acg_cross_spectrum_workspace_bytes, 16-byte aligned) holds both half spectra of
+ * every pair between the row and the column pass. */
+size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S);
+int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int S, long long x_row_stride,
+                       int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                       long long y_chan_stride, float *out, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */

@@ -30,6 +30,19 @@ and 512 x 512 x 1 x 32 (C4 NHWC, what the training step hands it), each over the
 gx (padded channels included).  One JSON line per case.
 
     python tools/spectrum_bench.py --backward [--reps 20] [--bwd-cases 128x3:32,256x3:32,512x1:32]
+
+--cpu-cross-tolerance, the same for the paired cross-spectra (tests/test_hip_cross_spectrum.py): Re(X conj Y) / S^2 from
+torch.fft.fft2 in float32 on the CPU, binned in float64, against tests/cross_spectrum_ref.py over that test's pair kinds and
+sizes; prints the smallest tau with |cxy - ref| <= tau (sqrt(pxx Ey) + sqrt(pyy Ex)) + tau^2 sqrt(Ex Ey) in every bin, and
+beside it what pxx and pyy need under --cpu-tolerance's bound.  The test's constant is 4 x the overall value.
+
+    python tools/spectrum_bench.py --cpu-cross-tolerance
+
+--cross: microseconds per pair of acg_cross_spectrum beside the polarisation route to the same three spectra (x + y and x - y
+materialised, acg_radial_spectrum on x, y and both: Cxy = (P(x+y) - P(x-y)) / 4), in one process with device events, at
+64 x 64 x 3, 256 x 256 x 3 and 512 x 512 x 1, x C4 NHWC (what the generator emits) against a planar y.  One JSON line per case.
+
+    python tools/spectrum_bench.py --cross [--reps 20] [--cross-cases 64x3:64,256x3:32,512x1:32]
 """
 import argparse
 import json
@@ -115,6 +128,76 @@ def cpu_grad_tolerance(loss_only=False):
                           grad_constant_4x=float("%.4e" % (4 * worst_g)))), flush=True)
 
 
+def cpu_cross_tolerance():
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cross_spectrum_ref as X
+    import spectrum_ref as R
+    worst = worst_p = 0.0
+    for S, rows, C in X.PAIR_CASES:
+        per, per_p = {}, {}
+        for kind in X.PAIR_KINDS:
+            x, y = X.make_pairs(kind, S, rows, C)
+            Fx, Fy = torch.fft.fft2(torch.from_numpy(x)), torch.fft.fft2(torch.from_numpy(y))     # complex64 on the CPU
+            cxy = (Fx.real.double() * Fy.real.double() + Fx.imag.double() * Fy.imag.double()).numpy() / float(S * S)
+            pxx = (Fx.real.double() ** 2 + Fx.imag.double() ** 2).numpy() / float(S * S)
+            pyy = (Fy.real.double() ** 2 + Fy.imag.double() ** 2).numpy() / float(S * S)
+            ref = X.cross_spectrum(x, y)
+            Ex, Ey = np.mean(x.astype(np.float64) ** 2, axis=(-2, -1)), np.mean(y.astype(np.float64) ** 2, axis=(-2, -1))
+            per[kind] = X.cross_tolerance_needed(R.bin_power(cxy), ref, Ex, Ey)
+            per_p[kind] = max(R.tolerance_needed(R.bin_power(pxx), ref[..., 0, :], Ex),
+                              R.tolerance_needed(R.bin_power(pyy), ref[..., 1, :], Ey))
+        worst, worst_p = max(worst, max(per.values())), max(worst_p, max(per_p.values()))
+        print(json.dumps(dict(tool="spectrum_bench", mode="cpu-cross-tolerance", S=S, rows=rows, C=C,
+                              tau_cxy={k: float("%.3e" % v) for k, v in per.items()},
+                              tau_pxx_pyy={k: float("%.3e" % v) for k, v in per_p.items()})), flush=True)
+    print(json.dumps(dict(tool="spectrum_bench", mode="cpu-cross-tolerance", tau_cxy_overall=float("%.4e" % worst),
+                          test_constant_4x=float("%.4e" % (4 * worst)), tau_pxx_pyy_overall=float("%.4e" % worst_p))), flush=True)
+
+
+def cross_bench(a):
+    import torch
+    import dtgan_amd  # noqa: F401
+    from dtgan_amd import _lib, ops
+    if not torch.cuda.is_available():
+        raise SystemExit("spectrum_bench needs a GPU (or one of the --cpu-* modes)")
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for case in a.cross_cases.split(","):
+        geo, rows = case.split(":")
+        S, C = (int(v) for v in geo.split("x"))
+        rows, Cp = int(rows), 4
+        x = torch.rand(rows, S, S, Cp, device="cuda", generator=gen) * 2 - 1
+        y = torch.rand(rows, C, S, S, device="cuda", generator=gen) * 2 - 1
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.reps + 1)]
+            ev[0].record()
+            for i in range(a.reps):
+                fn()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps))
+            return ms[len(ms) // 2]
+
+        def polarisation():
+            xp = x[..., :C].permute(0, 3, 1, 2)
+            s, d = (xp + y).contiguous(), (xp - y).contiguous()
+            pxx, pyy = ops.radial_spectrum(x, C, "nhwc"), ops.radial_spectrum(y, C, "nchw")
+            ps, pd = ops.radial_spectrum(s, C, "nchw"), ops.radial_spectrum(d, C, "nchw")
+            return torch.stack([pxx, pyy, (ps - pd) * 0.25], 2)
+        with torch.no_grad():
+            fused_ms = timed(lambda: ops.cross_spectrum(x, y, C, "nhwc", "nchw"))
+            kernel = _lib.query("acg_last_kernel").decode()
+            pol_ms = timed(polarisation)
+            diff = float((ops.cross_spectrum(x, y, C, "nhwc", "nchw") - polarisation()).abs().max())
+        pairs = rows * C
+        print(json.dumps(dict(tool="spectrum_bench", mode="cross", S=S, C=C, Cp=Cp, rows=rows, reps=a.reps, kernel=kernel,
+                              fused_us_per_pair=round(fused_ms * 1e3 / pairs, 2), polarisation_us_per_pair=round(pol_ms * 1e3 / pairs, 2),
+                              polarisation_over_fused=round(pol_ms / fused_ms, 2), max_abs_difference=float("%.3e" % diff))), flush=True)
+
+
 def backward_bench(a):
     import torch
     import dtgan_amd  # noqa: F401
@@ -161,9 +244,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu-tolerance", action="store_true")
     ap.add_argument("--cpu-grad-tolerance", action="store_true")
+    ap.add_argument("--cpu-cross-tolerance", action="store_true")
     ap.add_argument("--backward", action="store_true")
+    ap.add_argument("--cross", action="store_true")
+    ap.add_argument("--cross-cases", default="64x3:64,256x3:32,512x1:32")
     ap.add_argument("--bwd-cases", default="128x3:32,256x3:32,512x1:32")
-    ap.add_argument("--reps", type=int, default=None, help="default 3, with --backward 20")
+    ap.add_argument("--reps", type=int, default=None, help="default 3, with --backward or --cross 20")
     ap.add_argument("--precision", default="bf16x3")
     ap.add_argument("--N", type=int, default=200)
     ap.add_argument("--cases", default="256x3:16,512x1:16,64x3:16")
@@ -172,10 +258,14 @@ def main():
         return cpu_tolerance()
     if a.cpu_grad_tolerance:
         return cpu_grad_tolerance()
+    if a.cpu_cross_tolerance:
+        return cpu_cross_tolerance()
     if a.reps is None:
-        a.reps = 20 if a.backward else 3
+        a.reps = 20 if a.backward or a.cross else 3
     if a.backward:
         return backward_bench(a)
+    if a.cross:
+        return cross_bench(a)
     import torch
     import dtgan_amd  # noqa: F401
     from dtgan_amd import _lib, ops
