@@ -1,0 +1,355 @@
+// Neighbourhood fractions skill scores (ops.fss, model.translate_fss, test.py --metric fss; tests/fss_ref.py states the
+// definition).  Per field x, paired truth y, channel, threshold t and odd window n: events b = [x >= t] (NaN is no event),
+// window counts c(i, j) = sum of b over the cells of the centred n x n window inside the domain, and the triple
+// (sum cf^2, sum co^2, sum cf co) over the H x W cells.  Everything after the comparison is integer: the results are exact,
+// the same bits in every layout and launch order.  No atomics.
+//   events  one wave per image row (C4 NHWC: all channels of a pixel from one 16-byte load; otherwise per channel): the
+//           ballot of [x >= t] over 64 consecutive columns is one 64-bit word of the plane (row, c, t).  Rows are padded to
+//           whole words (WW = ceil(W / 64) per row); next to every row go WW + 1 16-bit prefixes, the events in the words
+//           before each.  Both live in the workspace: 10 bits per cell and threshold, never a plane per window.
+//   counts  the events of row i in columns [a, b) are pref(i, b) - pref(i, a), pref(i, k) = prefix[k / 64] + popcount of the
+//           low k % 64 bits of word k / 64: any window width costs two words and two prefixes.
+//   box     one workgroup per (x row, c, t), one thread per column j.  Per window the thread walks down its column with the
+//           running sums cf, co of the row counts of rows i - n/2 .. i + n/2 (one row enters, one leaves), and adds the three
+//           products in 64-bit registers.  No barrier inside the walk; a block reduction and one store per triple end it.
+//           Resident path (fss_box<lds>): the workgroup's planes and their prefixes, (8 WW + 2 (WW + 1)) H bytes each, are
+//           copied into LDS first (up to FSS_LDS_MAX: two planes take 21 KiB at 256^2, 39 KiB at 321^2); above
+//           (fss_box<global>) the walk reads them from the workspace through the caches.
+//   ens     E = sum over the M members of cf_m = the window count of e = sum_m b_m (box sums are linear).  e is kept as
+//           NS = bit_width(M) bit planes of the same format (fss_slices: per word a carry-save sum of the M member words, bit k
+//           of e in plane k), so the row count of e is sum_k 2^k (row count of plane k) and the ensemble's walk is the box
+//           kernel with NS planes on its x side, one workgroup per (truth row, c, t) (fss_ens<lds> while NS + 1 planes fit:
+//           16 members at 256^2 take 63 KiB).  M = 1: e is the member's own plane, no slices.
+#include "common.h"
+#include <stdint.h>
+
+#define FSS_MAX_HW 1024
+#define FSS_MAX_T 8
+#define FSS_MAX_NW 8
+#define FSS_MAX_M 64
+#define FSS_LDS_MAX (64 * 1024 - 512)      // of the 64 KiB a workgroup gets by default; the reduction takes 384 bytes
+#define FSS_MAX_NS 7                       // bit_width(FSS_MAX_M)
+#define FSS_SLICE_THREADS 256
+#define FSS_EVENT_THREADS 256
+
+typedef unsigned long long u64;
+
+struct FssPlanes {                       // event planes in the workspace: plane p at bits + p H WW, pref + p H (WW + 1)
+    u64 *bits;
+    unsigned short *pref;
+};
+
+static inline int fss_ww(int W) { return (W + 63) / 64; }
+static size_t fss_bits_bytes(size_t planes, int H, int W) { return acg_round_up(planes * H * fss_ww(W) * sizeof(u64), 16); }
+static size_t fss_pref_bytes(size_t planes, int H, int W)
+{
+    return acg_round_up(planes * H * (fss_ww(W) + 1) * sizeof(unsigned short), 16);
+}
+
+// One wave per (field row f, image row i [, channel]): words and prefixes of the planes (f, c, t), all t.  C4: x is NHWC with 4
+// stored channels, 16-byte aligned, and the wave covers channels 0 .. C - 1 (C <= 4); otherwise blockIdx.y is the channel.
+template <bool C4>
+__global__ __launch_bounds__(FSS_EVENT_THREADS) void fss_events_kernel(const float *__restrict__ x, int rows, int C, int H, int W,
+                                                                     long long row_stride, int pix_stride, long long chan_stride,
+                                                                     const float *__restrict__ thr, int T, FssPlanes pl)
+{
+    constexpr int NC = C4 ? 4 : 1;
+    const int lane = threadIdx.x & 63, WW = (W + 63) >> 6;
+    const long long item = (long long)blockIdx.x * (FSS_EVENT_THREADS / 64) + (threadIdx.x >> 6);
+    if (item >= (long long)rows * H) return;                       // whole waves leave: the ballots below see full waves
+    const int f = (int)(item / H), i = (int)(item - (long long)f * H);
+    const int c0 = C4 ? 0 : blockIdx.y, nc = C4 ? C : 1;
+    const float *xf = x + (long long)f * row_stride;
+    unsigned before = 0;                 // lane c FSS_MAX_T + t keeps the events of plane (c, t) in the words before w, and stores
+    for (int w = 0; w <= WW; ++w) {
+        const int j = w * 64 + lane;
+        const bool in = w < WW && j < W;
+        float v[NC];
+        if constexpr (C4) {
+            const float4 q = in ? reinterpret_cast<const float4 *>(xf)[(long long)i * W + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+        } else {
+            v[0] = in ? xf[(long long)c0 * chan_stride + ((long long)i * W + j) * pix_stride] : 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (c >= nc) continue;
+            for (int t = 0; t < T; ++t) {
+                const bool mine = lane == c * FSS_MAX_T + t;
+                const long long p = ((long long)f * C + c0 + c) * T + t;
+                if (mine) pl.pref[(p * H + i) * (WW + 1) + w] = (unsigned short)before;
+                if (w == WW) continue;
+                const u64 word = __ballot(in && v[c] >= thr[(c0 + c) * T + t]);   // NaN compares false: no event
+                if (mine) {
+                    pl.bits[(p * H + i) * WW + w] = word;
+                    before += __popcll(word);
+                }
+            }
+        }
+    }
+}
+
+// events of one row (bits: its WW words, pref: its WW + 1 prefixes) in columns [0, k), 0 <= k <= W
+__device__ __forceinline__ int fss_pref(const u64 *bits, const unsigned short *pref, int k)
+{
+    const int w = k >> 6, b = k & 63;
+    int n = pref[w];
+    if (b) n += __popcll(bits[w] & ((1ull << b) - 1ull));
+    return n;
+}
+__device__ __forceinline__ int fss_row_count(const u64 *bits, const unsigned short *pref, int i, int WW, int lo, int hi)
+{
+    const u64 *b = bits + (long long)i * WW;
+    const unsigned short *p = pref + (long long)i * (WW + 1);
+    return fss_pref(b, p, hi) - fss_pref(b, p, lo);
+}
+
+struct FssWindows {
+    int n, r[FSS_MAX_NW];                // radii n / 2, clamped to max(H, W) (the whole domain)
+};
+
+// sums of the workgroup's threads -> out[0..2] by thread 0; red: 3 * 16 words of LDS
+__device__ __forceinline__ void fss_block_store(u64 a, u64 b, u64 c, u64 *red, long long *out)
+{
+    u64 v[3] = {a, b, c};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned lo = __shfl_down((unsigned)v[k], off), hi = __shfl_down((unsigned)(v[k] >> 32), off);
+            v[k] += ((u64)hi << 32) | lo;
+        }
+    const int wave = threadIdx.x >> 6, nwaves = (blockDim.x + 63) >> 6;
+    __syncthreads();                                               // red is reused window after window
+    if ((threadIdx.x & 63) == 0) red[wave] = v[0], red[16 + wave] = v[1], red[32 + wave] = v[2];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 s0 = 0, s1 = 0, s2 = 0;
+        for (int w = 0; w < nwaves; ++w) s0 += red[w], s1 += red[16 + w], s2 += red[32 + w];
+        out[0] = (long long)s0, out[1] = (long long)s1, out[2] = (long long)s2;
+    }
+}
+
+// The walk of one workgroup: the x side is the sum over nx planes of 2^k times plane k's counts (nx = 1: a member's events;
+// nx = NS: the bit planes of an exceedance count), the y side one plane.  xsb, xsp: the words / prefixes between x planes.
+__device__ __forceinline__ void fss_walk(const u64 *xb, const unsigned short *xp, int nx, long long xsb, long long xsp, const u64 *yb,
+                                         const unsigned short *yp, int H, int W, const FssWindows &win, u64 *red, long long *out)
+{
+    const int j = threadIdx.x, WW = (W + 63) >> 6;
+    for (int k = 0; k < win.n; ++k) {
+        const int r = win.r[k];
+        u64 sff = 0, soo = 0, sfo = 0;
+        if (j < W) {
+            const int lo = max(j - r, 0), hi = min(j + r, W - 1) + 1;
+            auto xrow = [&](int i) {
+                int n = 0;
+                for (int m = 0; m < nx; ++m) n += fss_row_count(xb + m * xsb, xp + m * xsp, i, WW, lo, hi) << m;
+                return n;
+            };
+            long long cf = 0, co = 0;
+            for (int i = 0; i <= min(r, H - 1); ++i) {
+                cf += xrow(i);
+                co += fss_row_count(yb, yp, i, WW, lo, hi);
+            }
+            for (int i = 0; i < H; ++i) {
+                sff += (u64)(cf * cf), soo += (u64)(co * co), sfo += (u64)(cf * co);
+                const int enter = i + r + 1, leave = i - r;
+                if (enter < H) {
+                    cf += xrow(enter);
+                    co += fss_row_count(yb, yp, enter, WW, lo, hi);
+                }
+                if (leave >= 0) {
+                    cf -= xrow(leave);
+                    co -= fss_row_count(yb, yp, leave, WW, lo, hi);
+                }
+            }
+        }
+        fss_block_store(sff, soo, sfo, red, out + 3 * k);
+    }
+}
+
+// One workgroup per blockIdx.x = (x row f, c, t): its x side is the nx planes blockIdx.x nx .. of px, its truth plane
+// (f / x_per_y, c, t) of py.  The members: nx = 1 on the event planes; the ensemble: nx = NS on the slices, x_per_y = 1.
+// LDS: the nx + 1 planes are copied into dynamic LDS first (x's words, y's words, x's prefixes, y's prefixes).
+template <bool LDS>
+__global__ __launch_bounds__(FSS_MAX_HW) void fss_box_kernel(FssPlanes px, FssPlanes py, int nx, int CT, int x_per_y, int H, int W,
+                                                            FssWindows win, long long *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fss_lds[];
+    __shared__ u64 red[48];
+    const int WW = (W + 63) >> 6;
+    const long long p = blockIdx.x, f = p / CT, q = (f / x_per_y) * CT + (p - f * CT);
+    const long long nb = (long long)H * WW, np = (long long)H * (WW + 1);
+    const u64 *xb = px.bits + p * nx * nb, *yb = py.bits + q * nb;
+    const unsigned short *xp = px.pref + p * nx * np, *yp = py.pref + q * np;
+    long long *o = out + p * win.n * 3;
+    if constexpr (LDS) {
+        u64 *lb = reinterpret_cast<u64 *>(fss_lds);
+        unsigned short *lp = reinterpret_cast<unsigned short *>(lb + (nx + 1) * nb);
+        for (int t = threadIdx.x; t < nx * nb; t += blockDim.x) lb[t] = xb[t];
+        for (int t = threadIdx.x; t < nb; t += blockDim.x) lb[nx * nb + t] = yb[t];
+        for (int t = threadIdx.x; t < nx * np; t += blockDim.x) lp[t] = xp[t];
+        for (int t = threadIdx.x; t < np; t += blockDim.x) lp[nx * np + t] = yp[t];
+        __syncthreads();
+        fss_walk(lb, lp, nx, nb, np, lb + nx * nb, lp + nx * np, H, W, win, red, o);
+    } else {
+        fss_walk(xb, xp, nx, nb, np, yb, yp, H, W, win, red, o);
+    }
+}
+
+// e = the sum of the M member planes of a truth as NS bit planes: one thread per (truth plane q, image row i) adds the members'
+// words with a carry-save counter (bit k of the count in s[k]) and writes the words and row prefixes of planes q NS + k
+__global__ __launch_bounds__(FSS_SLICE_THREADS) void fss_slices_kernel(FssPlanes px, FssPlanes ps, long long planes_y, int CT, int M,
+                                                                      int NS, int H, int W)
+{
+    const long long idx = (long long)blockIdx.x * FSS_SLICE_THREADS + threadIdx.x;
+    if (idx >= planes_y * H) return;
+    const long long q = idx / H, g = q / CT, p0 = g * M * CT + (q - g * CT);     // member m's plane lies m CT planes after p0
+    const int i = (int)(idx - q * H), WW = (W + 63) >> 6;
+    unsigned before[FSS_MAX_NS];
+#pragma unroll
+    for (int k = 0; k < FSS_MAX_NS; ++k) before[k] = 0;
+    for (int w = 0; w <= WW; ++w) {
+        u64 s[FSS_MAX_NS];
+#pragma unroll
+        for (int k = 0; k < FSS_MAX_NS; ++k) s[k] = 0;
+        if (w < WW)
+            for (int m = 0; m < M; ++m) {
+                u64 carry = px.bits[((p0 + (long long)m * CT) * H + i) * WW + w];
+#pragma unroll
+                for (int k = 0; k < FSS_MAX_NS; ++k) {
+                    const u64 t = s[k] & carry;
+                    s[k] ^= carry;
+                    carry = t;
+                }
+            }
+#pragma unroll
+        for (int k = 0; k < FSS_MAX_NS; ++k) {
+            if (k >= NS) continue;
+            const long long row = (q * NS + k) * H + i;
+            ps.pref[row * (WW + 1) + w] = (unsigned short)before[k];
+            if (w < WW) ps.bits[row * WW + w] = s[k];
+            before[k] += __popcll(s[k]);
+        }
+    }
+}
+
+static int fss_slices(int M)             // bit_width(M): the planes of a count in 0 .. M; none of their own for M = 1
+{
+    int ns = 0;
+    while (M >> ns) ++ns;
+    return ns;
+}
+
+static bool fss_shape_ok(int rows, int x_per_y, int C, int H, int W, int T, int nw)
+{
+    return rows >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= FSS_MAX_HW && W <= FSS_MAX_HW && T >= 1 && T <= FSS_MAX_T && nw >= 1 &&
+           nw <= FSS_MAX_NW && x_per_y >= 1 && x_per_y <= FSS_MAX_M && rows % x_per_y == 0 &&
+           (long long)rows * C * T <= 0x7fffffffLL && (long long)rows * H <= 0x7fffffffLL;
+}
+
+// x's planes (words, prefixes), then y's, then with want_ens and x_per_y > 1 the bit_width(x_per_y) slices of every truth plane:
+// about 10 bits per cell and plane, whatever the windows
+extern "C" size_t acg_fss_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int nw, int want_ens)
+{
+    if (!fss_shape_ok(rows, x_per_y, C, H, W, T, nw)) return 0;
+    const size_t px = (size_t)rows * C * T, py = (size_t)(rows / x_per_y) * C * T;
+    const size_t ps = want_ens && x_per_y > 1 ? py * fss_slices(x_per_y) : 0;
+    return fss_bits_bytes(px, H, W) + fss_pref_bytes(px, H, W) + fss_bits_bytes(py, H, W) + fss_pref_bytes(py, H, W) +
+           fss_bits_bytes(ps, H, W) + fss_pref_bytes(ps, H, W);
+}
+
+static bool fss_c4(const float *x, int C, long long row_stride, int pix_stride, long long chan_stride)
+{
+    return pix_stride == 4 && chan_stride == 1 && C <= 4 && (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
+}
+
+static void fss_events(hipStream_t st, const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride,
+                       long long chan_stride, const float *thr, int T, FssPlanes pl)
+{
+    const unsigned blocks = (unsigned)acg_cdiv((long)rows * H, FSS_EVENT_THREADS / 64);
+    if (fss_c4(x, C, row_stride, pix_stride, chan_stride))
+        hipLaunchKernelGGL(fss_events_kernel<true>, dim3(blocks), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, row_stride,
+                           pix_stride, chan_stride, thr, T, pl);
+    else
+        hipLaunchKernelGGL(fss_events_kernel<false>, dim3(blocks, C), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, row_stride,
+                           pix_stride, chan_stride, thr, T, pl);
+}
+
+extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
+                       int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride,
+                       const float *thr, int T, const int *windows, int nw, long long *out, long long *ens_out, void *ws,
+                       size_t ws_bytes, void *stream)
+{
+    ACG_REQUIRE(x != nullptr && y != nullptr && thr != nullptr && windows != nullptr, "acg_fss: null tensor");
+    ACG_REQUIRE(out != nullptr || ens_out != nullptr, "acg_fss: out and ens_out are both NULL");
+    ACG_REQUIRE(H >= 1 && W >= 1 && H <= FSS_MAX_HW && W <= FSS_MAX_HW, "acg_fss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)",
+                FSS_MAX_HW, H, W);
+    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_fss: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    ACG_REQUIRE(T >= 1 && T <= FSS_MAX_T && nw >= 1 && nw <= FSS_MAX_NW, "acg_fss: need 1 <= T <= %d thresholds and 1 <= nw <= %d windows (T=%d, nw=%d)",
+                FSS_MAX_T, FSS_MAX_NW, T, nw);
+    ACG_REQUIRE((long long)rows * C * T <= 0x7fffffffLL && (long long)rows * H <= 0x7fffffffLL,
+                "acg_fss: too many planes (rows=%d, C=%d, T=%d, H=%d)", rows, C, T, H);
+    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
+                    y_chan_stride >= 1,
+                "acg_fss: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, channel %lld)",
+                x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
+    ACG_REQUIRE(x_per_y >= 1 && x_per_y <= FSS_MAX_M && rows % x_per_y == 0,
+                "acg_fss: x_per_y must lie in 1..%d and divide the rows of x (rows=%d, x_per_y=%d)", FSS_MAX_M, rows, x_per_y);
+    FssWindows win;
+    win.n = nw;
+    const int whole = H > W ? H : W;
+    for (int k = 0; k < FSS_MAX_NW; ++k) win.r[k] = 0;
+    for (int k = 0; k < nw; ++k) {
+        const int n = windows[k];
+        ACG_REQUIRE(n >= 1 && n % 2 == 1, "acg_fss: windows must be odd and positive (window %d is %d)", k, n);
+        win.r[k] = n / 2 < whole ? n / 2 : whole;
+        // the largest possible sum, every cell an event in every member: (v min(n, H) min(n, W))^2 H W, v = 1 or x_per_y
+        const unsigned __int128 side = (unsigned __int128)(n < H ? n : H) * (unsigned)(n < W ? n : W) * (ens_out ? x_per_y : 1);
+        ACG_REQUIRE(side * side * (unsigned)H * (unsigned)W < ((unsigned __int128)1 << 63),
+                    "acg_fss: overflow: window %d on %d x %d with %d members per truth can reach 2^63", n, H, W, ens_out ? x_per_y : 1);
+    }
+    const size_t need = acg_fss_workspace_bytes(rows, x_per_y, C, H, W, T, nw, ens_out != nullptr);
+    if (ws == nullptr || ws_bytes < need) {
+        acg_set_error("acg_fss: workspace too small (%zu < %zu)", ws_bytes, need);
+        return ACG_ERR_WORKSPACE;
+    }
+    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_fss: the workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_y = rows / x_per_y, CT = C * T;
+    const size_t npx = (size_t)rows * CT, npy = (size_t)rows_y * CT;
+    unsigned char *w8 = (unsigned char *)ws;
+    FssPlanes px, py, ps;
+    px.bits = (u64 *)w8, w8 += fss_bits_bytes(npx, H, W);
+    px.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npx, H, W);
+    py.bits = (u64 *)w8, w8 += fss_bits_bytes(npy, H, W);
+    py.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npy, H, W);
+    const int NS = fss_slices(x_per_y);
+    ps.bits = (u64 *)w8, w8 += fss_bits_bytes(npy * NS, H, W);
+    ps.pref = (unsigned short *)w8;
+    fss_events(st, x, rows, C, H, W, x_row_stride, x_pix_stride, x_chan_stride, thr, T, px);
+    fss_events(st, y, rows_y, C, H, W, y_row_stride, y_pix_stride, y_chan_stride, thr, T, py);
+    const unsigned threads = (unsigned)acg_round_up(W, 64);
+    const size_t plane = (size_t)H * fss_ww(W) * sizeof(u64) + (size_t)H * (fss_ww(W) + 1) * sizeof(unsigned short);
+    auto box = [&](const FssPlanes &xs, int nx, size_t blocks, int per, long long *o) {   // -> whether the planes went into LDS
+        const size_t lds = (nx + 1) * plane;
+        if (lds <= FSS_LDS_MAX)
+            hipLaunchKernelGGL(fss_box_kernel<true>, dim3((unsigned)blocks), dim3(threads), lds, st, xs, py, nx, CT, per, H, W, win, o);
+        else
+            hipLaunchKernelGGL(fss_box_kernel<false>, dim3((unsigned)blocks), dim3(threads), 0, st, xs, py, nx, CT, per, H, W, win, o);
+        return lds <= FSS_LDS_MAX;
+    };
+    char path[96] = "";
+    size_t len = 0;
+    if (out != nullptr) len += snprintf(path + len, sizeof(path) - len, " + fss_box<%s>", box(px, 1, npx, x_per_y, out) ? "lds" : "global");
+    if (ens_out != nullptr && x_per_y == 1) {                      // the member's own plane is the count plane
+        len += snprintf(path + len, sizeof(path) - len, " + fss_ens<%s>", box(px, 1, npy, 1, ens_out) ? "lds" : "global");
+    } else if (ens_out != nullptr) {
+        hipLaunchKernelGGL(fss_slices_kernel, dim3((unsigned)acg_cdiv((long)npy * H, FSS_SLICE_THREADS)), dim3(FSS_SLICE_THREADS), 0, st,
+                           px, ps, (long long)npy, CT, x_per_y, NS, H, W);
+        len += snprintf(path + len, sizeof(path) - len, " + fss_slices + fss_ens<%s>", box(ps, NS, npy, 1, ens_out) ? "lds" : "global");
+    }
+    acg_note_kernel("fss_events<%s>%s", fss_c4(x, C, x_row_stride, x_pix_stride, x_chan_stride) ? "c4" : "strided", path);
+    ACG_CHECK_LAUNCH("acg_fss");
+    return ACG_OK;
+}

@@ -615,6 +615,65 @@ class _Base(object):
                 m.training = mode
         return out
 
+    def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
+        """Whether A -> B puts its threshold exceedances close enough: the fractions-skill-score triples (ops.fss: per
+        channel, threshold and window the sums of cf^2, co^2 and cf co of the window counts of the events, x the translation,
+        y the paired real_B) of each of n_samples translations of every input, of the ensemble as a probability (the summed
+        counts of the M members of an input) and of their per-pixel mean.  thresholds: (C, T), windows: odd widths, as
+        ops.fss takes them.  z, chunk, the eval state, the grouping and the refusals are translate_coherence's.  Per group:
+        generator -> members (NHWC) -> one ops.fss call with x_per_y = M and the ensemble triples; acg_ensemble_stats for the
+        mean map alone -> its ops.fss.  Any H x W the generator accepts.  Returns int64 device tensors: members
+        (N, M, C, T, nw, 3), ens_prob (N, C, T, nw, 3) and ens_mean (N, C, T, nw, 3), to be summed over a set of pairs and
+        handed to ops.fss_summary (ens_prob with members=M).  Nothing is read back to the host."""
+        M = int(n_samples)
+        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+            raise ValueError("translate_fss: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        N, _, H, W = real_A.shape
+        C = self.opt.output_nc
+        win = ops.check_windows(windows)
+        if z is None:
+            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
+        if z.size(0) != N * M:
+            raise ValueError("translate_fss: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
+        if real_B.dim() != 4 or (real_B.size(0), real_B.size(1)) != (N, C):
+            raise ValueError("translate_fss: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
+        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
+        per = chunk // M
+        if per < 1:
+            raise ValueError("translate_fss: a group of %d images cannot hold one input's %d samples" % (chunk, M))
+        thr = thresholds
+        if not torch.is_tensor(thr):
+            thr = torch.tensor(thr, dtype=torch.float32)
+        thr = thr.detach().to(device=real_A.device, dtype=torch.float32).contiguous()    # once, not per group
+        if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= ops.FSS_MAX_T:
+            raise ValueError("translate_fss: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)"
+                             % (C, ops.FSS_MAX_T, tuple(thr.shape)))
+        T, nw = thr.size(1), len(win)
+        G = self.netG_A_B
+        i64 = dict(device=real_A.device, dtype=torch.int64)
+        out = dict(members=torch.empty((N, M, C, T, nw, 3), **i64), ens_prob=torch.empty((N, C, T, nw, 3), **i64),
+                   ens_mean=torch.empty((N, C, T, nw, 3), **i64))
+        real_B = real_B.detach().contiguous()
+        modes = [(m, m.training) for m in G.modules()]
+        G.eval()
+        try:
+            with torch.no_grad():
+                img_in = _starts_with_conv(G.model)
+                for g0 in range(0, N, per):
+                    n = min(per, N - g0)
+                    a, b = real_A[g0:g0 + n], real_B[g0:g0 + n]
+                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
+                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
+                    ops.fss(members, b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
+                            out=(out["members"][g0:g0 + n].view(n * M, C, T, nw, 3), out["ens_prob"][g0:g0 + n]))
+                    mean = torch.empty((n, C, H, W), device=real_A.device, dtype=torch.float32)
+                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
+                    ops.fss(mean, b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        return out
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)

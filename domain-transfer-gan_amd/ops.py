@@ -1596,6 +1596,131 @@ def coherence_summary(sums):
     return dict(coh=coh, r=r, perr=pxx + pyy - 2.0 * cxy, k_eff=k_eff)
 
 
+# ----------------------------------------------------------------------------------------------
+# neighbourhood fractions skill scores (model.translate_fss, test.py --metric fss)
+# ----------------------------------------------------------------------------------------------
+FSS_MAX_HW, FSS_MAX_T, FSS_MAX_NW, FSS_MAX_M = 1024, 8, 8, 64
+
+
+def check_windows(windows):
+    """-> the window widths as a tuple of ints; ValueError unless 1..8 odd positive widths"""
+    w = tuple(int(v) for v in windows)
+    if not 1 <= len(w) <= FSS_MAX_NW:
+        raise ValueError("need 1 to %d windows (got %d)" % (FSS_MAX_NW, len(w)))
+    if any(v < 1 or v % 2 == 0 or v != f for v, f in zip(w, windows)):
+        raise ValueError("windows must be odd positive integers (got %s)" % (tuple(windows),))
+    return w
+
+
+def _fss_args(x, C, layout, what):
+    """(rows, C, H, W, (row, pixel, channel) strides in floats) of a contiguous tensor in the layout"""
+    if x.dim() != 4 or layout not in ("nhwc", "nchw"):
+        raise _lib.AcgError("%s: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (what, tuple(x.shape), layout))
+    C = int(C)
+    if layout == "nhwc":
+        rows, H, W, Cp = x.shape
+        strides = (H * W * Cp, Cp, 1)
+    else:
+        rows, Cp, H, W = x.shape
+        strides = (Cp * H * W, 1, H * W)
+    if not (1 <= H <= FSS_MAX_HW and 1 <= W <= FSS_MAX_HW):
+        raise _lib.AcgError("%s: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (what, FSS_MAX_HW, H, W))
+    if not 1 <= C <= Cp or rows < 1:
+        raise _lib.AcgError("%s: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (what, Cp, rows, C))
+    return rows, C, int(H), int(W), strides
+
+
+def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=False, out=None):
+    """acg_fss: the fractions-skill-score triples of the C valid channels of x against y -> (rows, C, T, nw, 3) int64 on the
+    device: per threshold thresholds[c][t] and odd window n the sums over the H x W cells of cf^2, co^2 and cf co, cf / co the
+    counts of the events [x >= t] / [y >= t] (NaN is no event) in the centred n x n window of each cell, cells outside the
+    domain counting 0.  Exact integers, the same bits in every layout.  Row r of x pairs with row r / x_per_y of y.
+    thresholds: (C, T) float32 on the device, or a host array (copied to the device).  ensemble=True returns (out, ens) with ens
+    (rows / x_per_y, C, T, nw, 3) the triples (sum E^2, sum co^2, sum E co) of E = the members' summed counts; with x_per_y = 1
+    ens equals out.  `out`: the (rows, C, T, nw, 3) int64 tensor to write, or with ensemble=True the pair (out, ens).
+    Sum the triples over a set of pairs, then ops.fss_summary.  Nothing is read back to the host.  Not differentiable."""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    rows, C, H, W, sx = _fss_args(x, C, layout_x, "fss")
+    rows_y, _, Hy, Wy, sy = _fss_args(y, C, layout_y, "fss")
+    x_per_y = int(x_per_y)
+    if not 1 <= x_per_y <= FSS_MAX_M or rows % x_per_y:
+        raise _lib.AcgError("fss: x_per_y must lie in 1..%d and divide the rows of x (rows=%d, x_per_y=%d)" % (FSS_MAX_M, rows, x_per_y))
+    if (Hy, Wy) != (H, W) or rows_y * x_per_y != rows:
+        raise _lib.AcgError("fss: %d rows of %d x %d do not pair with %d rows of %d x %d at x_per_y=%d"
+                            % (rows, H, W, rows_y, Hy, Wy, x_per_y))
+    try:
+        win = check_windows(windows)
+    except ValueError as e:
+        raise _lib.AcgError("fss: %s" % e)
+    thr = thresholds
+    if not torch.is_tensor(thr):
+        import numpy as np
+        thr = torch.from_numpy(np.ascontiguousarray(np.asarray(thr, dtype=np.float32)))
+    if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= FSS_MAX_T:
+        raise _lib.AcgError("fss: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)" % (C, FSS_MAX_T, tuple(thr.shape)))
+    T, nw = int(thr.size(1)), len(win)
+    o, e = (out if ensemble else (out, None)) if out is not None else (None, None)
+    shapes = ((rows, C, T, nw, 3), (rows_y, C, T, nw, 3))
+    for t, shape, name in ((o, shapes[0], "out"), (e, shapes[1], "ens")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.int64 or not t.is_contiguous()):
+            raise _lib.AcgError("fss: %s %s %s is not a contiguous int64 %s" % (name, tuple(t.shape), t.dtype, shape))
+    if not torch.is_tensor(thresholds):
+        thr = thr.to(x.device)
+    thr = thr.detach().contiguous()
+    _check(x, y, thr)                                              # after the refusals that need no device
+    for t in (o, e):
+        if t is not None and not t.is_cuda:
+            raise _lib.AcgError("acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path" % t.device)
+    if o is None:
+        o = torch.empty(shapes[0], device=x.device, dtype=torch.int64)
+    if ensemble and e is None:
+        e = torch.empty(shapes[1], device=x.device, dtype=torch.int64)
+    nbytes = _lib.query("acg_fss_workspace_bytes", rows, x_per_y, C, H, W, T, nw, int(ensemble))
+    ws = workspace(nbytes, slot=2)
+    _lib.call("acg_fss", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
+              (ctypes.c_int * nw)(*win), nw, _ptr(o), _ptr(e), _ptr(ws), nbytes, _stream())
+    return (o, e) if ensemble else o
+
+
+def fss_summary(sums, windows, cells, members=1):
+    """(..., T, nw, 3) int64 triples (sum cf^2, sum co^2, sum cf co) summed over a set of pairs of `cells` cells in all ->
+    dict of float64 arrays on the host:
+      fss (..., T, nw)   2 sum cf co / (sum cf^2 + sum co^2), NaN where the denominator is 0 (no event on either side).
+                         members = M > 1: the triples are the ensemble's (sum E^2, sum co^2, sum E co) and the score is the
+                         probabilistic FSS_prob = 2 M sum E co / (sum E^2 + M^2 sum co^2);
+    and, when 1 is among the windows (its counts are the events themselves):
+      bias (..., T)      the frequency bias, forecast events / observed events (forecast events / M for an ensemble), NaN
+                         without observed events;
+      csi (..., T)       hits / (forecast + observed - hits), NaN where that is 0;
+      base_rate (..., T) observed events / cells;
+      useful_scale (..., T) int64: the smallest listed window with fss >= 0.5 + base_rate / 2, 0 if none qualifies."""
+    import numpy as np
+    t = np.asarray(sums)
+    win = check_windows(windows)
+    if t.ndim < 3 or t.shape[-1] != 3 or t.shape[-2] != len(win):
+        raise ValueError("fss_summary: need (..., T, %d, 3) triples (got %s)" % (len(win), t.shape))
+    M = float(int(members))
+    if M < 1:
+        raise ValueError("fss_summary: members must be at least 1 (got %s)" % (members,))
+    t = t.astype(np.float64)
+    ff, oo, fo = t[..., 0], t[..., 1], t[..., 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = ff + M * M * oo
+        res = dict(fss=np.where(den > 0, 2.0 * M * fo / den, np.nan))
+        if 1 in win:
+            k = win.index(1)
+            f1, o1, h1 = ff[..., k] / M, oo[..., k], fo[..., k] / M
+            union = f1 + o1 - h1
+            res["bias"] = np.where(o1 > 0, f1 / o1, np.nan)
+            res["csi"] = np.where(union > 0, h1 / union, np.nan)
+            res["base_rate"] = o1 / float(cells)
+            ok = res["fss"] >= (0.5 + res["base_rate"] / 2.0)[..., None]     # NaN compares false
+            order = np.argsort(win)
+            first = ok[..., order].argmax(-1)
+            res["useful_scale"] = np.where(ok.any(-1), np.asarray(win, dtype=np.int64)[order][first], 0).astype(np.int64)
+    return res
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

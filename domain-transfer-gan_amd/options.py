@@ -144,7 +144,8 @@ class TestOptions(object):
     """options.py:134-143 (the options of dtgan_amd.test).  Additions: the metric `mvgauss` (the reference's
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
-    `spectrum` and the metric `coherence` (both reuse --n_samples)."""
+    `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
+    --fss_quantiles, --fss_thresholds and --fss_windows."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -153,12 +154,21 @@ class TestOptions(object):
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
-                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence'])
+                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
+        self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),
+                                 help='--metric fss: the event thresholds as quantile levels of the real training fields, per '
+                                      'channel (trainB for A -> B, trainA for B -> A); comma-separated, inside [0, 1], at most 8')
+        self.parser.add_argument('--fss_thresholds', type=_fss_thresholds, default=None,
+                                 help='--metric fss: explicit event thresholds in data units, the same for every channel '
+                                      '(comma-separated, at most 8); overrides --fss_quantiles')
+        self.parser.add_argument('--fss_windows', type=_fss_windows, default=(1, 3, 5, 9, 17, 33),
+                                 help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
+                                      '(the cell itself: bias, CSI, base rate) is put in front if absent')
 
     def parse(self, argv=None):
         return self.parser.parse_args(argv)
@@ -179,3 +189,37 @@ def _quantiles(s):
     if not 1 <= len(q) <= 8 or any(not 0.0 <= v <= 1.0 for v in q) or any(b < a for a, b in zip(q, q[1:])):
         raise argparse.ArgumentTypeError("--quantiles: 1 to 8 levels, sorted inside [0, 1] (got %r)" % s)
     return q
+
+
+def _fss_quantiles(s):
+    try:
+        q = tuple(float(t) for t in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("--fss_quantiles: not a comma-separated list of numbers: %r" % s)
+    if not 1 <= len(q) <= 8 or any(not 0.0 <= v <= 1.0 for v in q):
+        raise argparse.ArgumentTypeError("--fss_quantiles: 1 to 8 levels inside [0, 1] (got %r)" % s)
+    return q
+
+
+def _fss_thresholds(s):
+    try:
+        t = tuple(float(v) for v in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("--fss_thresholds: not a comma-separated list of numbers: %r" % s)
+    if not 1 <= len(t) <= 8 or any(v != v for v in t):
+        raise argparse.ArgumentTypeError("--fss_thresholds: 1 to 8 numbers (got %r)" % s)
+    return t
+
+
+def _fss_windows(s):
+    try:
+        w = sorted(set(int(v) for v in s.split(",")))
+    except ValueError:
+        raise argparse.ArgumentTypeError("--fss_windows: not a comma-separated list of integers: %r" % s)
+    if not w or any(v < 1 or v % 2 == 0 for v in w):
+        raise argparse.ArgumentTypeError("--fss_windows: odd positive widths (got %r)" % s)
+    if w[0] != 1:
+        w.insert(0, 1)
+    if len(w) > 8:
+        raise argparse.ArgumentTypeError("--fss_windows: at most 8 widths, 1 included (got %r)" % s)
+    return tuple(w)

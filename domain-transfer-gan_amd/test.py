@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -29,6 +29,19 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               correlation, the error spectrum Pxx + Pyy - 2 Cxy (the MSE split by scale) and the effective resolution k_eff:
               the first ring whose coherence falls below 0.5 (S/2 + 1: none does), printed as its mean over the channels ->
               <res_dir>/coherence.npz.  Sizes as for spectrum.  No plot
+  fss         (new) whether threshold exceedances are put close enough: the fractions skill score (Roberts & Lean 2008) per
+              channel, threshold and neighbourhood width.  Events are [x >= t]; per odd window n the events around every cell
+              are counted (cells outside the domain count 0) for prediction (cf) and truth (co), and the integer triples
+              (sum cf^2, sum co^2, sum cf co) come from ops.fss (HIP, exact).  Thresholds: per channel the --fss_quantiles of
+              the real training fields (trainB for A -> B, trainA for B -> A; np.quantile in float64, cast to float32), or the
+              --fss_thresholds in data units; windows: --fss_windows.  Compared on the aligned dev and test pairs: the
+              --n_samples translations A -> B (members_B), the ensemble as a probability (ens_prob_B: the members' summed
+              counts, FSS_prob = 2 M sum E co / (sum E^2 + M^2 sum co^2)) and their per-pixel mean (ens_mean_B)
+              (model.translate_fss) against the paired B, and B -> A (fake_A) against the paired A.  The triples are summed
+              over the split in int64, then (ops.fss_summary, float64 on the host) FSS = 2 sum cf co / (sum cf^2 + sum co^2),
+              and from the window 1 the frequency bias, the CSI, the observed base rate f0 and the useful scale: the smallest
+              listed window with FSS >= 0.5 + f0 / 2 (0: none).  Printed: FSS at the median listed window and the highest
+              threshold, the mean over the channels -> <res_dir>/fss.npz.  Any H x W up to 1024.  No plot
 
 Deviations from the reference:
   * the pixel count is C*H*W of the data, not the hard-coded 64*64*3;
@@ -351,6 +364,59 @@ def eval_coherence(dataset, model, n_samples, use_gpu=True):
     return res
 
 
+FSS_PAIRS = ('members_B', 'ens_prob_B', 'ens_mean_B', 'fake_A')
+
+
+def fss_thresholds(train, quantiles, explicit=None):
+    """the event thresholds of one domain -> (C, T) float32: the explicit values for every channel, else per channel the
+    quantile levels of its real training fields (N, C, H, W), np.quantile in float64"""
+    train = np.asarray(train)
+    C = train.shape[1]
+    if explicit is not None:
+        return np.tile(np.asarray(explicit, dtype=np.float32)[None, :], (C, 1))
+    x = train.astype(np.float64).transpose(1, 0, 2, 3).reshape(C, -1)
+    return np.quantile(x, np.asarray(quantiles, dtype=np.float64), axis=1).T.astype(np.float32)
+
+
+def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use_gpu=True):
+    """fractions-skill-score triples on an aligned split, one read of the sums per batch.  A -> B: n_samples members per
+    input, the ensemble as a probability and the ensemble mean (model.translate_fss) against the paired real B; B -> A:
+    predict_A against the paired real A.  The int64 triples of every comparison are summed over the split (over the members
+    too) before anything is divided.  -> dict, per comparison k of FSS_PAIRS: sums_k (C, T, nw, 3) int64 and fss_k (C, T, nw),
+    bias_k, csi_k, base_rate_k (C, T), useful_scale_k (C, T) int64 of ops.fss_summary (ens_prob_B with members=n_samples)"""
+    sums = {k: 0 for k in FSS_PAIRS}
+    cells = {k: 0 for k in FSS_PAIRS}
+    thr_B = thr_A = None
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        if thr_B is None:
+            thr_B = torch.from_numpy(np.ascontiguousarray(thresholds_B)).to(real_B.device)
+            thr_A = torch.from_numpy(np.ascontiguousarray(thresholds_A)).to(real_A.device)
+        r = model.translate_fss(real_A, n_samples, real_B, thr_B, windows)
+        with torch.no_grad():
+            fake_A = ops.fss(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw", thr_A, windows)
+        parts = (r['members'].flatten(0, 1), r['ens_prob'], r['ens_mean'], fake_A)
+        host = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy()
+        o = 0
+        for k, t in zip(FSS_PAIRS, parts):
+            sums[k] = sums[k] + host[o:o + t.numel()].reshape(tuple(t.shape)).sum(0, dtype=np.int64)
+            cells[k] += t.size(0) * real_B.size(2) * real_B.size(3)
+            o += t.numel()
+    res = {}
+    for k in FSS_PAIRS:
+        res['sums_' + k] = np.asarray(sums[k], dtype=np.int64)
+        summary = ops.fss_summary(sums[k], windows, cells[k], members=n_samples if k == 'ens_prob_B' else 1)
+        res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
+    return res
+
+
+def _chan_mean(v):
+    v = np.asarray(v, dtype=np.float64)
+    return float(np.nanmean(v)) if np.isfinite(v).any() else float('nan')
+
+
 def _pooled_spread(spread):
     return float(np.sqrt(np.mean(np.square(spread))))
 
@@ -379,7 +445,8 @@ def test_model(argv=None):
     opt = argparse.Namespace(**vars(args))
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
-    for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles'):
+    for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles', 'fss_quantiles', 'fss_thresholds',
+              'fss_windows'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -480,6 +547,24 @@ def test_model(argv=None):
         print("DEV_KEFF_B: %.4f, TEST_KEFF_B: %.4f, TEST_KEFF_MEAN_B: %.4f, TEST_KEFF_A: %.4f, TEST_COH_B: %.4f"
               % (dev['k_eff_members_B'].mean(), test['k_eff_members_B'].mean(), test['k_eff_ens_mean_B'].mean(),
                  test['k_eff_fake_A'].mean(), test['coh_members_B'][:, 1:].mean()))
+    elif opt.metric == 'fss':
+        thr_B = fss_thresholds(trainB, opt.fss_quantiles, opt.fss_thresholds)     # once: dev and test share the climatology
+        thr_A = fss_thresholds(trainA, opt.fss_quantiles, opt.fss_thresholds)
+        win = tuple(opt.fss_windows)
+        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
+        dev = eval_fss(dev_dataset, model, opt.n_samples, thr_B, thr_A, win)
+        test = eval_fss(test_dataset, model, opt.n_samples, thr_B, thr_A, win)
+        arrays = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
+        for split, res in (('dev', dev), ('test', test)):
+            arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
+        np.savez(os.path.join(opt.res_dir, 'fss.npz'), **arrays)
+        levels = opt.fss_thresholds if opt.fss_thresholds is not None else opt.fss_quantiles
+        t, w = int(np.argmax(levels)), len(win) // 2     # the highest threshold, the median listed window
+        print("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "
+              "TEST_USEFUL_SCALE_B: %.4f"
+              % (_chan_mean(dev['fss_members_B'][:, t, w]), _chan_mean(test['fss_members_B'][:, t, w]),
+                 _chan_mean(test['fss_ens_prob_B'][:, t, w]), _chan_mean(test['fss_ens_mean_B'][:, t, w]),
+                 _chan_mean(test['fss_fake_A'][:, t, w]), float(test['useful_scale_members_B'][:, t].mean())))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

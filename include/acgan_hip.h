@@ -474,6 +474,38 @@ int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, in
                        int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                        long long y_chan_stride, float *out, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- neighbourhood fractions skill scores (ops.fss, model.translate_fss, test.py --metric fss; no reference call site: the
+ *      reference has no verification code, tests/fss_ref.py states the definition; Roberts & Lean 2008) ----
+ * x: rows x C fields of H x W fp32 cells, y: rows / x_per_y x C paired truths; row r of x pairs with row r / x_per_y of y
+ * (x_per_y ensemble members share one truth).  The strides (in floats) mean what they mean in acg_cross_spectrum: NHWC with
+ * Cp stored channels is (H W Cp, Cp, 1) - padded channels never reach a result - and planar NCHW is (C H W, 1, H W); each
+ * operand has its own.  thr: (C, T) thresholds on the device; windows: nw odd widths in HOST memory, read before the launch.
+ * Per field, channel c, threshold t and window n: the events are b = [x >= thr[c][t]] (NaN is no event), the count plane is
+ * c(i, j) = the events in the cells |i' - i| <= n/2, |j' - j| <= n/2 inside the domain (cells outside count 0; the fraction
+ * c / n^2 is never formed); with cf of x and co of its truth
+ *   out     (rows, C, T, nw, 3) int64: sum cf^2, sum co^2, sum cf co over the H W cells;
+ *   ens_out (rows / x_per_y, C, T, nw, 3) int64: sum E^2, sum co^2, sum E co with E = the sum of cf over the x_per_y members
+ *           of a truth (the window count of the exceedance-count plane).  With x_per_y = 1 it is allowed and equals out.
+ * Either may be NULL, not both; both are fully written.  FSS = 2 sum cf co / (sum cf^2 + sum co^2), after the triples of a
+ * set of pairs are summed (ops.fss_summary).  All arithmetic on counts is integer, products and sums in 64 bits: exact, no
+ * atomics, the same bits for every layout and launch order.  Nothing is read back; capturable in a HIP graph.
+ * Limits: 1 <= H, W <= 1024 (need not be equal), 1 <= T <= 8, 1 <= nw <= 8, 1 <= x_per_y <= 64; a window n >= 2 max(H, W) - 1
+ * is the whole domain.  Refused before a launch (-1, acg_last_error starts with "acg_fss"): an even or non-positive window,
+ * rows % x_per_y != 0, a stride < 1, both outputs NULL, a misaligned workspace (16 bytes), and "overflow": a window whose
+ * largest possible sum (v min(n, H) min(n, W))^2 H W reaches 2^63, v = x_per_y with ens_out, else 1 (1024^2 with the whole
+ * domain and v = 1 is exactly 2^60 and accepted).  A workspace below acg_fss_workspace_bytes returns -2.
+ * The workspace holds event planes, per plane one bit per cell in rows of WW = ceil(W / 64) 64-bit words and WW + 1 16-bit row
+ * prefixes: 16-byte rounded 8 P H WW + 2 P H (WW + 1) bytes for the P = rows C T planes of x, then the same for the planes of
+ * y, then, with want_ens and x_per_y > 1, for bit_width(x_per_y) slices per plane of y (the bits of the exceedance count); it
+ * does not depend on nw.  Kernels: fss_events (one wave per image row), then one workgroup per (row, c, t) walking all
+ * windows with its two planes in LDS when they fit 64 KiB - 512 (fss_box<lds>, up to 321^2 and beyond), else from the
+ * workspace (fss_box<global>); ens_out adds fss_slices and the same walk over the slices, one workgroup per (truth row, c, t)
+ * (fss_ens<lds>: 16 members at 256^2 fit; fss_ens<global> above). */
+size_t acg_fss_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int nw, int want_ens);
+int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride, int x_pix_stride,
+            long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr, int T,
+            const int *windows, int nw, long long *out, long long *ens_out, void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
