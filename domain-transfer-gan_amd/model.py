@@ -468,49 +468,37 @@ class _Base(object):
         """each A against multi_prior_z_B.size(0) / |A| consecutive codes (train.py:66)"""
         return self.predict_B(_each_n_times(real_A, multi_prior_z_B.size(0) // real_A.size(0)), multi_prior_z_B)
 
+    def ensemble_groups(self, real_A, z, M, per):
+        """The member loop of every translate_* method, a plain generator -> (g0, n, members): for inputs g0 .. g0 + n - 1
+        (n <= per whole inputs, plan_ensemble) the n*M translations as forward_nhwc gives them, NHWC, member m of input i at
+        row (i - g0)*M + m, made from rows i*M + m of z passed through _z (cycle_gan: a degenerate ensemble).  It keeps no
+        state of its own to undo: the caller iterates it inside `with eval_state(self.netG_A_B), torch.no_grad():`, so a
+        consumer that raises between two groups still leaves the flags and the grad mode as they were."""
+        G = self.netG_A_B
+        img_in = _starts_with_conv(G.model)
+        for g0 in range(0, real_A.size(0), per):
+            a = real_A[g0:g0 + per]
+            n = a.size(0)
+            x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
+            yield g0, n, G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
+
     def translate_ensemble(self, real_A, n_samples, z=None, real_B=None, quantiles=(0.05, 0.5, 0.95), chunk=None):
         """The distribution of A -> B: n_samples translations of every input, summarised per pixel on the device.
         z: (N*n_samples, nlatent, 1, 1) codes in generate_multi's order (input n takes rows n*M .. n*M + M - 1; default N(0, 1)
-        from torch's generator), passed through _z (cycle_gan: a degenerate ensemble).  The generator runs in eval state
-        under no_grad on groups of whole inputs of at most `chunk` images (default: ensemble_chunk), each group followed by
-        one acg_ensemble_stats launch into slices of the outputs.  Returns device tensors: mean, std (N, C, H, W) and
-        quantiles (N, nq, C, H, W); with real_B also the per-input crps, crps_fair (NaN for one sample), mse_mean, spread,
-        coverage (N,), rank_hist (N, M + 1) and crps_map (N, C, H, W).  Nothing is read back to the host."""
-        M = int(n_samples)
-        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
-            raise ValueError("translate_ensemble: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        from torch's generator); chunk: the most images one generator pass may hold (default: ensemble_chunk).  Arguments are
+        settled by plan_ensemble and the members come group by group from ensemble_groups, in eval state under no_grad; each
+        group is followed by one acg_ensemble_stats launch into slices of the outputs.  Returns device tensors: mean, std
+        (N, C, H, W) and quantiles (N, nq, C, H, W); with real_B also the per-input crps, crps_fair (NaN for one sample),
+        mse_mean, spread, coverage (N,), rank_hist (N, M + 1) and crps_map (N, C, H, W).  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_ensemble", self.opt, real_A, n_samples, z, real_B, chunk)
         q = ops.check_quantiles(quantiles)
-        N, _, H, W = real_A.shape
-        C = self.opt.output_nc
-        if z is None:
-            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
-        if z.size(0) != N * M:
-            raise ValueError("translate_ensemble: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
-        if real_B is not None and (real_B.size(0), real_B.size(1)) != (N, C):
-            raise ValueError("translate_ensemble: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
-        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
-        per = chunk // M
-        if per < 1:
-            raise ValueError("translate_ensemble: a group of %d images cannot hold one input's %d samples" % (chunk, M))
-        G = self.netG_A_B
         out = ops.ensemble_outputs(N, M, C, H, W, len(q), real_B is not None, real_A.device)
-        modes = [(m, m.training) for m in G.modules()]
-        G.eval()
-        try:
-            with torch.no_grad():
-                img_in = _starts_with_conv(G.model)
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a = real_A[g0:g0 + n]
-                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
-                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
-                    tgt = None
-                    if real_B is not None:
-                        tgt = ops.ToNHWC.apply(real_B[g0:g0 + n], members.shape[-1] == ops.cimg(C))
-                    ops.ensemble_stats(members, tgt, M, C, q, out={k: v[g0:g0 + n] for k, v in out.items()})
-        finally:
-            for m, mode in modes:
-                m.training = mode
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                tgt = None
+                if real_B is not None:
+                    tgt = ops.ToNHWC.apply(real_B[g0:g0 + n], members.shape[-1] == ops.cimg(C))
+                ops.ensemble_stats(members, tgt, M, C, q, out={k: v[g0:g0 + n] for k, v in out.items()})
         if real_B is None:
             return out
         sums, cells = out.pop("sums"), float(C * H * W)
@@ -524,123 +512,53 @@ class _Base(object):
 
     def translate_spectrum(self, real_A, n_samples, z=None, real_B=None, chunk=None):
         """The variance of A -> B at every spatial scale: the radially averaged power spectrum (ops.radial_spectrum) of each
-        of n_samples translations of every input and of their per-pixel mean.  z, chunk, the eval state and the grouping are
-        translate_ensemble's.  Per group: generator -> members (NHWC) -> their spectra; acg_ensemble_stats for the mean map
-        alone -> its spectrum.  Returns device tensors: members (N, M, C, nb), ens_mean (N, C, nb) and with real_B also
-        target (N, C, nb), nb = S/2 + 1.  Nothing is read back to the host."""
-        M = int(n_samples)
-        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
-            raise ValueError("translate_spectrum: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
-        N, _, H, W = real_A.shape
-        C = self.opt.output_nc
+        of n_samples translations of every input and of their per-pixel mean (_ensemble_mean).  z, chunk and the refusals:
+        plan_ensemble; the members: ensemble_groups.  Square fields of a power of two (ops.radial_spectrum's rule).  Returns
+        device tensors: members (N, M, C, nb), ens_mean (N, C, nb) and with real_B also target (N, C, nb), nb = S/2 + 1.
+        Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_spectrum", self.opt, real_A, n_samples, z, real_B, chunk)
         nb = ops._spectrum_size(H, W) // 2 + 1
-        if z is None:
-            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
-        if z.size(0) != N * M:
-            raise ValueError("translate_spectrum: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
-        if real_B is not None and (real_B.size(0), real_B.size(1)) != (N, C):
-            raise ValueError("translate_spectrum: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
-        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
-        per = chunk // M
-        if per < 1:
-            raise ValueError("translate_spectrum: a group of %d images cannot hold one input's %d samples" % (chunk, M))
-        G = self.netG_A_B
         f = dict(device=real_A.device, dtype=torch.float32)
         out = dict(members=torch.empty((N, M, C, nb), **f), ens_mean=torch.empty((N, C, nb), **f))
-        modes = [(m, m.training) for m in G.modules()]
-        G.eval()
-        try:
-            with torch.no_grad():
-                img_in = _starts_with_conv(G.model)
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a = real_A[g0:g0 + n]
-                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
-                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
-                    ops.radial_spectrum(members, C, "nhwc", out=out["members"][g0:g0 + n].view(n * M, C, nb))
-                    mean = torch.empty((n, C, H, W), **f)
-                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
-                    ops.radial_spectrum(mean, C, "nchw", out=out["ens_mean"][g0:g0 + n])
-                if real_B is not None:
-                    out["target"] = ops.radial_spectrum(real_B, C, "nchw")
-        finally:
-            for m, mode in modes:
-                m.training = mode
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                ops.radial_spectrum(members, C, "nhwc", out=out["members"][g0:g0 + n].view(n * M, C, nb))
+                ops.radial_spectrum(_ensemble_mean(members, M, C), C, "nchw", out=out["ens_mean"][g0:g0 + n])
+            if real_B is not None:
+                out["target"] = ops.radial_spectrum(real_B, C, "nchw")
         return out
 
     def translate_coherence(self, real_A, n_samples, real_B, z=None, chunk=None):
         """Whether the variance of A -> B is in the right place: the paired cross-spectra (ops.cross_spectrum: per ring the
         means of Pxx, Pyy and the co-spectrum Cxy, x the translation, y the paired real_B) of each of n_samples translations
-        of every input and of their per-pixel mean.  z, chunk, the eval state, the grouping and the refusals are
-        translate_spectrum's.  Per group: generator -> members (NHWC) -> their cross-spectra against the group's real_B rows
-        (one truth per M members); acg_ensemble_stats for the mean map alone -> its cross-spectra.  Returns device tensors:
-        members (N, M, C, 3, nb) and ens_mean (N, C, 3, nb), nb = S/2 + 1, to be summed over a set of pairs and handed to
-        ops.coherence_summary.  Nothing is read back to the host."""
-        M = int(n_samples)
-        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
-            raise ValueError("translate_coherence: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
-        N, _, H, W = real_A.shape
-        C = self.opt.output_nc
+        of every input, one truth per M members, and of their per-pixel mean (_ensemble_mean).  z, chunk and the refusals:
+        plan_ensemble, real_B required; the members: ensemble_groups.  Sizes as for translate_spectrum.  Returns device
+        tensors: members (N, M, C, 3, nb) and ens_mean (N, C, 3, nb), nb = S/2 + 1, to be summed over a set of pairs and handed
+        to ops.coherence_summary.  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_coherence", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         nb = ops._spectrum_size(H, W) // 2 + 1
-        if z is None:
-            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
-        if z.size(0) != N * M:
-            raise ValueError("translate_coherence: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
-        if real_B.dim() != 4 or (real_B.size(0), real_B.size(1)) != (N, C):
-            raise ValueError("translate_coherence: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
-        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
-        per = chunk // M
-        if per < 1:
-            raise ValueError("translate_coherence: a group of %d images cannot hold one input's %d samples" % (chunk, M))
-        G = self.netG_A_B
         f = dict(device=real_A.device, dtype=torch.float32)
         out = dict(members=torch.empty((N, M, C, 3, nb), **f), ens_mean=torch.empty((N, C, 3, nb), **f))
         real_B = real_B.detach().contiguous()
-        modes = [(m, m.training) for m in G.modules()]
-        G.eval()
-        try:
-            with torch.no_grad():
-                img_in = _starts_with_conv(G.model)
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a, b = real_A[g0:g0 + n], real_B[g0:g0 + n]
-                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
-                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
-                    ops.cross_spectrum(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 3, nb))
-                    mean = torch.empty((n, C, H, W), **f)
-                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
-                    ops.cross_spectrum(mean, b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
-        finally:
-            for m, mode in modes:
-                m.training = mode
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                b = real_B[g0:g0 + n]
+                ops.cross_spectrum(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 3, nb))
+                ops.cross_spectrum(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
         return out
 
     def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
         """Whether A -> B puts its threshold exceedances close enough: the fractions-skill-score triples (ops.fss: per
         channel, threshold and window the sums of cf^2, co^2 and cf co of the window counts of the events, x the translation,
         y the paired real_B) of each of n_samples translations of every input, of the ensemble as a probability (the summed
-        counts of the M members of an input) and of their per-pixel mean.  thresholds: (C, T), windows: odd widths, as
-        ops.fss takes them.  z, chunk, the eval state, the grouping and the refusals are translate_coherence's.  Per group:
-        generator -> members (NHWC) -> one ops.fss call with x_per_y = M and the ensemble triples; acg_ensemble_stats for the
-        mean map alone -> its ops.fss.  Any H x W the generator accepts.  Returns int64 device tensors: members
-        (N, M, C, T, nw, 3), ens_prob (N, C, T, nw, 3) and ens_mean (N, C, T, nw, 3), to be summed over a set of pairs and
-        handed to ops.fss_summary (ens_prob with members=M).  Nothing is read back to the host."""
-        M = int(n_samples)
-        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
-            raise ValueError("translate_fss: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
-        N, _, H, W = real_A.shape
-        C = self.opt.output_nc
+        counts of the M members of an input, the same ops.fss call with x_per_y = M) and of their per-pixel mean
+        (_ensemble_mean).  thresholds: (C, T), moved to the device once; windows: odd widths, as ops.fss takes them.  z,
+        chunk and the refusals: plan_ensemble, real_B required; the members: ensemble_groups.  Any H x W the generator
+        accepts.  Returns int64 device tensors: members (N, M, C, T, nw, 3), ens_prob (N, C, T, nw, 3) and ens_mean
+        (N, C, T, nw, 3), to be summed over a set of pairs and handed to ops.fss_summary (ens_prob with members=M).  Nothing is
+        read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_fss", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         win = ops.check_windows(windows)
-        if z is None:
-            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
-        if z.size(0) != N * M:
-            raise ValueError("translate_fss: z holds %d codes for %d inputs x %d samples" % (z.size(0), N, M))
-        if real_B.dim() != 4 or (real_B.size(0), real_B.size(1)) != (N, C):
-            raise ValueError("translate_fss: real_B %s does not pair with real_A %s" % (tuple(real_B.shape), tuple(real_A.shape)))
-        chunk = ensemble_chunk(self.opt.ngf, H, W) if chunk is None else int(chunk)
-        per = chunk // M
-        if per < 1:
-            raise ValueError("translate_fss: a group of %d images cannot hold one input's %d samples" % (chunk, M))
         thr = thresholds
         if not torch.is_tensor(thr):
             thr = torch.tensor(thr, dtype=torch.float32)
@@ -649,29 +567,16 @@ class _Base(object):
             raise ValueError("translate_fss: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)"
                              % (C, ops.FSS_MAX_T, tuple(thr.shape)))
         T, nw = thr.size(1), len(win)
-        G = self.netG_A_B
         i64 = dict(device=real_A.device, dtype=torch.int64)
         out = dict(members=torch.empty((N, M, C, T, nw, 3), **i64), ens_prob=torch.empty((N, C, T, nw, 3), **i64),
                    ens_mean=torch.empty((N, C, T, nw, 3), **i64))
         real_B = real_B.detach().contiguous()
-        modes = [(m, m.training) for m in G.modules()]
-        G.eval()
-        try:
-            with torch.no_grad():
-                img_in = _starts_with_conv(G.model)
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a, b = real_A[g0:g0 + n], real_B[g0:g0 + n]
-                    x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
-                    members = G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
-                    ops.fss(members, b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
-                            out=(out["members"][g0:g0 + n].view(n * M, C, T, nw, 3), out["ens_prob"][g0:g0 + n]))
-                    mean = torch.empty((n, C, H, W), device=real_A.device, dtype=torch.float32)
-                    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
-                    ops.fss(mean, b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
-        finally:
-            for m, mode in modes:
-                m.training = mode
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                b = real_B[g0:g0 + n]
+                ops.fss(members, b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
+                        out=(out["members"][g0:g0 + n].view(n * M, C, T, nw, 3), out["ens_prob"][g0:g0 + n]))
+                ops.fss(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
         return out
 
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
@@ -738,6 +643,50 @@ def ensemble_chunk(ngf, H, W):
     512 x 512 with ngf 32"""
     per_image = H * W * ops.cpad(2 * ngf) * 4
     return max(((1 << 32) - 1) // per_image, 1)
+
+
+def plan_ensemble(who, opt, real_A, n_samples, z=None, real_B=None, chunk=None, need_B=False):
+    """What every translate_* method settles before its generator runs -> (M, N, C, H, W, z, per): M samples of each of N
+    inputs, the C x H x W of a translation, the (N*M, nlatent, 1, 1) codes (drawn here, once, from torch's generator when none
+    are given) and `per`, the whole inputs of one group: chunk // M, chunk defaulting to ensemble_chunk.  ValueError (prefixed
+    `who`) for n_samples outside 1..ops.ENSEMBLE_MAX_M, codes that do not count N*M, a real_B (required with need_B) that does
+    not pair with real_A, and a chunk below M.  Shapes and Python only: no kernel, no device work beyond the draw."""
+    M = int(n_samples)
+    if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+        raise ValueError("%s: n_samples must lie in 1..%d (got %d)" % (who, ops.ENSEMBLE_MAX_M, M))
+    N, _, H, W = real_A.shape
+    C = opt.output_nc
+    if z is None:
+        z = real_A.new_empty((N * M, opt.nlatent, 1, 1)).normal_(0, 1)
+    if z.size(0) != N * M:
+        raise ValueError("%s: z holds %d codes for %d inputs x %d samples" % (who, z.size(0), N, M))
+    if (need_B and real_B.dim() != 4) or (real_B is not None and (real_B.size(0), real_B.size(1)) != (N, C)):
+        raise ValueError("%s: real_B %s does not pair with real_A %s" % (who, tuple(real_B.shape), tuple(real_A.shape)))
+    chunk = ensemble_chunk(opt.ngf, H, W) if chunk is None else int(chunk)
+    per = chunk // M
+    if per < 1:
+        raise ValueError("%s: a group of %d images cannot hold one input's %d samples" % (who, chunk, M))
+    return M, N, C, H, W, z, per
+
+
+@contextlib.contextmanager
+def eval_state(net):
+    """net.eval() inside the block, every module's own .training flag back on the way out; entered together with
+    torch.no_grad() by whoever iterates _Base.ensemble_groups"""
+    modes = [(m, m.training) for m in net.modules()]
+    net.eval()
+    try:
+        yield net
+    finally:
+        for m, mode in modes:
+            m.training = mode
+
+
+def _ensemble_mean(members, M, C):
+    """the per-pixel mean of every input's M members (NHWC) -> (n, C, H, W): acg_ensemble_stats writing its mean map alone"""
+    mean = torch.empty((members.size(0) // M, C, members.size(1), members.size(2)), device=members.device, dtype=torch.float32)
+    ops.ensemble_stats(members, None, M, C, (0.5,), out=dict(mean=mean))
+    return mean
 
 
 def _each_n_times(x, n):

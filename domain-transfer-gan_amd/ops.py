@@ -1453,8 +1453,9 @@ def spectrum_bins(S):
     return np.bincount(b[b <= S // 2], minlength=S // 2 + 1).astype(np.int64)
 
 
-def _spectrum_args(x, C, layout, what):
-    """(rows, C, Cp, S, (row, pixel, channel) strides in floats) of a contiguous tensor in the layout"""
+def _field_args(x, C, layout, what):
+    """(rows, C, Cp, H, W, (row, pixel, channel) strides in floats) of a contiguous tensor in the layout; the caller applies
+    its own rule for H x W (_spectrum_size, fss's 1..FSS_MAX_HW)"""
     if x.dim() != 4 or layout not in ("nhwc", "nchw"):
         raise _lib.AcgError("%s: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (what, tuple(x.shape), layout))
     C = int(C)
@@ -1464,16 +1465,28 @@ def _spectrum_args(x, C, layout, what):
     else:
         rows, Cp, H, W = x.shape
         strides = (Cp * H * W, 1, H * W)
-    S = _spectrum_size(H, W)
     if not 1 <= C <= Cp or rows < 1:
         raise _lib.AcgError("%s: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (what, Cp, rows, C))
-    return rows, C, Cp, S, strides
+    return rows, C, Cp, int(H), int(W), strides
+
+
+def _check_pairing(what, x_per_y, max_per, rows, rows_y, hw, hw_y):
+    """row r of x pairs with row r / x_per_y of y, fields of one size -> x_per_y as an int, or the refusal"""
+    x_per_y = int(x_per_y)
+    if not 1 <= x_per_y <= max_per or rows % x_per_y:
+        raise _lib.AcgError("%s: x_per_y must lie in 1..%d and divide the rows of x (rows=%d, x_per_y=%d)"
+                            % (what, max_per, rows, x_per_y))
+    if hw_y != hw or rows_y * x_per_y != rows:
+        raise _lib.AcgError("%s: %d rows of %d x %d do not pair with %d rows of %d x %d at x_per_y=%d"
+                            % ((what, rows) + hw + (rows_y,) + hw_y + (x_per_y,)))
+    return x_per_y
 
 
 def _radial_spectrum(x, C, layout, out=None):
     x = x.contiguous()
     _check(x, out)
-    rows, C, Cp, S, strides = _spectrum_args(x, C, layout, "radial_spectrum")
+    rows, C, Cp, H, W, strides = _field_args(x, C, layout, "radial_spectrum")
+    S = _spectrum_size(H, W)
     nb = S // 2 + 1
     if out is None:
         out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
@@ -1490,7 +1503,8 @@ def radial_spectrum_bwd(x, g, C, layout):
     S/2 + 1).  NHWC: the padded channels are written as 0.  One launch (and the ring counts') up to S = 128, three above."""
     x, g = x.contiguous(), g.contiguous()
     _check(x, g)
-    rows, C, Cp, S, strides = _spectrum_args(x, C, layout, "radial_spectrum_bwd")
+    rows, C, Cp, H, W, strides = _field_args(x, C, layout, "radial_spectrum_bwd")
+    S = _spectrum_size(H, W)
     if tuple(g.shape) != (rows, C, S // 2 + 1):
         raise _lib.AcgError("radial_spectrum_bwd: the cotangent %s is not (%d, %d, %d)" % (tuple(g.shape), rows, C, S // 2 + 1))
     gx = torch.empty_like(x)
@@ -1550,14 +1564,10 @@ def cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
     takes them).  One launch up to S = 64, a row and a column pass above; nothing is read back to the host.  Not
     differentiable."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, _, S, sx = _spectrum_args(x, C, layout_x, "cross_spectrum")
-    rows_y, _, _, Sy, sy = _spectrum_args(y, C, layout_y, "cross_spectrum")
-    x_per_y = int(x_per_y)
-    if x_per_y < 1 or rows % x_per_y:
-        raise _lib.AcgError("cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)" % (rows, x_per_y))
-    if Sy != S or rows_y * x_per_y != rows:
-        raise _lib.AcgError("cross_spectrum: %d rows of %d x %d do not pair with %d rows of %d x %d at x_per_y=%d"
-                            % (rows, S, S, rows_y, Sy, Sy, x_per_y))
+    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "cross_spectrum")
+    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "cross_spectrum")
+    S, Sy = _spectrum_size(H, W), _spectrum_size(Hy, Wy)
+    x_per_y = _check_pairing("cross_spectrum", x_per_y, rows, rows, rows_y, (S, S), (Sy, Sy))
     nb = S // 2 + 1
     if out is not None and tuple(out.shape) != (rows, C, 3, nb):
         raise _lib.AcgError("cross_spectrum: out %s is not (%d, %d, 3, %d)" % (tuple(out.shape), rows, C, nb))
@@ -1612,24 +1622,6 @@ def check_windows(windows):
     return w
 
 
-def _fss_args(x, C, layout, what):
-    """(rows, C, H, W, (row, pixel, channel) strides in floats) of a contiguous tensor in the layout"""
-    if x.dim() != 4 or layout not in ("nhwc", "nchw"):
-        raise _lib.AcgError("%s: need a 4-d tensor and layout 'nhwc' or 'nchw' (got %s, %r)" % (what, tuple(x.shape), layout))
-    C = int(C)
-    if layout == "nhwc":
-        rows, H, W, Cp = x.shape
-        strides = (H * W * Cp, Cp, 1)
-    else:
-        rows, Cp, H, W = x.shape
-        strides = (Cp * H * W, 1, H * W)
-    if not (1 <= H <= FSS_MAX_HW and 1 <= W <= FSS_MAX_HW):
-        raise _lib.AcgError("%s: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (what, FSS_MAX_HW, H, W))
-    if not 1 <= C <= Cp or rows < 1:
-        raise _lib.AcgError("%s: need rows >= 1 and 1 <= C <= %d stored channels (rows=%d, C=%d)" % (what, Cp, rows, C))
-    return rows, C, int(H), int(W), strides
-
-
 def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=False, out=None):
     """acg_fss: the fractions-skill-score triples of the C valid channels of x against y -> (rows, C, T, nw, 3) int64 on the
     device: per threshold thresholds[c][t] and odd window n the sums over the H x W cells of cf^2, co^2 and cf co, cf / co the
@@ -1640,14 +1632,12 @@ def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=Fa
     ens equals out.  `out`: the (rows, C, T, nw, 3) int64 tensor to write, or with ensemble=True the pair (out, ens).
     Sum the triples over a set of pairs, then ops.fss_summary.  Nothing is read back to the host.  Not differentiable."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, H, W, sx = _fss_args(x, C, layout_x, "fss")
-    rows_y, _, Hy, Wy, sy = _fss_args(y, C, layout_y, "fss")
-    x_per_y = int(x_per_y)
-    if not 1 <= x_per_y <= FSS_MAX_M or rows % x_per_y:
-        raise _lib.AcgError("fss: x_per_y must lie in 1..%d and divide the rows of x (rows=%d, x_per_y=%d)" % (FSS_MAX_M, rows, x_per_y))
-    if (Hy, Wy) != (H, W) or rows_y * x_per_y != rows:
-        raise _lib.AcgError("fss: %d rows of %d x %d do not pair with %d rows of %d x %d at x_per_y=%d"
-                            % (rows, H, W, rows_y, Hy, Wy, x_per_y))
+    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "fss")
+    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "fss")
+    for h, w in ((H, W), (Hy, Wy)):
+        if not (1 <= h <= FSS_MAX_HW and 1 <= w <= FSS_MAX_HW):
+            raise _lib.AcgError("fss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (FSS_MAX_HW, h, w))
+    x_per_y = _check_pairing("fss", x_per_y, FSS_MAX_M, rows, rows_y, (H, W), (Hy, Wy))
     try:
         win = check_windows(windows)
     except ValueError as e:

@@ -181,41 +181,32 @@ def _n_samples(s):
     return v
 
 
-def _quantiles(s):
+def _split(name, s, kind, noun):
     try:
-        q = tuple(float(t) for t in s.split(","))
+        return [kind(t) for t in s.split(",")]
     except ValueError:
-        raise argparse.ArgumentTypeError("--quantiles: not a comma-separated list of numbers: %r" % s)
-    if not 1 <= len(q) <= 8 or any(not 0.0 <= v <= 1.0 for v in q) or any(b < a for a, b in zip(q, q[1:])):
-        raise argparse.ArgumentTypeError("--quantiles: 1 to 8 levels, sorted inside [0, 1] (got %r)" % s)
-    return q
+        raise argparse.ArgumentTypeError("%s: not a comma-separated list of %s: %r" % (name, noun, s))
 
 
-def _fss_quantiles(s):
-    try:
-        q = tuple(float(t) for t in s.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError("--fss_quantiles: not a comma-separated list of numbers: %r" % s)
-    if not 1 <= len(q) <= 8 or any(not 0.0 <= v <= 1.0 for v in q):
-        raise argparse.ArgumentTypeError("--fss_quantiles: 1 to 8 levels inside [0, 1] (got %r)" % s)
-    return q
+def _floats(name, ok, rule, ordered=False):
+    """the argparse type of a comma-separated list of 1 to 8 floats that each pass `ok`, ascending where `ordered`; `rule`
+    words the refusal"""
+    def parse(s):
+        v = tuple(_split(name, s, float, "numbers"))
+        if not 1 <= len(v) <= 8 or not all(ok(x) for x in v) or (ordered and any(b < a for a, b in zip(v, v[1:]))):
+            raise argparse.ArgumentTypeError("%s: 1 to 8 %s (got %r)" % (name, rule, s))
+        return v
+    return parse
 
 
-def _fss_thresholds(s):
-    try:
-        t = tuple(float(v) for v in s.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError("--fss_thresholds: not a comma-separated list of numbers: %r" % s)
-    if not 1 <= len(t) <= 8 or any(v != v for v in t):
-        raise argparse.ArgumentTypeError("--fss_thresholds: 1 to 8 numbers (got %r)" % s)
-    return t
+_level = lambda x: 0.0 <= x <= 1.0
+_quantiles = _floats("--quantiles", _level, "levels, sorted inside [0, 1]", ordered=True)
+_fss_quantiles = _floats("--fss_quantiles", _level, "levels inside [0, 1]")
+_fss_thresholds = _floats("--fss_thresholds", lambda x: x == x, "numbers")
 
 
 def _fss_windows(s):
-    try:
-        w = sorted(set(int(v) for v in s.split(",")))
-    except ValueError:
-        raise argparse.ArgumentTypeError("--fss_windows: not a comma-separated list of integers: %r" % s)
+    w = sorted(set(_split("--fss_windows", s, int, "integers")))
     if not w or any(v < 1 or v % 2 == 0 for v in w):
         raise argparse.ArgumentTypeError("--fss_windows: odd positive widths (got %r)" % s)
     if w[0] != 1:

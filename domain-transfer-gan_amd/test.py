@@ -261,6 +261,14 @@ def train_logvar(dataset, model, epochs=1, use_gpu=True, dequant_seq=None, eps_s
     return logvar_B
 
 
+def _read_back(tensors):
+    """device tensors of one dtype -> host arrays of their shapes, through ONE device->host copy"""
+    tensors = list(tensors)
+    host = torch.cat([t.reshape(-1) for t in tensors]).cpu().numpy()
+    ends = np.cumsum([t.numel() for t in tensors])
+    return [host[e - t.numel():e].reshape(tuple(t.shape)) for e, t in zip(ends, tensors)]
+
+
 ENSEMBLE_SCORES = ('crps', 'crps_fair', 'mse_mean', 'spread', 'coverage')
 
 
@@ -273,10 +281,10 @@ def eval_ensemble_B(dataset, model, n_samples, quantiles, use_gpu=True):
         if use_gpu:
             real_A, real_B = real_A.cuda(), real_B.cuda()
         r = model.translate_ensemble(real_A, n_samples, real_B=real_B, quantiles=quantiles)
-        host = torch.cat([torch.stack([r[k] for k in ENSEMBLE_SCORES], 1).double(), r['rank_hist'].double()], 1).cpu().numpy()
-        for i, k in enumerate(ENSEMBLE_SCORES):
-            per[k].append(host[:, i])
-        hist += host[:, len(ENSEMBLE_SCORES):].sum(0).astype(np.int64)
+        *scores, ranks = _read_back([r[k].double() for k in ENSEMBLE_SCORES + ('rank_hist',)])
+        for k, v in zip(ENSEMBLE_SCORES, scores):
+            per[k].append(v)
+        hist += ranks.sum(0).astype(np.int64)
     return {k: np.concatenate(v) for k, v in per.items()}, hist
 
 
@@ -314,11 +322,8 @@ def eval_spectrum(dataset, model, n_samples, use_gpu=True):
         with torch.no_grad():
             r['fake_A'] = ops.radial_spectrum(model.predict_A(real_B), real_A.size(1), "nchw")
         r['real_A'] = ops.radial_spectrum(real_A, real_A.size(1), "nchw")
-        host = torch.cat([r[k].reshape(-1) for k in keys]).cpu().numpy().astype(np.float64)
-        o = 0
-        for k in keys:
-            parts[k].append(host[o:o + r[k].numel()].reshape(tuple(r[k].shape)))
-            o += r[k].numel()
+        for k, v in zip(keys, _read_back([r[k] for k in keys])):
+            parts[k].append(v.astype(np.float64))
     p = {k: np.concatenate(v) for k, v in parts.items()}
     res = dict(psd_real_B=p['target'].mean(0), psd_members_B=p['members'].mean((0, 1)), psd_ens_mean_B=p['ens_mean'].mean(0),
                psd_real_A=p['real_A'].mean(0), psd_fake_A=p['fake_A'].mean(0))
@@ -349,12 +354,9 @@ def eval_coherence(dataset, model, n_samples, use_gpu=True):
         with torch.no_grad():
             fake_A = ops.cross_spectrum(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw")
         parts = (r['members'].flatten(0, 1), r['ens_mean'], fake_A)
-        host = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy().astype(np.float64)
-        o = 0
-        for k, t in zip(COHERENCE_PAIRS, parts):
-            sums[k] = sums[k] + host[o:o + t.numel()].reshape(tuple(t.shape)).sum(0)
-            pairs[k] += t.size(0)
-            o += t.numel()
+        for k, v in zip(COHERENCE_PAIRS, _read_back(parts)):
+            sums[k] = sums[k] + v.astype(np.float64).sum(0)
+            pairs[k] += v.shape[0]
     res = {}
     for k in COHERENCE_PAIRS:
         res['sums_' + k] = sums[k]
@@ -398,12 +400,9 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
         with torch.no_grad():
             fake_A = ops.fss(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw", thr_A, windows)
         parts = (r['members'].flatten(0, 1), r['ens_prob'], r['ens_mean'], fake_A)
-        host = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy()
-        o = 0
-        for k, t in zip(FSS_PAIRS, parts):
-            sums[k] = sums[k] + host[o:o + t.numel()].reshape(tuple(t.shape)).sum(0, dtype=np.int64)
-            cells[k] += t.size(0) * real_B.size(2) * real_B.size(3)
-            o += t.numel()
+        for k, v in zip(FSS_PAIRS, _read_back(parts)):
+            sums[k] = sums[k] + v.sum(0, dtype=np.int64)
+            cells[k] += v.shape[0] * real_B.size(2) * real_B.size(3)
     res = {}
     for k in FSS_PAIRS:
         res['sums_' + k] = np.asarray(sums[k], dtype=np.int64)
@@ -419,6 +418,19 @@ def _chan_mean(v):
 
 def _pooled_spread(spread):
     return float(np.sqrt(np.mean(np.square(spread))))
+
+
+def _eval_splits(opt, metric, evaluate, dev_dataset, test_dataset, header, dtype=None):
+    """What the ensemble metrics share: evaluate(dataset) -> dict on dev, then on test, from the evaluator's seed alone (so
+    the codes of dev, then test, follow from it), both written under dev_ / test_ prefixes on top of the metric's `header`
+    entries to <res_dir>/<metric>.npz (dtype: what every value is cast to, None: as it comes) -> (dev, test)"""
+    torch.manual_seed(opt.seed)
+    dev, test = evaluate(dev_dataset), evaluate(test_dataset)
+    arrays = dict(header)
+    for split, res in (('dev', dev), ('test', test)):
+        arrays.update(('%s_%s' % (split, k), np.asarray(v, dtype=dtype)) for k, v in res.items())
+    np.savez(os.path.join(opt.res_dir, metric + '.npz'), **arrays)
+    return dev, test
 
 
 def _build(opt):
@@ -513,37 +525,25 @@ def test_model(argv=None):
         full_train = UnalignedIterator(trainA, trainB, batch_size=cap(len(trainA), 200))
         print("MVGauss BPP: %.4f" % compute_bpp_MVGauss_B(full_train, test_dataset))
     elif opt.metric == 'ensemble':
-        torch.manual_seed(opt.seed)          # the codes of dev, then test, follow from the evaluator's seed alone
-        dev, dev_hist = eval_ensemble_B(dev_dataset, model, opt.n_samples, opt.quantiles)
-        test, test_hist = eval_ensemble_B(test_dataset, model, opt.n_samples, opt.quantiles)
-        arrays = dict(n_samples=np.int64(opt.n_samples), quantiles=np.array(opt.quantiles, dtype=np.float64),
-                      dev_rank_hist=dev_hist, test_rank_hist=test_hist)
-        for split, scores in (('dev', dev), ('test', test)):
-            arrays.update(('%s_%s' % (split, k), v) for k, v in scores.items())
-        np.savez(os.path.join(opt.res_dir, 'ensemble.npz'), **arrays)
+        def scored(dataset):
+            scores, hist = eval_ensemble_B(dataset, model, opt.n_samples, opt.quantiles)
+            return dict(scores, rank_hist=hist)
+        dev, test = _eval_splits(opt, 'ensemble', scored, dev_dataset, test_dataset,
+                                 dict(n_samples=np.int64(opt.n_samples), quantiles=np.array(opt.quantiles, dtype=np.float64)))
         vis = next(iter(AlignedIterator(devA, devB, batch_size=cap(len(devA), 10))))
         visualize_ensemble(opt, vis['A'].cuda(), vis['B'].cuda(), model, 'ensemble_0.png')
         print("DEV_CRPS_B: %.4f, TEST_CRPS_B: %.4f, TEST_MSE_MEAN_B: %.4f, TEST_SPREAD_B: %.4f, TEST_COVERAGE_B: %.4f"
               % (dev['crps'].mean(), test['crps'].mean(), test['mse_mean'].mean(), _pooled_spread(test['spread']),
                  test['coverage'].mean()))
     elif opt.metric == 'spectrum':
-        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
-        dev = eval_spectrum(dev_dataset, model, opt.n_samples)
-        test = eval_spectrum(test_dataset, model, opt.n_samples)
-        arrays = dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1]))
-        for split, res in (('dev', dev), ('test', test)):
-            arrays.update(('%s_%s' % (split, k), np.asarray(v, dtype=np.float64)) for k, v in res.items())
-        np.savez(os.path.join(opt.res_dir, 'spectrum.npz'), **arrays)
+        dev, test = _eval_splits(opt, 'spectrum', lambda d: eval_spectrum(d, model, opt.n_samples), dev_dataset, test_dataset,
+                                 dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1])),
+                                 dtype=np.float64)
         print("DEV_LSD_B: %.4f, TEST_LSD_B: %.4f, TEST_LSD_MEAN_B: %.4f, TEST_LSD_A: %.4f"
               % (dev['lsd_B'], test['lsd_B'], test['lsd_mean_B'], test['lsd_A']))
     elif opt.metric == 'coherence':
-        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
-        dev = eval_coherence(dev_dataset, model, opt.n_samples)
-        test = eval_coherence(test_dataset, model, opt.n_samples)
-        arrays = dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1]))
-        for split, res in (('dev', dev), ('test', test)):
-            arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
-        np.savez(os.path.join(opt.res_dir, 'coherence.npz'), **arrays)
+        dev, test = _eval_splits(opt, 'coherence', lambda d: eval_coherence(d, model, opt.n_samples), dev_dataset, test_dataset,
+                                 dict(n_samples=np.int64(opt.n_samples), bin_counts=ops.spectrum_bins(devA.shape[-1])))
         print("DEV_KEFF_B: %.4f, TEST_KEFF_B: %.4f, TEST_KEFF_MEAN_B: %.4f, TEST_KEFF_A: %.4f, TEST_COH_B: %.4f"
               % (dev['k_eff_members_B'].mean(), test['k_eff_members_B'].mean(), test['k_eff_ens_mean_B'].mean(),
                  test['k_eff_fake_A'].mean(), test['coh_members_B'][:, 1:].mean()))
@@ -551,13 +551,9 @@ def test_model(argv=None):
         thr_B = fss_thresholds(trainB, opt.fss_quantiles, opt.fss_thresholds)     # once: dev and test share the climatology
         thr_A = fss_thresholds(trainA, opt.fss_quantiles, opt.fss_thresholds)
         win = tuple(opt.fss_windows)
-        torch.manual_seed(opt.seed)          # as for the ensemble: the codes of dev, then test, follow from the seed alone
-        dev = eval_fss(dev_dataset, model, opt.n_samples, thr_B, thr_A, win)
-        test = eval_fss(test_dataset, model, opt.n_samples, thr_B, thr_A, win)
-        arrays = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
-        for split, res in (('dev', dev), ('test', test)):
-            arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
-        np.savez(os.path.join(opt.res_dir, 'fss.npz'), **arrays)
+        header = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
+        dev, test = _eval_splits(opt, 'fss', lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win), dev_dataset,
+                                 test_dataset, header)
         levels = opt.fss_thresholds if opt.fss_thresholds is not None else opt.fss_quantiles
         t, w = int(np.argmax(levels)), len(win) // 2     # the highest threshold, the median listed window
         print("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "

@@ -100,3 +100,60 @@ def test_evaluator_fixture_digests(name):
         assert np.isclose(float(arr["bpp"]), arr["bpp_batches"].mean(), rtol=1e-12)
     if kind == "noisesens":
         assert arr["noise_sens"].shape == (8, meta["N"])
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int64"])
+def test_read_back_returns_every_tensor_with_its_shape(dtype):
+    import torch
+    g = torch.Generator().manual_seed(11)
+    shapes = [(3, 2, 5), (), (7,), (2, 1, 3, 3), (1,)]
+    ts = [(torch.randn(s, generator=g) * 100).to(getattr(torch, dtype)) for s in shapes]
+    got = T._read_back(ts)
+    assert len(got) == len(ts)
+    for a, t in zip(got, ts):
+        assert a.shape == tuple(t.shape) and a.dtype == np.dtype(dtype) and np.array_equal(a, t.numpy())
+    (only,) = T._read_back(iter(ts[:1]))                           # any iterable, a single tensor included
+    assert np.array_equal(only, ts[0].numpy())
+
+
+def _plan_opt():
+    import argparse
+    return argparse.Namespace(output_nc=3, nlatent=4, ngf=8)
+
+
+def test_plan_ensemble_on_cpu_tensors():
+    import torch
+    from dtgan_amd.model import ensemble_chunk, plan_ensemble
+    opt = _plan_opt()
+    A, B = torch.zeros(3, 3, 64, 64), torch.zeros(3, 3, 64, 64)
+    M, N, C, H, W, z, per = plan_ensemble("translate_x", opt, A, 4, real_B=B, chunk=9)
+    assert (M, N, C, H, W, per) == (4, 3, 3, 64, 64, 9 // 4) and tuple(z.shape) == (N * M, 4, 1, 1)
+    assert plan_ensemble("translate_x", opt, A, 4)[-1] == ensemble_chunk(8, 64, 64) // 4      # the default chunk
+    given = torch.ones(12, 4, 1, 1)
+    assert plan_ensemble("translate_x", opt, A, 4, z=given)[5] is given
+    torch.manual_seed(5)                                           # the draw: one normal_ of the whole block of codes
+    drawn = plan_ensemble("translate_x", opt, A, 4)[5]
+    torch.manual_seed(5)
+    assert torch.equal(drawn, A.new_empty((12, 4, 1, 1)).normal_(0, 1))
+
+
+def test_plan_ensemble_refusals_on_cpu_tensors():
+    import torch
+    from dtgan_amd import ops
+    from dtgan_amd.model import plan_ensemble
+    opt = _plan_opt()
+    A, B = torch.zeros(2, 3, 64, 64), torch.zeros(2, 3, 64, 64)
+    with pytest.raises(ValueError, match=r"^translate_x: n_samples must lie in 1\.\.64 \(got 65\)$"):
+        plan_ensemble("translate_x", opt, A, 65)
+    with pytest.raises(ValueError, match=r"^translate_x: z holds 3 codes for 2 inputs x 2 samples$"):
+        plan_ensemble("translate_x", opt, A, 2, z=torch.zeros(3, 4, 1, 1))
+    with pytest.raises(ValueError, match=r"^translate_x: a group of 3 images cannot hold one input's 4 samples$"):
+        plan_ensemble("translate_x", opt, A, 4, chunk=3)
+    pair = r"^translate_x: real_B \(1, 3, 64, 64\) does not pair with real_A \(2, 3, 64, 64\)$"
+    for need_B in (False, True):
+        with pytest.raises(ValueError, match=pair):
+            plan_ensemble("translate_x", opt, A, 2, real_B=B[:1], need_B=need_B)
+    with pytest.raises(ValueError, match="does not pair"):
+        plan_ensemble("translate_x", opt, A, 2, real_B=B[0], need_B=True)
+    with pytest.raises(ValueError, match="sorted"):               # translate_ensemble's fifth refusal, next to its plan
+        ops.check_quantiles((0.9, 0.1))

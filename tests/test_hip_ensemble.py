@@ -155,6 +155,56 @@ def test_translate_ensemble_host_syncs_do_not_grow_with_groups():
     assert n1 == n4 and n1 <= 1, (n1, n4)
 
 
+def test_translate_ensemble_refusals():
+    m = _model()
+    A, B, _ = _inputs(2)
+    with pytest.raises(ValueError, match="n_samples"):
+        m.translate_ensemble(A, 65)
+    with pytest.raises(ValueError, match="codes"):
+        m.translate_ensemble(A, 2, z=torch.zeros(3, m.opt.nlatent, 1, 1, device="cuda"))
+    with pytest.raises(ValueError, match="cannot hold"):
+        m.translate_ensemble(A, 4, chunk=3)
+    with pytest.raises(ValueError, match="does not pair"):
+        m.translate_ensemble(A, 2, real_B=B[:1])
+    with pytest.raises(ValueError, match="sorted"):
+        m.translate_ensemble(A, 2, quantiles=(0.9, 0.1))
+
+
+def _translate_calls(m, A, B, M):
+    thr, win = np.zeros((3, 2), np.float32), (1, 3)
+    return dict(ensemble=lambda **kw: m.translate_ensemble(A, M, real_B=B, **kw),
+                spectrum=lambda **kw: m.translate_spectrum(A, M, real_B=B, **kw),
+                coherence=lambda **kw: m.translate_coherence(A, M, B, **kw),
+                fss=lambda **kw: m.translate_fss(A, M, B, thr, win, **kw))
+
+
+@pytest.mark.parametrize("which", ["ensemble", "spectrum", "coherence", "fss"])
+def test_flags_and_grad_mode_survive_a_raising_consumer(which, monkeypatch):
+    """every translate_* leaves the generator's .training flags and the grad mode as it found them: after a normal call from
+    either state, and when the consumer of a group raises (a host-side exception in place of ops.ensemble_stats) with
+    further groups still to come"""
+    from dtgan_amd import ops
+    m = _model()
+    G = m.netG_A_B
+    M = 2
+    A, B, _ = _inputs(3, seed=9)
+    call = _translate_calls(m, A, B, M)[which]
+    assert torch.is_grad_enabled()
+    for state in (True, False):
+        G.train(state)
+        call(chunk=M)                                              # three groups
+        assert all(mod.training is state for mod in G.modules()) and torch.is_grad_enabled()
+    G.train()
+
+    def boom(*a, **kw):
+        raise RuntimeError("consumer failed")
+    monkeypatch.setattr(ops, "ensemble_stats", boom)
+    with pytest.raises(RuntimeError, match="consumer failed"):
+        call(chunk=M)
+    assert all(mod.training is True for mod in G.modules())
+    assert torch.is_grad_enabled()
+
+
 def test_metric_ensemble(experiment):
     from test_hip_eval_driver import _png_shape, S
     from dtgan_amd import ops

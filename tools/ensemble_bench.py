@@ -3,9 +3,9 @@
 
   256 x 256 x 3 and 512 x 512 x 1, N = 200 inputs, M = 16 and 64 samples, the bench model (ngf 32, 9 residual blocks)
 
-For each case: the generator forwards of every group and the acg_ensemble_stats launches, each timed with device events
-around the same groups translate_ensemble forms, and the stats kernel's bytes (members and target read, maps written) over
-its time as GB/s and as a fraction of 8 TB/s.  One JSON line per case.
+For each case: the generator forwards of every group (the steps of model.ensemble_groups, the loop translate_ensemble runs)
+and the acg_ensemble_stats launches, each timed with device events, and the stats kernel's bytes (members and target read,
+maps written) over its time as GB/s and as a fraction of 8 TB/s.  One JSON line per case.
 
 A case whose M samples of one input do not fit one generator pass (512 x 512 with M = 64: 63 images) is reported as skipped.
 
@@ -38,8 +38,7 @@ def main():
     import torch
     import dtgan_amd  # noqa: F401
     from dtgan_amd import ops
-    from dtgan_amd.model import AugmentedCycleGAN, ensemble_chunk
-    from dtgan_amd.modules import _starts_with_conv, as_latent
+    from dtgan_amd.model import AugmentedCycleGAN, ensemble_chunk, eval_state
     if not torch.cuda.is_available():
         raise SystemExit("ensemble_bench needs a GPU")
     ops.set_precision(a.precision)
@@ -55,7 +54,6 @@ def main():
                                  n_blocks=9)
         model = AugmentedCycleGAN(opt, testing=True)
         G = model.netG_A_B
-        G.eval()
         gen = torch.Generator(device="cuda").manual_seed(1)
         A = torch.rand(N, C, S, S, device="cuda", generator=gen) * 2 - 1
         B = torch.rand(N, C, S, S, device="cuda", generator=gen) * 2 - 1
@@ -67,22 +65,22 @@ def main():
             continue
         out = ops.ensemble_outputs(N, M, C, S, S, len(QS), True, A.device)
 
+        def stamp():
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            return e
+
         def run():
             ev = []
-            with torch.no_grad():
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a_ = A[g0:g0 + n]
-                    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                    e[0].record()
-                    x = ops.ToNHWC.apply(a_.unsqueeze(1).expand(n, M, C, S, S).reshape(n * M, C, S, S), _starts_with_conv(G.model))
-                    members = G.forward_nhwc(x, as_latent(z[g0 * M:(g0 + n) * M]))
+            with eval_state(G), torch.no_grad():
+                e0 = stamp()                                       # the generator half: the step that advances the model's loop
+                for g0, n, members in model.ensemble_groups(A, z, M, per):
                     tgt = ops.ToNHWC.apply(B[g0:g0 + n], members.shape[-1] == ops.cimg(C))
-                    e[1].record()
+                    e1 = stamp()
                     ops.ensemble_stats(members, tgt, M, C, QS, out={k: v[g0:g0 + n] for k, v in out.items()})
-                    e[2].record()
-                    ev.append(e)
-                    cp = members.shape[-1]
+                    e2 = stamp()
+                    ev.append((e0, e1, e2))
+                    e0, cp = e2, members.shape[-1]
             torch.cuda.synchronize()
             return sum(e[0].elapsed_time(e[1]) for e in ev), sum(e[1].elapsed_time(e[2]) for e in ev), cp
 

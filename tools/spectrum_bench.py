@@ -269,8 +269,7 @@ def main():
     import torch
     import dtgan_amd  # noqa: F401
     from dtgan_amd import _lib, ops
-    from dtgan_amd.model import AugmentedCycleGAN, ensemble_chunk
-    from dtgan_amd.modules import _starts_with_conv, as_latent
+    from dtgan_amd.model import AugmentedCycleGAN, ensemble_chunk, eval_state
     if not torch.cuda.is_available():
         raise SystemExit("spectrum_bench needs a GPU (or --cpu-tolerance)")
     ops.set_precision(a.precision)
@@ -286,28 +285,27 @@ def main():
                                  n_blocks=9)
         model = AugmentedCycleGAN(opt, testing=True)
         G = model.netG_A_B
-        G.eval()
         gen = torch.Generator(device="cuda").manual_seed(1)
         A = torch.rand(N, C, S, S, device="cuda", generator=gen) * 2 - 1
         z = torch.randn(N * M, 16, device="cuda", generator=gen)
         per = ensemble_chunk(32, S, S) // M
         psd = torch.empty((N * M, C, S // 2 + 1), device="cuda")
 
+        def stamp():
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            return e
+
         def run():
             ev = []
-            with torch.no_grad():
-                for g0 in range(0, N, per):
-                    n = min(per, N - g0)
-                    a_ = A[g0:g0 + n]
-                    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                    e[0].record()
-                    x = ops.ToNHWC.apply(a_.unsqueeze(1).expand(n, M, C, S, S).reshape(n * M, C, S, S), _starts_with_conv(G.model))
-                    members = G.forward_nhwc(x, as_latent(z[g0 * M:(g0 + n) * M]))
-                    e[1].record()
+            with eval_state(G), torch.no_grad():
+                e0 = stamp()                                       # the generator half: the step that advances the model's loop
+                for g0, n, members in model.ensemble_groups(A, z, M, per):
+                    e1 = stamp()
                     ops.radial_spectrum(members, C, "nhwc", out=psd[g0 * M:(g0 + n) * M])
-                    e[2].record()
-                    ev.append(e)
-                    cp = members.shape[-1]
+                    e2 = stamp()
+                    ev.append((e0, e1, e2))
+                    e0, cp = e2, members.shape[-1]
             torch.cuda.synchronize()
             return sum(e[0].elapsed_time(e[1]) for e in ev), sum(e[1].elapsed_time(e[2]) for e in ev), cp
 
