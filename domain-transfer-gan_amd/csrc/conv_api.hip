@@ -916,7 +916,7 @@ __global__ __launch_bounds__(256) void dgrad_colfix_kernel(const char *__restric
 
 // data gradient (and ConvTranspose forward): gathers from the conv-OUTPUT side tensor `src`
 // (N,Ho,Wo,Co) with packed wb, writes the conv-INPUT side tensor `dst` (N,Hi,Wi,Ci).
-// addend (optional): tensor of dst's shape added to the result; only the frame path below implements it
+// (DgradSide.addend / relu_src: only the frame path and the un-padded grid below implement them)
 static void dgrad_geom(const acg_conv_desc *d, int act, Geom *g)   // the fields both strides share
 {
     g->Hin = d->Ho; g->Win = d->Wo; g->Cin = d->Co;
@@ -952,12 +952,39 @@ static bool dgrad_unpad_ok(const acg_conv_desc *d)
            d->Hi % 32 == 0 && d->Hi >= 64 && d->Co % 128 == 0;
 }
 
-static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb, const float *bias, float *dst,
-                       int act, void *ws, size_t ws_bytes, hipStream_t st, const float *addend = nullptr,
-                       const float *relu_src = nullptr, const unsigned *addend_mask = nullptr, int in_s16 = 0, int out_s16 = 0,
-                       int relu_s16 = 0, float *stats = nullptr, const acg_norm_sums *ns = nullptr,
-                       const unsigned *relu_mask = nullptr)
+static bool bf16x3_mfma() { return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA; }
+// a sign bitmask over a tensor of dx's shape (one bit per element, acg_norm_apply's layout) as the kernels index it
+static bool sign_mask_fits(const acg_conv_desc *d) { return ((long long)d->Hi * d->Wi * (d->Ci / 4)) % 8 == 0; }
+
+// the fused side inputs of a data gradient (the acg_conv2d_bwd_data* entry points, the ConvTranspose2d forwards): all optional
+struct DgradSide {
+    const float *addend = nullptr, *relu_src = nullptr;   // dst = (gradient + addend) masked by relu_src > 0; both of dst's shape
+    const unsigned *addend_mask = nullptr, *relu_mask = nullptr;   // sign bitmask gating the addend / standing in for relu_src
+    int in_s16 = 0, out_s16 = 0, relu_s16 = 0;            // src / dst / relu_src are pre-split
+    float *stats = nullptr;                               // per-tile (mean, M2) of dst (ConvTranspose2d forward)
+    const acg_norm_sums *ns = nullptr;                    // the norm in front: its backward sums leave with the tiles
+};
+
+// what the pre-split kernel can combine: a pre-split ReLU source only with pre-split output, an addend only with fp32 output
+static bool presplit_combo_ok(const Geom &g, const Taps &t, const DgradSide &s)
 {
+    return acg_igemm_x3_pre_ok(g, t) && (s.relu_s16 == 0 || s.out_s16) && (s.out_s16 == 0 || s.addend == nullptr) &&
+           (s.relu_src == nullptr || s.relu_s16 == s.out_s16);
+}
+
+// *ns -> g's ns_* fields.  Returns whether it is well-formed for rows of C channels (a sums buffer; per-sample scale / shift
+// rows at least C wide in whole float4s): what the un-padded pre-split path asks; the fp32-operand paths have their own conditions
+static bool geom_norm_sums(Geom *g, const acg_norm_sums *ns, int C)
+{
+    g->ns_x = ns->x; g->ns_mean = ns->mean; g->ns_rstd = ns->rstd; g->ns_gamma = ns->gamma; g->ns_beta = ns->beta;
+    g->ns_gstride = ns->gstride; g->ns_mask = ns->sign_mask; g->ns_act = ns->act; g->ns_part = ns->part;
+    return ns->part != nullptr && (ns->gstride == 0 || (ns->gstride >= C && ns->gstride % 4 == 0));
+}
+
+static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb, const float *bias, float *dst, int act,
+                       void *ws, size_t ws_bytes, hipStream_t st, const DgradSide &s)
+{
+    const acg_norm_sums *const ns = s.ns;
     ACG_REQUIRE(act != ACG_ACT_SIGMOID, "dgrad / ConvTranspose2d: no sigmoid epilogue");
     Geom g; Taps t;
     const int p = d->pad, K = d->K;
@@ -976,42 +1003,35 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
         }
         // Pre-split operands, 3x3, pad 1, rows that are whole tiles: the un-padded grid (Geom.unpad) — 3 % fewer tiles than the
         // padded grid, one row segment per tile, and the fold pass over the frame goes away
-        if (refl && in_s16 && dgrad_unpad_ok(d) && dgrad_frame_ok(d, g)) {
+        if (refl && s.in_s16 && dgrad_unpad_ok(d) && dgrad_frame_ok(d, g)) {
             dgrad_s1_geom(d, act, true, &g, &t);
-            ACG_REQUIRE(acg_igemm_x3_pre_ok(g, t) && (relu_s16 == 0 || out_s16) && (out_s16 == 0 || addend == nullptr) &&
-                        (relu_src == nullptr || relu_s16 == out_s16) && d->Co % 128 == 0,
+            ACG_REQUIRE(presplit_combo_ok(g, t, s) && d->Co % 128 == 0,
                         "dgrad: unsupported pre-split combination (query acg_conv2d_s16_supported)");
             const int CiP = acg_ncols_pad(d->Ci);
             hipLaunchKernelGGL(dgrad_colfix_kernel, dim3(d->N * (d->Hi / 32), 2, CiP / 128), dim3(256), 0, st, (const char *)src,
                                (const __bf16 *)wb, g.w_elems, (float *)ws, d->Hi, d->Wi, d->Co, CiP, d->Ci);
             ACG_CHECK_LAUNCH("dgrad_colfix_kernel");
-            g.unpad = 1; g.colfix = (const float *)ws; g.out2 = dst; g.addend = addend; g.relu_src = relu_src; g.addend_mask = addend_mask;
-            g.out_s16 = out_s16; g.relu_s16 = relu_s16; g.relu_mask = relu_mask;
-            if (ns != nullptr) {
-                g.ns_x = ns->x; g.ns_mean = ns->mean; g.ns_rstd = ns->rstd; g.ns_gamma = ns->gamma; g.ns_beta = ns->beta;
-                g.ns_gstride = ns->gstride; g.ns_mask = ns->sign_mask; g.ns_act = ns->act; g.ns_part = ns->part;
-                ACG_REQUIRE(ns->part != nullptr && (ns->gstride == 0 || (ns->gstride >= d->Ci && ns->gstride % 4 == 0)), "dgrad: bad acg_norm_sums");
-            }
+            g.unpad = 1; g.colfix = (const float *)ws; g.out2 = dst; g.addend = s.addend; g.relu_src = s.relu_src; g.addend_mask = s.addend_mask;
+            g.out_s16 = s.out_s16; g.relu_s16 = s.relu_s16; g.relu_mask = s.relu_mask;
+            if (ns != nullptr) ACG_REQUIRE(geom_norm_sums(&g, ns, d->Ci), "dgrad: bad acg_norm_sums");
             return acg_igemm_x3_pre_launch(src, wb, bias, dst, g, t, g.w_elems, st);
         }
-        ACG_REQUIRE((ns == nullptr || (!refl && !in_s16 && !out_s16 && addend == nullptr && relu_src == nullptr)) && relu_mask == nullptr,
+        ACG_REQUIRE((ns == nullptr || (!refl && !s.in_s16 && !s.out_s16 && s.addend == nullptr && s.relu_src == nullptr)) && s.relu_mask == nullptr,
                     "dgrad: norm sums / a sign bitmask as the ReLU source need the un-padded pre-split path or the row pipeline (query acg_conv2d_bwd_data_s16_sums_supported / acg_conv2d_bwd_data_sums_supported)");
         // the wave-specialised kernel stores the pixels nothing is mirrored onto straight into dst: only the frame is folded
         const bool frame = refl && dgrad_frame_ok(d, g);
-        ACG_REQUIRE((addend == nullptr && relu_src == nullptr) || frame,
+        ACG_REQUIRE((s.addend == nullptr && s.relu_src == nullptr) || frame,
                     "dgrad: the fused addend / ReLU mask need the frame path (query acg_conv2d_bwd_data_add_supported)");
-        if (frame) { g.fold_p = p; g.fold_H = d->Hi; g.fold_W = d->Wi; g.out2 = dst; g.addend = addend; g.relu_src = relu_src; g.addend_mask = addend_mask; }
+        if (frame) { g.fold_p = p; g.fold_H = d->Hi; g.fold_W = d->Wi; g.out2 = dst; g.addend = s.addend; g.relu_src = s.relu_src; g.addend_mask = s.addend_mask; }
         int rc;
-        if (in_s16 || out_s16 || relu_s16) { // pre-split operands: the frame path of the pre-split kernel only
-            ACG_REQUIRE(in_s16 && frame && acg_igemm_x3_pre_ok(g, t) && (relu_s16 == 0 || out_s16) && (out_s16 == 0 || addend == nullptr) &&
-                        (relu_src == nullptr || relu_s16 == out_s16),
+        if (s.in_s16 || s.out_s16 || s.relu_s16) { // pre-split operands: the frame path of the pre-split kernel only
+            ACG_REQUIRE(s.in_s16 && frame && presplit_combo_ok(g, t, s),
                         "dgrad: unsupported pre-split combination (query acg_conv2d_s16_supported)");
-            g.out_s16 = out_s16; g.relu_s16 = relu_s16;
+            g.out_s16 = s.out_s16; g.relu_s16 = s.relu_s16;
             rc = acg_igemm_x3_pre_launch(src, wb, bias, out, g, t, g.w_elems, st);
         } else {
             if (ns != nullptr) {   // fp32 operands: only the persistent row pipeline (conv_rows.hip) emits the norm-backward sums
-                g.ns_x = ns->x; g.ns_mean = ns->mean; g.ns_rstd = ns->rstd; g.ns_gamma = ns->gamma; g.ns_beta = ns->beta;
-                g.ns_gstride = ns->gstride; g.ns_mask = ns->sign_mask; g.ns_act = ns->act; g.ns_part = ns->part;
+                geom_norm_sums(&g, ns, d->Ci);
                 // (which kernel takes them is checked where the launch is dispatched: conv_bf16.hip / conv_igemm.hip refuse a
                 // geometry that would land on a kernel without the sums epilogue)
                 ACG_REQUIRE(ns->part != nullptr && !thin_in_valu_dgrad(d) && !frame && acg_conv2d_bwd_data_sums_supported(d),
@@ -1024,7 +1044,7 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
             const long long total = (long long)d->N * (2 * p * d->Wi + 2 * p * (d->Hi - 2 * p)) * (d->Ci / 4);
             const int blocks = acg_cdiv(total, 256) > 4096 ? 4096 : acg_cdiv(total, 256);
             hipLaunchKernelGGL(reflect_fold_frame_kernel, dim3(blocks), dim3(256), 0, st, (const float *)ws, dst, d->N, d->Hi,
-                               d->Wi, d->Ci, p, addend, relu_src, addend_mask, out_s16, relu_s16);
+                               d->Wi, d->Ci, p, s.addend, s.relu_src, s.addend_mask, s.out_s16, s.relu_s16);
             ACG_CHECK_LAUNCH("reflect_fold_frame_kernel");
         } else if (refl) {
             const long long total = (long long)d->N * d->Hi * d->Wi * (d->Ci / 4);
@@ -1038,7 +1058,7 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
     ACG_REQUIRE(!thin_out(d), "dgrad: stride 2 with <= 4 output channels is not supported by the thin packing");
     // stride 2: four sub-pixel phases, each a dense small-tap convolution (no zero insertion)
     ACG_REQUIRE(d->pad_mode == ACG_PAD_ZERO, "dgrad: stride 2 needs zero padding");
-    ACG_REQUIRE(addend == nullptr && relu_src == nullptr && relu_mask == nullptr && !in_s16 && !out_s16, "dgrad: stride 2 takes no fused side inputs");
+    ACG_REQUIRE(s.addend == nullptr && s.relu_src == nullptr && s.relu_mask == nullptr && !s.in_s16 && !s.out_s16, "dgrad: stride 2 takes no fused side inputs");
     ACG_REQUIRE(ns == nullptr || acg_conv2d_bwd_data_sums_supported(d), "dgrad: norm sums on this stride-2 geometry (query acg_conv2d_bwd_data_sums_supported)");
     dgrad_geom(d, act, &g);
     g.Hout = d->Hi; g.Wout = d->Wi; g.os = 2;
@@ -1074,18 +1094,17 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
             g.ph_ntaps |= nt << (8 * ph);
             ntp[ph] = nt;
         }
-        if (stats != nullptr) {
+        if (s.stats != nullptr) {
             const int per = (int)(((long long)g.GH * g.GW) / 128);
-            g.stats = stats; g.stats_cpi = 4 * per; g.stats_chunk0 = 0;
+            g.stats = s.stats; g.stats_cpi = 4 * per; g.stats_chunk0 = 0;
         }
         // 64 output channels in the bf16x3 arithmetic: all four phases in one tile, the input rows fetched once (conv_ph4.hip)
         Geom g4 = g;
         g4.nphase = 0; g4.ph_ntaps = 0;
         Taps plan;
         if (ns != nullptr) {   // the first backward pass of the norm in front of the stride-2 convolution rides on the four-phase tile
-            g4.ns_x = ns->x; g4.ns_mean = ns->mean; g4.ns_rstd = ns->rstd; g4.ns_gamma = ns->gamma; g4.ns_beta = ns->beta;
-            g4.ns_gstride = ns->gstride; g4.ns_mask = ns->sign_mask; g4.ns_act = ns->act; g4.ns_part = ns->part;
-            ACG_REQUIRE(ns->part != nullptr && stats == nullptr && acg_igemm_ph4_ok(g4) && acg_ph4_plan(t, ntp, &plan),
+            geom_norm_sums(&g4, ns, d->Ci);
+            ACG_REQUIRE(ns->part != nullptr && s.stats == nullptr && acg_igemm_ph4_ok(g4) && acg_ph4_plan(t, ntp, &plan),
                         "dgrad: norm sums on a stride-2 data gradient need the four-phase tile (query acg_conv2d_bwd_data_sums_supported)");
             return acg_igemm_ph4_launch(src, wb, bias, dst, g4, plan, g.w_elems, st);
         }
@@ -1101,9 +1120,9 @@ static int dgrad_igemm(const acg_conv_desc *d, const float *src, const float *wb
             g.Mtot = (long long)d->N * g.GH * g.GW;
             t.n = phase_taps(py, px, t, 0);
             ACG_REQUIRE(t.n > 0, "dgrad: empty phase (K=%d p=%d)", K, p);
-            if (stats != nullptr) { // each phase owns a quarter of every image's 128-pixel chunks
+            if (s.stats != nullptr) { // each phase owns a quarter of every image's 128-pixel chunks
                 const int per = (int)(((long long)g.GH * g.GW) / 128);
-                g.stats = stats; g.stats_cpi = 4 * per; g.stats_chunk0 = (py * 2 + px) * per;
+                g.stats = s.stats; g.stats_cpi = 4 * per; g.stats_chunk0 = (py * 2 + px) * per;
             }
             int rc = thin_in_valu_dgrad(d) ? thin_out_launch(src, wb, bias, dst, g, t, st) : acg_igemm_launch(src, wb, bias, dst, g, t, st);
             if (rc != ACG_OK) return rc;
@@ -1193,7 +1212,7 @@ extern "C" int acg_conv2d_bwd_data(const acg_conv_desc *d, const float *dy, cons
         ACG_CHECK_LAUNCH("direct_dgrad_kernel");
         return ACG_OK;
     }
-    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, st);
+    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, st, DgradSide());
 }
 
 // dx = data gradient + addend (a tensor of dx's shape): the residual-path gradient of a ResnetBlock joins the gradient
@@ -1213,9 +1232,9 @@ extern "C" int acg_conv2d_bwd_data_add(const acg_conv_desc *d, const float *dy, 
     int rc = check_desc(d, "acg_conv2d_bwd_data_add");
     if (rc) return rc;
     ACG_REQUIRE(addend != nullptr && acg_conv2d_bwd_data_add_supported(d), "acg_conv2d_bwd_data_add: unsupported shape or mode");
-    ACG_REQUIRE(addend_mask == nullptr || ((long long)d->Hi * d->Wi * (d->Ci / 4)) % 8 == 0,
-                "acg_conv2d_bwd_data_add: the sign bitmask layout needs Hi*Wi*Ci/4 %% 8 == 0");
-    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, addend, nullptr, addend_mask);
+    ACG_REQUIRE(addend_mask == nullptr || sign_mask_fits(d), "acg_conv2d_bwd_data_add: the sign bitmask layout needs Hi*Wi*Ci/4 %% 8 == 0");
+    DgradSide s; s.addend = addend; s.addend_mask = addend_mask;
+    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
 
 extern "C" int acg_conv2d_bwd_data_relu(const acg_conv_desc *d, const float *dy, const float *wb, const float *x,
@@ -1224,7 +1243,8 @@ extern "C" int acg_conv2d_bwd_data_relu(const acg_conv_desc *d, const float *dy,
     int rc = check_desc(d, "acg_conv2d_bwd_data_relu");
     if (rc) return rc;
     ACG_REQUIRE(x != nullptr && acg_conv2d_bwd_data_add_supported(d), "acg_conv2d_bwd_data_relu: unsupported shape or mode");
-    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, nullptr, x);
+    DgradSide s; s.relu_src = x;
+    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
 
 // ---- pre-split ("S16") activation storage for the MFMA-bound 3x3 layers (conv_x3_pre.hip) ---------------------------------
@@ -1252,7 +1272,7 @@ static bool s16_dgrad_geom_ok(const acg_conv_desc *d)
 
 extern "C" int acg_conv2d_s16_supported(const acg_conv_desc *d)
 {
-    if (d == nullptr || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
+    if (d == nullptr || !bf16x3_mfma()) return 0;
     if (check_desc(d, "acg_conv2d_s16_supported") != ACG_OK || thin_in(d) || thin_out(d)) return 0;
     Geom g; Taps t;
     fwd_geom(d, &g, &t, 0);
@@ -1265,7 +1285,7 @@ extern "C" int acg_conv2d_fwd_s16(const acg_conv_desc *d, const void *x, const f
 {
     int rc = check_desc(d, "acg_conv2d_fwd_s16");
     if (rc) return rc;
-    ACG_REQUIRE(g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA, "acg_conv2d_fwd_s16: bf16x3 MFMA mode only");
+    ACG_REQUIRE(bf16x3_mfma(), "acg_conv2d_fwd_s16: bf16x3 MFMA mode only");
     Geom g; Taps t;
     fwd_geom(d, &g, &t, stats != nullptr ? (int)ACG_ACT_NONE : act);
     ACG_REQUIRE(stats == nullptr || act == ACG_ACT_NONE, "acg_conv2d_fwd_s16: statistics with an activation");
@@ -1281,12 +1301,12 @@ extern "C" int acg_conv2d_bwd_data_s16(const acg_conv_desc *d, const void *dy, c
 {
     int rc = check_desc(d, "acg_conv2d_bwd_data_s16");
     if (rc) return rc;
-    ACG_REQUIRE(g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && s16_dgrad_geom_ok(d),
-                "acg_conv2d_bwd_data_s16: unsupported shape or mode");
-    ACG_REQUIRE(addend_mask == nullptr || (addend != nullptr && ((long long)d->Hi * d->Wi * (d->Ci / 4)) % 8 == 0),
+    ACG_REQUIRE(bf16x3_mfma() && s16_dgrad_geom_ok(d), "acg_conv2d_bwd_data_s16: unsupported shape or mode");
+    ACG_REQUIRE(addend_mask == nullptr || (addend != nullptr && sign_mask_fits(d)),
                 "acg_conv2d_bwd_data_s16: the sign bitmask needs an addend and Hi*Wi*Ci/4 %% 8 == 0");
-    return dgrad_igemm(d, (const float *)dy, wb, nullptr, (float *)dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, addend,
-                       (const float *)relu_src, addend_mask, 1, out_s16, relu_src != nullptr ? 1 : 0);
+    DgradSide s; s.addend = addend; s.addend_mask = addend_mask; s.relu_src = (const float *)relu_src;
+    s.in_s16 = 1; s.out_s16 = out_s16; s.relu_s16 = relu_src != nullptr ? 1 : 0;
+    return dgrad_igemm(d, (const float *)dy, wb, nullptr, (float *)dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
 
 // conv + ReLU with pre-split output that also leaves the sign bitmask of that output, and the data gradient of the NEXT
@@ -1296,7 +1316,7 @@ extern "C" int acg_conv2d_fwd_s16_mask(const acg_conv_desc *d, const void *x, co
 {
     int rc = check_desc(d, "acg_conv2d_fwd_s16_mask");
     if (rc) return rc;
-    ACG_REQUIRE(g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA && sign_mask != nullptr && d->Co % 32 == 0,
+    ACG_REQUIRE(bf16x3_mfma() && sign_mask != nullptr && d->Co % 32 == 0,
                 "acg_conv2d_fwd_s16_mask: bf16x3 MFMA mode, 32-multiple output channels");
     Geom g; Taps t;
     fwd_geom(d, &g, &t, ACG_ACT_RELU);
@@ -1311,8 +1331,8 @@ extern "C" int acg_conv2d_bwd_data_s16_mask(const acg_conv_desc *d, const void *
     if (rc) return rc;
     ACG_REQUIRE(relu_sign_mask != nullptr && acg_conv2d_bwd_data_s16_sums_supported(d) && d->Ci % 32 == 0,
                 "acg_conv2d_bwd_data_s16_mask: unsupported shape or mode (query acg_conv2d_bwd_data_s16_sums_supported)");
-    return dgrad_igemm(d, (const float *)dy, wb, nullptr, (float *)dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr,
-                       nullptr, 1, 1, 0, nullptr, nullptr, relu_sign_mask);
+    DgradSide s; s.relu_mask = relu_sign_mask; s.in_s16 = 1; s.out_s16 = 1;
+    return dgrad_igemm(d, (const float *)dy, wb, nullptr, (float *)dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
 
 extern "C" int acg_conv2d_bwd_data_s16_sums_supported(const acg_conv_desc *d)
@@ -1327,11 +1347,11 @@ extern "C" int acg_conv2d_bwd_data_s16_sums(const acg_conv_desc *d, const void *
     int rc = check_desc(d, "acg_conv2d_bwd_data_s16_sums");
     if (rc) return rc;
     ACG_REQUIRE(ns != nullptr && acg_conv2d_bwd_data_s16_sums_supported(d), "acg_conv2d_bwd_data_s16_sums: unsupported shape or mode");
-    ACG_REQUIRE(addend_mask == nullptr || (addend != nullptr && ((long long)d->Hi * d->Wi * (d->Ci / 4)) % 8 == 0),
+    ACG_REQUIRE(addend_mask == nullptr || (addend != nullptr && sign_mask_fits(d)),
                 "acg_conv2d_bwd_data_s16_sums: the sign bitmask needs an addend and Hi*Wi*Ci/4 %% 8 == 0");
-    ACG_REQUIRE(ns->sign_mask == nullptr || ((long long)d->Hi * d->Wi * (d->Ci / 4)) % 8 == 0, "acg_conv2d_bwd_data_s16_sums: bitmask layout");
-    return dgrad_igemm(d, (const float *)dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, addend, nullptr,
-                       addend_mask, 1, 0, 0, nullptr, ns);
+    ACG_REQUIRE(ns->sign_mask == nullptr || sign_mask_fits(d), "acg_conv2d_bwd_data_s16_sums: bitmask layout");
+    DgradSide s; s.addend = addend; s.addend_mask = addend_mask; s.in_s16 = 1; s.ns = ns;
+    return dgrad_igemm(d, (const float *)dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
 
 // The same on fp32 operands, where the data gradient runs on the persistent row pipeline (conv_rows_x3: zero-padded 3x3 stride 1,
@@ -1340,7 +1360,7 @@ extern "C" int acg_conv2d_bwd_data_s16_sums(const acg_conv_desc *d, const void *
 // pre-split kernel's (where a workgroup owns several chunks its sums sit in the first, zeros in the others)
 extern "C" int acg_conv2d_bwd_data_sums_supported(const acg_conv_desc *d)
 {
-    if (d == nullptr || g_acg_precision != ACG_PREC_BF16X3 || g_acg_conv_impl != ACG_IMPL_MFMA) return 0;
+    if (d == nullptr || !bf16x3_mfma()) return 0;
     if (check_desc(d, "acg_conv2d_bwd_data_sums_supported") != ACG_OK) return 0;
     // the four-phase tile of the stride-2 3x3 data gradient (igemm_conv_ph4<SUMS>): 64 input channels of the convolution, phase
     // grid rows that are whole 128-pixel tiles
@@ -1367,12 +1387,9 @@ extern "C" int acg_conv2d_bwd_data_sums(const acg_conv_desc *d, const float *dy,
     int rc = check_desc(d, "acg_conv2d_bwd_data_sums");
     if (rc) return rc;
     ACG_REQUIRE(ns != nullptr && ns->sign_mask == nullptr && acg_conv2d_bwd_data_sums_supported(d), "acg_conv2d_bwd_data_sums: unsupported shape or mode");
-    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, ns);
+    DgradSide s; s.ns = ns;
+    return dgrad_igemm(d, dy, wb, nullptr, dx, ACG_ACT_NONE, ws, ws_bytes, (hipStream_t)stream, s);
 }
-
-// x and dy pre-split; dw / db fp32 as in acg_conv2d_bwd_weight (db = column sums of dy, produced by the same launch)
-extern "C" int acg_conv2d_bwd_weight_s16(const acg_conv_desc *d, const void *x, const void *dy, float *dw, float *db, int Or,
-                                         int Ir, void *ws, size_t ws_bytes, int accumulate, void *stream);
 
 // split-K plan shared by the workspace query and the launch
 static bool wgrad_thin(const acg_conv_desc *d) { return thin_in(d); }
@@ -1388,22 +1405,27 @@ static int wgrad_thin_patch_splits(const acg_conv_desc *d)
     return (int)(ntiles < 768 ? ntiles : 768);
 }
 
-static void wgrad_plan(const acg_conv_desc *d, int *CiP, int *CoP, int *nsplit, long long *mps)
+struct WgradPlan {
+    int CiP, CoP, nsplit;
+    long long m_per_split;
+};
+static WgradPlan wgrad_plan(const acg_conv_desc *d)
 {
+    WgradPlan p;
     const int Cx = d->Ci, Cg = d->Co;
     const long long Mtot = (long long)d->N * d->Ho * d->Wo;
     int bci, bco;
     acg_wgrad_tiles(Cx, Cg, &bci, &bco, wgrad_thin(d) ? 0 : d->K * d->K);
-    *CiP = (Cx + bci - 1) / bci * bci;
-    *CoP = (Cg + bco - 1) / bco * bco;
+    p.CiP = (Cx + bci - 1) / bci * bci;
+    p.CoP = (Cg + bco - 1) / bco * bco;
     if (wgrad_thin(d)) { // gathered columns = (tap, 4 channels): 32 per 8 taps, ONE tap-block
         bci = bco = 32;
-        *CiP = 32 * ((d->K * d->K + 7) / 8);
-        *CoP = (Cg + 31) / 32 * 32;
+        p.CiP = 32 * ((d->K * d->K + 7) / 8);
+        p.CoP = (Cg + 31) / 32 * 32;
     }
     const int KP = 256; // multiple of every kernel variant's pixels-per-stage (fp32: 32/128, bf16: 64/256)
     const int nt = acg_wgrad_taps_per_wg(Cx, Cg, d->K * d->K, wgrad_thin(d) ? 1 : 0);   // taps per workgroup (bf16 kernels)
-    const long long base = (wgrad_thin(d) ? 1LL : (long long)d->K * d->K / nt) * (*CiP / bci) * (*CoP / bco);
+    const long long base = (wgrad_thin(d) ? 1LL : (long long)d->K * d->K / nt) * (p.CiP / bci) * (p.CoP / bco);
     // workgroups per launch: a whole number of residency waves.  The bf16 128x128 kernel holds 2 workgroups per CU:
     // 512 = exactly one wave (vs 1536: -6..-10 %, and a third of the partial-sum traffic); 768 = 1.5 waves is the worst
     // choice (+15 %).  The smaller tiles hold 3-4 per CU and keep more, shorter workgroups.
@@ -1412,7 +1434,7 @@ static void wgrad_plan(const acg_conv_desc *d, int *CiP, int *CoP, int *nsplit, 
     int gran = KP;
     // kernel-row weight gradient: three taps per workgroup, one 512-thread workgroup per CU -> one residency wave of 256
     if (wgrad_krow(d)) {
-        nblk = 3LL * (*CiP / 128) * (*CoP / 128);
+        nblk = 3LL * (p.CiP / 128) * (p.CoP / 128);
         target = 256;
         gran = 32; // its stage is a 32-pixel run: splits this fine fill 255 of the 256 CUs at batch 32 (256-pixel splits: 246)
     } else if (wgrad_krow_s(d)) {
@@ -1421,14 +1443,14 @@ static void wgrad_plan(const acg_conv_desc *d, int *CiP, int *CoP, int *nsplit, 
         gran = 128;
     }
     if (!wgrad_thin(d) && acg_wgrad_krowg_shape_ok(d->K, d->stride, d->pad, d->pad_mode == ACG_PAD_REFLECT, d->Wi, d->Wo, Cx, Cg)) {
-        nblk = (long long)d->K * (*CiP / (Cx == 64 ? 64 : 128)) * (*CoP / 128);   // wgrad_x3_krowg (conv_wgrad_k4.hip): a kernel row per
+        nblk = (long long)d->K * (p.CiP / (Cx == 64 ? 64 : 128)) * (p.CoP / 128);   // wgrad_x3_krowg (conv_wgrad_k4.hip): a kernel row per
         target = 256;                                                             // workgroup, one workgroup per CU, whole output rows
         gran = d->Wo;                                                             // per split
     }
     if (wgrad_thin(d) && wgrad_thin_patch_splits(d) > 0) {   // one slab per persistent workgroup
-        *nsplit = wgrad_thin_patch_splits(d);
-        *mps = (Mtot + *nsplit - 1) / *nsplit;
-        return;
+        p.nsplit = wgrad_thin_patch_splits(d);
+        p.m_per_split = (Mtot + p.nsplit - 1) / p.nsplit;
+        return p;
     }
     long long ns = target / nblk;
     const long long cap = Mtot / (KP * 4);
@@ -1438,8 +1460,9 @@ static void wgrad_plan(const acg_conv_desc *d, int *CiP, int *CoP, int *nsplit, 
     long long per = (Mtot + ns - 1) / ns;
     per = (per + gran - 1) / gran * gran;
     ns = (Mtot + per - 1) / per;
-    *nsplit = (int)ns;
-    *mps = per;
+    p.nsplit = (int)ns;
+    p.m_per_split = per;
+    return p;
 }
 
 // wgrad_thin_out's split plan (<= 512 splits, or one slab per workgroup of the patch kernel).  slabs: what the workspace
@@ -1467,14 +1490,12 @@ static ThinOutPlan wgrad_thin_out_plan(const acg_conv_desc *d)
     return p;
 }
 
-static size_t wgrad_ws_bytes(const acg_conv_desc *d)
+static size_t wgrad_ws_bytes(const acg_conv_desc *d, const WgradPlan &wp)
 {
-    int CiP, CoP, ns; long long mps;
-    wgrad_plan(d, &CiP, &CoP, &ns, &mps);
-    const size_t part = (size_t)ns * d->K * d->K * CiP * CoP * sizeof(float);
+    const size_t part = (size_t)wp.nsplit * d->K * d->K * wp.CiP * wp.CoP * sizeof(float);
     const int Cmax = d->Ci > d->Co ? d->Ci : d->Co;
     const long long Mbig = (long long)d->N * (d->Hi > d->Ho ? d->Hi : d->Ho) * (d->Wi > d->Wo ? d->Wi : d->Wo);
-    const size_t bias_part = (size_t)ns * 2 * (CiP > CoP ? CiP : CoP) * sizeof(float);   // x-side sums: `stride` slots per split
+    const size_t bias_part = (size_t)wp.nsplit * 2 * (wp.CiP > wp.CoP ? wp.CiP : wp.CoP) * sizeof(float);   // x-side sums: `stride` slots per split
     size_t total = acg_round_up(part, 256) + acg_round_up(colsum_ws_bytes(Mbig, Cmax) + bias_part, 256);
     if (thin_out(d) && d->stride == 1) { // wgrad_thin_out's partial buffer
         const ThinOutPlan p = wgrad_thin_out_plan(d);
@@ -1488,14 +1509,14 @@ extern "C" size_t acg_conv2d_bwd_weight_workspace_bytes(const acg_conv_desc *d)
 {
     if (d == nullptr) return 0;
     // covers both orientations (Conv2d and ConvTranspose2d use of the same descriptor)
-    return wgrad_ws_bytes(d);
+    return wgrad_ws_bytes(d, wgrad_plan(d));
 }
 
 // x_side: conv-input-side tensor (N,Hi,Wi,Ci); g_side: conv-output-side tensor (N,Ho,Wo,Co)
 // bias_from: 0 none; 1 db[c] = column sums of g_side (Conv2d bias, Or entries); 2 of x_side (ConvTranspose bias, Ir entries)
-static int wgrad_common(const acg_conv_desc *d, const float *x_side, const float *g_side, float *dw, int Or, int Ir,
-                        void *ws, size_t ws_bytes, hipStream_t st, int accumulate, int bias_from = 0, float *db = nullptr,
-                        bool thin_conv = false, bool s16 = false)
+static int wgrad_common(const acg_conv_desc *d, const WgradPlan &wp, const float *x_side, const float *g_side, float *dw, int Or,
+                        int Ir, void *ws, size_t ws_bytes, hipStream_t st, int accumulate, int bias_from, float *db,
+                        bool thin_conv, bool s16)
 {
     ACG_REQUIRE(Or <= d->Co && Ir <= d->Ci, "wgrad: Or=%d Ir=%d exceed padded dims", Or, Ir);
     if (g_acg_conv_impl == ACG_IMPL_DIRECT) {
@@ -1510,7 +1531,7 @@ static int wgrad_common(const acg_conv_desc *d, const float *x_side, const float
     g.is = d->stride; g.reflect = d->pad_mode == ACG_PAD_REFLECT;
     g.thin = (thin_conv && wgrad_thin(d)) ? 1 : 0;
     g.Mtot = (long long)d->N * d->Ho * d->Wo;
-    wgrad_plan(d, &g.CiP, &g.CoP, &g.nsplit, &g.m_per_split);
+    g.CiP = wp.CiP; g.CoP = wp.CoP; g.nsplit = wp.nsplit; g.m_per_split = wp.m_per_split;
     const int ntb = g.thin ? 1 : t.n;
     const size_t need = (size_t)g.nsplit * ntb * g.CiP * g.CoP * sizeof(float);
     if (ws == nullptr || ws_bytes < need) {
@@ -1573,11 +1594,9 @@ static int wgrad_thin_out(const acg_conv_desc *d, const float *x, const float *d
     return ACG_OK;
 }
 
-static float *colsum_area(const acg_conv_desc *d, void *ws, size_t ws_bytes, size_t *avail)
+static float *colsum_area(const acg_conv_desc *d, const WgradPlan &wp, void *ws, size_t ws_bytes, size_t *avail)
 {
-    int CiP, CoP, ns; long long mps;
-    wgrad_plan(d, &CiP, &CoP, &ns, &mps);
-    const size_t part = acg_round_up((size_t)ns * d->K * d->K * CiP * CoP * sizeof(float), 256);
+    const size_t part = acg_round_up((size_t)wp.nsplit * d->K * d->K * wp.CiP * wp.CoP * sizeof(float), 256);
     *avail = ws_bytes > part ? ws_bytes - part : 0;
     return (float *)((char *)ws + part);
 }
@@ -1588,18 +1607,19 @@ extern "C" int acg_conv2d_bwd_weight(const acg_conv_desc *d, const float *x, con
     int rc = check_desc(d, "acg_conv2d_bwd_weight");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    ACG_REQUIRE(ws != nullptr && ws_bytes >= acg_conv2d_bwd_weight_workspace_bytes(d), "acg_conv2d_bwd_weight: workspace too small");
+    const WgradPlan wp = wgrad_plan(d);
+    ACG_REQUIRE(ws != nullptr && ws_bytes >= wgrad_ws_bytes(d, wp), "acg_conv2d_bwd_weight: workspace too small");
     // the mirrored thin formulation walks the UNPADDED input pixels: right for zero padding only (a reflected border
     // pairs x[refl(q)] with dy of pixels outside that walk); reflect-padded thin-output layers take the general path
     const bool tout = thin_out(d) && d->stride == 1 && !(d->pad_mode == ACG_PAD_REFLECT && d->pad > 0);
     const bool fused = dw != nullptr && db != nullptr && g_acg_conv_impl == ACG_IMPL_MFMA && !tout;
     if (dw != nullptr) {
         rc = tout ? wgrad_thin_out(d, x, dy, dw, Or, Ir, ws, ws_bytes, st, accumulate)
-                  : wgrad_common(d, x, dy, dw, Or, Ir, ws, ws_bytes, st, accumulate, 1, fused ? db : nullptr, true);
+                  : wgrad_common(d, wp, x, dy, dw, Or, Ir, ws, ws_bytes, st, accumulate, 1, fused ? db : nullptr, /* thin_conv */ true, /* s16 */ false);
         if (rc) return rc;
     }
     if (db != nullptr && !fused) {
-        size_t avail; float *cw = colsum_area(d, ws, ws_bytes, &avail);
+        size_t avail; float *cw = colsum_area(d, wp, ws, ws_bytes, &avail);
         const long long M = (long long)d->N * d->Ho * d->Wo;
         ACG_REQUIRE(avail >= colsum_ws_bytes(M, d->Co), "acg_conv2d_bwd_weight: colsum workspace");
         rc = colsum_launch(dy, M, d->Co, Or, db, cw, st, accumulate);
@@ -1607,14 +1627,16 @@ extern "C" int acg_conv2d_bwd_weight(const acg_conv_desc *d, const float *x, con
     return rc;
 }
 
+// x and dy pre-split; dw / db fp32 as in acg_conv2d_bwd_weight (db = column sums of dy, produced by the same launch)
 extern "C" int acg_conv2d_bwd_weight_s16(const acg_conv_desc *d, const void *x, const void *dy, float *dw, float *db, int Or,
                                          int Ir, void *ws, size_t ws_bytes, int accumulate, void *stream)
 {
     int rc = check_desc(d, "acg_conv2d_bwd_weight_s16");
     if (rc) return rc;
-    ACG_REQUIRE(dw != nullptr && ws != nullptr && ws_bytes >= acg_conv2d_bwd_weight_workspace_bytes(d),
-                "acg_conv2d_bwd_weight_s16: workspace too small");
-    return wgrad_common(d, (const float *)x, (const float *)dy, dw, Or, Ir, ws, ws_bytes, (hipStream_t)stream, accumulate, 1, db, false, true);
+    const WgradPlan wp = wgrad_plan(d);
+    ACG_REQUIRE(dw != nullptr && ws != nullptr && ws_bytes >= wgrad_ws_bytes(d, wp), "acg_conv2d_bwd_weight_s16: workspace too small");
+    return wgrad_common(d, wp, (const float *)x, (const float *)dy, dw, Or, Ir, ws, ws_bytes, (hipStream_t)stream, accumulate, 1, db,
+                        /* thin_conv */ false, /* s16 */ true);
 }
 
 extern "C" int acg_conv_transpose2d_fwd(const acg_conv_desc *d, const float *x, const float *wb, const float *bias,
@@ -1631,7 +1653,7 @@ extern "C" int acg_conv_transpose2d_fwd(const acg_conv_desc *d, const float *x, 
         ACG_CHECK_LAUNCH("direct_dgrad_kernel");
         return ACG_OK;
     }
-    return dgrad_igemm(d, x, wb, bias, y, act, nullptr, 0, st);
+    return dgrad_igemm(d, x, wb, bias, y, act, /* ws */ nullptr, /* ws_bytes */ 0, st, DgradSide());
 }
 
 extern "C" int acg_conv_transpose2d_fwd_stats(const acg_conv_desc *d, const float *x, const float *wb, const float *bias,
@@ -1640,7 +1662,8 @@ extern "C" int acg_conv_transpose2d_fwd_stats(const acg_conv_desc *d, const floa
     int rc = check_desc(d, "acg_conv_transpose2d_fwd_stats");
     if (rc) return rc;
     ACG_REQUIRE(acg_conv_transpose2d_fwd_stats_supported(d) && stats != nullptr, "acg_conv_transpose2d_fwd_stats: unsupported shape or mode");
-    return dgrad_igemm(d, x, wb, bias, y, ACG_ACT_NONE, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, 0, 0, stats);
+    DgradSide s; s.stats = stats;
+    return dgrad_igemm(d, x, wb, bias, y, ACG_ACT_NONE, /* ws */ nullptr, /* ws_bytes */ 0, (hipStream_t)stream, s);
 }
 
 extern "C" int acg_conv_transpose2d_bwd_data(const acg_conv_desc *d, const float *dy, const float *wf, float *dx,
@@ -1659,7 +1682,8 @@ extern "C" int acg_conv_transpose2d_bwd_weight(const acg_conv_desc *d, const flo
     int rc = check_desc(d, "acg_conv_transpose2d_bwd_weight");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    ACG_REQUIRE(ws != nullptr && ws_bytes >= acg_conv2d_bwd_weight_workspace_bytes(d), "acg_conv_transpose2d_bwd_weight: workspace too small");
+    const WgradPlan wp = wgrad_plan(d);
+    ACG_REQUIRE(ws != nullptr && ws_bytes >= wgrad_ws_bytes(d, wp), "acg_conv_transpose2d_bwd_weight: workspace too small");
     // the bias sums the GATHERED-side operand (dy of the ConvTranspose), whose tap-0 gather visits only a strided subset of
     // its pixels: fused only in the kernel-row kernel (conv_wgrad_k4.hip), where kernel rows 1 .. stride visit every row
     // once; otherwise one separate column-sum pass
@@ -1667,11 +1691,11 @@ extern "C" int acg_conv_transpose2d_bwd_weight(const acg_conv_desc *d, const flo
                        d->Hi == d->stride * d->Ho && d->Wi == d->stride * d->Wo &&
                        acg_wgrad_krowg_shape_ok(d->K, d->stride, d->pad, d->pad_mode == ACG_PAD_REFLECT, d->Wi, d->Wo, d->Ci, d->Co);
     if (dw != nullptr) {
-        rc = wgrad_common(d, dy, x, dw, Or, Ir, ws, ws_bytes, st, accumulate, fused ? 2 : 0, fused ? db : nullptr);
+        rc = wgrad_common(d, wp, dy, x, dw, Or, Ir, ws, ws_bytes, st, accumulate, fused ? 2 : 0, fused ? db : nullptr, /* thin_conv */ false, /* s16 */ false);
         if (rc) return rc;
     }
     if (db != nullptr && !fused) {
-        size_t avail; float *cw = colsum_area(d, ws, ws_bytes, &avail);
+        size_t avail; float *cw = colsum_area(d, wp, ws, ws_bytes, &avail);
         const long long M = (long long)d->N * d->Hi * d->Wi;
         ACG_REQUIRE(avail >= colsum_ws_bytes(M, d->Ci), "acg_conv_transpose2d_bwd_weight: colsum workspace");
         rc = colsum_launch(dy, M, d->Ci, Ir, db, cw, st, accumulate);

@@ -517,6 +517,14 @@ def _weight_grad(ctx, entry, x, g, nbias, st, timed=True):
     return None, None
 
 
+def _call_with_norm_sums(ns, d, dx, st, entry, *args):
+    """a data-gradient entry point whose epilogue leaves the backward sums of the norm in front (NormSums `ns`; dx: the
+    tensor they belong to): entry(*args, &acg_norm_sums, st)"""
+    part = torch.empty((d.N, (d.Hi * d.Wi) // STATS_ROWS, 2, d.Ci), device=dx.device, dtype=torch.float32)
+    _lib.call(entry, *args, ctypes.byref(ns.desc(part)), st)
+    ns.part, ns.dx = part, dx
+
+
 class Conv2dFn(torch.autograd.Function):
     """nn.Conv2d (+ preceding ReflectionPad2d) + bias + fused activation; `fusion`: a ConvFusion or None."""
 
@@ -532,6 +540,7 @@ class Conv2dFn(torch.autograd.Function):
         if d.Ho <= 0 or d.Wo <= 0:
             raise _lib.AcgError("conv: input %dx%d too small for kernel %d" % (Hi, Wi, packed.K))
         y = torch.empty((N, d.Ho, d.Wo, packed.Cos), device=x.device, dtype=torch.float32)
+        pbias = _ptr(packed.bias if bias is not None else None)
         span = ConvTimer.span("fwd", d)
         if s16 is not None and s16.x:   # pre-split input (and, for a conv + ReLU inside the trunk, output)
             part = None
@@ -543,22 +552,20 @@ class Conv2dFn(torch.autograd.Function):
                 # conv + ReLU feeding the next trunk convolution: its data gradient needs only the SIGN of y (same shape: d fits both)
                 link_out.mask = torch.empty((y.numel() + 31) // 32, device=x.device, dtype=torch.int32)
                 _fused("conv_fwd_s16_relu_bitmask")
-                _lib.call("acg_conv2d_fwd_s16_mask", ctypes.byref(d), _ptr(x), _ptr(packed.wf), _ptr(packed.bias if bias is not None else None),
-                          _ptr(y), _ptr(link_out.mask), _stream())
+                _lib.call("acg_conv2d_fwd_s16_mask", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), _ptr(link_out.mask),
+                          _stream())
             else:
                 _fused("conv_fwd_s16")
-                _lib.call("acg_conv2d_fwd_s16", ctypes.byref(d), _ptr(x), _ptr(packed.wf), _ptr(packed.bias if bias is not None else None),
-                          _ptr(y), act, _ptr(part), 1 if s16.y else 0, _stream())
+                _lib.call("acg_conv2d_fwd_s16", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), act, _ptr(part),
+                          1 if s16.y else 0, _stream())
         elif want_stats is not None and CONV_STATS_ENABLED and act == ACT_NONE and \
                 _lib.query("acg_conv2d_fwd_stats_supported", ctypes.byref(d)):
             part = torch.empty((N, (d.Ho * d.Wo) // STATS_ROWS, 2, packed.Co), device=x.device, dtype=torch.float32)
             _fused("conv_fwd_tile_stats")
-            _lib.call("acg_conv2d_fwd_stats", ctypes.byref(d), _ptr(x), _ptr(packed.wf),
-                      _ptr(packed.bias if bias is not None else None), _ptr(y), _ptr(part), _stream())
+            _lib.call("acg_conv2d_fwd_stats", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), _ptr(part), _stream())
             want_stats.part = part
         else:
-            _lib.call("acg_conv2d_fwd", ctypes.byref(d), _ptr(x), _ptr(packed.wf), _ptr(packed.bias if bias is not None else None),
-                      _ptr(y), act, _stream())
+            _lib.call("acg_conv2d_fwd", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), act, _stream())
         span.done()
         ctx.d, ctx.packed, ctx.act, ctx.has_bias = d, packed, act, bias is not None
         ctx.wparam, ctx.bparam = weight, bias
@@ -574,125 +581,93 @@ class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, y = ctx.saved_tensors
-        d, pk = ctx.d, ctx.packed
         dy = dy.contiguous()
         st = _stream()
-        if ctx.s16 is not None:
-            return Conv2dFn._backward_s16(ctx, x, dy, dskip)
-        if ctx.link_out is not None and ctx.link_out.done:
+        s16 = ctx.s16 is not None
+        g = dy   # the gradient w.r.t. the pre-activation
+        if s16:
+            # x and dy are pre-split: dy comes from the norm behind this convolution, or (a conv + ReLU: s16.y) from the next
+            # convolution's data gradient, which already applied the ReLU mask
+            if ctx.s16.y:
+                if ctx.link_out is None or not ctx.link_out.done:
+                    raise _lib.AcgError("pre-split trunk: the gradient of a conv + ReLU output must come from the next convolution's "
+                                        "fused data gradient")
+                ctx.link_out.done = False
+        elif ctx.link_out is not None and ctx.link_out.done:
             ctx.link_out.done = False   # the consumer's data-gradient epilogue already applied this ReLU's mask
-            g = dy
         elif ctx.act != ACT_NONE:
             g = torch.empty_like(dy)
             _lib.call("acg_act_bwd", _ptr(dy), _ptr(y), _ptr(g), dy.numel(), ctx.act, st)
-        else:
-            g = dy
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            nb = _lib.query("acg_conv2d_bwd_data_workspace_bytes", ctypes.byref(d))
-            ws = workspace(nb) if nb else None
-            smask = None
-            span = ConvTimer.span("dgrad", d)
-            if dskip is not None:
-                dskip = dskip.contiguous()
-                if ctx.skip_grad is not None:   # the skip gradient is dskip * sign-bitmask (NormAct lazy_dres)
-                    dskip, smask = ctx.skip_grad.take(dskip)
-            if dskip is not None and _lib.query("acg_conv2d_bwd_data_add_supported", ctypes.byref(d)) and \
-                    (smask is None or (d.Hi * d.Wi * (d.Ci // 4)) % 8 == 0):
-                _fused("dgrad_skip_addend")
-                _lib.call("acg_conv2d_bwd_data_add", ctypes.byref(d), _ptr(g), _ptr(pk.wb), _ptr(dskip), _ptr(smask), _ptr(dx),
-                          _ptr(ws), nb, st)
-                smask = None
-            elif (dskip is None and ctx.link_in is not None and RELU_LINK
-                  and _lib.query("acg_conv2d_bwd_data_add_supported", ctypes.byref(d))):
-                _fused("dgrad_relu_link")
-                _lib.call("acg_conv2d_bwd_data_relu", ctypes.byref(d), _ptr(g), _ptr(pk.wb), _ptr(x), _ptr(dx), _ptr(ws), nb, st)
-                ctx.link_in.done = True
-            elif (dskip is None and ctx.norm_sums is not None and ctx.norm_sums.x is not None and ctx.norm_sums.mask is None and
-                  tuple(ctx.norm_sums.x.shape) == tuple(dx.shape) and _lib.query("acg_conv2d_bwd_data_sums_supported", ctypes.byref(d))):
-                # dx is the gradient w.r.t. the output of the norm in front: the data-gradient kernel (row pipeline, four-phase
-                # stride-2 tile, generic tile, thin-row kernel of the head) leaves that norm's backward sums
-                ns = ctx.norm_sums
-                part = torch.empty((d.N, (d.Hi * d.Wi) // STATS_ROWS, 2, d.Ci), device=dx.device, dtype=torch.float32)
-                desc = ns.desc(part)
-                _fused("dgrad_f32_norm_sums")
-                _lib.call("acg_conv2d_bwd_data_sums", ctypes.byref(d), _ptr(g), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, ctypes.byref(desc), st)
-                ns.part, ns.dx = part, dx
-            else:
-                _lib.call("acg_conv2d_bwd_data", ctypes.byref(d), _ptr(g), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, st)
-                if dskip is not None:
-                    if smask is not None:   # not fusable here: materialise the masked skip gradient
-                        m = torch.empty_like(dskip)
-                        _lib.call("acg_mask_apply", _ptr(dskip), _ptr(smask), _ptr(m), dskip.numel(), st)
-                        dskip = m
-                    dx = dx + dskip
-            span.done()
+            dx = Conv2dFn._data_grad(ctx, x, g, dskip, st)
         if ctx.needs_input_grad[1]:
-            dw, db = _weight_grad(ctx, "acg_conv2d_bwd_weight", x, g, pk.Or, st)
+            if s16:
+                _fused("wgrad_s16")
+            dw, db = _weight_grad(ctx, "acg_conv2d_bwd_weight_s16" if s16 else "acg_conv2d_bwd_weight", x, g, ctx.packed.Or, st)
         return dx, dw, db, None, None, None, None, None, None
 
     @staticmethod
-    def _backward_s16(ctx, x, dy, dskip):
-        """Conv2dFn.backward on pre-split operands: x and dy are S16 (dy comes from the norm behind this convolution, or — for
-        a conv + ReLU — from the next convolution's data gradient, which already applied the ReLU mask)."""
-        d, pk, p = ctx.d, ctx.packed, ctx.s16
-        st = _stream()
-        if p.y:
-            if ctx.link_out is None or not ctx.link_out.done:
-                raise _lib.AcgError("pre-split trunk: the gradient of a conv + ReLU output must come from the next convolution's "
-                                    "fused data gradient")
-            ctx.link_out.done = False
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            nb = _lib.query("acg_conv2d_bwd_data_workspace_bytes", ctypes.byref(d))
-            ws = workspace(nb) if nb else None
-            ns = ctx.norm_sums if not p.dx else None
-            if ns is not None and not (ns.x is not None and tuple(ns.x.shape) == tuple(dx.shape) and
-                                       _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d))):
-                ns = None
-            span = ConvTimer.span("dgrad_sums" if ns is not None else "dgrad", d)
-            if p.dx:     # the gradient w.r.t. the pre-activation of the conv + ReLU in front, pre-split for its own backward
-                if dskip is not None or ctx.link_in is None:
-                    raise _lib.AcgError("pre-split trunk: unexpected skip gradient / missing ReLU link")
-                if ctx.link_in.mask is not None and ctx.link_in.mask.numel() == (x.numel() + 31) // 32 and \
-                        _lib.query("acg_conv2d_bwd_data_s16_sums_supported", ctypes.byref(d)):
-                    _fused("dgrad_s16_relu_bitmask")
-                    _lib.call("acg_conv2d_bwd_data_s16_mask", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb,
-                              _ptr(ctx.link_in.mask), st)
-                else:
-                    _fused("dgrad_s16_relu_src")
-                    _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, None, None,
-                              _ptr(x), 1, st)
-                ctx.link_in.done = True
+    def _data_grad(ctx, x, g, dskip, st):
+        """-> dx from g, the gradient w.r.t. this convolution's pre-activation.  With ctx.s16, x and g are pre-split, and so is
+        dx where the plan says so (masked by the ReLU in front for that convolution's own backward)."""
+        d, pk, p, D = ctx.d, ctx.packed, ctx.s16, ctypes.byref(ctx.d)
+        dx = torch.empty_like(x)
+        nb = _lib.query("acg_conv2d_bwd_data_workspace_bytes", D)
+        ws = workspace(nb) if nb else None
+        # the norm in front whose backward sums this data gradient can leave: dx is the gradient w.r.t. its output
+        ns = ctx.norm_sums
+        if ns is not None and (ns.x is None or tuple(ns.x.shape) != tuple(dx.shape) or (
+                p is not None and (p.dx or not _lib.query("acg_conv2d_bwd_data_s16_sums_supported", D)))):
+            ns = None
+        span = ConvTimer.span("dgrad_sums" if (p is not None and ns is not None) else "dgrad", d)
+        if p is not None and p.dx and (dskip is not None or ctx.link_in is None):
+            raise _lib.AcgError("pre-split trunk: unexpected skip gradient / missing ReLU link")
+        smask = None
+        if dskip is not None:
+            dskip = dskip.contiguous()
+            if ctx.skip_grad is not None:   # the skip gradient is dskip * sign-bitmask (NormAct lazy_dres)
+                dskip, smask = ctx.skip_grad.take(dskip)
+        head, tail = (D, _ptr(g), _ptr(pk.wb)), (_ptr(dx), _ptr(ws), nb)
+        if p is not None and p.dx:   # the gradient w.r.t. the pre-activation of the conv + ReLU in front, pre-split
+            if ctx.link_in.mask is not None and ctx.link_in.mask.numel() == (x.numel() + 31) // 32 and \
+                    _lib.query("acg_conv2d_bwd_data_s16_sums_supported", D):
+                _fused("dgrad_s16_relu_bitmask")
+                _lib.call("acg_conv2d_bwd_data_s16_mask", *head, *tail, _ptr(ctx.link_in.mask), st)
             else:
-                smask = None
-                if dskip is not None:
-                    dskip = dskip.contiguous()
-                    if ctx.skip_grad is not None:
-                        dskip, smask = ctx.skip_grad.take(dskip)
-                if ns is not None:
-                    # dx is the gradient w.r.t. the output of the norm in front: its backward sums leave with the tiles
-                    part = torch.empty((d.N, (d.Hi * d.Wi) // STATS_ROWS, 2, d.Ci), device=dx.device, dtype=torch.float32)
-                    desc = ns.desc(part)
-                    _fused("dgrad_s16_norm_sums")
-                    if smask is not None:
-                        _fused("dgrad_s16_lazy_skip")
-                    _lib.call("acg_conv2d_bwd_data_s16_sums", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
-                              _ptr(smask), ctypes.byref(desc), st)
-                    ns.part, ns.dx = part, dx
-                else:
-                    _fused("dgrad_s16_plain")
-                    if smask is not None:
-                        _fused("dgrad_s16_lazy_skip")
-                    _lib.call("acg_conv2d_bwd_data_s16", ctypes.byref(d), _ptr(dy), _ptr(pk.wb), _ptr(dx), _ptr(ws), nb, _ptr(dskip),
-                              _ptr(smask), None, 0, st)
-            span.done()
-        if ctx.needs_input_grad[1]:
-            _fused("wgrad_s16")
-            dw, db = _weight_grad(ctx, "acg_conv2d_bwd_weight_s16", x, dy, pk.Or, st)
-        return dx, dw, db, None, None, None, None, None, None
+                _fused("dgrad_s16_relu_src")
+                _lib.call("acg_conv2d_bwd_data_s16", *head, *tail, None, None, _ptr(x), 1, st)
+            ctx.link_in.done = True
+        elif p is not None:
+            _fused("dgrad_s16_norm_sums" if ns is not None else "dgrad_s16_plain")
+            if smask is not None:
+                _fused("dgrad_s16_lazy_skip")
+            if ns is not None:
+                _call_with_norm_sums(ns, d, dx, st, "acg_conv2d_bwd_data_s16_sums", *head, *tail, _ptr(dskip), _ptr(smask))
+            else:
+                _lib.call("acg_conv2d_bwd_data_s16", *head, *tail, _ptr(dskip), _ptr(smask), None, 0, st)
+        elif dskip is not None and _lib.query("acg_conv2d_bwd_data_add_supported", D) and \
+                (smask is None or (d.Hi * d.Wi * (d.Ci // 4)) % 8 == 0):
+            _fused("dgrad_skip_addend")
+            _lib.call("acg_conv2d_bwd_data_add", *head, _ptr(dskip), _ptr(smask), *tail, st)
+        elif dskip is None and ctx.link_in is not None and RELU_LINK and _lib.query("acg_conv2d_bwd_data_add_supported", D):
+            _fused("dgrad_relu_link")
+            _lib.call("acg_conv2d_bwd_data_relu", *head, _ptr(x), *tail, st)
+            ctx.link_in.done = True
+        elif dskip is None and ns is not None and ns.mask is None and _lib.query("acg_conv2d_bwd_data_sums_supported", D):
+            # the row pipeline, the four-phase stride-2 tile, the generic tile or the thin-row kernel of the head
+            _fused("dgrad_f32_norm_sums")
+            _call_with_norm_sums(ns, d, dx, st, "acg_conv2d_bwd_data_sums", *head, *tail)
+        else:
+            _lib.call("acg_conv2d_bwd_data", *head, *tail, st)
+            if dskip is not None:
+                if smask is not None:   # not fusable here: materialise the masked skip gradient
+                    m = torch.empty_like(dskip)
+                    _lib.call("acg_mask_apply", _ptr(dskip), _ptr(smask), _ptr(m), dskip.numel(), st)
+                    dskip = m
+                dx = dx + dskip
+        span.done()
+        return dx
 
 
 class ConvTranspose2dFn(torch.autograd.Function):
@@ -714,15 +689,14 @@ class ConvTranspose2dFn(torch.autograd.Function):
         if (d.Ho, d.Wo) != (H, W):
             raise _lib.AcgError("conv_transpose: inconsistent geometry")
         y = torch.empty((N, Hl, Wl, packed.Ci), device=x.device, dtype=torch.float32)
+        pbias = _ptr(packed.bias if bias is not None else None)
         if want_stats is not None and CONV_STATS_ENABLED and act == ACT_NONE and \
                 _lib.query("acg_conv_transpose2d_fwd_stats_supported", ctypes.byref(d)):
             part = torch.empty((N, (Hl * Wl) // STATS_ROWS, 2, packed.Ci), device=x.device, dtype=torch.float32)
-            _lib.call("acg_conv_transpose2d_fwd_stats", ctypes.byref(d), _ptr(x), _ptr(packed.wb),
-                      _ptr(packed.bias if bias is not None else None), _ptr(y), _ptr(part), _stream())
+            _lib.call("acg_conv_transpose2d_fwd_stats", ctypes.byref(d), _ptr(x), _ptr(packed.wb), pbias, _ptr(y), _ptr(part), _stream())
             want_stats.part = part
         else:
-            _lib.call("acg_conv_transpose2d_fwd", ctypes.byref(d), _ptr(x), _ptr(packed.wb),
-                      _ptr(packed.bias if bias is not None else None), _ptr(y), act, _stream())
+            _lib.call("acg_conv_transpose2d_fwd", ctypes.byref(d), _ptr(x), _ptr(packed.wb), pbias, _ptr(y), act, _stream())
         ctx.d, ctx.packed, ctx.act, ctx.has_bias = d, packed, act, bias is not None
         ctx.wparam, ctx.bparam = weight, bias
         ctx.save_for_backward(x, y if act != ACT_NONE else None)

@@ -774,3 +774,74 @@ def test_conv_epilogue_statistics_equal_the_statistics_pass(case):
                      np.max(np.abs(n(r1) * np.sqrt(var + 1e-5) - 1)), np.max(np.abs(n(r2) * np.sqrt(var + 1e-5) - 1))))
             assert np.max(np.abs(n(m1) - n(m2))) < 1e-5 * np.max(np.abs(n(m2))), np.max(np.abs(n(m1) - n(m2)))
             assert np.max(np.abs(n(r1) / n(r2) - 1)) < 1e-5, np.max(np.abs(n(r1) / n(r2) - 1))
+
+
+# (entry point, descriptor, what the call carries, substring of the refusal).  Descriptors: "small" = N 1, 8 x 8, 16 stored
+# channels, K 3 with the given stride / padding; "trunk" = the smallest frame-path pre-split shape (1 x 8 x 32, 128 -> 128,
+# reflect pad 1: H = 8 is no un-padded grid).
+REFUSALS = [
+    ("acg_conv2d_bwd_data_add", ("small", 2, "zero"), "addend", "unsupported shape or mode"),
+    ("acg_conv2d_bwd_data_relu", ("small", 1, "zero"), "relu", "unsupported shape or mode"),
+    ("acg_conv2d_bwd_data_sums", ("small", 1, "reflect"), "sums", "unsupported shape or mode"),
+    ("acg_conv2d_bwd_data_s16", ("small", 2, "zero"), "plain", "unsupported shape or mode"),
+    ("acg_conv2d_bwd_data_s16_mask", ("trunk", 1, "reflect"), "relu_mask", "acg_conv2d_bwd_data_s16_sums_supported"),
+    ("acg_conv2d_bwd_data_s16", ("trunk", 1, "reflect"), "addend_out_s16", "unsupported pre-split combination"),
+    ("acg_conv2d_bwd_data_s16", ("trunk", 1, "reflect"), "mask_without_addend", "needs an addend"),
+    ("acg_conv2d_bwd_data", ("small", 1, "reflect"), "no_workspace", "workspace"),
+    ("acg_conv_transpose2d_fwd", ("small", 2, "zero"), "sigmoid", "no sigmoid epilogue"),
+]
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=lambda c: "%s-%s" % (c[0][4:], c[2]))
+def test_data_gradient_refusals(case):
+    """Side-input combinations the data-gradient entry points must refuse BEFORE anything is enqueued: the call raises
+    AcgError with the given text and the NaN-filled destination is still all NaN afterwards.  Every pointer handed over is a
+    real tensor of the size its role asks for (and the workspace pointer is real even where its byte count is 0)."""
+    import ctypes
+    from dtgan_amd import ops, _lib
+    from hip_util import precision
+    entry, (shape, stride, mode), what, text = case
+    P = ops._ptr
+    N, H, W, Ci, Co = (1, 8, 8, 16, 16) if shape == "small" else (1, 8, 32, 128, 128)
+    with precision("bf16x3"):
+        st = ops._stream()
+        d = ops.conv_desc(N, H, W, Ci, Co, 3, stride, 1, ops.PAD_REFLECT if mode == "reflect" else ops.PAD_ZERO, Ci, Co)
+        D = ctypes.byref(d)
+        g = torch.Generator().manual_seed(len(what))
+        pk = ops.PackedConv(torch.randn((Co, Ci, 3, 3), generator=g).cuda(), None, Ci, Co)
+        dy = torch.randn((N, d.Ho, d.Wo, Co), generator=g).cuda()
+        like_dx = torch.randn((N, H, W, Ci), generator=g).cuda()     # addend / ReLU source / the norm's input
+        bits = torch.zeros((N * H * W * Ci + 31) // 32, dtype=torch.int32, device="cuda")
+        dx = torch.full((N, H, W, Ci), float("nan"), device="cuda")
+        nb = max(_lib.query("acg_conv2d_bwd_data_workspace_bytes", D), 1)
+        ws = ops.workspace(nb)
+        head = (D, P(dy), P(pk.wb))
+        if what == "addend":
+            args = head + (P(like_dx), None, P(dx), P(ws), nb, st)
+        elif what == "relu":
+            args = head + (P(like_dx), P(dx), P(ws), nb, st)
+        elif what == "sums":
+            vec = torch.ones(N * Ci, device="cuda")
+            part = torch.zeros((N, (H * W + 127) // 128, 2, Ci), device="cuda")
+            ns = _lib.NormSumsDesc()
+            ns.x, ns.mean, ns.rstd, ns.gamma, ns.beta = P(like_dx), P(vec), P(vec), P(vec), P(vec)
+            ns.gstride, ns.sign_mask, ns.act, ns.part = 0, None, ops.ACT_NONE, P(part)
+            args = head + (P(dx), P(ws), nb, ctypes.byref(ns), st)
+        elif what == "plain":
+            args = head + (P(dx), P(ws), nb, None, None, None, 0, st)
+        elif what == "relu_mask":
+            args = head + (P(dx), P(ws), nb, P(bits), st)
+        elif what == "addend_out_s16":
+            args = head + (P(dx), P(ws), nb, P(like_dx), None, None, 1, st)
+        elif what == "mask_without_addend":
+            args = head + (P(dx), P(ws), nb, None, P(bits), None, 0, st)
+        elif what == "no_workspace":
+            args = head + (P(dx), P(ws), 0, st)
+        else:   # the transposed convolution: dy is its input, dx its output
+            args = head + (None, P(dx), ops.ACT_SIGMOID, st)
+        with pytest.raises(_lib.AcgError) as err:
+            _lib.call(entry, *args)
+        torch.cuda.synchronize()
+    print("refusal:", err.value)
+    assert text in str(err.value), str(err.value)
+    assert bool(torch.isnan(dx).all()), "something was launched"
