@@ -1,38 +1,64 @@
-// Radially averaged power spectra of square fields (model.translate_spectrum, test.py --metric spectrum): per field of one
-// channel of one image, S x S real pixels, P = |fft2(x)|^2 / S^2 averaged over rings of integer wavenumber 0 .. S/2.
-// There is no reference call site: the reference has no spectral code; tests/spectrum_ref.py states the definition.
+// Radially averaged power spectra of square fields (model.translate_spectrum, test.py --metric spectrum) and the paired
+// cross-spectra of two (ops.cross_spectrum, model.translate_coherence, test.py --metric coherence).  Per field of one channel of
+// one image, S x S real pixels: P = |fft2(x)|^2 / S^2 averaged over rings of integer wavenumber 0 .. S/2.  Per pair of fields
+// x, y and ring: the means of Pxx = |X|^2 / S^2, Pyy = |Y|^2 / S^2 and the co-spectrum Cxy = Re(X conj Y) / S^2; the quadrature part
+// Im(X conj Y) sums to 0 over every ring of two real fields (the twin cell holds the conjugate product) and is no output.
+// There is no reference call site: the reference has no spectral code; tests/spectrum_ref.py and tests/cross_spectrum_ref.py
+// state the definitions.
 //
-// A batched real 2-D FFT in fp32 with the power and the ring sums fused behind it, no vendor FFT:
+// One set of kernels, templated on the fields a workgroup carries: NF = 1 (a field, one sum per ring) or NF = 2 (a pair, three).
+// A batched real 2-D FFT in fp32 with the products and the ring sums fused behind it, no vendor FFT:
 //   rows     two real rows per complex transform (z = row 2r + i row 2r+1), radix-2 Stockham autosort in LDS (every stage reads
 //            unit-stride and writes runs of the stage's width: no bit-reversal gather, no stride-2^k access), then the two rows'
 //            half spectra are untangled.  Columns kx = 0 and kx = S/2 of a real row are real, so they travel packed in one
 //            complex column (re: kx = 0, im: kx = S/2): the half spectrum is exactly S x S/2 complex, the field's own bytes.
-//   columns  the same Stockham stages down the columns of a [ky][kx] tile with the lanes along kx, so every LDS access is
+//            The half spectra of a workgroup's NF fields lie side by side in one [ky][NF S/2] tile, X's columns in front and
+//            Y's behind.  A pair shares every pass, but never a complex transform: tangled as z = x + i y, the rounding of the
+//            stronger field would leak into the weaker one's spectrum at the stronger one's scale (a generator against a truth
+//            1000 times fainter).
+//   columns  the same Stockham stages down the columns of that tile with the lanes along kx, so every LDS access is
 //            unit-stride across the wave and the twiddle is a broadcast.
-//   power    w |F|^2 / S^2 per cell, w = 2 for 0 < kx < S/2 (the Hermitian twin lies in the same ring), 1 for kx = 0 and S/2,
-//            whose packed column is untangled here.
+//   products w |F|^2 / S^2 per cell (a pair: w |X|^2, w |Y|^2, w Re(X conj Y), each / S^2, into three planes), w = 2 for
+//            0 < kx < S/2 (the Hermitian twin lies in the same ring), 1 for kx = 0 and S/2, whose packed column is untangled
+//            here, for both fields of a pair before their product is taken.  Of the column kx = S/2 only the rows
+//            |fy| < spec_nyq(S) / 2 are kept: a ring reaches no further (fy^2 <= S/2).
 //   rings    ring b holds the cells with b (b - 1) < fx^2 + fy^2 <= b (b + 1) (integers: sqrt(s) rounded to nearest).  One
-//            work item per (ring, sign of fy) enumerates its cells row by row from the integer rule and sums them in double in
-//            that fixed order, and counts them; psd[b] = (sum+ + sum-) / count.  No float atomics: two runs give the same bits,
-//            and the arithmetic does not depend on the input's layout.
-// S <= 128: one workgroup per field does all of it in LDS and writes nothing but psd.  Above, a row pass writes the packed half
-// spectrum to the workspace and a column pass (one workgroup per field, tile after tile of columns) reads it back and bins.
+//            work item per (ring, sign of fy) enumerates its cells row by row from the integer rule and sums every plane in
+//            double in that fixed order, and counts the cells; out[k][b] = (sum+ + sum-) / count.  No float atomics: two runs
+//            give the same bits, and the arithmetic does not depend on the input's layout.
+// While the NF half spectra fit one workgroup's LDS twice (S <= 128 for a field, S <= 64 for a pair), one workgroup per field or
+// pair does all of it in LDS and writes nothing but its ring means.  Above, a row pass writes the tile to the workspace (S x NF S/2
+// complex per field or pair) and a column pass (one workgroup per field or pair, SPEC_TILE / S columns at a time, an equal
+// share of them from every field) reads it back and bins.
 // Twiddles: sincospif on exact arguments, one table per stage laid out by butterfly index (unit-stride reads).
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <type_traits>
 #include "common.h"
 
 #define SPEC_TILE 4096                   // complex elements of one LDS buffer of the two-pass kernels (32 KiB)
 #define SPEC_MIN_S 16
 #define SPEC_MAX_S 1024
-#define SPEC_ONE_WG_MAX_S 128            // the half spectrum of a field fits one workgroup's LDS up to here
 
-// threads of a workgroup: the one-workgroup kernel by the butterflies of a stage (S^2 / 4) and, at S = 128, by its being alone on
-// the CU (129 KiB of LDS); the two passes share a CU two workgroups at a time (66-72 KiB of LDS each): 16 waves of the row pass,
-// all 32 of the column pass, whose one workgroup per field is a serial chain of tiles and wants the widest workgroup
-__host__ __device__ constexpr int spec_field_threads(int S) { return S <= 16 ? 64 : S <= 64 ? 256 : 1024; }
+// one workgroup does a field or pair in LDS while two buffers of NF half spectra (8 NF S^2 bytes) fit beside the twiddles:
+// S <= 128 for a field, S <= 64 for a pair
+__host__ __device__ constexpr bool spec_one_wg(int S, int NF) { return 8 * NF * S * S <= 128 * 1024; }
+// threads of a workgroup: the one-workgroup kernel has four butterflies of a stage (NF S^2 / 4 of them) per thread, which is the
+// widest workgroup at S = 128 (129 KiB of LDS: alone on the CU) and half of it for a pair at S = 64 (65 KiB: two share a CU), but
+// no fewer than four waves, and one at S = 16.  The two passes share a CU two workgroups at a time (66-72 KiB of LDS each): 16
+// waves of the row pass, all 32 of the column pass, whose one workgroup per field or pair is a serial chain of tiles and wants
+// the widest workgroup
+__host__ __device__ constexpr int spec_field_threads(int S, int NF) { return S <= 16 ? 64 : NF * S * S / 16 < 256 ? 256 : NF * S * S / 16; }
+static_assert(spec_field_threads(16, 1) == 64 && spec_field_threads(32, 1) == 256 && spec_field_threads(64, 1) == 256 &&
+              spec_field_threads(128, 1) == 1024 && spec_field_threads(16, 2) == 64 && spec_field_threads(32, 2) == 256 &&
+              spec_field_threads(64, 2) == 512 && spec_one_wg(128, 1) && !spec_one_wg(256, 1) && spec_one_wg(64, 2) &&
+              !spec_one_wg(128, 2), "the launch geometry of every size");
 #define SPEC_ROWS_THREADS 512
 #define SPEC_COLS_THREADS 1024
+__host__ __device__ constexpr int spec_planes(int NF) { return NF == 1 ? 1 : 3; }   // |X|^2; with a second field |Y|^2 and Re(X conj Y)
+// slots of the kept rows of the column kx = S/2: row fy in slot fy & (slots - 1); fy^2 <= S/2 <= 512 lies well inside
+__host__ __device__ constexpr int spec_nyq(int S) { return S < 64 ? S : 64; }
 
 enum { SPEC_SCALAR = 0, SPEC_PLANAR = 1, SPEC_C4 = 2 };   // how a field's pixels are loaded
 
@@ -159,22 +185,45 @@ __device__ __forceinline__ void spec_untangle_rows(const float2 *z, float2 *h, i
     }
 }
 
-// The weighted power of a transformed [S][KT] tile of columns kx0 .. kx0 + KT - 1 -> pw[S][KT]; the tile of kx0 = 0 untangles
-// the packed column into pw[ky][0] (kx = 0) and pn[ky] (kx = S/2), both of weight 1
-template <int S, int KT>
-__device__ __forceinline__ void spec_power(const float2 *f, int kx0, float *pw, float *pn)
+// a b + c d of the packed column as one fused multiply-add behind the rounded c d: pinned, because the results keep their bits
+// only while the compiler makes this choice, and beside the guarded store of the column kx = S/2 it does not make it by itself
+__device__ __forceinline__ float spec_dot2(float a, float b, float c, float d) { return fmaf(a, b, c * d); }
+
+// A transformed [S][NF KH] tile, columns kx0 .. kx0 + KH - 1 of X in front and of Y behind -> pl[K][S][KH]: the weighted |X|^2
+// of every cell and, of a pair, |Y|^2 and Re(X conj Y) behind it; the tile of kx0 = 0 untangles the packed column of every
+// field into kx = 0 (pl[.][ky][0]) and kx = S/2 (pn[K][spec_nyq(S)]: the kept rows), both of weight 1
+template <int S, int KH, int NF>
+__device__ __forceinline__ void spec_products(const float2 *f, int kx0, float *pl, float *pn)
 {
+    constexpr int KT = NF * KH, H = S / 2, NQ = spec_nyq(S);
     const float inv = 1.f / ((float)S * (float)S);
-    for (int t = threadIdx.x; t < S * KT; t += blockDim.x) {
-        const int ky = t / KT, c = t & (KT - 1);
-        const float2 u = f[t];
+    for (int t = threadIdx.x; t < S * KH; t += blockDim.x) {
+        const int ky = t / KH, c = t & (KH - 1);
+        const float2 u = f[ky * KT + c], v = f[ky * KT + (NF - 1) * KH + c];   // v: the cell of Y (NF = 1: u again, unused)
         if (kx0 + c == 0) {
-            const float2 v = f[((S - ky) & (S - 1)) * KT];
-            const float dr = u.x + v.x, di = u.y - v.y, nr = u.x - v.x, ni = u.y + v.y;
-            pw[t] = (dr * dr + di * di) * (0.25f * inv);
-            pn[ky] = (nr * nr + ni * ni) * (0.25f * inv);
+            const int kz = (S - ky) & (S - 1), fy = ky < H ? ky : ky - S;
+            const float2 u2 = f[kz * KT], v2 = f[kz * KT + (NF - 1) * KH];
+            const float xdr = u.x + u2.x, xdi = u.y - u2.y, xnr = u.x - u2.x, xni = u.y + u2.y;
+            const float ydr = v.x + v2.x, ydi = v.y - v2.y, ynr = v.x - v2.x, yni = v.y + v2.y;
+            pl[t] = spec_dot2(xdr, xdr, xdi, xdi) * (0.25f * inv);
+            if constexpr (NF == 2) {
+                pl[S * KH + t] = spec_dot2(ydr, ydr, ydi, ydi) * (0.25f * inv);
+                pl[2 * S * KH + t] = spec_dot2(xdr, ydr, xdi, ydi) * (0.25f * inv);
+            }
+            if (fy > -NQ / 2 && fy < NQ / 2) {
+                const int slot = fy & (NQ - 1);
+                pn[slot] = spec_dot2(xnr, xnr, xni, xni) * (0.25f * inv);
+                if constexpr (NF == 2) {
+                    pn[NQ + slot] = spec_dot2(ynr, ynr, yni, yni) * (0.25f * inv);
+                    pn[2 * NQ + slot] = spec_dot2(xnr, ynr, xni, yni) * (0.25f * inv);
+                }
+            }
         } else {
-            pw[t] = (u.x * u.x + u.y * u.y) * (2.f * inv);
+            pl[t] = (u.x * u.x + u.y * u.y) * (2.f * inv);
+            if constexpr (NF == 2) {
+                pl[S * KH + t] = (v.x * v.x + v.y * v.y) * (2.f * inv);
+                pl[2 * S * KH + t] = (u.x * v.x + u.y * v.y) * (2.f * inv);
+            }
         }
     }
 }
@@ -225,170 +274,281 @@ __device__ __forceinline__ void spec_ring_cells(int b, bool neg, int kx0, int &c
     }
 }
 
-template <int S, int KT>
-__device__ __forceinline__ void spec_bin_item(int b, bool neg, int kx0, const float *pw, const float *pn, double &acc, int &cnt)
-{
-    spec_ring_cells<S, KT>(b, neg, kx0, cnt, [&](int i) { acc += (double)pw[i]; }, [&](int ky) { acc += (double)pn[ky]; });
-}
-
-template <int S, int T>                  // T: threads of the workgroup
-struct SpecBins {
+// The ring sums of a workgroup of T threads over K planes: one (ring, sign of fy) item per thread and turn
+template <int S, int T, int K>
+struct RingBins {
     static constexpr int NB = S / 2 + 1;
     static constexpr int NI = (2 * NB + T - 1) / T;    // (ring, sign) items per thread
-    double acc[NI];
+    static constexpr size_t LDS_BYTES = 2 * NB * (K * sizeof(double) + sizeof(int));
+    double acc[NI][K];
     int cnt[NI];
     __device__ __forceinline__ void clear()
     {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            acc[i] = 0.0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[i][k] = 0.0;
             cnt[i] = 0;
         }
     }
-    template <int KT>
-    __device__ __forceinline__ void add_tile(int kx0, const float *pw, const float *pn)
+    // the cells of the tile of columns kx0 .. kx0 + KH - 1: pl[K][S][KH] and, of the column kx = S/2, pn[K][spec_nyq(S)]
+    template <int KH>
+    __device__ __forceinline__ void add_tile(int kx0, const float *pl, const float *pn)
     {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int it = threadIdx.x + i * T;
-            if (it < 2 * NB) spec_bin_item<S, KT>(it >> 1, it & 1, kx0, pw, pn, acc[i], cnt[i]);
+            if (it >= 2 * NB) continue;
+            double(&a)[K] = acc[i];
+            spec_ring_cells<S, KH>(
+                it >> 1, it & 1, kx0, cnt[i],
+                [&](int c) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) a[k] += (double)pl[k * S * KH + c];
+                },
+                [&](int ky) {
+                    const int slot = (ky < S / 2 ? ky : ky - S) & (spec_nyq(S) - 1);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) a[k] += (double)pn[k * spec_nyq(S) + slot];
+                });
         }
     }
-    // psd[b] = (sum of the positive side + sum of the negative side) / cells; lds: 2 NB doubles and 2 NB ints, free to overwrite
-    __device__ __forceinline__ void store(void *lds, float *__restrict__ psd)
+    // out[k][b] = (sum of the positive side + sum of the negative side) / cells; lds: LDS_BYTES, free to overwrite
+    __device__ __forceinline__ void store(void *lds, float *__restrict__ out)
     {
         double *fin = reinterpret_cast<double *>(lds);
-        int *fcnt = reinterpret_cast<int *>(fin + 2 * NB);
+        int *fcnt = reinterpret_cast<int *>(fin + 2 * K * NB);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int it = threadIdx.x + i * T;
             if (it < 2 * NB) {
-                fin[it] = acc[i];
+#pragma unroll
+                for (int k = 0; k < K; ++k) fin[K * it + k] = acc[i][k];
                 fcnt[it] = cnt[i];
             }
         }
         __syncthreads();
-        for (int b = threadIdx.x; b < NB; b += blockDim.x)
-            psd[b] = (float)((fin[2 * b] + fin[2 * b + 1]) / (double)(fcnt[2 * b] + fcnt[2 * b + 1]));
+        for (int t = threadIdx.x; t < K * NB; t += blockDim.x) {
+            const int k = t / NB, b = t - k * NB;
+            out[t] = (float)((fin[2 * K * b + k] + fin[2 * K * b + K + k]) / (double)(fcnt[2 * b] + fcnt[2 * b + 1]));
+        }
     }
 };
 
-__device__ __forceinline__ const float *spec_field(const float *x, int f, int C, long long row_stride, long long chan_stride,
-                                                   int mode, int &c)
+// one operand of a launch: where its fields lie and how their pixels are loaded
+struct SpecField {
+    const float *x;
+    long long row, chan;
+    int pix, mode;
+};
+// what a launch reads: field or pair p is channel c of row r of operand 0 and, of a pair, channel c of row r / x_per_y of operand 1
+template <int NF>
+struct SpecSrc {
+    SpecField f[NF];
+    int C, x_per_y;
+};
+// the first pixel of field or pair p in operand i (SPEC_C4: the image's; c: the channel to pick)
+template <int NF>
+__device__ __forceinline__ const float *spec_field(const SpecSrc<NF> &s, int i, int p, int &c)
 {
-    const int row = f / C;
-    c = f - row * C;
-    return x + (long long)row * row_stride + (mode == SPEC_C4 ? 0 : (long long)c * chan_stride);
+    int row = p / s.C;
+    c = p - row * s.C;
+    if (i == 1) row /= s.x_per_y;
+    const SpecField &f = s.f[i];
+    return f.x + (long long)row * f.row + (f.mode == SPEC_C4 ? 0 : (long long)c * f.chan);
 }
 
-// S <= 128: one workgroup per field; nothing but psd is written
-template <int S>
-__global__ __launch_bounds__(spec_field_threads(S)) void spectrum_field_kernel(const float *__restrict__ x, int C, long long row_stride,
-                                                                      int pix_stride, long long chan_stride, int mode,
-                                                                      float *__restrict__ psd)
+// 16-byte copies between the half spectra of a field or pair in the workspace, hf[ky][NF S/2], and a [ky][KT] LDS tile that
+// holds columns kx0 .. kx0 + KT / NF - 1 of every field, X's in front and Y's behind
+template <int S, int KT, int NF>
+__device__ __forceinline__ long long spec_tile_cell(int ky, int cc, int kx0)
 {
-    constexpr int H = S / 2;
-    __shared__ __attribute__((aligned(16))) float2 buf0[H * S];
-    __shared__ __attribute__((aligned(16))) float2 buf1[H * S];
+    constexpr int KH = KT / NF;
+    static_assert(KH >= 2, "a 16-byte copy stays inside one field's columns");
+    return (long long)ky * (NF * (S / 2)) + (NF == 1 || cc < KH ? kx0 + cc : S / 2 + kx0 + cc - KH);
+}
+template <int S, int KT, int NF>
+__device__ __forceinline__ void spec_load_tile(const float2 *hf, int kx0, float2 *tile)
+{
+    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+        *reinterpret_cast<float4 *>(tile + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + spec_tile_cell<S, KT, NF>(ky, cc, kx0));
+    }
+}
+template <int S, int KT, int NF>
+__device__ __forceinline__ void spec_store_tile(const float2 *tile, int kx0, float2 *hf)
+{
+    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
+        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
+        *reinterpret_cast<float4 *>(hf + spec_tile_cell<S, KT, NF>(ky, cc, kx0)) = *reinterpret_cast<const float4 *>(tile + ky * KT + cc);
+    }
+}
+
+// spec_one_wg(S, NF): one workgroup per field or pair; nothing but out is written
+template <int S, int NF>
+__global__ __launch_bounds__(spec_field_threads(S, NF)) void spectrum_field_kernel(SpecSrc<NF> src, float *__restrict__ out)
+{
+    constexpr int H = S / 2, K = spec_planes(NF);
+    using Bins = RingBins<S, spec_field_threads(S, NF), K>;
+    __shared__ __attribute__((aligned(16))) float2 buf0[NF * H * S];
+    __shared__ __attribute__((aligned(16))) float2 buf1[NF * H * S];
     __shared__ float2 tw[S];
-    int c;
-    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
+    static_assert(K * (S * H + spec_nyq(S)) * sizeof(float) <= sizeof(buf0) && Bins::LDS_BYTES <= sizeof(buf0), "LDS");
     spec_twiddles<S>(tw);
-    spec_load_rows<S, H>(xf, pix_stride, mode, c, 0, buf0);
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        int c;
+        const float *xf = spec_field(src, i, blockIdx.x, c);
+        spec_load_rows<S, H>(xf, src.f[i].pix, src.f[i].mode, c, 0, buf0 + i * H * S);
+    }
     __syncthreads();
-    float2 *z = spec_fft_rows<S, H>(buf0, buf1, tw);
+    float2 *z = spec_fft_rows<S, NF * H>(buf0, buf1, tw);          // x's S/2 row pairs, then y's
     float2 *h = z == buf0 ? buf1 : buf0;
-    spec_untangle_rows<S, H>(z, h);                                // [ky][S/2]: the column tile of the whole field
+#pragma unroll
+    for (int i = 0; i < NF; ++i) spec_untangle_rows<S, H>(z + i * H * S, h + i * H, NF * H);   // [ky][NF S/2]: the whole column tile
     __syncthreads();
-    float2 *f = spec_fft_cols<S, H>(h, z, tw);
-    float *pw = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pw + S * H;
-    spec_power<S, H>(f, 0, pw, pn);
+    float2 *f = spec_fft_cols<S, NF * H>(h, z, tw);
+    float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + K * S * H;
+    spec_products<S, H, NF>(f, 0, pl, pn);
     __syncthreads();
-    SpecBins<S, spec_field_threads(S)> bins;
+    Bins bins;
     bins.clear();
-    bins.template add_tile<H>(0, pw, pn);
-    bins.store(f, psd + (long long)blockIdx.x * SpecBins<S, spec_field_threads(S)>::NB);
+    bins.template add_tile<H>(0, pl, pn);
+    bins.store(f, out + (long long)blockIdx.x * K * Bins::NB);
 }
 
-// S > 128, first pass: SPEC_TILE / S row pairs of one field per workgroup -> their rows of the packed half spectrum
-template <int S>
-__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(const float *__restrict__ x, int C, long long row_stride,
-                                                                     int pix_stride, long long chan_stride, int mode,
-                                                                     float2 *__restrict__ half)
+// above, first pass: SPEC_TILE / S row pairs of one field per workgroup (blockIdx.y: x's tiles, then y's) -> their rows of that
+// field's side of the [ky][NF S/2] tile in the workspace
+template <int S, int NF>
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(SpecSrc<NF> src, float2 *__restrict__ half)
 {
-    constexpr int NRP = SPEC_TILE / S;
+    constexpr int NRP = SPEC_TILE / S, TILES = (S / 2) / NRP, H = S / 2;
     __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
     __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
     __shared__ float2 tw[S];
+    const int i = NF == 1 ? 0 : blockIdx.y / TILES, rp0 = (blockIdx.y - i * TILES) * NRP;
     int c;
-    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
-    const int rp0 = blockIdx.y * NRP;
+    const float *xf = spec_field(src, i, blockIdx.x, c);
     spec_twiddles<S>(tw);
-    spec_load_rows<S, NRP>(xf, pix_stride, mode, c, rp0, buf0);
+    spec_load_rows<S, NRP>(xf, src.f[i].pix, src.f[i].mode, c, rp0, buf0);
     __syncthreads();
     const float2 *z = spec_fft_rows<S, NRP>(buf0, buf1, tw);
-    spec_untangle_rows<S, NRP>(z, half + ((long long)blockIdx.x * S + 2 * rp0) * (S / 2));
+    spec_untangle_rows<S, NRP>(z, half + ((long long)blockIdx.x * S + 2 * rp0) * (NF * H) + i * H, NF * H);
 }
 
-// S > 128, second pass: one workgroup per field walks its half spectrum in tiles of SPEC_TILE / S columns
-template <int S>
-__global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const float2 *__restrict__ half, float *__restrict__ psd)
+// above, second pass: one workgroup per field or pair walks its half spectra in tiles of SPEC_TILE / (NF S) columns of each
+template <int S, int NF>
+__global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const float2 *__restrict__ half, float *__restrict__ out)
 {
-    constexpr int KT = SPEC_TILE / S, H = S / 2;
+    constexpr int KT = SPEC_TILE / S, KH = KT / NF, H = S / 2, K = spec_planes(NF);
+    using Bins = RingBins<S, SPEC_COLS_THREADS, K>;
     __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
     __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
     __shared__ float2 tw[S];
-    const float2 *hf = half + (long long)blockIdx.x * S * H;
+    static_assert(K * (S * KH + spec_nyq(S)) * sizeof(float) <= sizeof(buf0) && Bins::LDS_BYTES <= sizeof(buf0), "LDS");
+    const float2 *hf = half + (long long)blockIdx.x * S * (NF * H);
     spec_twiddles<S>(tw);
-    SpecBins<S, SPEC_COLS_THREADS> bins;
+    Bins bins;
     bins.clear();
     float2 *f = buf0;
-    for (int kx0 = 0; kx0 < H; kx0 += KT) {
-        for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
-            const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
-            *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * H + kx0 + cc);
-        }
+    for (int kx0 = 0; kx0 < H; kx0 += KH) {
+        spec_load_tile<S, KT, NF>(hf, kx0, buf0);
         __syncthreads();
         f = spec_fft_cols<S, KT>(buf0, buf1, tw);
-        float *pw = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pw + SPEC_TILE;
-        spec_power<S, KT>(f, kx0, pw, pn);
+        float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + K * S * KH;
+        spec_products<S, KH, NF>(f, kx0, pl, pn);
         __syncthreads();
-        bins.template add_tile<KT>(kx0, pw, pn);
-        __syncthreads();                                           // pw may be buf0, which the next tile's load overwrites
+        bins.template add_tile<KH>(kx0, pl, pn);
+        __syncthreads();                                           // pl may be buf0, which the next tile's load overwrites
     }
-    bins.store(f, psd + (long long)blockIdx.x * SpecBins<S, SPEC_COLS_THREADS>::NB);
+    bins.store(f, out + (long long)blockIdx.x * K * Bins::NB);
 }
 
 static bool spec_size_ok(int S) { return S >= SPEC_MIN_S && S <= SPEC_MAX_S && (S & (S - 1)) == 0; }
 
-// 16-byte loads where the layout allows them: four pixels of a planar row, or a C4 pixel's channels
-static int spec_load_mode(const float *x, int C, long long row_stride, int pix_stride, long long chan_stride)
+// an operand as the caller describes it; its load mode follows once the call has been let pass
+static SpecField spec_operand(const float *x, long long row_stride, int pix_stride, long long chan_stride)
 {
-    const bool aligned = (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
-    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) return SPEC_PLANAR;
-    if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) return SPEC_C4;
+    SpecField f;
+    f.x = x, f.row = row_stride, f.chan = chan_stride, f.pix = pix_stride, f.mode = SPEC_SCALAR;
+    return f;
+}
+
+// 16-byte accesses where the layout allows them: four pixels of a planar row, or a C4 pixel's channels; gx: a second tensor
+// of the same strides (the gradient), or null
+static int spec_load_mode(const SpecField &f, int C, const float *gx = nullptr)
+{
+    const bool aligned = (uintptr_t)f.x % 16 == 0 && (uintptr_t)gx % 16 == 0 && f.row % 4 == 0;
+    if (f.pix == 1 && f.chan % 4 == 0 && aligned) return SPEC_PLANAR;
+    if (f.pix == 4 && f.chan == 1 && C <= 4 && aligned) return SPEC_C4;
     return SPEC_SCALAR;
 }
 
-extern "C" size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S)
+// What every entry point refuses, under its own name fn: a size, a count (of `what`: fields or pairs) or a stride of one of its
+// nf operands it cannot serve, and a workspace of fewer than `need` bytes (ACG_ERR_WORKSPACE) or off the 16-byte grid.  An
+// entry point's own refusals keep their places among these: own(SPEC_SHAPE_OK) and own(SPEC_STRIDES_OK) return them
+enum { SPEC_SHAPE_OK, SPEC_STRIDES_OK };
+template <class Own>
+static int spec_refuse(const char *fn, const char *what, int S, int rows, int C, const SpecField *f, int nf, const void *ws,
+                       size_t ws_bytes, size_t need, Own own)
 {
-    if (rows < 1 || C < 1 || !spec_size_ok(S) || S <= SPEC_ONE_WG_MAX_S) return 0;
-    return (size_t)rows * (size_t)C * (size_t)S * (size_t)(S / 2) * sizeof(float2);
+    ACG_REQUIRE(spec_size_ok(S), "%s: fields must be S x S with S a power of two in %d..%d (S=%d)", fn, SPEC_MIN_S, SPEC_MAX_S, S);
+    ACG_REQUIRE(rows >= 1 && C >= 1, "%s: need rows >= 1 and C >= 1 (rows=%d, C=%d)", fn, rows, C);
+    if (const int rc = own(SPEC_SHAPE_OK)) return rc;
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many %s (rows=%d, C=%d)", fn, what, rows, C);
+    bool positive = true;
+    char strides[256];
+    int n = 0;
+    for (int i = 0; i < nf; ++i) {                                 // one operand: "row ..", two: "x: row ..; y: row .."
+        positive = positive && f[i].row >= 1 && f[i].pix >= 1 && f[i].chan >= 1;
+        n += snprintf(strides + n, sizeof(strides) - n, "%s%srow %lld, pixel %d, channel %lld", i ? "; " : "",
+                      nf == 1 ? "" : i ? "y: " : "x: ", f[i].row, f[i].pix, f[i].chan);
+    }
+    ACG_REQUIRE(positive, "%s: strides must be positive (%s)", fn, strides);
+    if (const int rc = own(SPEC_STRIDES_OK)) return rc;
+    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
+        acg_set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
+        return ACG_ERR_WORKSPACE;
+    }
+    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "%s: the workspace must be 16-byte aligned", fn);
+    return ACG_OK;
 }
 
-template <int S>
-static void spec_launch(hipStream_t st, const float *x, int fields, int C, long long row_stride, int pix_stride,
-                        long long chan_stride, int mode, float *psd, float2 *half)
+// f(std::integral_constant<int, S>) for the size S of a call that spec_refuse has let pass
+template <class F>
+static void spec_for_size(int S, F f)
 {
-    if constexpr (S <= SPEC_ONE_WG_MAX_S) {
-        hipLaunchKernelGGL(spectrum_field_kernel<S>, dim3(fields), dim3(spec_field_threads(S)), 0, st, x, C, row_stride, pix_stride,
-                           chan_stride, mode, psd);
-        acg_note_kernel("spectrum_field<%d>", S);
+    switch (S) {
+    case 16: f(std::integral_constant<int, 16>()); break;
+    case 32: f(std::integral_constant<int, 32>()); break;
+    case 64: f(std::integral_constant<int, 64>()); break;
+    case 128: f(std::integral_constant<int, 128>()); break;
+    case 256: f(std::integral_constant<int, 256>()); break;
+    case 512: f(std::integral_constant<int, 512>()); break;
+    default: f(std::integral_constant<int, 1024>()); break;
+    }
+}
+
+// the workspace of n fields or pairs: their [ky][NF S/2] tiles between the two passes
+static size_t spec_half_bytes(int rows, int C, int S, int NF)
+{
+    if (rows < 1 || C < 1 || !spec_size_ok(S) || spec_one_wg(S, NF)) return 0;
+    return (size_t)rows * (size_t)C * (size_t)S * (size_t)(NF * (S / 2)) * sizeof(float2);
+}
+extern "C" size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S) { return spec_half_bytes(rows, C, S, 1); }
+extern "C" size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S) { return spec_half_bytes(rows, C, S, 2); }
+
+template <int S, int NF>
+static void spec_launch(hipStream_t st, const SpecSrc<NF> &src, int n, float *out, float2 *half)
+{
+    if constexpr (spec_one_wg(S, NF)) {
+        hipLaunchKernelGGL((spectrum_field_kernel<S, NF>), dim3(n), dim3(spec_field_threads(S, NF)), 0, st, src, out);
+        acg_note_kernel(NF == 1 ? "spectrum_field<%d>" : "cross_spectrum_field<%d>", S);
     } else {
-        hipLaunchKernelGGL(spectrum_rows_kernel<S>, dim3(fields, (S / 2) / (SPEC_TILE / S)), dim3(SPEC_ROWS_THREADS), 0, st, x, C,
-                           row_stride, pix_stride, chan_stride, mode, half);
-        hipLaunchKernelGGL(spectrum_cols_kernel<S>, dim3(fields), dim3(SPEC_COLS_THREADS), 0, st, (const float2 *)half, psd);
-        acg_note_kernel("spectrum_rows<%d> + spectrum_cols<%d>", S, S);
+        constexpr int TILES = (S / 2) / (SPEC_TILE / S);           // of every field: x's, then y's
+        hipLaunchKernelGGL((spectrum_rows_kernel<S, NF>), dim3(n, NF * TILES), dim3(SPEC_ROWS_THREADS), 0, st, src, half);
+        hipLaunchKernelGGL((spectrum_cols_kernel<S, NF>), dim3(n), dim3(SPEC_COLS_THREADS), 0, st, (const float2 *)half, out);
+        acg_note_kernel(NF == 1 ? "spectrum_rows<%d> + spectrum_cols<%d>" : "cross_spectrum_rows<%d> + cross_spectrum_cols<%d>", S, S);
     }
 }
 
@@ -396,33 +556,39 @@ extern "C" int acg_radial_spectrum(const float *x, int rows, int C, int S, long 
                                    long long chan_stride, float *psd, void *ws, size_t ws_bytes, void *stream)
 {
     ACG_REQUIRE(x != nullptr && psd != nullptr, "acg_radial_spectrum: null tensor");
-    ACG_REQUIRE(spec_size_ok(S), "acg_radial_spectrum: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
-                SPEC_MAX_S, S);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_radial_spectrum: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_radial_spectrum: too many fields (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
-                "acg_radial_spectrum: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride,
-                chan_stride);
-    const size_t need = acg_radial_spectrum_workspace_bytes(rows, C, S);
-    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-        acg_set_error("acg_radial_spectrum: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_radial_spectrum: the workspace must be 16-byte aligned");
-    const int mode = spec_load_mode(x, C, row_stride, pix_stride, chan_stride);
-    hipStream_t st = (hipStream_t)stream;
-    const int fields = rows * C;
-    float2 *half = (float2 *)ws;
-    switch (S) {
-    case 16: spec_launch<16>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    case 32: spec_launch<32>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    case 64: spec_launch<64>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    case 128: spec_launch<128>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    case 256: spec_launch<256>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    case 512: spec_launch<512>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    default: spec_launch<1024>(st, x, fields, C, row_stride, pix_stride, chan_stride, mode, psd, half); break;
-    }
+    SpecSrc<1> src;
+    src.f[0] = spec_operand(x, row_stride, pix_stride, chan_stride);
+    src.C = C, src.x_per_y = 1;
+    if (const int rc = spec_refuse("acg_radial_spectrum", "fields", S, rows, C, src.f, 1, ws, ws_bytes,
+                                   acg_radial_spectrum_workspace_bytes(rows, C, S), [](int) { return (int)ACG_OK; }))
+        return rc;
+    src.f[0].mode = spec_load_mode(src.f[0], C);
+    spec_for_size(S, [&](auto s) { spec_launch<decltype(s)::value, 1>((hipStream_t)stream, src, rows * C, psd, (float2 *)ws); });
     ACG_CHECK_LAUNCH("acg_radial_spectrum");
+    return ACG_OK;
+}
+
+extern "C" int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int S, long long x_row_stride,
+                                  int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                                  long long y_chan_stride, float *out, void *ws, size_t ws_bytes, void *stream)
+{
+    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_cross_spectrum: null tensor");
+    SpecSrc<2> src;
+    src.f[0] = spec_operand(x, x_row_stride, x_pix_stride, x_chan_stride);
+    src.f[1] = spec_operand(y, y_row_stride, y_pix_stride, y_chan_stride);
+    src.C = C, src.x_per_y = x_per_y;
+    const auto own = [&](int after) -> int {
+        if (after == SPEC_STRIDES_OK)
+            ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0,
+                        "acg_cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)", rows, x_per_y);
+        return ACG_OK;
+    };
+    if (const int rc = spec_refuse("acg_cross_spectrum", "pairs", S, rows, C, src.f, 2, ws, ws_bytes,
+                                   acg_cross_spectrum_workspace_bytes(rows, C, S), own))
+        return rc;
+    for (SpecField &f : src.f) f.mode = spec_load_mode(f, C);
+    spec_for_size(S, [&](auto s) { spec_launch<decltype(s)::value, 2>((hipStream_t)stream, src, rows * C, out, (float2 *)ws); });
+    ACG_CHECK_LAUNCH("acg_cross_spectrum");
     return ACG_OK;
 }
 
@@ -564,28 +730,28 @@ __device__ __forceinline__ void spec_store_rows(const float2 *z, float *__restri
     }
 }
 
-// what a workgroup needs to place its field's gradient: the field's first pixel, its image's, and the padded channels it clears
+// what a workgroup needs to place its field's gradient in gx, laid out as x (src): the field's first pixel, its image's, and
+// the padded channels it clears
 struct SpecDst {
     float *gf, *gi;
     int zero_from, zero_ch;
 };
-__device__ __forceinline__ SpecDst spec_dst(float *gx, int f, int C, int Cp, long long row_stride, long long chan_stride)
+__device__ __forceinline__ SpecDst spec_dst(float *gx, const SpecSrc<1> &src, int f, int Cp)
 {
-    const int row = f / C, c = f - row * C;
+    const int row = f / src.C, c = f - row * src.C;
     SpecDst d;
-    d.gi = gx + (long long)row * row_stride;
-    d.gf = d.gi + (long long)c * chan_stride;
-    d.zero_from = C;
-    d.zero_ch = c == 0 ? Cp - C : 0;
+    d.gi = gx + (long long)row * src.f[0].row;
+    d.gf = d.gi + (long long)c * src.f[0].chan;
+    d.zero_from = src.C;
+    d.zero_ch = c == 0 ? Cp - src.C : 0;
     return d;
 }
 
 // S <= 128: one workgroup per field
 template <int S>
-__global__ __launch_bounds__(spec_field_threads(S)) void spectrum_bwd_field_kernel(const float *__restrict__ x, const float *__restrict__ g,
-                                                                          const int *__restrict__ cnt, int C, int Cp,
-                                                                          long long row_stride, int pix_stride,
-                                                                          long long chan_stride, int mode, float *__restrict__ gx)
+__global__ __launch_bounds__(spec_field_threads(S, 1)) void spectrum_bwd_field_kernel(SpecSrc<1> src, const float *__restrict__ g,
+                                                                             const int *__restrict__ cnt, int Cp,
+                                                                             float *__restrict__ gx)
 {
     constexpr int H = S / 2;
     __shared__ __attribute__((aligned(16))) float2 buf0[H * S];
@@ -593,10 +759,10 @@ __global__ __launch_bounds__(spec_field_threads(S)) void spectrum_bwd_field_kern
     __shared__ float2 tw[S];
     __shared__ float gw[H + 1];
     int c;
-    const float *xf = spec_field(x, blockIdx.x, C, row_stride, chan_stride, mode, c);
+    const float *xf = spec_field(src, 0, blockIdx.x, c);
     spec_twiddles<S>(tw);
     spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
-    spec_load_rows<S, H>(xf, pix_stride, mode, c, 0, buf0);
+    spec_load_rows<S, H>(xf, src.f[0].pix, src.f[0].mode, c, 0, buf0);
     __syncthreads();
     float2 *z = spec_fft_rows<S, H>(buf0, buf1, tw);
     float2 *h = z == buf0 ? buf1 : buf0;
@@ -611,8 +777,8 @@ __global__ __launch_bounds__(spec_field_threads(S)) void spectrum_bwd_field_kern
     spec_tangle_rows<S, H>(t, o);
     __syncthreads();
     const float2 *r = spec_fft_rows<S, H>(o, t, tw);
-    const SpecDst d = spec_dst(gx, blockIdx.x, C, Cp, row_stride, chan_stride);
-    spec_store_rows<S, H>(r, d.gf, d.gi, pix_stride, chan_stride, mode == SPEC_PLANAR, 0, d.zero_from, d.zero_ch);
+    const SpecDst d = spec_dst(gx, src, blockIdx.x, Cp);
+    spec_store_rows<S, H>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == SPEC_PLANAR, 0, d.zero_from, d.zero_ch);
 }
 
 // S > 128, second pass: one workgroup per tile of SPEC_TILE / S columns of a field's half spectrum, in place
@@ -626,29 +792,22 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_bwd_cols_kernel(fl
     __shared__ float2 tw[S];
     __shared__ float gw[H + 1];
     const int kx0 = blockIdx.y * KT;
-    float2 *hf = half + (long long)blockIdx.x * S * H + kx0;
+    float2 *hf = half + (long long)blockIdx.x * S * H;
     spec_twiddles<S>(tw);
     spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
-    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
-        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
-        *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * H + cc);
-    }
+    spec_load_tile<S, KT, 1>(hf, kx0, buf0);
     __syncthreads();
     float2 *f = spec_fft_cols<S, KT>(buf0, buf1, tw);
     spec_scale_conj<S, KT>(f, kx0, gw);
     __syncthreads();
     const float2 *r = spec_fft_cols<S, KT>(f, f == buf0 ? buf1 : buf0, tw);
-    for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
-        const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
-        *reinterpret_cast<float4 *>(hf + (long long)ky * H + cc) = *reinterpret_cast<const float4 *>(r + ky * KT + cc);
-    }
+    spec_store_tile<S, KT, 1>(r, kx0, hf);
 }
 
 // S > 128, third pass: SPEC_TILE / S row pairs of one field per workgroup, half spectra -> the real rows of gx
 template <int S>
-__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(const float2 *__restrict__ half, int C, int Cp,
-                                                                         long long row_stride, int pix_stride,
-                                                                         long long chan_stride, int mode, float *__restrict__ gx)
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(const float2 *__restrict__ half, SpecSrc<1> src, int Cp,
+                                                                         float *__restrict__ gx)
 {
     constexpr int NRP = SPEC_TILE / S;
     __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
@@ -659,8 +818,8 @@ __global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(co
     spec_tangle_rows<S, NRP>(half + ((long long)blockIdx.x * S + 2 * rp0) * (S / 2), buf0);
     __syncthreads();
     const float2 *r = spec_fft_rows<S, NRP>(buf0, buf1, tw);
-    const SpecDst d = spec_dst(gx, blockIdx.x, C, Cp, row_stride, chan_stride);
-    spec_store_rows<S, NRP>(r, d.gf, d.gi, pix_stride, chan_stride, mode == SPEC_PLANAR, rp0, d.zero_from, d.zero_ch);
+    const SpecDst d = spec_dst(gx, src, blockIdx.x, Cp);
+    spec_store_rows<S, NRP>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == SPEC_PLANAR, rp0, d.zero_from, d.zero_ch);
 }
 
 extern "C" size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S)
@@ -670,22 +829,21 @@ extern "C" size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S
 }
 
 template <int S>
-static void spec_bwd_launch(hipStream_t st, const float *x, const float *g, int fields, int C, int Cp, long long row_stride,
-                            int pix_stride, long long chan_stride, int mode, float *gx, int *cnt, float2 *half)
+static void spec_bwd_launch(hipStream_t st, const SpecSrc<1> &src, const float *g, int fields, int Cp, float *gx, int *cnt,
+                            float2 *half)
 {
     hipLaunchKernelGGL(spectrum_ring_counts_kernel, dim3(S / 2 + 1), dim3(SPEC_COUNT_THREADS), 0, st, S, cnt);
-    if constexpr (S <= SPEC_ONE_WG_MAX_S) {
-        hipLaunchKernelGGL(spectrum_bwd_field_kernel<S>, dim3(fields), dim3(spec_field_threads(S)), 0, st, x, g, (const int *)cnt, C,
-                           Cp, row_stride, pix_stride, chan_stride, mode, gx);
+    if constexpr (spec_one_wg(S, 1)) {
+        hipLaunchKernelGGL(spectrum_bwd_field_kernel<S>, dim3(fields), dim3(spec_field_threads(S, 1)), 0, st, src, g, (const int *)cnt,
+                           Cp, gx);
         acg_note_kernel("spectrum_bwd_field<%d>", S);
     } else {
         constexpr int TILES = (S / 2) / (SPEC_TILE / S);
-        hipLaunchKernelGGL(spectrum_rows_kernel<S>, dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, x, C, row_stride, pix_stride,
-                           chan_stride, mode, half);
+        hipLaunchKernelGGL((spectrum_rows_kernel<S, 1>), dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, src, half);
         hipLaunchKernelGGL(spectrum_bwd_cols_kernel<S>, dim3(fields, TILES), dim3(SPEC_COLS_THREADS), 0, st, half, g,
                            (const int *)cnt);
-        hipLaunchKernelGGL(spectrum_bwd_rows_kernel<S>, dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, (const float2 *)half, C,
-                           Cp, row_stride, pix_stride, chan_stride, mode, gx);
+        hipLaunchKernelGGL(spectrum_bwd_rows_kernel<S>, dim3(fields, TILES), dim3(SPEC_ROWS_THREADS), 0, st, (const float2 *)half, src,
+                           Cp, gx);
         acg_note_kernel("spectrum_rows<%d> + spectrum_bwd_cols<%d> + spectrum_bwd_rows<%d>", S, S, S);
     }
 }
@@ -694,314 +852,23 @@ extern "C" int acg_radial_spectrum_bwd(const float *x, const float *g, int rows,
                                        int pix_stride, long long chan_stride, float *gx, void *ws, size_t ws_bytes, void *stream)
 {
     ACG_REQUIRE(x != nullptr && g != nullptr && gx != nullptr, "acg_radial_spectrum_bwd: null tensor");
-    ACG_REQUIRE(spec_size_ok(S), "acg_radial_spectrum_bwd: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
-                SPEC_MAX_S, S);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_radial_spectrum_bwd: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE(Cp >= C, "acg_radial_spectrum_bwd: the stored channels cannot be fewer than the valid ones (C=%d, Cp=%d)", C, Cp);
-    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_radial_spectrum_bwd: too many fields (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
-                "acg_radial_spectrum_bwd: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride,
-                chan_stride);
-    ACG_REQUIRE(x != gx, "acg_radial_spectrum_bwd: gx must not alias x");
-    const size_t need = acg_radial_spectrum_bwd_workspace_bytes(rows, C, S);
-    if (ws == nullptr || ws_bytes < need) {
-        acg_set_error("acg_radial_spectrum_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_radial_spectrum_bwd: the workspace must be 16-byte aligned");
-    const bool aligned = (uintptr_t)x % 16 == 0 && (uintptr_t)gx % 16 == 0 && row_stride % 4 == 0;
-    int mode = SPEC_SCALAR;
-    if (pix_stride == 1 && chan_stride % 4 == 0 && aligned) mode = SPEC_PLANAR;
-    else if (pix_stride == 4 && chan_stride == 1 && C <= 4 && aligned) mode = SPEC_C4;
-    hipStream_t st = (hipStream_t)stream;
-    const int fields = rows * C;
+    SpecSrc<1> src;
+    src.f[0] = spec_operand(x, row_stride, pix_stride, chan_stride);
+    src.C = C, src.x_per_y = 1;
+    const auto own = [&](int after) -> int {
+        if (after == SPEC_SHAPE_OK)
+            ACG_REQUIRE(Cp >= C, "acg_radial_spectrum_bwd: the stored channels cannot be fewer than the valid ones (C=%d, Cp=%d)", C, Cp);
+        else
+            ACG_REQUIRE(x != gx, "acg_radial_spectrum_bwd: gx must not alias x");
+        return ACG_OK;
+    };
+    if (const int rc = spec_refuse("acg_radial_spectrum_bwd", "fields", S, rows, C, src.f, 1, ws, ws_bytes,
+                                   acg_radial_spectrum_bwd_workspace_bytes(rows, C, S), own))
+        return rc;
+    src.f[0].mode = spec_load_mode(src.f[0], C, gx);
     int *cnt = (int *)ws;
     float2 *half = (float2 *)((char *)ws + spec_counts_bytes(S));
-    switch (S) {
-    case 16: spec_bwd_launch<16>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    case 32: spec_bwd_launch<32>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    case 64: spec_bwd_launch<64>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    case 128: spec_bwd_launch<128>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    case 256: spec_bwd_launch<256>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    case 512: spec_bwd_launch<512>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    default: spec_bwd_launch<1024>(st, x, g, fields, C, Cp, row_stride, pix_stride, chan_stride, mode, gx, cnt, half); break;
-    }
+    spec_for_size(S, [&](auto s) { spec_bwd_launch<decltype(s)::value>((hipStream_t)stream, src, g, rows * C, Cp, gx, cnt, half); });
     ACG_CHECK_LAUNCH("acg_radial_spectrum_bwd");
-    return ACG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Paired cross-spectra (ops.cross_spectrum, model.translate_coherence, test.py --metric coherence): per pair of fields x, y
-// and ring, the means of Pxx = |X|^2 / S^2, Pyy = |Y|^2 / S^2 and the co-spectrum Cxy = Re(X conj Y) / S^2.  The quadrature part
-// Im(X conj Y) sums to 0 over every ring of two real fields (the twin cell holds the conjugate product) and is no output.
-// The two fields share every pass, but never a complex transform: tangled as z = x + i y, the rounding of the stronger field
-// would leak into the weaker one's spectrum at the stronger one's scale (a generator against a truth 1000 times fainter).
-//   rows     each field as in the forward (rows 2r and 2r + 1 of ONE field per complex transform), untangled into a [ky][S]
-//            tile: X's packed half spectrum in columns 0 .. S/2 - 1, Y's behind.
-//   columns  the forward's column stages on that tile (above S = 64: S/2 columns of it at a time, half of them X's, half Y's).
-//   products w |X|^2, w |Y|^2, w Re(X conj Y), each / S^2, per cell into three planes, w as in spec_power; the packed column
-//            (kx = 0 and S/2) is untangled for both fields before their product is taken.  Of the column kx = S/2 only the rows
-//            |fy| < cross_nyq(S) / 2 are kept: a ring reaches no further (fy^2 <= S/2).
-//   rings    the forward's enumeration and order, three double sums per (ring, sign of fy).  No float atomics.
-// A pair holds two half spectra, 64 KiB of LDS in two buffers at S = 64: one workgroup per pair up to there (two share a CU),
-// above a row pass and a column pass (one workgroup per pair) through a workspace of S x S complex per pair.
-#define CROSS_ONE_WG_MAX_S 64
-// slots of the kept rows of the column kx = S/2: row fy in slot fy & (slots - 1); fy^2 <= S/2 <= 512 lies well inside
-__host__ __device__ constexpr int cross_nyq(int S) { return S < 64 ? S : 64; }
-
-// threads of the one-workgroup kernel: a stage has S^2 / 2 butterflies
-__host__ __device__ constexpr int cross_field_threads(int S) { return S <= 16 ? 64 : S <= 32 ? 256 : 512; }
-
-// A transformed [S][2 KH] tile, X's columns kx0 .. kx0 + KH - 1 in front and Y's behind -> pl[3][S][KH]: the weighted Pxx, Pyy,
-// Cxy of every cell; the tile of kx0 = 0 untangles both packed columns into kx = 0 (pl[.][ky][0]) and kx = S/2 (pn[3][cross_nyq(S)])
-template <int S, int KH>
-__device__ __forceinline__ void cross_products(const float2 *f, int kx0, float *pl, float *pn)
-{
-    constexpr int KT = 2 * KH, H = S / 2, NQ = cross_nyq(S);
-    const float inv = 1.f / ((float)S * (float)S);
-    for (int t = threadIdx.x; t < S * KH; t += blockDim.x) {
-        const int ky = t / KH, c = t & (KH - 1);
-        const float2 u = f[ky * KT + c], v = f[ky * KT + KH + c];
-        if (kx0 + c == 0) {
-            const int kz = (S - ky) & (S - 1), fy = ky < H ? ky : ky - S;
-            const float2 u2 = f[kz * KT], v2 = f[kz * KT + KH];
-            const float xdr = u.x + u2.x, xdi = u.y - u2.y, xnr = u.x - u2.x, xni = u.y + u2.y;
-            const float ydr = v.x + v2.x, ydi = v.y - v2.y, ynr = v.x - v2.x, yni = v.y + v2.y;
-            pl[t] = (xdr * xdr + xdi * xdi) * (0.25f * inv);
-            pl[S * KH + t] = (ydr * ydr + ydi * ydi) * (0.25f * inv);
-            pl[2 * S * KH + t] = (xdr * ydr + xdi * ydi) * (0.25f * inv);
-            if (fy > -NQ / 2 && fy < NQ / 2) {
-                const int slot = fy & (NQ - 1);
-                pn[slot] = (xnr * xnr + xni * xni) * (0.25f * inv);
-                pn[NQ + slot] = (ynr * ynr + yni * yni) * (0.25f * inv);
-                pn[2 * NQ + slot] = (xnr * ynr + xni * yni) * (0.25f * inv);
-            }
-        } else {
-            pl[t] = (u.x * u.x + u.y * u.y) * (2.f * inv);
-            pl[S * KH + t] = (v.x * v.x + v.y * v.y) * (2.f * inv);
-            pl[2 * S * KH + t] = (u.x * v.x + u.y * v.y) * (2.f * inv);
-        }
-    }
-}
-
-template <int S, int T>                  // SpecBins with the three sums of a pair; T: threads of the workgroup
-struct CrossBins {
-    static constexpr int NB = S / 2 + 1;
-    static constexpr int NI = (2 * NB + T - 1) / T;
-    static constexpr size_t LDS_BYTES = 2 * NB * (3 * sizeof(double) + sizeof(int));
-    double acc[NI][3];
-    int cnt[NI];
-    __device__ __forceinline__ void clear()
-    {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
-            cnt[i] = 0;
-        }
-    }
-    template <int KH>
-    __device__ __forceinline__ void add_tile(int kx0, const float *pl, const float *pn)
-    {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int it = threadIdx.x + i * T;
-            if (it >= 2 * NB) continue;
-            double &a0 = acc[i][0], &a1 = acc[i][1], &a2 = acc[i][2];
-            spec_ring_cells<S, KH>(
-                it >> 1, it & 1, kx0, cnt[i],
-                [&](int c) {
-                    a0 += (double)pl[c];
-                    a1 += (double)pl[S * KH + c];
-                    a2 += (double)pl[2 * S * KH + c];
-                },
-                [&](int ky) {
-                    const int slot = (ky < S / 2 ? ky : ky - S) & (cross_nyq(S) - 1);
-                    a0 += (double)pn[slot];
-                    a1 += (double)pn[cross_nyq(S) + slot];
-                    a2 += (double)pn[2 * cross_nyq(S) + slot];
-                });
-        }
-    }
-    // out[k][b] = (sum+ + sum-) / cells for k = Pxx, Pyy, Cxy; lds: LDS_BYTES, free to overwrite
-    __device__ __forceinline__ void store(void *lds, float *__restrict__ out)
-    {
-        double *fin = reinterpret_cast<double *>(lds);
-        int *fcnt = reinterpret_cast<int *>(fin + 6 * NB);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int it = threadIdx.x + i * T;
-            if (it < 2 * NB) {
-                fin[3 * it] = acc[i][0];
-                fin[3 * it + 1] = acc[i][1];
-                fin[3 * it + 2] = acc[i][2];
-                fcnt[it] = cnt[i];
-            }
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < 3 * NB; t += blockDim.x) {
-            const int k = t / NB, b = t - k * NB;
-            out[t] = (float)((fin[6 * b + k] + fin[6 * b + 3 + k]) / (double)(fcnt[2 * b] + fcnt[2 * b + 1]));
-        }
-    }
-};
-
-// where a workgroup's pair reads its two fields: pair p is channel c of row r of x against channel c of row r / x_per_y of y
-struct CrossSrc {
-    const float *x, *y;
-    long long x_row, x_chan, y_row, y_chan;
-    int x_pix, y_pix, x_mode, y_mode, x_per_y, C;
-};
-__device__ __forceinline__ void cross_fields(const CrossSrc &s, int p, const float *&xf, int &cx, const float *&yf, int &cy)
-{
-    const int row = p / s.C, c = p - row * s.C;
-    xf = spec_field(s.x, p, s.C, s.x_row, s.x_chan, s.x_mode, cx);
-    yf = spec_field(s.y, (row / s.x_per_y) * s.C + c, s.C, s.y_row, s.y_chan, s.y_mode, cy);
-}
-
-// S <= 64: one workgroup per pair; nothing but out is written
-template <int S>
-__global__ __launch_bounds__(cross_field_threads(S)) void cross_spectrum_field_kernel(CrossSrc src, float *__restrict__ out)
-{
-    constexpr int H = S / 2, T = cross_field_threads(S);
-    __shared__ __attribute__((aligned(16))) float2 buf0[S * S];
-    __shared__ __attribute__((aligned(16))) float2 buf1[S * S];
-    __shared__ float2 tw[S];
-    static_assert(3 * (S * H + cross_nyq(S)) * sizeof(float) <= sizeof(buf0) && CrossBins<S, T>::LDS_BYTES <= sizeof(buf0), "LDS");
-    const float *xf, *yf;
-    int cx, cy;
-    cross_fields(src, blockIdx.x, xf, cx, yf, cy);
-    spec_twiddles<S>(tw);
-    spec_load_rows<S, H>(xf, src.x_pix, src.x_mode, cx, 0, buf0);
-    spec_load_rows<S, H>(yf, src.y_pix, src.y_mode, cy, 0, buf0 + H * S);
-    __syncthreads();
-    float2 *z = spec_fft_rows<S, S>(buf0, buf1, tw);               // x's S/2 row pairs, then y's
-    float2 *h = z == buf0 ? buf1 : buf0;
-    spec_untangle_rows<S, H>(z, h, S);                             // [ky][S]: X's half spectrum | Y's
-    spec_untangle_rows<S, H>(z + H * S, h + H, S);
-    __syncthreads();
-    float2 *f = spec_fft_cols<S, S>(h, z, tw);
-    float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + 3 * S * H;
-    cross_products<S, H>(f, 0, pl, pn);
-    __syncthreads();
-    CrossBins<S, T> bins;
-    bins.clear();
-    bins.template add_tile<H>(0, pl, pn);
-    bins.store(f, out + (long long)blockIdx.x * 3 * CrossBins<S, T>::NB);
-}
-
-// S > 64, first pass: SPEC_TILE / S row pairs of one field of a pair per workgroup (blockIdx.y: x's tiles, then y's) -> their
-// rows of that field's side of the pair's [ky][S] tile in the workspace
-template <int S>
-__global__ __launch_bounds__(SPEC_ROWS_THREADS) void cross_spectrum_rows_kernel(CrossSrc src, float2 *__restrict__ half)
-{
-    constexpr int NRP = SPEC_TILE / S, TILES = (S / 2) / NRP;
-    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
-    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
-    __shared__ float2 tw[S];
-    const float *xf, *yf;
-    int cx, cy;
-    cross_fields(src, blockIdx.x, xf, cx, yf, cy);
-    const bool of_y = blockIdx.y >= TILES;
-    const int rp0 = (blockIdx.y - (of_y ? TILES : 0)) * NRP;
-    spec_twiddles<S>(tw);
-    if (of_y) spec_load_rows<S, NRP>(yf, src.y_pix, src.y_mode, cy, rp0, buf0);
-    else spec_load_rows<S, NRP>(xf, src.x_pix, src.x_mode, cx, rp0, buf0);
-    __syncthreads();
-    const float2 *z = spec_fft_rows<S, NRP>(buf0, buf1, tw);
-    spec_untangle_rows<S, NRP>(z, half + ((long long)blockIdx.x * S + 2 * rp0) * S + (of_y ? S / 2 : 0), S);
-}
-
-// S > 64, second pass: one workgroup per pair walks both half spectra in tiles of SPEC_TILE / (2 S) columns of each
-template <int S>
-__global__ __launch_bounds__(SPEC_COLS_THREADS) void cross_spectrum_cols_kernel(const float2 *__restrict__ half, float *__restrict__ out)
-{
-    constexpr int KT = SPEC_TILE / S, KH = KT / 2, H = S / 2;
-    __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
-    __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
-    __shared__ float2 tw[S];
-    static_assert(KH >= 2 && 3 * (S * KH + cross_nyq(S)) * sizeof(float) <= sizeof(buf0) &&
-                      CrossBins<S, SPEC_COLS_THREADS>::LDS_BYTES <= sizeof(buf0), "LDS");
-    const float2 *hf = half + (long long)blockIdx.x * S * S;
-    spec_twiddles<S>(tw);
-    CrossBins<S, SPEC_COLS_THREADS> bins;
-    bins.clear();
-    float2 *f = buf0;
-    for (int kx0 = 0; kx0 < H; kx0 += KH) {
-        for (int t = threadIdx.x; t < S * (KT / 2); t += blockDim.x) {
-            const int ky = t / (KT / 2), cc = (t & (KT / 2 - 1)) * 2;
-            const int col = cc < KH ? kx0 + cc : H + kx0 + cc - KH;  // X's columns, then Y's
-            *reinterpret_cast<float4 *>(buf0 + ky * KT + cc) = *reinterpret_cast<const float4 *>(hf + (long long)ky * S + col);
-        }
-        __syncthreads();
-        f = spec_fft_cols<S, KT>(buf0, buf1, tw);
-        float *pl = reinterpret_cast<float *>(f == buf0 ? buf1 : buf0), *pn = pl + 3 * S * KH;
-        cross_products<S, KH>(f, kx0, pl, pn);
-        __syncthreads();
-        bins.template add_tile<KH>(kx0, pl, pn);
-        __syncthreads();                                           // pl may be buf0, which the next tile's load overwrites
-    }
-    bins.store(f, out + (long long)blockIdx.x * 3 * CrossBins<S, SPEC_COLS_THREADS>::NB);
-}
-
-extern "C" size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S)
-{
-    if (rows < 1 || C < 1 || !spec_size_ok(S) || S <= CROSS_ONE_WG_MAX_S) return 0;
-    return (size_t)rows * (size_t)C * (size_t)S * (size_t)S * sizeof(float2);
-}
-
-template <int S>
-static void cross_launch(hipStream_t st, const CrossSrc &src, int pairs, float *out, float2 *half)
-{
-    if constexpr (S <= CROSS_ONE_WG_MAX_S) {
-        hipLaunchKernelGGL(cross_spectrum_field_kernel<S>, dim3(pairs), dim3(cross_field_threads(S)), 0, st, src, out);
-        acg_note_kernel("cross_spectrum_field<%d>", S);
-    } else {
-        hipLaunchKernelGGL(cross_spectrum_rows_kernel<S>, dim3(pairs, S / (SPEC_TILE / S)), dim3(SPEC_ROWS_THREADS), 0, st, src, half);  // x's and y's tiles
-        hipLaunchKernelGGL(cross_spectrum_cols_kernel<S>, dim3(pairs), dim3(SPEC_COLS_THREADS), 0, st, (const float2 *)half, out);
-        acg_note_kernel("cross_spectrum_rows<%d> + cross_spectrum_cols<%d>", S, S);
-    }
-}
-
-extern "C" int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int S, long long x_row_stride,
-                                  int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
-                                  long long y_chan_stride, float *out, void *ws, size_t ws_bytes, void *stream)
-{
-    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_cross_spectrum: null tensor");
-    ACG_REQUIRE(spec_size_ok(S), "acg_cross_spectrum: fields must be S x S with S a power of two in %d..%d (S=%d)", SPEC_MIN_S,
-                SPEC_MAX_S, S);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_cross_spectrum: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_cross_spectrum: too many pairs (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
-                    y_chan_stride >= 1,
-                "acg_cross_spectrum: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, "
-                "channel %lld)", x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
-    ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0,
-                "acg_cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)", rows, x_per_y);
-    const size_t need = acg_cross_spectrum_workspace_bytes(rows, C, S);
-    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-        acg_set_error("acg_cross_spectrum: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_cross_spectrum: the workspace must be 16-byte aligned");
-    CrossSrc src;
-    src.x = x, src.y = y;
-    src.x_row = x_row_stride, src.x_chan = x_chan_stride, src.y_row = y_row_stride, src.y_chan = y_chan_stride;
-    src.x_pix = x_pix_stride, src.y_pix = y_pix_stride;
-    src.x_mode = spec_load_mode(x, C, x_row_stride, x_pix_stride, x_chan_stride);
-    src.y_mode = spec_load_mode(y, C, y_row_stride, y_pix_stride, y_chan_stride);
-    src.x_per_y = x_per_y, src.C = C;
-    hipStream_t st = (hipStream_t)stream;
-    const int pairs = rows * C;
-    float2 *half = (float2 *)ws;
-    switch (S) {
-    case 16: cross_launch<16>(st, src, pairs, out, half); break;
-    case 32: cross_launch<32>(st, src, pairs, out, half); break;
-    case 64: cross_launch<64>(st, src, pairs, out, half); break;
-    case 128: cross_launch<128>(st, src, pairs, out, half); break;
-    case 256: cross_launch<256>(st, src, pairs, out, half); break;
-    case 512: cross_launch<512>(st, src, pairs, out, half); break;
-    default: cross_launch<1024>(st, src, pairs, out, half); break;
-    }
-    ACG_CHECK_LAUNCH("acg_cross_spectrum");
     return ACG_OK;
 }

@@ -82,11 +82,22 @@ def _red(rs, shape):
     return x / np.abs(x).max(axis=(-2, -1), keepdims=True)
 
 
-def make_fields(kind, S, rows=3, C=3, seed=0):
+def nyquist_row(S):
+    """the last row m of the column kx = S/2 that ring S/2 still holds: (S/2)^2 + m^2 <= (S/2) (S/2 + 1), m = floor(sqrt(S/2))"""
+    return int(np.floor(np.sqrt(S // 2)))
+
+
+def make_fields(kind, S, rows=3, C=3, seed=0, m=None):
     """(rows, C, S, S) float32 test fields, seeded by (kind, S, seed): U(-1, 1) white noise; a red field; tanh(3 red) (what a
-    generator head emits); the plane wave cos(2 pi (3 h + 4 w) / S); the constant 0.7 plus 1e-3 noise"""
-    rs = np.random.RandomState(1000 * FIELD_KINDS.index(kind) + 7 * S + seed)
+    generator head emits); the plane wave cos(2 pi (3 h + 4 w) / S); the constant 0.7 plus 1e-3 noise.  Beside FIELD_KINDS, the
+    exact kind nyquist_column: (-1)^w cos(2 pi m h / S), all of its power S^2 / 4 each in the cells (ky = +-m, kx = S/2); m
+    defaults to nyquist_row(S), one row further the cells lie in the dropped corner"""
     shape = (rows, C, S, S)
+    if kind == "nyquist_column":
+        h, w = np.meshgrid(np.arange(S), np.arange(S), indexing="ij")
+        x = (1.0 - 2.0 * (w % 2)) * np.cos(2 * np.pi * (nyquist_row(S) if m is None else m) * h / S)
+        return np.ascontiguousarray(np.broadcast_to(x, shape), dtype=np.float32)
+    rs = np.random.RandomState(1000 * FIELD_KINDS.index(kind) + 7 * S + seed)
     if kind == "white":
         x = rs.uniform(-1, 1, shape)
     elif kind == "red":

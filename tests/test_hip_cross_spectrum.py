@@ -90,6 +90,29 @@ def test_exact_cases(S):
     assert np.all(zero[..., 1, :] == 0) and np.all(zero[..., 2, :] == 0), np.abs(zero[..., 1:, :]).max()
 
 
+@pytest.mark.parametrize("S", SIZES)
+def test_the_nyquist_column_away_from_fy_0(S):
+    """x = (-1)^w cos(2 pi m h / S) against itself and against 0.5 x: the cells (+-m, S/2) of both packed columns.  At
+    m = nyquist_row(S) ring S/2 holds P = (S^2 / 2) / count of Pxx, and Pyy and Cxy in the ratios of the amplitudes; one row
+    further the cells lie in the dropped corner and every ring of every output stays empty.  Empty: within TAU^2 of the mean
+    squares Ex, Ey and, for Cxy, sqrt(Ex Ey)"""
+    m, last = R.nyquist_row(S), S // 2
+    for mm in (m, m + 1):
+        x = R.make_fields("nyquist_column", S, rows=1, C=3, m=mm)
+        Ex = _ms(x)
+        xd = _device(x, "nchw", 3, 3)
+        for a in (1.0, 0.5):
+            got = _cross(xd, _y_device(np.float32(a) * x, "nhwc", 3, 4), 3, "nchw", "nhwc")
+            for k, (name, scale) in enumerate((("pxx", 1.0), ("pyy", a * a), ("cxy", a))):
+                g = got[..., k, :]
+                empty = np.delete(g, last, axis=-1) if mm == m else g
+                print("nyquist column S=%d m=%d y=%gx %s: bin %d holds %.6e, largest other bin %.3e (allowed %.3e)"
+                      % (S, mm, a, name, last, g[..., last].max(), np.abs(empty).max(), TAU ** 2 * scale * Ex.min()))
+                assert np.all(np.abs(empty) <= TAU ** 2 * scale * Ex[..., None]), (mm, a, name)
+                if mm == m:
+                    assert np.allclose(g[..., last], scale * (S * S / 2.) / R.bin_counts(S)[last], rtol=1e-4), (a, name)
+
+
 @pytest.mark.parametrize("S", (32, 128))
 def test_members_share_a_truth_through_x_per_y(S):
     """6 members against 2 truth rows at x_per_y = 3: bit for bit the call with every truth row repeated three times"""

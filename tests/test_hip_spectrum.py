@@ -84,6 +84,23 @@ def test_exact_cases_leak_nothing(S):
 
 
 @pytest.mark.parametrize("S", R.FIELD_SIZES)
+def test_the_nyquist_column_away_from_fy_0(S):
+    """(-1)^w cos(2 pi m h / S): the cells (+-m, S/2) of the packed column.  At m = nyquist_row(S) they are the last of ring
+    S/2, one row further they lie in the dropped corner and every ring stays empty"""
+    m, last = R.nyquist_row(S), S // 2
+    for mm, layout, Cp in ((m, "nhwc", 4), (m + 1, "nchw", 3)):
+        x = R.make_fields("nyquist_column", S, rows=1, C=3, m=mm)
+        E = np.mean(x.astype(np.float64) ** 2, axis=(-2, -1))
+        got = _spectrum(_device(x, layout, 3, Cp), 3, layout)
+        empty = np.delete(got, last, axis=-1) if mm == m else got
+        print("nyquist column S=%d m=%d: bin %d holds %.6e, largest other bin %.3e (allowed %.3e)"
+              % (S, mm, last, got[..., last].max(), np.abs(empty).max(), TAU ** 2 * E.min()))
+        assert np.all(np.isfinite(got)) and np.all(np.abs(empty) <= TAU ** 2 * E[..., None])
+        if mm == m:
+            assert np.allclose(got[..., last], (S * S / 2.) / R.bin_counts(S)[last], rtol=1e-4)
+
+
+@pytest.mark.parametrize("S", R.FIELD_SIZES)
 def test_repeatable_and_the_same_bits_in_both_layouts(S):
     x, _, _ = _case("tanh_red", S)
     nhwc, nchw = _device(x, "nhwc", 3, 4), _device(x, "nchw", 3, 3)

@@ -25,6 +25,20 @@ def test_a_plane_wave_puts_its_power_into_two_cells_of_bin_5(S):
     assert np.all(np.delete(psd, 5) < 1e-9 * psd[5])
 
 
+@pytest.mark.parametrize("S", SIZES)
+def test_the_nyquist_column_fills_ring_half_s_up_to_its_last_row_only(S):
+    m, nb = R.nyquist_row(S), S // 2 + 1
+    assert m * m <= S // 2 < (m + 1) * (m + 1)
+    x = R.make_fields("nyquist_column", S, rows=1, C=1)[0, 0]
+    P = R.power_plane(x)
+    assert np.allclose(P[m, S // 2], S * S / 4., rtol=1e-6) and np.allclose(P[S - m, S // 2], S * S / 4., rtol=1e-6)
+    psd = R.rapsd(x)
+    assert np.allclose(psd[nb - 1], (S * S / 2.) / R.bin_counts(S)[nb - 1], rtol=1e-6)
+    assert np.all(psd[:nb - 1] < 1e-9 * psd[nb - 1])
+    beyond = R.rapsd(R.make_fields("nyquist_column", S, rows=1, C=1, m=m + 1)[0, 0])    # the dropped corner: no ring is filled
+    assert np.all(beyond < 1e-9 * psd[nb - 1])
+
+
 def test_a_constant_field_has_only_bin_0():
     S, c = 32, 0.7
     psd = R.rapsd(np.full((S, S), c, dtype=np.float32))
