@@ -41,6 +41,11 @@ class AdamGroup(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_size_t), ("sumsq", c_void_p)]
 
 
+class EmaGroup(ctypes.Structure):
+    """acg_ema_group (include/acgan_hip.h)."""
+    _fields_ = [("p", c_void_p), ("e", c_void_p), ("n", c_size_t)]
+
+
 class PackItem(ctypes.Structure):
     """acg_pack_item (include/acgan_hip.h)."""
     _fields_ = [("w", c_void_p), ("wf", c_void_p), ("wb", c_void_p), ("Or", c_int), ("Ir", c_int), ("K", c_int), ("Ci", c_int), ("Co", c_int)]
@@ -61,6 +66,7 @@ class NormSumsDesc(ctypes.Structure):
 
 
 ADAM_MAX_GROUPS = 8
+EMA_MAX_GROUPS = 8
 _P = c_void_p
 _D = ctypes.POINTER(ConvDesc)
 _MP = ctypes.POINTER(LatentMlpParams)
@@ -173,6 +179,8 @@ SIGNATURES = {
                                     c_size_t, _P]),
     "acg_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, c_float, c_float, c_float, c_float, c_int,
                               c_int, _P]),
+    "acg_ema_multi": (c_int, [ctypes.POINTER(EmaGroup), c_int, c_float, c_int, _P, _P]),
+    "acg_swap_multi": (c_int, [ctypes.POINTER(EmaGroup), c_int, _P]),
 }
 
 _lib = None

@@ -760,3 +760,108 @@ extern "C" int acg_adam_step(float *p, float *g, float *m, float *v, size_t n, c
     ACG_CHECK_LAUNCH("adam_kernel");
     return ACG_OK;
 }
+
+// ---------------------------------------------------------------- averaged weights (exponential moving average of p in e)
+// One launch for the flat buffers of an optimiser (acg_ema_multi) and the in-place exchange of the two (acg_swap_multi), on a
+// per-group block table as adam_multi_kernel's.  Bandwidth kernels (12 / 16 B per element): a group whose two pointers are
+// 16-byte aligned moves f32x4 per thread, at most EMA_BLOCK_CAP blocks of 256 threads per group (about 8 per CU) grid-striding
+// the rest; the n % 4 tail elements, and every element of a misaligned group, go one float at a time.
+#define EMA_BLOCK_CAP 2048
+struct EmaGroups {
+    acg_ema_group gr[ACG_EMA_MAX_GROUPS];
+    int nb[ACG_EMA_MAX_GROUPS], first[ACG_EMA_MAX_GROUPS + 1]; // blocks of group i: [first[i], first[i] + nb[i])
+    int n;
+};
+__device__ __forceinline__ int ema_group_of(const EmaGroups &G, int block)
+{
+    int gi = 0;
+#pragma unroll
+    for (int i = 1; i < ACG_EMA_MAX_GROUPS; ++i) gi += (i < G.n && block >= G.first[i]) ? 1 : 0;
+    return gi;
+}
+__device__ __forceinline__ bool ema_vec_ok(const acg_ema_group &q)
+{
+    return (((unsigned long long)q.p | (unsigned long long)q.e) & 15ull) == 0;
+}
+__global__ __launch_bounds__(256) void ema_multi_kernel(EmaGroups G, float decay, int step, const int *__restrict__ step_dev)
+{
+    const int gi = ema_group_of(G, blockIdx.x), lb = blockIdx.x - G.first[gi], nb = G.nb[gi];
+    const acg_ema_group q = G.gr[gi];
+    // the weight follows from the integer step inside the kernel in both cases: a replayed launch (step on the device) and an
+    // eager one at the same step take the same instructions
+    const float t = (float)(step_dev != nullptr ? step_dev[0] + 1 : step);
+    const float warm = (1.f + t) / (10.f + t);
+    const float w = 1.f - (decay < warm ? decay : warm);
+    const long long n = (long long)q.n, stride = nb * 256LL, i0 = lb * 256LL + threadIdx.x;
+    long long done = 0;
+    if (ema_vec_ok(q)) {
+        const long long n4 = n >> 2;
+        for (long long i = i0; i < n4; i += stride) {
+            const f32x4 p = *(const f32x4 *)(q.p + i * 4);
+            f32x4 e = *(const f32x4 *)(q.e + i * 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = fmaf(w, p[k] - e[k], e[k]);
+            *(f32x4 *)(q.e + i * 4) = e;
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + i0; i < n; i += stride) q.e[i] = fmaf(w, q.p[i] - q.e[i], q.e[i]);
+}
+__global__ __launch_bounds__(256) void swap_multi_kernel(EmaGroups G)
+{
+    const int gi = ema_group_of(G, blockIdx.x), lb = blockIdx.x - G.first[gi], nb = G.nb[gi];
+    const acg_ema_group q = G.gr[gi];
+    const long long n = (long long)q.n, stride = nb * 256LL, i0 = lb * 256LL + threadIdx.x;
+    long long done = 0;
+    if (ema_vec_ok(q)) {
+        const long long n4 = n >> 2;
+        for (long long i = i0; i < n4; i += stride) {
+            const f32x4 p = *(const f32x4 *)(q.p + i * 4), e = *(const f32x4 *)(q.e + i * 4);
+            *(f32x4 *)(q.p + i * 4) = e;
+            *(f32x4 *)(q.e + i * 4) = p;
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + i0; i < n; i += stride) {
+        const float p = q.p[i], e = q.e[i];
+        q.p[i] = e;
+        q.e[i] = p;
+    }
+}
+// the block table of both launches: ceil(n / 1024) blocks per group (one f32x4 per thread and trip), capped
+static int ema_table(const char *who, const acg_ema_group *groups, int ngroups, EmaGroups &G)
+{
+    ACG_REQUIRE(groups != nullptr && ngroups >= 1 && ngroups <= ACG_EMA_MAX_GROUPS, "%s: 1..%d groups, got %d", who,
+                ACG_EMA_MAX_GROUPS, ngroups);
+    G.n = ngroups;
+    G.first[0] = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const acg_ema_group &q = groups[i];
+        ACG_REQUIRE(q.p && q.e && q.n > 0, "%s: group %d has a null pointer or no elements", who, i);
+        G.gr[i] = q;
+        const size_t nbl = (q.n + 1023) / 1024;
+        G.nb[i] = (int)(nbl > EMA_BLOCK_CAP ? EMA_BLOCK_CAP : nbl);
+        G.first[i + 1] = G.first[i] + G.nb[i];
+    }
+    return ACG_OK;
+}
+extern "C" int acg_ema_multi(const acg_ema_group *groups, int ngroups, float decay, int step, const int *step_dev, void *stream)
+{
+    ACG_REQUIRE(decay > 0.f && decay < 1.f, "acg_ema_multi: decay must lie inside (0, 1), got %g", (double)decay);
+    ACG_REQUIRE(step >= 1 || step_dev != nullptr, "acg_ema_multi: step must be >= 1");
+    EmaGroups G;
+    const int rc = ema_table("acg_ema_multi", groups, ngroups, G);
+    if (rc != ACG_OK) return rc;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(G.first[ngroups]), dim3(256), 0, (hipStream_t)stream, G, decay, step, step_dev);
+    ACG_CHECK_LAUNCH("acg_ema_multi");
+    return ACG_OK;
+}
+extern "C" int acg_swap_multi(const acg_ema_group *groups, int ngroups, void *stream)
+{
+    EmaGroups G;
+    const int rc = ema_table("acg_swap_multi", groups, ngroups, G);
+    if (rc != ACG_OK) return rc;
+    hipLaunchKernelGGL(swap_multi_kernel, dim3(G.first[ngroups]), dim3(256), 0, (hipStream_t)stream, G);
+    ACG_CHECK_LAUNCH("acg_swap_multi");
+    return ACG_OK;
+}

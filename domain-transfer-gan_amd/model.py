@@ -12,6 +12,7 @@ What differs from the reference, by design:
   * multi-GPU = one process per GPU, gradients averaged by RCCL all-reduce before clipping (dist.py).
 Aliases for the north-star names: AugmentedCycleGAN_Model, .optimize_parameters(), .set_input().
 """
+import contextlib
 import functools  # noqa: F401
 import math
 import os
@@ -128,6 +129,11 @@ class FlatNet(object):
         if acg_dist.exchange_on():
             acg_dist.hook_params(self)
 
+    def enable_ema(self):
+        """allocate `ema`: the exponential moving average of `p` (n floats, starts as a copy), kept by FusedAdam behind every
+        step.  A FlatNet without it has no such attribute."""
+        self.ema = self.p.clone()
+
     def check(self):
         p0 = self.params[0]
         if p0.data_ptr() != self.p.data_ptr() or p0.grad is None or p0.grad.data_ptr() != self.g.data_ptr():
@@ -153,6 +159,7 @@ class FusedAdam(object):
         self.t = 0
         self.t_dev = None      # int32 device copy of t, read by the kernels of a captured step graph (StepGraph)
         self.dev_step = False  # True only while StepGraph captures: the recorded launches take the step from t_dev
+        self.ema_decay = 0.0   # the decay of the flats' averages (those that have one: FlatNet.enable_ema), set by the model
 
     def zero_grad(self):
         for f in self.flats:
@@ -164,6 +171,9 @@ class FusedAdam(object):
         self.t += 1
         ops.clip_adam_multi([(f.p, f.gv, f.m, f.v, f.sumsq) for f in self.flats], max_norm, g['lr'], g['betas'][0],
                             g['betas'][1], g['eps'], self.t, self.t_dev if self.dev_step else None)
+        avg = [(f.p, f.ema) for f in self.flats if hasattr(f, "ema")]
+        if avg:                # the averaged weights follow the step just taken: one launch, the step number as Adam's
+            ops.ema_multi(avg, self.ema_decay, self.t, self.t_dev if self.dev_step else None)
         for f in self.flats:   # the packed copies follow the parameters: one launch per network (modules.repack)
             repack(f.net)
         return [f.sumsq for f in self.flats]
@@ -250,7 +260,7 @@ class StepGraph(object):
         # configuration (precision / implementation switch) and the scalar options of the step
         baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
                                                         "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
-                                                        "lambda_spec_B"))
+                                                        "lambda_spec_B", "ema_decay"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -446,6 +456,64 @@ class _Base(object):
             if sg is not None:
                 sg.defer_scalars = bool(defer_scalars)
 
+    # ---- averaged generator weights (--ema_decay; no reference counterpart) ---------------------
+    # An exponential moving average of the parameters of the generator-side networks (EMA_NETS), kept in FlatNet.ema by the
+    # optimiser step (ops.ema_multi behind the Adam launch).  BatchNorm running buffers are not averaged: they are themselves
+    # running averages of the live network's statistics, and the averaged model uses them as they are.
+    _ema = ()              # [(checkpoint key of the network, its FlatNet)] of a model built with opt.ema_decay > 0
+    _ema_active = False    # inside ema_weights(): `p` holds the averages and `ema` the live parameters
+
+    def _setup_ema(self):
+        """called once the optimisers exist; 0 for options written before the averaging existed (opt.pkl)"""
+        d = float(getattr(self.opt, 'ema_decay', 0.0) or 0.0)
+        if not 0.0 <= d < 1.0:
+            raise ValueError("ema_decay must lie in [0, 1) (got %r)" % d)
+        if d == 0.0:
+            return
+        flats = {id(f.net): f for opt in self._optimizers().values() for f in opt.flats}
+        self._ema = [(k, flats[id(n)]) for k, n in self._net_dict().items() if k in self.EMA_NETS]
+        for _, f in self._ema:
+            f.enable_ema()
+        for opt in self._optimizers().values():
+            opt.ema_decay = d
+
+    def _swap_ema(self):
+        ops.swap_multi([(f.p, f.ema) for _, f in self._ema])
+        for _, f in self._ema:     # the packed convolution weights follow in place: a captured step graph stays valid
+            repack(f.net)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the averaged networks run on their averaged parameters (one ops.swap_multi over their flat buffers
+        and a repack per network on entry, the same on exit), so every forward-only method and metric scores the average.
+        RuntimeError: a model without averages, a nested entry, and a training step or load() inside the block."""
+        if not self._ema:
+            raise RuntimeError("ema_weights: this model keeps no averaged weights (ema_decay is 0)")
+        if self._ema_active:
+            raise RuntimeError("ema_weights: already inside the block")
+        self._swap_ema()
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            self._ema_active = False
+            self._swap_ema()
+
+    def _live_only(self, what):
+        if self._ema_active:
+            raise RuntimeError("%s inside ema_weights(): the networks hold the averaged parameters" % what)
+
+    @staticmethod
+    def _state_dict_from(f, flat):
+        """f.net.state_dict() with every parameter (under each of its keys) taken from `flat`, a buffer laid out as f.p; the
+        buffers of the network as they are"""
+        at = {f.p.data_ptr() + 4 * o: (o, p.numel()) for p, o in zip(f.params, f.offs)}
+        out = OrderedDict()
+        for k, v in f.net.state_dict().items():
+            hit = at.get(v.data_ptr())
+            out[k] = flat[hit[0]:hit[0] + hit[1]].view(v.shape) if hit is not None else v
+        return out
+
     # ---- forward-only helpers shared by both models (model.py:210-280, 606-733): compositions of the two generators.
     # Subclass hooks: _z (noise transform), _cycle_code (the latent the B -> A -> B cycle is closed with).
     def _draw_prior(self, like):
@@ -621,9 +689,6 @@ class _Base(object):
             n.train()
 
 
-import contextlib  # noqa: E402
-
-
 @contextlib.contextmanager
 def _in_train_step():
     """SyncBN collectives are issued only inside a training step, where every rank runs the same forward/backward; the
@@ -739,8 +804,12 @@ class StochCycleGAN(_Base):
         self.f_D_A, self.f_D_B = FlatNet(self.netD_A), FlatNet(self.netD_B)
         self.optimizer_G = FusedAdam([self.f_G_A_B, self.f_G_B_A], o.lr, (o.beta1, 0.999))      # model.py:109-111
         self.optimizer_D = FusedAdam([self.f_D_A, self.f_D_B], o.lr / 5., (o.beta1, 0.999))     # model.py:112-114
+        self._setup_ema()
+
+    EMA_NETS = ('netG_A_B', 'netG_B_A')      # the networks of optimizer_G
 
     def train_instance(self, real_A, real_B, prior_z_B):
+        self._live_only("train_instance")
         if self._step_graph is not None and not acg_dist.exchange_on():
             return self._step_graph(real_A, real_B, prior_z_B)
         with _in_train_step():
@@ -838,19 +907,47 @@ class StochCycleGAN(_Base):
         self.old_lr = lr
 
     def save(self, chk_name):
-        """model.py:293-303 / 750-764: same checkpoint keys, torch.load-able"""
+        """model.py:293-303 / 750-764: same checkpoint keys, torch.load-able.  A model with averaged weights adds `ema_<net>`
+        per averaged network (a full state_dict: the averaged parameters, the live buffers) and `ema_decay`; the reference's
+        keys hold the live weights, inside ema_weights() too."""
         chk_path = os.path.join(self.opt.expr_dir, chk_name)
         checkpoint = {k: n.state_dict() for k, n in self._net_dict().items()}
+        for k, f in self._ema:
+            avg = self._state_dict_from(f, f.ema)      # inside ema_weights() the two buffers have changed places
+            checkpoint[k], checkpoint['ema_' + k] = (avg, checkpoint[k]) if self._ema_active else (checkpoint[k], avg)
+        if self._ema:
+            checkpoint['ema_decay'] = float(self.opt.ema_decay)
         checkpoint.update({k: o.state_dict() for k, o in self._optimizers().items()})
         torch.save(checkpoint, chk_path)
 
-    def load(self, chk_path):
+    def load(self, chk_path, use_ema=False):
+        """use_ema: the networks themselves take the checkpoint's averaged weights (`ema_<net>`; KeyError naming the missing
+        key for a checkpoint without them), on any model.  A model that keeps averages restores them from the checkpoint, or,
+        from one without them, starts them at the loaded parameters."""
+        self._live_only("load")
         checkpoint = torch.load(chk_path, map_location=self._dev())
+        if use_ema:
+            for k in self.EMA_NETS:
+                if 'ema_' + k not in checkpoint:
+                    raise KeyError("checkpoint %s holds no averaged weights: key 'ema_%s' is missing (written by a run "
+                                   "without --ema_decay?)" % (chk_path, k))
         for k, n in self._net_dict().items():
-            n.load_state_dict(checkpoint[k])
+            n.load_state_dict(checkpoint['ema_' + k if use_ema and k in self.EMA_NETS else k])
             mark_dirty(n)
         for k, o in self._optimizers().items():
             o.load_state_dict(checkpoint[k])
+        restart = []
+        for k, f in self._ema:
+            sd = None if use_ema else checkpoint.get('ema_' + k)
+            if sd is None:
+                f.ema.copy_(f.p)
+                restart.append(k)
+                continue
+            for (name, p), o in zip(f.net.named_parameters(), f.offs):
+                f.ema[o:o + p.numel()].copy_(sd[name].reshape(-1))
+        if restart and not use_ema:
+            print("load: %s holds no averaged weights for %s; the averages start at the loaded parameters"
+                  % (chk_path, ", ".join(restart)))
 
 
 def _as2d(t):
@@ -917,6 +1014,9 @@ class AugmentedCycleGAN(_Base):
         self.optimizer_G_B = FusedAdam([self.f_G_A_B, self.f_E_B], o.lr, b)                     # model.py:381-383
         self.optimizer_D_A = FusedAdam([self.f_D_A], o.lr / 5., b)                              # model.py:384-385
         self.optimizer_D_B = FusedAdam([self.f_D_B, self.f_D_z_B], o.lr / 5., b)                # model.py:386-389
+        self._setup_ema()
+
+    EMA_NETS = ('netG_A_B', 'netG_B_A', 'netE_B')    # the networks of optimizer_G_A and optimizer_G_B
 
     def _encode(self, a_or_fake_a, b):
         """E_B on cat((A-side, B-side), 1) (A first: model.py:410, 472) -> (mu, logvar) (N, cpad(nl))"""
@@ -925,6 +1025,7 @@ class AugmentedCycleGAN(_Base):
         return self.netE_B.forward_nhwc(x)
 
     def train_instance(self, real_A, real_B, prior_z_B):
+        self._live_only("train_instance")
         if self._step_graph is not None and not acg_dist.exchange_on():
             return self._step_graph(real_A, real_B, prior_z_B)
         with _in_train_step():
@@ -1041,6 +1142,7 @@ class AugmentedCycleGAN(_Base):
 
     def supervised_train_instance(self, real_A, real_B, prior_z_B):
         """model.py:541-604 (paired step; off by default, --supervised)"""
+        self._live_only("supervised_train_instance")
         if self._sup_step_graph is not None and not acg_dist.exchange_on():
             return self._sup_step_graph(real_A, real_B, prior_z_B)
         with _in_train_step():

@@ -1723,6 +1723,31 @@ def clip_adam_multi(groups, max_norm, lr, beta1, beta2, eps, step, step_dev=None
               _ptr(step_dev), _ptr(ws), nb, _stream())
 
 
+def _ema_groups(who, groups):
+    n = len(groups)
+    arr = (_lib.EmaGroup * n)()
+    for i, (p, e) in enumerate(groups):
+        _check(p, e)
+        if p.numel() != e.numel():
+            raise _lib.AcgError("%s: group %d buffers differ in size" % (who, i))
+        arr[i].p, arr[i].e, arr[i].n = p.data_ptr(), e.data_ptr(), p.numel()
+    return arr, n
+
+
+def ema_multi(groups, decay, step, step_dev=None):
+    """the averaged weights of all networks of an optimiser in one launch; groups = [(p, e), ...] flat fp32 buffers:
+    e += (1 - d) (p - e), d = min(decay, (1 + t) / (10 + t)), t = `step` (the 1-based step just taken) or, with step_dev
+    (int32 device tensor holding the number of COMPLETED steps, graph capture), step_dev + 1 read by the kernel."""
+    arr, n = _ema_groups("ema_multi", groups)
+    _lib.call("acg_ema_multi", arr, n, float(decay), int(step), _ptr(step_dev), _stream())
+
+
+def swap_multi(groups):
+    """exchange p and e of every group in place, one launch; groups as ema_multi's"""
+    arr, n = _ema_groups("swap_multi", groups)
+    _lib.call("acg_swap_multi", arr, n, _stream())
+
+
 def adam_step(p, g, m, v, sumsq_t, max_norm, lr, beta1, beta2, eps, step, scale_grads=True):
     """clip (coefficient from the device-side sum of squares) + Adam on one flat buffer."""
     _check(p, g, m, v)

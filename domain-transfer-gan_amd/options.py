@@ -1,7 +1,7 @@
 """Command-line options — Py3 counterpart of /root/reference/augmented_cyclegan/options.py (which is Python 2:
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
 (options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
---step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B."""
+--step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B, --ema_decay, --ema_eval."""
 import argparse
 import os
 import pickle
@@ -88,6 +88,11 @@ _T = [
                                   "batch-mean radially averaged power spectra (ops.spectral_loss); 0: off; needs --grid_size "
                                   "a power of two in 16..1024"),
     ("lambda_spec_B", float, 0.0, "the same on fake_B against the real B"),
+    ("ema_decay", float, 0.0, "keep an exponential moving average of the generator-side weights (G_A_B, G_B_A, E_B) behind every "
+                              "optimiser step, with this decay (e.g. 0.999; warm-up min(decay, (1 + t) / (10 + t))); saved as "
+                              "ema_<net> next to the live weights; 0: off; inside [0, 1)"),
+    ("ema_eval", ("choice", int, [0, 1]), 1, "with --ema_decay: the per-epoch evaluation and the dev-set visualisations score "
+                                             "the averaged weights (1) or the live ones (0)"),
 ]
 
 
@@ -119,6 +124,8 @@ class TrainOptions(object):
         if (opt.lambda_spec_A > 0 or opt.lambda_spec_B > 0) and (not 16 <= g <= 1024 or g & (g - 1)):
             self.parser.error("--lambda_spec_A / --lambda_spec_B: the spectral loss needs fields of S x S with S a power of two "
                               "in 16..1024 (--grid_size %d)" % g)
+        if not 0.0 <= opt.ema_decay < 1.0:
+            self.parser.error("--ema_decay must lie in [0, 1) (got %r)" % opt.ema_decay)
         opt.gpu_ids = [i for i in (int(tok) for tok in opt.gpu_ids.split(",")) if i >= 0]      # options.py:92-97
         if opt.gpu_ids and torch.cuda.is_available():
             local = int(os.environ.get("LOCAL_RANK", opt.gpu_ids[0]))
@@ -145,7 +152,7 @@ class TestOptions(object):
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
     `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
-    --fss_quantiles, --fss_thresholds and --fss_windows."""
+    --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric)."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -169,6 +176,10 @@ class TestOptions(object):
         self.parser.add_argument('--fss_windows', type=_fss_windows, default=(1, 3, 5, 9, 17, 33),
                                  help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
                                       '(the cell itself: bias, CSI, base rate) is put in front if absent')
+
+        self.parser.add_argument('--ema', type=int, choices=[0, 1], default=0,
+                                 help='1: every metric runs on the averaged weights the checkpoint holds under ema_<net> '
+                                      '(a run trained with --ema_decay); 0: on the live weights')
 
     def parse(self, argv=None):
         return self.parser.parse_args(argv)

@@ -43,6 +43,9 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               listed window with FSS >= 0.5 + f0 / 2 (0: none).  Printed: FSS at the median listed window and the highest
               threshold, the mean over the channels -> <res_dir>/fss.npz.  Any H x W up to 1024.  No plot
 
+--ema 1 loads the averaged weights of a run trained with --ema_decay (the checkpoint's ema_<net> entries) into the networks
+instead of the live ones; every metric then runs unchanged.  A checkpoint without them ends the run with a message.
+
 Deviations from the reference:
   * the pixel count is C*H*W of the data, not the hard-coded 64*64*3;
   * every output file goes under res_dir (the reference writes noise_sens.npy to the working directory);
@@ -458,7 +461,7 @@ def test_model(argv=None):
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
     for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles', 'fss_quantiles', 'fss_thresholds',
-              'fss_windows'):
+              'fss_windows', 'ema'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -488,7 +491,14 @@ def test_model(argv=None):
     print('#dev images = %d' % len(dev_dataset))
 
     model, vis_inf = _build(opt)
-    model.load(opt.chk_path)
+    if opt.ema:
+        try:
+            model.load(opt.chk_path, use_ema=True)
+        except KeyError as e:
+            raise SystemExit(e.args[0])
+        print("evaluating the averaged weights (ema_decay %g)" % getattr(opt, 'ema_decay', 0.0))
+    else:
+        model.load(opt.chk_path)
 
     if opt.metric == 'bpp':
         logvar_B = None

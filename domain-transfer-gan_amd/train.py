@@ -5,6 +5,7 @@ nets.txt, results.json, history_mse_A.npy / history_ubo_B.npy, best_mse_A.txt / 
 `latest` / `best_A` / `best_B`, PNG grids under vis_*/ (written by a small built-in PNG encoder: torchvision is not
 required).  Additions: a working --continue_train, --synthetic data, one-process-per-GPU data parallelism
 (`python -m torch.distributed.run --nproc-per-node N -m ...train` shards every batch by rank)."""
+import contextlib
 import itertools
 import json
 import os
@@ -195,6 +196,8 @@ class Trainer(object):
         if getattr(o, "step_graph", False):           # both steps (unsupervised and paired) replay from graphs; ignored while
             self.model.enable_step_graph(defer_scalars=self.defer)   # the data-parallel exchange is on (model.train_instance)
         self.upload = PinnedUploads(torch.device("cuda")) if self.defer and self.gpu else None
+        # --ema_decay with --ema_eval 1: the evaluation and the dev-set pictures run on the averaged weights
+        self.ema_eval = bool(getattr(o, "ema_decay", 0.0) > 0 and getattr(o, "ema_eval", 1))
         if o.continue_train:
             chk = os.path.join(o.expr_dir, o.which_epoch)
             self.model.load(chk)
@@ -207,15 +210,21 @@ class Trainer(object):
         n = t.size(0) // self.ws
         return t[self.rank * n:(self.rank + 1) * n]
 
+    def _scored(self):
+        """the weights the evaluation and the dev-set pictures see: the model's averaged ones (model.ema_weights) under
+        --ema_decay with --ema_eval 1, else the live ones"""
+        return self.model.ema_weights() if self.ema_eval else contextlib.nullcontext()
+
     def _visualize(self, real_A, visuals, epoch, it):
         o, m = self.opt, self.model
         visualize_cycle(o, real_A, visuals, epoch, it, train=True)
         batch = next(self.dev_cycle)
         dA, dB = _cuda(batch['A'], self.gpu), _cuda(batch['B'], self.gpu)
         dz = dA.new_empty((dA.size(0), o.nlatent, 1, 1)).normal_(0, 1)
-        with torch.no_grad():
-            visualize_cycle(o, dA, m.generate_cycle(dA, dB, dz), epoch, it, train=False)
-        visualize_multi(o, dA, m, epoch, it)
+        with self._scored():
+            with torch.no_grad():
+                visualize_cycle(o, dA, m.generate_cycle(dA, dB, dz), epoch, it, train=False)
+            visualize_multi(o, dA, m, epoch, it)
 
     def _train_batches(self):
         """this rank's shard of every training batch; on the GPU the next batch is uploaded through pinned memory on a
@@ -330,7 +339,11 @@ class Trainer(object):
                 if epoch % o.save_epoch_freq == 0:
                     self.log('saving the model at the end of epoch %d, iters %d' % (epoch, self.total_steps))
                     self.model.save('latest')
-                self.evaluate(epoch)
+                if self.ema_eval:
+                    self.log("[%d] evaluating the averaged weights (ema_decay %g); the checkpoints hold the live weights "
+                             "under the usual keys and the averaged ones under ema_<net>" % (epoch, o.ema_decay))
+                with self._scored():
+                    self.evaluate(epoch)
             self.log('End of epoch %d / %d \t Time Taken: %d sec' % (epoch, last, time.time() - t0))
             if epoch > o.niter:
                 self.model.update_learning_rate()

@@ -530,6 +530,25 @@ size_t acg_clip_adam_multi_workspace_bytes(int ngroups);
 int acg_clip_adam_multi(const acg_adam_group *groups, int ngroups, float max_norm, float lr, float beta1, float beta2, float eps,
                         int step, const int *step_dev, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- averaged weights (new, no reference counterpart; --ema_decay): an exponential moving average of the parameters of
+ *      one or more networks, kept behind their optimiser step.  One launch for all groups.  Per element
+ *      e += (1 - d_t) (p - e), d_t = min(decay, (1 + t) / (10 + t)), t the 1-based number of the optimiser step just taken:
+ *      t = step, or, with step_dev (device, may be NULL), *step_dev + 1 read by the kernel, the convention of
+ *      acg_clip_adam_multi for a launch recorded into a HIP graph (`step` is then ignored).  d_t is formed inside the kernel
+ *      from the integer t in both cases, so an eager and a replayed launch at the same t give the same bits.  p is read
+ *      only; any n, 128-bit accesses where p and e of a group are both 16-byte aligned; no workspace.  The group array is
+ *      host memory, read during the call.  Refused before a launch (-1): decay outside (0, 1), ngroups outside
+ *      1..ACG_EMA_MAX_GROUPS, a null pointer, n == 0, step < 1 without step_dev.
+ *      acg_swap_multi exchanges p[i] and e[i] in place on the same table (the averaged weights become the live ones and
+ *      back; twice is the identity). ---- */
+#define ACG_EMA_MAX_GROUPS 8
+typedef struct {
+    float *p, *e; /* device: the live parameters of one network and their average, n floats each */
+    size_t n;
+} acg_ema_group;
+int acg_ema_multi(const acg_ema_group *groups, int ngroups, float decay, int step, const int *step_dev, void *stream);
+int acg_swap_multi(const acg_ema_group *groups, int ngroups, void *stream);
+
 /* ---- gradient exchange of the data-parallel step (replaces nn.parallel.data_parallel, networks.py:193-197 etc.): one
  *      process per GPU; rank 0 makes an id and ships its ACG_COMM_ID_BYTES to the other ranks by any side channel; every
  *      rank then joins with its current HIP device.  acg_comm_allreduce_mean averages a flat fp32 buffer (a network's
