@@ -260,7 +260,7 @@ class StepGraph(object):
         # configuration (precision / implementation switch) and the scalar options of the step
         baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
                                                         "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
-                                                        "lambda_spec_B", "ema_decay"))
+                                                        "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -350,6 +350,12 @@ class StepGraph(object):
         return deferred if deferred is not None else self.pending.resolve()
 
 
+def optional_loss_names(spec_on, marg_on):
+    """the names of the optional loss scalars a step appends to its fixed ones, in the order of its sums: the spectral pair
+    (--lambda_spec_A/B), then the marginal pair (--lambda_marg_A/B), each present when one of its weights is positive"""
+    return (['Spec_A', 'Spec_B'] if spec_on else []) + (['Marg_A', 'Marg_B'] if marg_on else [])
+
+
 class _Base(object):
     def _gan_loss(self, pred_c16, target_is_real):
         """the model's criterionGAN on an internal prediction map: LSGAN, or BCE under --no_lsgan"""
@@ -358,31 +364,46 @@ class _Base(object):
     def _dev(self):
         return next(self.netG_A_B.parameters()).device
 
-    def _spec_lambdas(self):
-        """(lambda_spec_A, lambda_spec_B); 0 for options written before the spectral loss existed (opt.pkl)"""
+    def _lambda_pair(self, name):
+        """(lambda_<name>_A, lambda_<name>_B); 0 for options written before that loss existed (opt.pkl)"""
         o = self.opt
-        return float(getattr(o, 'lambda_spec_A', 0.0) or 0.0), float(getattr(o, 'lambda_spec_B', 0.0) or 0.0)
+        return float(getattr(o, 'lambda_%s_A' % name, 0.0) or 0.0), float(getattr(o, 'lambda_%s_B' % name, 0.0) or 0.0)
 
-    def _spectral_terms(self, fake_A, A, fake_B, B):
-        """The spectral loss of the first-pass outputs against the real batches (ops.spectral_loss on the internal NHWC
-        tensors; unpaired: batch-mean spectra): None when both weights are 0 (the default: no launch is issued), else
-        (Spec_A, Spec_B, weighted sum for loss_G).  A term of weight 0 is a monitor without gradient."""
-        lam_A, lam_B = self._spec_lambdas()
+    def _spec_lambdas(self):
+        return _Base._lambda_pair(self, 'spec')
+
+    def _marg_lambdas(self):
+        return _Base._lambda_pair(self, 'marg')
+
+    def _optional_terms(self, loss, lams, fake_A, A, fake_B, B):
+        """An optional loss family on the first-pass outputs against the real batches (`loss(fake, real, C, "nhwc")` on the
+        internal NHWC tensors; unpaired: batch statistics): None when both weights are 0 (the default: no launch is issued),
+        else (term_A, term_B, weighted sum for loss_G).  A term of weight 0 is a monitor without gradient."""
+        lam_A, lam_B = lams
         if lam_A <= 0 and lam_B <= 0:
             return None
 
         def term(fake, real, C, lam):
             if lam > 0:
-                return ops.spectral_loss(fake, real, C, "nhwc")
+                return loss(fake, real, C, "nhwc")
             with torch.no_grad():
-                return ops.spectral_loss(fake.detach(), real, C, "nhwc")
-        spec_A = term(fake_A, A, self.opt.input_nc, lam_A)
-        spec_B = term(fake_B, B, self.opt.output_nc, lam_B)
+                return loss(fake.detach(), real, C, "nhwc")
+        t_A = term(fake_A, A, self.opt.input_nc, lam_A)
+        t_B = term(fake_B, B, self.opt.output_nc, lam_B)
         add = None
-        for v, lam in ((spec_A, lam_A), (spec_B, lam_B)):
+        for v, lam in ((t_A, lam_A), (t_B, lam_B)):
             if lam > 0:
                 add = v * lam if add is None else add + v * lam
-        return spec_A, spec_B, add
+        return t_A, t_B, add
+
+    def _spectral_terms(self, fake_A, A, fake_B, B):
+        """Spec_A, Spec_B (ops.spectral_loss: batch-mean radial spectra) under --lambda_spec_A/B, as _optional_terms gives them"""
+        return _Base._optional_terms(self, ops.spectral_loss, self._spec_lambdas(), fake_A, A, fake_B, B)
+
+    def _marginal_terms(self, fake_A, A, fake_B, B):
+        """Marg_A, Marg_B (ops.marginal_loss: the distance of the two batches' mean quantile functions) under
+        --lambda_marg_A/B, as _optional_terms gives them"""
+        return _Base._optional_terms(self, ops.marginal_loss, self._marg_lambdas(), fake_A, A, fake_B, B)
 
     def _nchw(self, x, C):
         return ops.ToNCHW.apply(x, C).detach()
@@ -852,11 +873,16 @@ class StochCycleGAN(_Base):
             spec = self._spectral_terms(fake_A, A, fake_B, B)
             if spec is not None:
                 loss_G = loss_G + spec[2]
+            marg = self._marginal_terms(fake_A, A, fake_B, B)
+            if marg is not None:
+                loss_G = loss_G + marg[2]
             self.optimizer_G.zero_grad()
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_D_B, loss_G_B, loss_cycle_B,
                     m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
             if spec is not None:
                 sums += [spec[0], spec[1]]
+            if marg is not None:
+                sums += [marg[0], marg[1]]
             ex_G = self._backward(loss_G, "stoch.G", [self.f_G_B_A, self.f_G_A_B], tail=(self.f_G_A_B, sums))
         finally:
             self.f_D_A.set_requires_grad(True); self.f_D_B.set_requires_grad(True)
@@ -865,7 +891,8 @@ class StochCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + \
-                ['Spec_A', 'Spec_B'][:n_loss - 10] + ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
+                optional_loss_names(spec is not None, marg is not None) + \
+                ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_D_B, ss_D_A])
         visuals = OrderedDict([('real_A', real_A.detach()), ('fake_B', self._nchw(fake_B, nB)),
                                ('rec_A', self._nchw(rec_A, nA)), ('real_B', real_B.detach()),
@@ -1100,12 +1127,17 @@ class AugmentedCycleGAN(_Base):
             spec = self._spectral_terms(fake_A, A, fake_B, B)
             if spec is not None:
                 loss_G = loss_G + spec[2]
+            marg = self._marginal_terms(fake_A, A, fake_B, B)
+            if marg is not None:
+                loss_G = loss_G + marg[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             mu_v, lv_v = mu_rB.detach()[:, :nl], lv_rB.detach()[:, :nl]
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_cycle_z_B, kld_z_B, loss_D_B, loss_G_B, loss_cycle_B,
                     loss_D_z_B, m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
             if spec is not None:
                 sums += [spec[0], spec[1]]
+            if marg is not None:
+                sums += [marg[0], marg[1]]
             mins, maxs = [mu_v.min(), lv_v.min()], [mu_v.max(), lv_v.max()]
             # completion order of the G backward: E_B (its first call is the last of the three first-pass networks to have
             # been built), then G_B_A, then G_A_B — which therefore carries the scalar tail
@@ -1121,7 +1153,7 @@ class AugmentedCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B',
-                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + ['Spec_A', 'Spec_B'][:n_loss - 13] + [
+                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + optional_loss_names(spec is not None, marg is not None) + [
                  'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_B', 'gnorm_D_z_B', 'gnorm_D_A',
                  'mu_min', 'logvar_min', 'mu_max', 'logvar_max']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, mins, maxs,

@@ -1581,6 +1581,83 @@ def coherence_summary(sums):
 
 
 # ----------------------------------------------------------------------------------------------
+# the marginal loss (model._marginal_terms, --lambda_marg_A / --lambda_marg_B): sorted fields and the distance of two
+# batches' mean quantile functions
+# ----------------------------------------------------------------------------------------------
+FIELD_SORT_MAX_P = 1 << 20
+
+
+def _field_sort_size(what, H, W):
+    if H < 1 or W < 1 or H * W > FIELD_SORT_MAX_P:
+        raise _lib.AcgError("%s: fields must hold 1 .. %d pixels (got %d x %d)" % (what, FIELD_SORT_MAX_P, H, W))
+    return int(H * W)
+
+
+def field_sort(x, C, layout, want_rank=True):
+    """acg_field_sort of the C valid channels of every row of x -> (sorted, rank): sorted (rows, C, H W) float32, each field's
+    values in ascending order, and rank (rows, C, H W) int32, the position of every pixel in that order (None with
+    want_rank=False).  Pixel p comes before q iff x[p] < x[q], or x[p] == x[q] and p < q (-0.0 and +0.0 tie; a stable
+    argsort).  layout "nhwc": x (rows, H, W, Cp), padded channels never read; "nchw": x (rows, C, H, W).  Both outputs are
+    planar and hold the same bits in either layout.  H W <= 2^20.  Nothing is read back to the host.  Not differentiable."""
+    x = x.detach().contiguous()
+    rows, C, Cp, H, W, strides = _field_args(x, C, layout, "field_sort")
+    P = _field_sort_size("field_sort", H, W)
+    _check(x)
+    srt = torch.empty((rows, C, P), device=x.device, dtype=torch.float32)
+    rank = torch.empty((rows, C, P), device=x.device, dtype=torch.int32) if want_rank else None
+    nbytes = _lib.query("acg_field_sort_workspace_bytes", rows, C, H, W)
+    ws = workspace(nbytes, slot=2) if nbytes else None
+    _lib.call("acg_field_sort", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(srt), _ptr(rank), _ptr(ws), nbytes,
+              _stream())
+    return srt, rank
+
+
+class MarginalLoss(torch.autograd.Function):
+    """marginal_loss with its data gradient in x: forward acg_field_sort of both batches and acg_marginal_loss_fwd, backward
+    acg_marginal_loss_bwd, a gather of the saved quantile differences d through the saved ranks of x, scaled by the upstream
+    gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, C, layout):
+        x, y = x.detach().contiguous(), y.detach().contiguous()
+        rows, C, Cp, H, W, strides = _field_args(x, C, layout, "marginal_loss")
+        rows_y, _, _, Hy, Wy, _ = _field_args(y, C, layout, "marginal_loss")
+        P = _field_sort_size("marginal_loss", H, W)
+        if (Hy, Wy) != (H, W):
+            raise _lib.AcgError("marginal_loss: fields of %d x %d against fields of %d x %d" % (H, W, Hy, Wy))
+        sx, rank = field_sort(x, C, layout, want_rank=ctx.needs_input_grad[0])
+        sy, _ = field_sort(y, C, layout, want_rank=False)
+        d = torch.empty((C, P), device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        nbytes = _lib.query("acg_marginal_loss_workspace_bytes", C, P)
+        ws = workspace(nbytes, slot=2)
+        _lib.call("acg_marginal_loss_fwd", _ptr(sx), rows, _ptr(sy), rows_y, C, P, _ptr(d), _ptr(loss), _ptr(ws), nbytes, _stream())
+        ctx.cfg = (rows, C, Cp if layout == "nhwc" else C, H, W, strides, tuple(x.shape))
+        if rank is not None:
+            ctx.save_for_backward(d, rank)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d, rank = ctx.saved_tensors
+        rows, C, Cp, H, W, strides, shape = ctx.cfg
+        g = g.detach().to(torch.float32).contiguous()
+        gx = torch.empty(shape, device=d.device, dtype=torch.float32)
+        _lib.call("acg_marginal_loss_bwd", _ptr(d), _ptr(rank), _ptr(g), rows, C, Cp, H, W, strides[0], strides[1], strides[2],
+                  _ptr(gx), _stream())
+        return gx, None, None, None
+
+
+def marginal_loss(x, y, C, layout):
+    """The squared 2-Wasserstein distance of the value distributions of two batches, averaged over the C channels -> device
+    scalar, differentiable in x: with s_x the sorted fields (field_sort), Q_x[c, k] = mean over the rows of s_x[r, c, k] (the
+    batch's mean quantile function, its Wasserstein barycentre) and the same for y (detached), mean over c, k of
+    (Q_x - Q_y)^2.  d loss / d x[r, c, p] = 2 (Q_x - Q_y)[c, rank_x[r, c, p]] / (C H W rows_x): a gather, deterministic.  x and y
+    share the layout and the field size but need not pair (nor hold the same number of rows).  No host synchronisation."""
+    return MarginalLoss.apply(x, y, C, layout)
+
+
+# ----------------------------------------------------------------------------------------------
 # neighbourhood fractions skill scores (model.translate_fss, test.py --metric fss)
 # ----------------------------------------------------------------------------------------------
 FSS_MAX_HW, FSS_MAX_T, FSS_MAX_NW, FSS_MAX_M = 1024, 8, 8, 64

@@ -1,7 +1,8 @@
 """Command-line options — Py3 counterpart of /root/reference/augmented_cyclegan/options.py (which is Python 2:
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
 (options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
---step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B, --ema_decay, --ema_eval."""
+--step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B, --ema_decay, --ema_eval,
+--lambda_marg_A, --lambda_marg_B."""
 import argparse
 import os
 import pickle
@@ -93,6 +94,10 @@ _T = [
                               "ema_<net> next to the live weights; 0: off; inside [0, 1)"),
     ("ema_eval", ("choice", int, [0, 1]), 1, "with --ema_decay: the per-epoch evaluation and the dev-set visualisations score "
                                              "the averaged weights (1) or the live ones (0)"),
+    ("lambda_marg_A", float, 0.0, "weight of the marginal loss on fake_A against the real A: the squared 2-Wasserstein distance "
+                                  "of the two batches' mean quantile functions, per channel (ops.marginal_loss: every field is "
+                                  "sorted); 0: off; needs --grid_size up to 1024"),
+    ("lambda_marg_B", float, 0.0, "the same on fake_B against the real B"),
 ]
 
 
@@ -124,6 +129,12 @@ class TrainOptions(object):
         if (opt.lambda_spec_A > 0 or opt.lambda_spec_B > 0) and (not 16 <= g <= 1024 or g & (g - 1)):
             self.parser.error("--lambda_spec_A / --lambda_spec_B: the spectral loss needs fields of S x S with S a power of two "
                               "in 16..1024 (--grid_size %d)" % g)
+        if opt.lambda_marg_A < 0 or opt.lambda_marg_B < 0:
+            self.parser.error("--lambda_marg_A / --lambda_marg_B must not be negative (got %r, %r)"
+                              % (opt.lambda_marg_A, opt.lambda_marg_B))
+        if (opt.lambda_marg_A > 0 or opt.lambda_marg_B > 0) and not 1 <= g <= 1024:
+            self.parser.error("--lambda_marg_A / --lambda_marg_B: the marginal loss sorts fields of up to 1024 x 1024 "
+                              "(--grid_size %d)" % g)
         if not 0.0 <= opt.ema_decay < 1.0:
             self.parser.error("--ema_decay must lie in [0, 1) (got %r)" % opt.ema_decay)
         opt.gpu_ids = [i for i in (int(tok) for tok in opt.gpu_ids.split(",")) if i >= 0]      # options.py:92-97

@@ -506,6 +506,46 @@ int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H,
             long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr, int T,
             const int *windows, int nw, long long *out, long long *ens_out, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- the marginal loss (ops.field_sort, ops.marginal_loss, --lambda_marg_A / --lambda_marg_B; no reference call site: the
+ *      reference has no distributional loss, tests/marginal_ref.py states the definition) ----
+ * acg_field_sort: a stable sort of each of the rows x C fields of H x W fp32 pixels of x, with its permutation.  The strides
+ * (in floats) mean what they mean in acg_radial_spectrum: NHWC with Cp stored channels is (H W Cp, Cp, 1) - padded channels are
+ * never read - and planar NCHW is (C H W, 1, H W).  Pixel p = h W + w comes before pixel q iff x[p] < x[q] as floats, or
+ * x[p] == x[q] and p < q: -0.0 and +0.0 tie, ties break by pixel index (numpy.argsort(kind="stable") of x + 0.0).  sorted
+ * (rows, C, P), P = H W: the values in that order, the bits of x (a -0.0 leaves as +0.0); rank (rows, C, P) int32, or NULL:
+ * rank[r][c][p] is the position of pixel p.  Both are planar whatever the layout of x, and the same bits for every layout.
+ * NaN is outside the contract; the kernels still end and write only inside sorted and rank.  Any H, W >= 1 with H W <= 2^20.
+ * A bitonic network on the words (key << 32) | p, fields padded to Ppad = the next power of two: up to Ppad = 8192 one
+ * launch and no workspace (one workgroup per 8192 words: a field, or several small ones); above, the words live in the
+ * workspace (acg_field_sort_workspace_bytes = 8 rows C Ppad, 16-byte aligned) and a sort takes 1 + sum over s = 1 .. log2(Ppad
+ * / 8192) of (ceil(s / 2) + 1) launches: the chunk sorts, then per merge stage s its s strides >= 8192 two per launch and one
+ * launch that finishes the stage in LDS (3 at Ppad = 2^14, 8 at 2^16, 24 at 2^20; acg_last_kernel names the path and the
+ * count).  Refused before a launch (-1, acg_last_error starts with the
+ * entry's name): a null x or sorted, rows < 1, C < 1, H W outside 1 .. 2^20, a stride < 1, outputs that alias x or each other,
+ * a misaligned workspace; a workspace below acg_field_sort_workspace_bytes returns -2.  The size query is 0 for a refused
+ * size. */
+size_t acg_field_sort_workspace_bytes(int rows, int C, int H, int W);
+int acg_field_sort(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
+                   float *sorted, int *rank, void *workspace, size_t ws_bytes, void *stream);
+/* The loss on two sorted batches sx (rows_x, C, P) and sy (rows_y, C, P) (the rows need not pair): d (C, P) = the mean of sx
+ * over its rows - the mean of sy over its rows (the difference of the two batches' mean quantile functions, their Wasserstein
+ * barycentres), loss[0] = the mean of d^2 over C P: the squared 2-Wasserstein distance of the barycentres, averaged over the
+ * channels.  The row sums run in row order in fp32 and d is fp32; its squares are summed in double over fixed slices into the workspace
+ * (acg_marginal_loss_workspace_bytes, 16-byte aligned, never 0 for a valid size) and from there by one workgroup: the same
+ * bits on every call.  Two launches.  Refused before a launch: a null pointer, rows_x, rows_y or C < 1, P outside 1 .. 2^20,
+ * d or loss aliasing an input (-1); a short workspace (-2). */
+size_t acg_marginal_loss_workspace_bytes(int C, long long P);
+int acg_marginal_loss_fwd(const float *sx, int rows_x, const float *sy, int rows_y, int C, long long P, float *d, float *loss,
+                          void *workspace, size_t ws_bytes, void *stream);
+/* Its data gradient: gx[r][c][p] = gscale[0] (2 / (C P rows)) d[c][rank[r][c][p]] in the layout the strides describe (those
+ * of the x that acg_field_sort ranked); gscale is the upstream gradient, one float on the device, so nothing is read back
+ * and the launch can be captured.  A gather, one thread per pixel: no atomics, deterministic.  Cp: the channels stored per
+ * pixel of gx, channels C .. Cp - 1 are written as 0 (NHWC: Cp = pix_stride; planar: Cp = C); the C4 image layout leaves as
+ * one 16-byte store per pixel.  One launch.  Refused before a launch (-1): a null pointer, rows < 1, C < 1, C > Cp, H W
+ * outside 1 .. 2^20, a stride < 1, gx aliasing an input. */
+int acg_marginal_loss_bwd(const float *d, const int *rank, const float *gscale, int rows, int C, int Cp, int H, int W,
+                          long long row_stride, int pix_stride, long long chan_stride, float *gx, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
