@@ -119,6 +119,49 @@ int acg_wgrad_krowg_launch(const float *x, const float *dy, float *part, const W
 
 extern int g_acg_precision;
 extern int g_acg_conv_impl;
+
+// ---- what packing (conv_pack.hip) and dispatch (conv_api.hip) must agree on, stated once ------------------------------------
+// packed weights are bf16 (hi, and for BF16X3 also lo right behind it) whenever the bf16 matrix pipe is used
+static inline bool use_bf16() { return g_acg_precision != ACG_PREC_F32 && g_acg_conv_impl == ACG_IMPL_MFMA; }
+static inline bool bf16x3_mfma() { return g_acg_precision == ACG_PREC_BF16X3 && g_acg_conv_impl == ACG_IMPL_MFMA; }
+// thin-channel K-flattening (fp32 MFMA kernels): the gathered tensor has <= 4 real channels and K > 1
+// (thin layers keep the fp32-tile thin kernels — loader, LDS tiles, packed weights — in every mode: they beat the padded bf16
+// path; outside the strict fp32 mode their products run as bf16x3, conv_igemm.hip / conv_wgrad.hip X3)
+static inline bool thin_ok(int creal, int K) { return creal >= 1 && creal <= 4 && K > 1 && g_acg_conv_impl == ACG_IMPL_MFMA; }
+// a layer is treated as thin on exactly one side (3->3 convolutions do not occur on this path and stay regular)
+static inline bool thin_in(const acg_conv_desc *d) { return thin_ok(d->Cir, d->K) && !thin_ok(d->Cor, d->K); }
+static inline bool thin_out(const acg_conv_desc *d) { return thin_ok(d->Cor, d->K) && !thin_ok(d->Cir, d->K); }
+// The VALU thin-output kernel (conv_aux.hip) beats the padded 32-column MFMA tile only against the fp32 matrix pipe (1.7 vs
+// 2.9 ms on the 7x7 32->3 head); on the bf16 pipe the MFMA tile wins 2x (0.87 ms in bf16x3).  It pays off up to 64 gathered
+// channels (>= 4 pixels per wave) and needs C/4 lanes per pixel to divide a wave: 16, 32 or 64 stored channels
+static inline bool thin_valu_c(int C) { return !use_bf16() && (C == 16 || C == 32 || C == 64); }
+// Packed weights are laid out on channel counts padded to 16 whatever the stored width of the activation tensors: an image
+// tensor (<= 4 real channels) may be stored with 4 channels ("C4", acg_conv_desc), its layer's weights are packed as before.
+__host__ __device__ static inline int c16(int c) { return (c + 15) / 16 * 16; }
+// K == 3: three more wb slabs behind the nine taps, 9 + kw = w[0][kw] + w[2][kw] (bf16 packings only): what the kernel row that
+// reads a mirrored row uses in the un-padded data gradient of a reflection-padded layer (Geom.unpad)
+__host__ __device__ static inline int wb_slabs(int K) { return K * K + (K == 3 ? 3 : 0); }
+// One packed operand gathers Ck channels and has Cn columns (wf: Ck = Ci, Cn = Co; wb: Ck = Co, Cn = Ci).  Its regular form
+// [slab][Ck/8][ncols_pad(Cn)][8] floats always has room; a second form may sit right behind it (the "tail"):
+//   N-packed   — thin-OUTPUT operands with 32 gathered channels (7x7 32 -> nc head, data gradient of the nc -> 32 stem;
+//                conv_patch.hip conv_patchn_x3): K rows x (K + 3) window columns of 1 KB hi + 1 KB lo, where the 16 MFMA
+//                columns are (4 horizontally adjacent output pixels) x (4 channels);
+//   row-packed — thin-INPUT operands with 32 columns (7x7 nc -> 32 stem forward, data gradient of the 32 -> nc head;
+//                conv_patch.hip conv_thinrow_x3): per kernel row one 32-deep K step = 8 window columns (the eighth zero)
+//                x 4 channels, [row][k-group 4][32 columns][8] bf16 hi + lo = 4 KB per row.
+enum { ACG_TAIL_NONE = 0, ACG_TAIL_NPACK, ACG_TAIL_TROW };
+static inline int pack_tail(int K, int Ck, int Cn)
+{
+    if (K <= 1 || K > 7) return ACG_TAIL_NONE;
+    return c16(Cn) == 16 && c16(Ck) == 32 ? ACG_TAIL_NPACK : (c16(Ck) == 16 && c16(Cn) == 32 ? ACG_TAIL_TROW : ACG_TAIL_NONE);
+}
+static inline size_t pack_tail_elems(int tail, int K)   // floats
+{
+    return tail == ACG_TAIL_NPACK ? (size_t)K * (K + 3) * 512 : (tail == ACG_TAIL_TROW ? (size_t)K * 1024 : 0);
+}
+// element count of the regular form = float offset of the tail (Geom.w_elems)
+static inline size_t wf_regular_elems(int K, int Ci, int Co) { return (size_t)K * K * (c16(Ci) / 8) * acg_ncols_pad(c16(Co)) * 8; }
+static inline size_t wb_regular_elems(int K, int Ci, int Co) { return (size_t)wb_slabs(K) * (c16(Co) / 8) * acg_ncols_pad(c16(Ci)) * 8; }
 int acg_igemm_x3_ws_launch(const float *in, const void *wp, const float *bias, float *out, const Geom &g, const Taps &t,
                            long long n_w_elems, hipStream_t st, float *stats = nullptr);
 bool acg_igemm_uses_ws(const Geom &g);
@@ -161,6 +204,21 @@ bool acg_wgrad_thin_patch_ok(const WGeom &g, const Taps &t, int *K, int *flip);
 int acg_wgrad_thin_patch_tiles(const WGeom &g);
 int acg_wgrad_thin_patch_launch(const float *thin, const float *wide, float *part, const WGeom &g, const Taps &t, hipStream_t st);
 int acg_wgrad_krow_s_launch(const float *x, const float *dy, float *part, const WGeom &g, hipStream_t st);
+
+// conv_aux.hip: the support kernels of the entry points in conv_api.hip
+int acg_thin_out_launch(const float *in, const float *wn, const float *bias, float *out, const Geom &g, const Taps &t, hipStream_t st);
+int acg_dgrad_colfix_launch(const acg_conv_desc *d, const void *dy, const float *wb, long long w_lo_elems, float *colfix, hipStream_t st);
+int acg_reflect_fold_launch(const acg_conv_desc *d, const float *dxp, float *dx, hipStream_t st);
+int acg_reflect_fold_frame_launch(const acg_conv_desc *d, const float *dxp, float *dx, const float *addend, const float *relu_src,
+                                  const unsigned *addend_mask, int out_s16, int relu_s16, hipStream_t st);
+size_t acg_colsum_ws_bytes(long long M, int C);
+int acg_colsum_launch(const float *dy, long long M, int C, int Cr, float *db, float *ws, hipStream_t st, int accumulate);
+int acg_wgrad_reduce_launch(const float *part, int nsplit, int KK, int CiP, int CoP, int Or, int Ir, float *dw, int thin,
+                            int accumulate, const float *bias_part, int Cp, int Cr, float *db, int bias_slots, hipStream_t st);
+// conv_direct.hip: the naive cross-check kernels (ACG_IMPL_DIRECT)
+int acg_direct_fwd_launch(const acg_conv_desc *d, const float *x, const float *wf, const float *bias, float *y, int act, hipStream_t st);
+int acg_direct_dgrad_launch(const acg_conv_desc *d, const float *dy, const float *wb, const float *bias, float *dx, int act, hipStream_t st);
+int acg_direct_wgrad_launch(const acg_conv_desc *d, const float *x, const float *dy, float *dw, int Or, int Ir, int accumulate, hipStream_t st);
 
 #ifdef __HIPCC__
 // bf16x3 operand split of 8 fp32 values: hi = RNE bf16(x), lo = RNE bf16(x - hi), each returned as 8 packed bf16
