@@ -65,6 +65,14 @@ class NormSumsDesc(ctypes.Structure):
                 ("gstride", c_int), ("sign_mask", c_void_p), ("act", c_int), ("part", c_void_p)]
 
 
+WINDOW_MAX = 64
+
+
+class WindowPlan(ctypes.Structure):
+    """acg_window_plan (include/acgan_hip.h)."""
+    _fields_ = [(k, c_int) for k in ("H", "W", "S", "R", "ny", "nx")] + [("oy", c_int * WINDOW_MAX), ("ox", c_int * WINDOW_MAX)]
+
+
 ADAM_MAX_GROUPS = 8
 EMA_MAX_GROUPS = 8
 _P = c_void_p
@@ -176,6 +184,8 @@ SIGNATURES = {
     "acg_marginal_loss_fwd": (c_int, [_P, c_int, _P, c_int, c_int, ctypes.c_longlong, _P, _P, _P, c_size_t, _P]),
     "acg_marginal_loss_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
                                       _P, _P]),
+    "acg_window_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "acg_window_blend": (c_int, [_P, ctypes.POINTER(WindowPlan), _P, c_int, c_int, c_int, _P]),
     "acg_comm_unique_id": (c_int, [_P]),
     "acg_comm_init": (c_int, [ctypes.POINTER(c_void_p), _P, c_int, c_int]),
     "acg_comm_allreduce_mean": (c_int, [_P, _P, c_size_t, _P]),

@@ -4,7 +4,9 @@ per-channel min-max to [-1, 1] -> optional resize -> NHWC->NCHW float32 -> seed-
 AlignedIterator / UnalignedIterator with the reference's batch-count and last-batch-wrap semantics.
 
 Differences: skimage.transform.resize (not installed) is replaced by an anti-aliased bilinear resize (area-averaging
-prefilter when shrinking); Python 3's random.shuffle yields a different permutation than Python 2's for seed 123."""
+prefilter when shrinking); Python 3's random.shuffle yields a different permutation than Python 2's for seed 123.
+Addition: --native_res keeps the stored resolution (load_numpy_data(native_res=True), centre_windows) and window_tables
+draws the random training windows that ops.window_gather cuts on the device."""
 import os
 import random
 
@@ -134,13 +136,57 @@ def split_train_dev(trainA, trainB, shuffle=True):
     return trainA[n:], trainB[n:], trainA[:n], trainB[:n]
 
 
-def load_numpy_data(root, shuffle=True, grid_size=None):
+def load_numpy_data(root, shuffle=True, grid_size=None, native_res=False, centre_eval=True):
+    """native_res (--native_res): the fields keep their stored H x W (no resize; ValueError if an extent is below
+    grid_size, the size of the windows cut from them), and with centre_eval the dev and test sets are cut once to their
+    centre grid_size windows, so the evaluation sees the squares it always saw."""
     def _load(fname):
-        print("Loading %s" % os.path.join(root, fname))
-        return prepare(np.load(os.path.join(root, fname))['data'], grid_size)
+        path = os.path.join(root, fname)
+        print("Loading %s" % path)
+        arr = prepare(np.load(path)['data'], None if native_res else grid_size)
+        if native_res and min(arr.shape[2:]) < grid_size:
+            raise ValueError("--native_res: the fields of %s are %d x %d, below the %d x %d window (--grid_size)"
+                             % (path, arr.shape[2], arr.shape[3], grid_size, grid_size))
+        return arr
     trainA, trainB, testA, testB = _load("trainA.npz"), _load("trainB.npz"), _load("testA.npz"), _load("testB.npz")
     trainA, trainB, devA, devB = split_train_dev(trainA, trainB, shuffle)
+    if native_res and centre_eval:
+        devA, devB, testA, testB = (centre_windows(a, grid_size) for a in (devA, devB, testA, testB))
     return trainA, trainB, devA, devB, testA, testB
+
+
+def centre_windows(arr, size):
+    """(N, C, H, W) -> (N, C, size, size): the central window of every field (origin (H - size) // 2, (W - size) // 2)"""
+    H, W = arr.shape[2:]
+    if H < size or W < size:
+        raise ValueError("fields of %d x %d are below the %d x %d window" % (H, W, size, size))
+    oy, ox = (H - size) // 2, (W - size) // 2
+    return np.ascontiguousarray(arr[:, :, oy:oy + size, ox:ox + size])
+
+
+def window_tables(n, hw_A, hw_B, size, flip=False, paired=False, rng=np.random):
+    """The random training windows of one batch of n samples per side -> (table_A, table_B), (n, 4) int32 rows
+    (src, oy, ox, flip) as ops.window_gather takes them: src = 0 .. n-1, the origin uniform over the positions a
+    size x size window has in an hw = (H, W) field, flip uniform in 0..3 (bit 0 mirrors x, bit 1 mirrors y) or 0.  Drawn
+    from `rng` (np.random: --seed reproduces them).  paired (the --supervised step): ONE draw, both tables the same rows,
+    so A and B stay aligned; it needs fields of one size."""
+    def draw(hw):
+        H, W = hw
+        if H < size or W < size:
+            raise ValueError("fields of %d x %d are below the %d x %d window" % (H, W, size, size))
+        t = np.zeros((n, 4), dtype=np.int32)
+        t[:, 0] = np.arange(n)
+        t[:, 1] = rng.randint(0, H - size + 1, n)
+        t[:, 2] = rng.randint(0, W - size + 1, n)
+        if flip:
+            t[:, 3] = rng.randint(0, 4, n)
+        return t
+    if not paired:
+        return draw(hw_A), draw(hw_B)
+    if tuple(hw_A) != tuple(hw_B):
+        raise ValueError("paired windows need A and B fields of one size (got %s and %s)" % (tuple(hw_A), tuple(hw_B)))
+    t = draw(hw_A)
+    return t, t.copy()
 
 
 def synthetic_data(n, nc_a, nc_b, size, seed=0):

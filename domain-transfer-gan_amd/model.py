@@ -668,6 +668,63 @@ class _Base(object):
                 ops.fss(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
         return out
 
+    def _field_groups(self, who, G, x, copies, C, overlap, chunk, code=None):
+        """What translate_field and translate_field_A share -> (copies*N, C, H, W): every (N, Cin, H, W) field of x, `copies`
+        times in a row, through G in windows of grid_size (ops.window_plan) blended on canvases (ops.window_blend).  Groups
+        hold whole canvases: T = ny*nx windows each, at most chunk // T canvases per pass; canvas k of a group is cut
+        (ops.window_gather) from field k // copies, tile (ky, kx) at row (k*ny + ky)*nx + kx.  code(k0, n): the latent rows
+        of canvases k0 .. k0 + n - 1, one each, repeated here for the T windows of a canvas."""
+        S = int(self.opt.grid_size)
+        if x.dim() != 4 or x.size(2) < S or x.size(3) < S:
+            raise ValueError("%s: fields %s are smaller than the %d x %d window (grid_size)" % (who, tuple(x.shape), S, S))
+        N, _, H, W = x.shape
+        plan = ops.window_plan(H, W, S, S // 4 if overlap is None else overlap)
+        T = plan.ny * plan.nx
+        chunk = ensemble_chunk(self.opt.ngf, S, S) if chunk is None else int(chunk)
+        per = chunk // T
+        if per < 1:
+            raise ValueError("%s: a group of %d images cannot hold the %d windows of one %d x %d field" % (who, chunk, T, H, W))
+        x = x.detach()
+        out = torch.empty((N * copies, C, H, W), device=x.device, dtype=torch.float32)
+        win = [(oy, ox, 0) for oy in plan.oy[:plan.ny] for ox in plan.ox[:plan.nx]]
+        img_in = _starts_with_conv(G.model)
+        with eval_state(G), torch.no_grad():
+            for k0 in range(0, N * copies, per):
+                n = min(per, N * copies - k0)
+                tiles = ops.window_gather(x, [(k // copies,) + w for k in range(k0, k0 + n) for w in win], S, img=img_in)
+                if code is None:
+                    y = G.forward_nhwc(tiles)
+                else:
+                    y = G.forward_nhwc(tiles, as_latent(code(k0, n)).repeat_interleave(T, dim=0))
+                ops.window_blend(y, plan, n, C, out=out[k0:k0 + n])
+        return out
+
+    def translate_field(self, real_A, n_samples=1, z=None, overlap=None, chunk=None):
+        """A -> B on fields of any H x W >= grid_size at their own resolution -> (N, M, C_out, H, W) on the device: every
+        field is cut into overlapping grid_size windows (ops.window_plan; overlap defaults to grid_size // 4), the windows
+        go through netG_A_B as they would in training, and the translations are blended at the seams with a linear ramp
+        (ops.window_blend).  One code per (field, member), shared by all windows of that member: z is (N*M, nlatent, 1, 1) in
+        generate_multi's order, drawn as in plan_ensemble when absent.  chunk: the most windows one generator pass may hold
+        (default ensemble_chunk at the window size); ValueError if one field's windows do not fit, for a field below
+        grid_size, n_samples outside 1..ops.ENSEMBLE_MAX_M and a wrong number of codes.  For H = W = grid_size this is
+        predict_B, bit for bit.  Eval state under no_grad, both restored; nothing is kept, nothing is read back."""
+        M = int(n_samples)
+        if not 1 <= M <= ops.ENSEMBLE_MAX_M:
+            raise ValueError("translate_field: n_samples must lie in 1..%d (got %d)" % (ops.ENSEMBLE_MAX_M, M))
+        N = real_A.size(0)
+        if z is None:
+            z = real_A.new_empty((N * M, self.opt.nlatent, 1, 1)).normal_(0, 1)
+        if z.size(0) != N * M:
+            raise ValueError("translate_field: z holds %d codes for %d fields x %d samples" % (z.size(0), N, M))
+        out = self._field_groups("translate_field", self.netG_A_B, real_A, M, self.opt.output_nc, overlap, chunk,
+                                 code=lambda k0, n: self._z(z[k0:k0 + n]))
+        return out.view(N, M, *out.shape[1:])
+
+    def translate_field_A(self, real_B, overlap=None, chunk=None):
+        """B -> A on fields of any H x W >= grid_size -> (N, C_in, H, W): translate_field's windows and blend through the
+        deterministic netG_B_A; for H = W = grid_size this is predict_A, bit for bit."""
+        return self._field_groups("translate_field_A", self.netG_B_A, real_B, 1, self.opt.input_nc, overlap, chunk)
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)

@@ -1400,6 +1400,95 @@ def ensemble_stats(members_nhwc, target_nhwc, M, C, quantiles, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# windows of native-resolution fields (model.translate_field, train.py --native_res)
+# ----------------------------------------------------------------------------------------------
+WINDOW_MAX = _lib.WINDOW_MAX
+
+
+def _window_axis(extent, S, overlap):
+    """origins of the windows along one axis: one when the extent is S, else ceil((extent - overlap) / (S - overlap)) of
+    them, evenly spread from 0 to extent - S and rounded, so neighbours share at least `overlap` pixels"""
+    if extent == S:
+        return [0]
+    n = -(-(extent - overlap) // (S - overlap))
+    if n > WINDOW_MAX:
+        raise ValueError("window_plan: %d windows of %d along an extent of %d (at most %d)" % (n, S, extent, WINDOW_MAX))
+    return [int(round(k * (extent - S) / (n - 1))) for k in range(n)]
+
+
+def window_plan(H, W, S, overlap):
+    """The separable grid of S x S windows that covers an H x W field -> _lib.WindowPlan (acg_window_plan): H, W, S, the ramp
+    R = max(overlap, 1) of the blend weight, ny, nx and the origins oy[:ny], ox[:nx] (_window_axis).  ValueError for an extent
+    below S, an overlap outside 0..S//2 and more than WINDOW_MAX windows along an axis.  Pure Python, no device work."""
+    H, W, S, overlap = int(H), int(W), int(S), int(overlap)
+    if S < 1 or H < S or W < S:
+        raise ValueError("window_plan: a %d x %d field is smaller than the %d x %d window" % (H, W, S, S))
+    if not 0 <= overlap <= S // 2:
+        raise ValueError("window_plan: overlap must lie in 0..%d (got %d)" % (S // 2, overlap))
+    oy, ox = _window_axis(H, S, overlap), _window_axis(W, S, overlap)
+    plan = _lib.WindowPlan(H=H, W=W, S=S, R=max(overlap, 1), ny=len(oy), nx=len(ox))
+    plan.oy[:len(oy)], plan.ox[:len(ox)] = oy, ox
+    return plan
+
+
+def check_window_table(table_rows, N, H, W, S):
+    """-> the rows (src, oy, ox, flip) as a (T, 4) int32 host tensor; ValueError unless every row has 0 <= src < N, 0 <= oy <= H-S,
+    0 <= ox <= W-S and flip in 0..3 — the kernel does not clamp, this is the only check the rows get"""
+    t = torch.as_tensor(table_rows, dtype=torch.int64, device="cpu").reshape(-1, 4)
+    if t.size(0) < 1:
+        raise ValueError("window table: no rows")
+    lo = t.min(0).values.tolist()
+    hi = t.max(0).values.tolist()
+    if min(lo) < 0 or hi[0] >= N or hi[1] > H - S or hi[2] > W - S or hi[3] > 3:
+        raise ValueError("window table: rows (src, oy, ox, flip) span %s..%s, outside %d fields of %d x %d with windows of %d"
+                         % (lo, hi, N, H, W, S))
+    return t.to(torch.int32).contiguous()
+
+
+def window_gather(fields, table_rows, S, out=None, upload=None, img=True):
+    """acg_window_gather: fields (N, C, H, W) NCHW -> (T, S, S, Cp) NHWC (Cp = cimg(C), or cpad(C) with img=False: ToNHWC's
+    rule), row t the S x S window table_rows[t] =
+    (src, oy, ox, flip) of field src (flip bit 0 mirrors x, bit 1 mirrors y), padding channels zero.  table_rows: a host
+    sequence / array / tensor of T rows, checked here (check_window_table) and uploaded (`upload`: a callable that takes the
+    checked (T, 4) int32 host tensor to the device, e.g. through pinned memory; default a plain copy).  `out`: a tensor to
+    write instead.  One launch, nothing read back."""
+    x = fields.contiguous()
+    _check(x)
+    N, C, H, W = x.shape
+    S = int(S)
+    if S < 1 or H < S or W < S:
+        raise ValueError("window_gather: fields of %d x %d are smaller than the %d x %d window" % (H, W, S, S))
+    tab = check_window_table(table_rows, N, H, W, S)
+    tab = upload(tab) if upload is not None else tab.to(x.device)
+    T, Cp = tab.size(0), cimg(C) if img else cpad(C)
+    if out is None:
+        out = torch.empty((T, S, S, Cp), device=x.device, dtype=torch.float32)
+    _check(out)
+    if tuple(out.shape) != (T, S, S, Cp):
+        raise _lib.AcgError("window_gather: out %s is not %s" % (tuple(out.shape), (T, S, S, Cp)))
+    _lib.call("acg_window_gather", _ptr(x), _ptr(tab), _ptr(out), N, C, H, W, T, S, Cp, _stream())
+    return out
+
+
+def window_blend(tiles, plan, rows, C, out=None):
+    """acg_window_blend: tiles (rows*ny*nx, S, S, Cp) NHWC, tile (ky, kx) of canvas r at row (r*ny + ky)*nx + kx, blended into
+    (rows, C, H, W) NCHW (`out`: such a tensor to write instead, e.g. a slice of a larger one) with the weights of `plan`
+    (window_plan).  The library checks the plan.  One launch, nothing read back."""
+    x = tiles.contiguous()
+    _check(x, out)
+    rows, C = int(rows), int(C)
+    want = (rows * plan.ny * plan.nx, plan.S, plan.S)
+    if x.dim() != 4 or tuple(x.shape[:3]) != want:
+        raise _lib.AcgError("window_blend: tiles %s are not %s x Cp" % (tuple(x.shape), want))
+    if out is None:
+        out = torch.empty((rows, C, plan.H, plan.W), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, C, plan.H, plan.W):
+        raise _lib.AcgError("window_blend: out %s is not %s" % (tuple(out.shape), (rows, C, plan.H, plan.W)))
+    _lib.call("acg_window_blend", _ptr(x), ctypes.byref(plan), _ptr(out), rows, C, x.size(3), _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum), the spectral loss on them and the
 # paired cross-spectra (model.translate_coherence, test.py --metric coherence)
 # ----------------------------------------------------------------------------------------------

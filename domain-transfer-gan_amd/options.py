@@ -2,7 +2,7 @@
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
 (options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
 --step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B, --ema_decay, --ema_eval,
---lambda_marg_A, --lambda_marg_B."""
+--lambda_marg_A, --lambda_marg_B, --native_res, --window_flip."""
 import argparse
 import os
 import pickle
@@ -98,6 +98,11 @@ _T = [
                                   "of the two batches' mean quantile functions, per channel (ops.marginal_loss: every field is "
                                   "sorted); 0: off; needs --grid_size up to 1024"),
     ("lambda_marg_B", float, 0.0, "the same on fake_B against the real B"),
+    ("native_res", "flag", False, "keep the fields at their stored resolution (no resize to --grid_size; both extents must be at "
+                                  "least --grid_size): every training step cuts a fresh random --grid_size window per sample on "
+                                  "the device (ops.window_gather), dev and test are cut once to their centre windows; whole "
+                                  "fields are translated by model.translate_field / test.py --metric translate"),
+    ("window_flip", ("choice", int, [0, 1]), 0, "with --native_res: 1 also mirrors every training window at random in x and y"),
 ]
 
 
@@ -135,6 +140,10 @@ class TrainOptions(object):
         if (opt.lambda_marg_A > 0 or opt.lambda_marg_B > 0) and not 1 <= g <= 1024:
             self.parser.error("--lambda_marg_A / --lambda_marg_B: the marginal loss sorts fields of up to 1024 x 1024 "
                               "(--grid_size %d)" % g)
+        if opt.native_res and opt.synthetic:
+            self.parser.error("--native_res cuts windows from stored fields; --synthetic fields are --grid_size already")
+        if opt.window_flip and not opt.native_res:
+            self.parser.error("--window_flip 1 requires --native_res")
         if not 0.0 <= opt.ema_decay < 1.0:
             self.parser.error("--ema_decay must lie in [0, 1) (got %r)" % opt.ema_decay)
         opt.gpu_ids = [i for i in (int(tok) for tok in opt.gpu_ids.split(",")) if i >= 0]      # options.py:92-97
@@ -163,7 +172,8 @@ class TestOptions(object):
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
     `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
-    --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric)."""
+    --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric);
+    the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -172,7 +182,7 @@ class TestOptions(object):
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
-                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss'])
+                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
         self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss: translations per input (1..64)')
@@ -187,7 +197,9 @@ class TestOptions(object):
         self.parser.add_argument('--fss_windows', type=_fss_windows, default=(1, 3, 5, 9, 17, 33),
                                  help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
                                       '(the cell itself: bias, CSI, base rate) is put in front if absent')
-
+        self.parser.add_argument('--overlap', type=_overlap, default=None,
+                                 help='--metric translate: pixels neighbouring windows share, 0 .. grid_size // 2 '
+                                      '(default: grid_size // 4)')
         self.parser.add_argument('--ema', type=int, choices=[0, 1], default=0,
                                  help='1: every metric runs on the averaged weights the checkpoint holds under ema_<net> '
                                       '(a run trained with --ema_decay); 0: on the live weights')
@@ -201,6 +213,23 @@ def _n_samples(s):
     if not 1 <= v <= 64:
         raise argparse.ArgumentTypeError("--n_samples must lie in 1..64 (got %d)" % v)
     return v
+
+
+def _overlap(s):
+    v = int(s)
+    if v < 0:
+        raise argparse.ArgumentTypeError("--overlap must lie in 0 .. grid_size // 2 (got %d)" % v)
+    return v
+
+
+def check_overlap(overlap, grid_size):
+    """--overlap against the run's grid_size (known only once the saved options are read) -> the overlap in pixels
+    (None: grid_size // 4); ValueError outside 0 .. grid_size // 2"""
+    if overlap is None:
+        return grid_size // 4
+    if not 0 <= overlap <= grid_size // 2:
+        raise ValueError("--overlap must lie in 0 .. grid_size // 2 = %d (got %d)" % (grid_size // 2, overlap))
+    return int(overlap)
 
 
 def _split(name, s, kind, noun):

@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -42,6 +42,17 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               and from the window 1 the frequency bias, the CSI, the observed base rate f0 and the useful scale: the smallest
               listed window with FSS >= 0.5 + f0 / 2 (0: none).  Printed: FSS at the median listed window and the highest
               threshold, the mean over the channels -> <res_dir>/fss.npz.  Any H x W up to 1024.  No plot
+  translate   (new) whole fields at their stored resolution: the data is loaded UNRESIZED, every dev and test field of any
+              H x W >= grid_size is cut into overlapping grid_size windows (--overlap pixels shared by neighbours, default
+              grid_size // 4), translated window by window and blended at the seams (model.translate_field, --n_samples
+              members per field with one code each; model.translate_field_A for B -> A).  Per split, float32:
+              <split>_mean_B, <split>_std_B (over the members, unbiased; 0 for one member), <split>_member0_B and
+              <split>_fake_A, each (N, C, H, W), with n_samples, window, overlap, origins_y, origins_x ->
+              <res_dir>/translate.npz.  Printed: the RMSE of the member mean against the paired B and of fake_A against the
+              paired A.  No plot
+
+A run trained with --native_res (its saved options say so) is scored by every other metric on what it was trained on: the
+centre grid_size windows of the stored fields in place of resized ones.
 
 --ema 1 loads the averaged weights of a run trained with --ema_decay (the checkpoint's ema_<net> entries) into the networks
 instead of the live ones; every metric then runs unchanged.  A checkpoint without them ends the run with a message.
@@ -67,11 +78,11 @@ import numpy as np
 import torch
 
 from . import ops
-from .dataloader import AlignedIterator, UnalignedIterator, load_numpy_data
+from .dataloader import AlignedIterator, UnalignedIterator, centre_windows, load_numpy_data
 from .evaluate import eval_mse_A, eval_ubo_B, one_to_three_channels
 from .model import AugmentedCycleGAN, StochCycleGAN, gauss_reparametrize, kld_std_guss
 from .modules import _starts_with_conv
-from .options import TestOptions
+from .options import TestOptions, check_overlap
 from .train import save_image_grid
 
 NOISE_STDS = (0, 0.1, 0.2, 0.5, 1, 2, 3, 5)      # test.py:101
@@ -414,6 +425,32 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
     return res
 
 
+def eval_translate(dataset, model, n_samples, overlap, use_gpu=True):
+    """whole-field translation of an aligned split at its stored resolution (model.translate_field, translate_field_A), one
+    read per batch -> dict of float32 arrays (N, C, H, W): mean_B and std_B over the members (torch on the canvases; std
+    unbiased, 0 for one member), member0_B, fake_A; and the scalars rmse_mean_B, rmse_A against the paired real fields, pooled
+    over the split in float64"""
+    keys = ('mean_B', 'std_B', 'member0_B', 'fake_A')
+    parts = {k: [] for k in keys}
+    sse, cells = np.zeros(2), np.zeros(2)
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        fake_B = model.translate_field(real_A, n_samples, overlap=overlap)
+        r = dict(mean_B=fake_B.mean(1), std_B=fake_B.std(1) if n_samples > 1 else torch.zeros_like(fake_B[:, 0]),
+                 member0_B=fake_B[:, 0], fake_A=model.translate_field_A(real_B, overlap=overlap))
+        err = torch.stack([(r['mean_B'] - real_B).double().pow(2).sum(), (r['fake_A'] - real_A).double().pow(2).sum()])
+        *maps, err = _read_back([r[k].double() for k in keys] + [err])
+        for k, v in zip(keys, maps):
+            parts[k].append(v.astype(np.float32))
+        sse += err
+        cells += (real_B.numel(), real_A.numel())
+    res = {k: np.concatenate(v) for k, v in parts.items()}
+    res['rmse_mean_B'], res['rmse_A'] = np.sqrt(sse / cells)
+    return res
+
+
 def _chan_mean(v):
     v = np.asarray(v, dtype=np.float64)
     return float(np.nanmean(v)) if np.isfinite(v).any() else float('nan')
@@ -461,7 +498,7 @@ def test_model(argv=None):
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
     for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles', 'fss_quantiles', 'fss_thresholds',
-              'fss_windows', 'ema'):
+              'fss_windows', 'ema', 'overlap'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -480,7 +517,19 @@ def test_model(argv=None):
     opt.res_dir = os.path.join(opt.expr_dir, opt.res_dir)
     os.makedirs(opt.res_dir, exist_ok=True)
 
-    trainA, trainB, devA, devB, testA, testB = load_numpy_data(opt.dataroot, grid_size=getattr(opt, 'grid_size', None))
+    grid_size = getattr(opt, 'grid_size', None)
+    if opt.metric == 'translate':
+        try:
+            opt.overlap = check_overlap(opt.overlap, grid_size)
+        except ValueError as e:
+            raise SystemExit(e.args[0])
+    # whole fields for --metric translate; a --native_res run's other metrics score the centre windows it was trained to
+    # translate; everything else sees fields resized to grid_size
+    native = opt.metric == 'translate' or bool(getattr(opt, 'native_res', False))
+    arrays = load_numpy_data(opt.dataroot, grid_size=grid_size, native_res=native, centre_eval=False)
+    if native and opt.metric != 'translate':
+        arrays = [centre_windows(a, grid_size) for a in arrays]
+    trainA, trainB, devA, devB, testA, testB = arrays
     sub_size = max(int(len(trainA) * 0.2), 1)
     cap = lambda n, b: max(min(b, n), 1)
     train_dataset = UnalignedIterator(trainA[:sub_size], trainB[:sub_size], batch_size=cap(sub_size, 200))
@@ -571,6 +620,20 @@ def test_model(argv=None):
               % (_chan_mean(dev['fss_members_B'][:, t, w]), _chan_mean(test['fss_members_B'][:, t, w]),
                  _chan_mean(test['fss_ens_prob_B'][:, t, w]), _chan_mean(test['fss_ens_mean_B'][:, t, w]),
                  _chan_mean(test['fss_fake_A'][:, t, w]), float(test['useful_scale_members_B'][:, t].mean())))
+    elif opt.metric == 'translate':
+        plan = ops.window_plan(devA.shape[2], devA.shape[3], grid_size, opt.overlap)
+        header = dict(n_samples=np.int64(opt.n_samples), window=np.int64(grid_size), overlap=np.int64(opt.overlap),
+                      origins_y=np.array(plan.oy[:plan.ny], dtype=np.int64), origins_x=np.array(plan.ox[:plan.nx], dtype=np.int64))
+        # batches of at most 8 fields: a batch's canvases of every member stay on the device until they are read
+        small = lambda a, b: AlignedIterator(a, b, batch_size=cap(len(a), 8))
+        rmse = []
+
+        def translated(dataset):          # the file holds the maps; the two scalars are only printed
+            res = eval_translate(dataset, model, opt.n_samples, opt.overlap)
+            rmse.append((res.pop('rmse_mean_B'), res.pop('rmse_A')))
+            return res
+        _eval_splits(opt, 'translate', translated, small(devA, devB), small(testA, testB), header, dtype=np.float32)
+        print("DEV_RMSE_MEAN_B: %.4f, TEST_RMSE_MEAN_B: %.4f, TEST_RMSE_A: %.4f" % (rmse[0][0], rmse[1][0], rmse[1][1]))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

@@ -4,7 +4,8 @@ Same flags (options.py), same `results.txt` line format (train.py:39-45), same a
 nets.txt, results.json, history_mse_A.npy / history_ubo_B.npy, best_mse_A.txt / best_bpp_B.txt, checkpoints
 `latest` / `best_A` / `best_B`, PNG grids under vis_*/ (written by a small built-in PNG encoder: torchvision is not
 required).  Additions: a working --continue_train, --synthetic data, one-process-per-GPU data parallelism
-(`python -m torch.distributed.run --nproc-per-node N -m ...train` shards every batch by rank)."""
+(`python -m torch.distributed.run --nproc-per-node N -m ...train` shards every batch by rank), --native_res (fields at
+their stored resolution, a fresh random --grid_size window per sample and step)."""
 import contextlib
 import itertools
 import json
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import dist as D, ops
-from .dataloader import AlignedIterator, DevicePrefetcher, UnalignedIterator, load_numpy_data, synthetic_data
+from .dataloader import AlignedIterator, DevicePrefetcher, UnalignedIterator, load_numpy_data, synthetic_data, window_tables
 from .evaluate import eval_mse_A, eval_ubo_B, one_to_three_channels
 from .model import AugmentedCycleGAN, DeferredStep, StochCycleGAN
 from .options import TrainOptions, create_sub_dirs
@@ -167,7 +168,7 @@ class Trainer(object):
         if o.synthetic:
             arrays = synthetic_data(o.synthetic, o.input_nc, o.output_nc, o.grid_size, o.seed or 0)
         else:
-            arrays = load_numpy_data(o.dataroot, grid_size=o.grid_size)
+            arrays = load_numpy_data(o.dataroot, grid_size=o.grid_size, native_res=bool(getattr(o, "native_res", False)))
         trainA, trainB, devA, devB, testA, testB = arrays
         self.train_it = UnalignedIterator(trainA, trainB, batch_size=o.batchSize)
         self.test_it = AlignedIterator(testA, testB, batch_size=100)
@@ -252,11 +253,27 @@ class Trainer(object):
             return self.upload(name, t)
         return _cuda(t, self.gpu)
 
+    def _windows(self, name, real_A, real_B, n_full, paired=False):
+        """--native_res: this rank's fields (n, C, H, W) of a batch of n_full -> their random grid_size windows, NCHW as the
+        step takes them.  The tables are drawn on the host for the full batch (dataloader.window_tables; np.random, so
+        --seed reproduces them), sharded like prior_z_B and uploaded like it; paired: one table for both sides.  Two
+        launches per side (ops.window_gather, ops.ToNCHW), before the step and outside its captured graph."""
+        o = self.opt
+        tabs = window_tables(n_full, real_A.shape[2:], real_B.shape[2:], o.grid_size, flip=bool(o.window_flip), paired=paired)
+        out = []
+        for side, x, tab in zip("AB", (real_A, real_B), tabs):
+            tab = self._shard(torch.from_numpy(tab)).clone()
+            tab[:, 0] -= tab[0, 0].clone()                     # src counts inside this rank's shard
+            y = ops.window_gather(x, tab, o.grid_size, upload=lambda t, k="%s_%s" % (name, side): self._to_device(k, t))
+            out.append(ops.ToNCHW.apply(y, x.size(1)))
+        return out
+
     def train_epoch(self, epoch):
         """one pass over the training batches.  Under --defer_scalars a replayed step returns a model.DeferredStep: its
         numbers are read (.result()) only on a step that logs or visualises, before the next step is enqueued (its visuals
         are the graph's static buffers), and at most RUN_AHEAD steps are in flight."""
         o, m = self.opt, self.model
+        native = bool(getattr(o, "native_res", False))        # options saved before the flag existed: off
         seen = 0
         in_flight = []
         for data in self._train_batches():
@@ -270,11 +287,15 @@ class Trainer(object):
             if len(in_flight) >= RUN_AHEAD:
                 in_flight.pop(0).wait()
             prior_z_B = self._to_device('prior_z_B', self._shard(prior_z_B))
+            if native:
+                real_A, real_B = self._windows('win', real_A, real_B, nA)
             out = m.train_instance(real_A, real_B, prior_z_B)
             sup_losses = None
             if self.sup_it is not None:
                 sd = next(self.sup_it)
                 sA, sB = self._to_device('sup_A', self._shard(sd['A'])), self._to_device('sup_B', self._shard(sd['B']))
+                if native:
+                    sA, sB = self._windows('sup_win', sA, sB, sd['A'].size(0), paired=True)
                 sup_losses = m.supervised_train_instance(sA, sB, prior_z_B[:sA.size(0)])
             last = sup_losses if sup_losses is not None else out
             if isinstance(last, DeferredStep):     # completes after everything this iteration enqueued

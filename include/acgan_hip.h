@@ -589,6 +589,32 @@ typedef struct {
 int acg_ema_multi(const acg_ema_group *groups, int ngroups, float decay, int step, const int *step_dev, void *stream);
 int acg_swap_multi(const acg_ema_group *groups, int ngroups, void *stream);
 
+/* ---- windows of native-resolution fields (new, no reference counterpart: the reference resizes every field to one grid,
+ *      dataloader.py:17-35; ops.window_gather / ops.window_blend, model.translate_field, train.py --native_res) ----
+ * acg_window_gather cuts T windows of S x S out of fields (N, C, H, W) NCHW and writes them (T, S, S, Cp) NHWC, Cp the stored
+ *   width (4 for C4 images, else a multiple of 16), channels C..Cp-1 zero: the layout change of acg_nchw_to_nhwc16 fused into
+ *   the cut, an exact copy.  table: T rows of 4 ints in DEVICE memory, 16-byte aligned: src (the field), oy, ox (the window's
+ *   origin), flip (bit 0 mirrors x, bit 1 mirrors y: window pixel (i, j) is field pixel (oy + i', ox + j'), i' = S-1-i resp.
+ *   j' = S-1-j where mirrored).  PRECONDITION for direct callers: every row has 0 <= src < N, 0 <= oy <= H-S,
+ *   0 <= ox <= W-S and 0 <= flip <= 3.  The scalars are checked here; the rows live on the device and are NOT: the kernel
+ *   does not clamp (a clamp would hide a wrong table), a row outside these ranges reads outside `fields`.
+ * acg_window_blend is the inverse for a separable window grid: tiles (rows*ny*nx, S, S, Cp) NHWC, tile (ky, kx) of canvas row r
+ *   at index (r*ny + ky)*nx + kx with its origin at (oy[ky], ox[kx]), blended into canvas (rows, C, H, W) NCHW.  Tile pixel
+ *   (i, j) weighs w(i) w(j), w(i) = min(i+1, S-i, R) / R; a canvas pixel is sum(w v) / sum(w) over the tiles that cover it, in
+ *   the fixed order ky, kx ascending with one lane per canvas pixel (no atomics: a repeat gives the same bits); a pixel under
+ *   exactly ONE tile takes that tile's bits, no multiply and no divide.  The record is host memory, passed to the kernel by
+ *   value.  Refused before a launch (-1): counts outside 1..ACG_WINDOW_MAX, origins not strictly ascending, a first origin
+ *   other than 0, a last one other than H-S (W-S), a gap between neighbours above S, R outside 1..S, S above 4096. ---- */
+#define ACG_WINDOW_MAX 64
+typedef struct {
+    int H, W, S, R; /* canvas extents, window edge, ramp length of the weight */
+    int ny, nx;     /* windows along y and x */
+    int oy[ACG_WINDOW_MAX], ox[ACG_WINDOW_MAX];
+} acg_window_plan;
+int acg_window_gather(const float *fields, const int *table, float *out, int N, int C, int H, int W, int T, int S, int Cp,
+                      void *stream);
+int acg_window_blend(const float *tiles, const acg_window_plan *plan, float *canvas, int rows, int C, int Cp, void *stream);
+
 /* ---- gradient exchange of the data-parallel step (replaces nn.parallel.data_parallel, networks.py:193-197 etc.): one
  *      process per GPU; rank 0 makes an id and ships its ACG_COMM_ID_BYTES to the other ranks by any side channel; every
  *      rank then joins with its current HIP device.  acg_comm_allreduce_mean averages a flat fp32 buffer (a network's
