@@ -175,6 +175,11 @@ SIGNATURES = {
     "acg_cross_spectrum_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "acg_cross_spectrum": (c_int, [_P, _P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
                                    ctypes.c_longlong, c_int, ctypes.c_longlong, _P, _P, c_size_t, _P]),
+    "acg_field_spectrum_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "acg_field_spectrum": (c_int, [_P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, _P, _P, c_size_t, _P]),
+    "acg_field_cross_spectrum_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "acg_field_cross_spectrum": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
+                                         ctypes.c_longlong, c_int, ctypes.c_longlong, _P, _P, c_size_t, _P]),
     "acg_fss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "acg_fss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_longlong,
                         c_int, ctypes.c_longlong, _P, c_int, ctypes.POINTER(c_int), c_int, _P, _P, _P, c_size_t, _P]),

@@ -725,6 +725,31 @@ class _Base(object):
         deterministic netG_B_A; for H = W = grid_size this is predict_A, bit for bit."""
         return self._field_groups("translate_field_A", self.netG_B_A, real_B, 1, self.opt.input_nc, overlap, chunk)
 
+    def translate_field_spectrum(self, real_A, n_samples, real_B, z=None, overlap=None, chunk=None):
+        """translate_coherence for whole fields: the paired cross-spectra (ops.field_cross_spectrum: per elliptical ring the
+        means of Pxx, Pyy and Cxy, x the translation, y the paired whole real_B) of each of n_samples tiled translations of
+        every field (translate_field: z, overlap, chunk and the refusals are its own) and of their per-pixel mean
+        (_ensemble_mean).  Any H x W >= grid_size with both extents in 16 .. 1024; real_B is required and has the fields'
+        H x W.  This is where seams (power at the window pitch) and the blend ramp (lost small-scale variance) show.  Returns
+        device tensors: members (N, M, C, 3, nb) and ens_mean (N, C, 3, nb), nb = min(H, W) // 2 + 1, to be summed over a set
+        of pairs and handed to ops.coherence_summary; Pxx and Pyy are the plain spectra.  For H = W = grid_size a power of two
+        this is translate_coherence, bit for bit.  Nothing is read back to the host."""
+        C = self.opt.output_nc
+        if real_B is None or real_B.dim() != 4 or real_A.dim() != 4 or \
+                tuple(real_B.shape) != (real_A.size(0), C) + tuple(real_A.shape[2:]):
+            raise ValueError("translate_field_spectrum: real_B %s does not pair with real_A %s"
+                             % (None if real_B is None else tuple(real_B.shape), tuple(real_A.shape)))
+        fields = self.translate_field(real_A, n_samples, z=z, overlap=overlap, chunk=chunk)
+        N, M, _, H, W = fields.shape
+        members = fields.view(N * M, C, H, W)
+        real_B = real_B.detach().contiguous()
+        with torch.no_grad():
+            out = dict(members=ops.field_cross_spectrum(members, real_B, C, "nchw", "nchw", x_per_y=M))
+            out["members"] = out["members"].view(N, M, C, 3, -1)
+            mean = _ensemble_mean(ops.ToNHWC.apply(members, True), M, C)
+            out["ens_mean"] = ops.field_cross_spectrum(mean, real_B, C, "nchw", "nchw")
+        return out
+
     def generate_cycle_B_multi(self, real_B, multi_prior_z_B):
         fake_A = self.predict_A(real_B)
         return fake_A, self.netG_A_B.forward(_each_n_times(fake_A, multi_prior_z_B.size(0) // real_B.size(0)), multi_prior_z_B)

@@ -1490,7 +1490,8 @@ def window_blend(tiles, plan, rows, C, out=None):
 
 # ----------------------------------------------------------------------------------------------
 # radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum), the spectral loss on them and the
-# paired cross-spectra (model.translate_coherence, test.py --metric coherence)
+# paired cross-spectra (model.translate_coherence, test.py --metric coherence); both again for whole fields of any H x W
+# (model.translate_field_spectrum, test.py --metric field_spectrum)
 # ----------------------------------------------------------------------------------------------
 SPECTRUM_MIN_S, SPECTRUM_MAX_S = 16, 1024
 
@@ -1641,6 +1642,68 @@ def cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
     ws = workspace(nbytes, slot=2) if nbytes else None
     _lib.call("acg_cross_spectrum", _ptr(x), _ptr(y), rows, x_per_y, C, S, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(out),
               _ptr(ws), nbytes, _stream())
+    return out
+
+
+FIELD_SPECTRUM_MIN, FIELD_SPECTRUM_MAX = 16, 1024
+
+
+def _field_spectrum_size(what, H, W):
+    if not (FIELD_SPECTRUM_MIN <= H <= FIELD_SPECTRUM_MAX and FIELD_SPECTRUM_MIN <= W <= FIELD_SPECTRUM_MAX):
+        raise _lib.AcgError("%s: fields must be H x W with both extents in %d..%d (got %d x %d)"
+                            % (what, FIELD_SPECTRUM_MIN, FIELD_SPECTRUM_MAX, H, W))
+    return int(H), int(W)
+
+
+def field_spectrum_bins(H, W):
+    """the rings of an H x W field: bins 0 .. min(H, W) // 2 -> nb.  Pure Python."""
+    H, W = _field_spectrum_size("field_spectrum_bins", int(H), int(W))
+    return min(H, W) // 2 + 1
+
+
+def field_spectrum(x, C, layout, out=None):
+    """acg_field_spectrum: radial_spectrum for whole fields of any H x W with both extents in 16 .. 1024 -> (rows, C, nb)
+    float32 on the device, nb = min(H, W) // 2 + 1.  P = |fft2(x)|^2 / (H W) averaged over elliptical rings: ring b holds the
+    cells whose radius L sqrt((fy/H)^2 + (fx/W)^2), L = min(H, W), rounds to b ("b cycles per L pixels" along either axis;
+    the integer rule of tests/field_spectrum_ref.py).  Layouts as radial_spectrum takes them.  A length that is no power of
+    two is transformed by Bluestein's chirp-z on the HIP FFT's stages; H = W a power of two gives radial_spectrum's bits.
+    Nothing is read back to the host.  Not differentiable."""
+    x = x.detach().contiguous()
+    rows, C, _, H, W, strides = _field_args(x, C, layout, "field_spectrum")
+    H, W = _field_spectrum_size("field_spectrum", H, W)
+    nb = field_spectrum_bins(H, W)
+    if out is not None and tuple(out.shape) != (rows, C, nb):
+        raise _lib.AcgError("field_spectrum: out %s is not (%d, %d, %d)" % (tuple(out.shape), rows, C, nb))
+    _check(x, out)
+    if out is None:
+        out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
+    nbytes = _lib.query("acg_field_spectrum_workspace_bytes", rows, C, H, W)
+    ws = workspace(nbytes, slot=2) if nbytes else None
+    _lib.call("acg_field_spectrum", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(out), _ptr(ws), nbytes,
+              _stream())
+    return out
+
+
+def field_cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
+    """acg_field_cross_spectrum: cross_spectrum for whole fields of any H x W with both extents in 16 .. 1024 ->
+    (rows, C, 3, nb) float32 on the device: per ring of field_spectrum the means of Pxx, Pyy and Cxy = Re(X conj Y) / (H W).
+    Pairing and layouts as cross_spectrum; Pxx has the bits of field_spectrum(x); H = W a power of two gives
+    cross_spectrum's bits.  The triples go to coherence_summary as cross_spectrum's do.  Not differentiable."""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "field_cross_spectrum")
+    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "field_cross_spectrum")
+    H, W = _field_spectrum_size("field_cross_spectrum", H, W)
+    x_per_y = _check_pairing("field_cross_spectrum", x_per_y, rows, rows, rows_y, (H, W), (Hy, Wy))
+    nb = field_spectrum_bins(H, W)
+    if out is not None and tuple(out.shape) != (rows, C, 3, nb):
+        raise _lib.AcgError("field_cross_spectrum: out %s is not (%d, %d, 3, %d)" % (tuple(out.shape), rows, C, nb))
+    _check(x, y, out)                                              # after the refusals that need no device
+    if out is None:
+        out = torch.empty((rows, C, 3, nb), device=x.device, dtype=torch.float32)
+    nbytes = _lib.query("acg_field_cross_spectrum_workspace_bytes", rows, C, H, W)
+    ws = workspace(nbytes, slot=2) if nbytes else None
+    _lib.call("acg_field_cross_spectrum", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2],
+              _ptr(out), _ptr(ws), nbytes, _stream())
     return out
 
 

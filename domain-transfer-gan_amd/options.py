@@ -173,7 +173,8 @@ class TestOptions(object):
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
     `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
     --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric);
-    the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap."""
+    the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap; the metric
+    `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap)."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -182,10 +183,11 @@ class TestOptions(object):
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
-                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate'])
+                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate',
+                                          'field_spectrum'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
         self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),
@@ -198,7 +200,7 @@ class TestOptions(object):
                                  help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
                                       '(the cell itself: bias, CSI, base rate) is put in front if absent')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
-                                 help='--metric translate: pixels neighbouring windows share, 0 .. grid_size // 2 '
+                                 help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
         self.parser.add_argument('--ema', type=int, choices=[0, 1], default=0,
                                  help='1: every metric runs on the averaged weights the checkpoint holds under ema_<net> '

@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -50,6 +50,19 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               <split>_fake_A, each (N, C, H, W), with n_samples, window, overlap, origins_y, origins_x ->
               <res_dir>/translate.npz.  Printed: the RMSE of the member mean against the paired B and of fake_A against the
               paired A.  No plot
+  field_spectrum (new) spectrum and coherence for those whole fields, in one pass: the data is loaded UNRESIZED as for translate,
+              every dev and test field (any H x W >= grid_size, both extents in 16 .. 1024) is translated by the tiled
+              model.translate_field (--n_samples members, --overlap), and the members and their per-pixel mean are paired with
+              the whole real B, translate_field_A(real B) with the whole real A (model.translate_field_spectrum,
+              ops.field_cross_spectrum: Bluestein's chirp-z on the HIP FFT for lengths that are no powers of two).  Rings are
+              elliptical: ring b holds the cells of radius L sqrt((fy/H)^2 + (fx/W)^2) rounded to b, L = min(H, W), bins
+              0 .. L // 2, "b cycles per L pixels".  The (Pxx, Pyy, Cxy) triples are summed over the split in float64 before
+              anything is divided; they carry both families: psd_real_B, psd_members_B, psd_ens_mean_B, psd_real_A, psd_fake_A
+              (C, nb) with lsd_B, lsd_mean_B, lsd_A as for spectrum, and sums_k, coh_k, r_k, perr_k, k_eff_k for k in members_B,
+              ens_mean_B, fake_A as for coherence, with n_samples, window, overlap, height, width ->
+              <res_dir>/field_spectrum.npz.  Seams put power at the window pitch and its multiples, the blend ramp removes
+              small-scale variance: neither shows in translate's RMSE.  Printed: LSD_B, LSD_A and the channel mean of k_eff
+              of the members.  No plot
 
 A run trained with --native_res (its saved options say so) is scored by every other metric on what it was trained on: the
 centre grid_size windows of the stored fields in place of resized ones.
@@ -351,6 +364,17 @@ def eval_spectrum(dataset, model, n_samples, use_gpu=True):
 COHERENCE_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
 
 
+def _coherence_entries(sums, pairs):
+    """per comparison k of COHERENCE_PAIRS: the summed triples sums_k and ops.coherence_summary of them, perr_k per pair"""
+    res = {}
+    for k in COHERENCE_PAIRS:
+        res['sums_' + k] = sums[k]
+        summary = ops.coherence_summary(sums[k])
+        summary['perr'] = summary['perr'] / pairs[k]
+        res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
+    return res
+
+
 def eval_coherence(dataset, model, n_samples, use_gpu=True):
     """paired cross-spectra on an aligned split, one read of the bin arrays per batch.  A -> B: n_samples members per input
     and their ensemble mean (model.translate_coherence) against the paired real B; B -> A: predict_A against the paired real
@@ -371,13 +395,7 @@ def eval_coherence(dataset, model, n_samples, use_gpu=True):
         for k, v in zip(COHERENCE_PAIRS, _read_back(parts)):
             sums[k] = sums[k] + v.astype(np.float64).sum(0)
             pairs[k] += v.shape[0]
-    res = {}
-    for k in COHERENCE_PAIRS:
-        res['sums_' + k] = sums[k]
-        summary = ops.coherence_summary(sums[k])
-        summary['perr'] = summary['perr'] / pairs[k]
-        res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
-    return res
+    return _coherence_entries(sums, pairs)
 
 
 FSS_PAIRS = ('members_B', 'ens_prob_B', 'ens_mean_B', 'fake_A')
@@ -451,6 +469,40 @@ def eval_translate(dataset, model, n_samples, overlap, use_gpu=True):
     return res
 
 
+def eval_field_spectrum(dataset, model, n_samples, overlap, use_gpu=True):
+    """whole-field cross-spectra of an aligned split at its stored resolution, one read of the bin arrays per batch.  A -> B:
+    n_samples tiled translations per field and their per-pixel mean (model.translate_field_spectrum) against the paired whole
+    real B; B -> A: translate_field_A against the paired whole real A.  The (pxx, pyy, cxy) triples of every comparison are
+    summed over the split (over the members too) in float64 before anything is divided.  -> dict: per comparison k of
+    COHERENCE_PAIRS what eval_coherence gives (sums_k, coh_k, r_k, perr_k, k_eff_k); the split-mean spectra the triples carry,
+    (C, nb) float64: psd_members_B, psd_ens_mean_B, psd_fake_A (pxx) and psd_real_B, psd_real_A (pyy, once per input); and the
+    distances lsd_B, lsd_mean_B, lsd_A of those means"""
+    sums = {k: 0.0 for k in COHERENCE_PAIRS}
+    pairs = {k: 0 for k in COHERENCE_PAIRS}
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        r = model.translate_field_spectrum(real_A, n_samples, real_B, overlap=overlap)
+        fake_A = ops.field_cross_spectrum(model.translate_field_A(real_B, overlap=overlap), real_A, real_A.size(1), "nchw", "nchw")
+        parts = (r['members'].flatten(0, 1), r['ens_mean'], fake_A)
+        for k, v in zip(COHERENCE_PAIRS, _read_back(parts)):
+            sums[k] = sums[k] + v.astype(np.float64).sum(0)
+            pairs[k] += v.shape[0]
+    res = _coherence_entries(sums, pairs)
+    for k in COHERENCE_PAIRS:
+        res['psd_' + k] = sums[k][:, 0] / pairs[k]
+    res['psd_real_B'] = sums['ens_mean_B'][:, 1] / pairs['ens_mean_B']
+    res['psd_real_A'] = sums['fake_A'][:, 1] / pairs['fake_A']
+    res['lsd_B'] = float(log_spectral_distance(res['psd_members_B'], res['psd_real_B']))
+    res['lsd_mean_B'] = float(log_spectral_distance(res['psd_ens_mean_B'], res['psd_real_B']))
+    res['lsd_A'] = float(log_spectral_distance(res['psd_fake_A'], res['psd_real_A']))
+    return res
+
+
+WHOLE_FIELD_METRICS = ('translate', 'field_spectrum')     # load the fields unresized and take --overlap
+
+
 def _chan_mean(v):
     v = np.asarray(v, dtype=np.float64)
     return float(np.nanmean(v)) if np.isfinite(v).any() else float('nan')
@@ -518,16 +570,16 @@ def test_model(argv=None):
     os.makedirs(opt.res_dir, exist_ok=True)
 
     grid_size = getattr(opt, 'grid_size', None)
-    if opt.metric == 'translate':
+    if opt.metric in WHOLE_FIELD_METRICS:
         try:
             opt.overlap = check_overlap(opt.overlap, grid_size)
         except ValueError as e:
             raise SystemExit(e.args[0])
-    # whole fields for --metric translate; a --native_res run's other metrics score the centre windows it was trained to
-    # translate; everything else sees fields resized to grid_size
-    native = opt.metric == 'translate' or bool(getattr(opt, 'native_res', False))
+    # whole fields for --metric translate and field_spectrum; a --native_res run's other metrics score the centre windows it
+    # was trained to translate; everything else sees fields resized to grid_size
+    native = opt.metric in WHOLE_FIELD_METRICS or bool(getattr(opt, 'native_res', False))
     arrays = load_numpy_data(opt.dataroot, grid_size=grid_size, native_res=native, centre_eval=False)
-    if native and opt.metric != 'translate':
+    if native and opt.metric not in WHOLE_FIELD_METRICS:
         arrays = [centre_windows(a, grid_size) for a in arrays]
     trainA, trainB, devA, devB, testA, testB = arrays
     sub_size = max(int(len(trainA) * 0.2), 1)
@@ -634,6 +686,15 @@ def test_model(argv=None):
             return res
         _eval_splits(opt, 'translate', translated, small(devA, devB), small(testA, testB), header, dtype=np.float32)
         print("DEV_RMSE_MEAN_B: %.4f, TEST_RMSE_MEAN_B: %.4f, TEST_RMSE_A: %.4f" % (rmse[0][0], rmse[1][0], rmse[1][1]))
+    elif opt.metric == 'field_spectrum':
+        header = dict(n_samples=np.int64(opt.n_samples), window=np.int64(grid_size), overlap=np.int64(opt.overlap),
+                      height=np.int64(devA.shape[2]), width=np.int64(devA.shape[3]))
+        small = lambda a, b: AlignedIterator(a, b, batch_size=cap(len(a), 8))     # as translate: whole canvases of every member
+        dev, test = _eval_splits(opt, 'field_spectrum', lambda d: eval_field_spectrum(d, model, opt.n_samples, opt.overlap),
+                                 small(devA, devB), small(testA, testB), header)
+        print("DEV_LSD_B: %.4f, TEST_LSD_B: %.4f, DEV_LSD_A: %.4f, TEST_LSD_A: %.4f, DEV_K_EFF_B: %.4f, TEST_K_EFF_B: %.4f"
+              % (dev['lsd_B'], test['lsd_B'], dev['lsd_A'], test['lsd_A'], dev['k_eff_members_B'].mean(),
+                 test['k_eff_members_B'].mean()))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

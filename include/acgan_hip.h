@@ -473,6 +473,28 @@ size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S);
 int acg_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int S, long long x_row_stride,
                        int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                        long long y_chan_stride, float *out, void *workspace, size_t ws_bytes, void *stream);
+/* Whole-field spectra (ops.field_spectrum, ops.field_cross_spectrum, model.translate_field_spectrum, test.py --metric
+ * field_spectrum; tests/field_spectrum_ref.py states the definition): the two above for fields of any H x W with both extents
+ * in 16 .. 1024.  Pixel (h, w) sits at (h W + w) pix_stride; the strides, x_per_y and the outputs' order mean what they mean
+ * above.  F = fft2(x), P = |F|^2 / (H W); with L = min(H, W) and signed wavenumbers (fy, fx) the cell's bin is 0 for
+ * fy = fx = 0, else the largest b with b (b - 1) H^2 W^2 < L^2 (fy^2 W^2 + fx^2 H^2): the radius L sqrt((fy/H)^2 + (fx/W)^2)
+ * rounded to nearest, in int64.  nb = L/2 + 1 bins, psd (rows, C, nb), out (rows, C, 3, nb); the cells beyond are dropped.
+ * H = W = S a power of two is forwarded to acg_radial_spectrum / acg_cross_spectrum: their bits, their workspace.  Otherwise
+ * four launches on the stream: the chirps and transformed filters of the axes that are no power of two into the head of the
+ * workspace (nothing is cached between calls), a row pass (two real rows per complex transform -> half spectra of W/2 + 1
+ * columns), a column pass (-> weighted products per cell) and the ring sums.  A length that is no power of two is Bluestein's
+ * chirp-z on radix-2 Stockham stages of the power of two M >= 2 N - 1 (M <= 2048), the chirp's arguments reduced mod 2 N in
+ * integers; the axes choose independently.  fp32 transform, ring sums in double in a fixed order: deterministic, no float
+ * atomics, the same bits for every layout, and Pxx of a pair has the bits of acg_field_spectrum(x).  acg_last_kernel names the
+ * path and each axis' M.  Refused before any launch with ACG_ERR_INVALID: an extent outside 16 .. 1024, C < 1, rows < 1, a
+ * stride < 1, rows % x_per_y != 0, a null tensor, a workspace off the 16-byte grid; a short workspace: ACG_ERR_WORKSPACE. */
+size_t acg_field_spectrum_workspace_bytes(int rows, int C, int H, int W);
+int acg_field_spectrum(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
+                       float *psd, void *workspace, size_t ws_bytes, void *stream);
+size_t acg_field_cross_spectrum_workspace_bytes(int rows, int C, int H, int W);
+int acg_field_cross_spectrum(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
+                             int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                             long long y_chan_stride, float *out, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- neighbourhood fractions skill scores (ops.fss, model.translate_fss, test.py --metric fss; no reference call site: the
  *      reference has no verification code, tests/fss_ref.py states the definition; Roberts & Lean 2008) ----
