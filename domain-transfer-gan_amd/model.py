@@ -260,7 +260,8 @@ class StepGraph(object):
         # configuration (precision / implementation switch) and the scalar options of the step
         baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
                                                         "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
-                                                        "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B"))
+                                                        "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B",
+                                                        "lambda_ssim_A", "lambda_ssim_B"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -350,10 +351,12 @@ class StepGraph(object):
         return deferred if deferred is not None else self.pending.resolve()
 
 
-def optional_loss_names(spec_on, marg_on):
+def optional_loss_names(spec_on, marg_on, ssim_on=False):
     """the names of the optional loss scalars a step appends to its fixed ones, in the order of its sums: the spectral pair
-    (--lambda_spec_A/B), then the marginal pair (--lambda_marg_A/B), each present when one of its weights is positive"""
-    return (['Spec_A', 'Spec_B'] if spec_on else []) + (['Marg_A', 'Marg_B'] if marg_on else [])
+    (--lambda_spec_A/B), then the marginal pair (--lambda_marg_A/B), then the structural-similarity pair (--lambda_ssim_A/B),
+    each present when one of its weights is positive"""
+    return (['Spec_A', 'Spec_B'] if spec_on else []) + (['Marg_A', 'Marg_B'] if marg_on else []) + \
+           (['Ssim_A', 'Ssim_B'] if ssim_on else [])
 
 
 class _Base(object):
@@ -374,6 +377,9 @@ class _Base(object):
 
     def _marg_lambdas(self):
         return _Base._lambda_pair(self, 'marg')
+
+    def _ssim_lambdas(self):
+        return _Base._lambda_pair(self, 'ssim')
 
     def _optional_terms(self, loss, lams, fake_A, A, fake_B, B):
         """An optional loss family on the first-pass outputs against the real batches (`loss(fake, real, C, "nhwc")` on the
@@ -404,6 +410,12 @@ class _Base(object):
         """Marg_A, Marg_B (ops.marginal_loss: the distance of the two batches' mean quantile functions) under
         --lambda_marg_A/B, as _optional_terms gives them"""
         return _Base._optional_terms(self, ops.marginal_loss, self._marg_lambdas(), fake_A, A, fake_B, B)
+
+    def _ssim_terms(self, rec_A, A, rec_B, B):
+        """Ssim_A, Ssim_B (ops.ssim_loss: 1 - the mean structural similarity) under --lambda_ssim_A/B, as _optional_terms gives
+        them, of the pairs a step has: the CYCLE reconstructions against their real batches in an unpaired step, the
+        predictions against their paired fields in the paired one"""
+        return _Base._optional_terms(self, ops.ssim_loss, self._ssim_lambdas(), rec_A, A, rec_B, B)
 
     def _nchw(self, x, C):
         return ops.ToNCHW.apply(x, C).detach()
@@ -634,6 +646,24 @@ class _Base(object):
                 b = real_B[g0:g0 + n]
                 ops.cross_spectrum(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 3, nb))
                 ops.cross_spectrum(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
+        return out
+
+    def translate_ssim(self, real_A, n_samples, real_B, z=None, chunk=None):
+        """The local structure of A -> B: the structural similarity (ops.ssim: per channel the mean S and the mean
+        contrast-structure factor cs, x the translation, y the paired real_B) of each of n_samples translations of every input,
+        one truth per M members, and of their per-pixel mean (_ensemble_mean): the mean of an ensemble is smoother than any
+        member, so it scores a higher luminance term and a lower cs.  z, chunk and the refusals: plan_ensemble, real_B
+        required; the members: ensemble_groups.  11 <= H, W <= 1024.  Returns device tensors: members (N, M, C, 2) and
+        ens_mean (N, C, 2).  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_ssim", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
+        f = dict(device=real_A.device, dtype=torch.float32)
+        out = dict(members=torch.empty((N, M, C, 2), **f), ens_mean=torch.empty((N, C, 2), **f))
+        real_B = real_B.detach().contiguous()
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                b = real_B[g0:g0 + n]
+                ops.ssim(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 2))
+                ops.ssim(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
         return out
 
     def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
@@ -958,6 +988,9 @@ class StochCycleGAN(_Base):
             marg = self._marginal_terms(fake_A, A, fake_B, B)
             if marg is not None:
                 loss_G = loss_G + marg[2]
+            ssim = self._ssim_terms(rec_A, A, rec_B, B)
+            if ssim is not None:
+                loss_G = loss_G + ssim[2]
             self.optimizer_G.zero_grad()
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_D_B, loss_G_B, loss_cycle_B,
                     m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
@@ -965,6 +998,8 @@ class StochCycleGAN(_Base):
                 sums += [spec[0], spec[1]]
             if marg is not None:
                 sums += [marg[0], marg[1]]
+            if ssim is not None:
+                sums += [ssim[0], ssim[1]]
             ex_G = self._backward(loss_G, "stoch.G", [self.f_G_B_A, self.f_G_A_B], tail=(self.f_G_A_B, sums))
         finally:
             self.f_D_A.set_requires_grad(True); self.f_D_B.set_requires_grad(True)
@@ -973,7 +1008,7 @@ class StochCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + \
-                optional_loss_names(spec is not None, marg is not None) + \
+                optional_loss_names(spec is not None, marg is not None, ssim is not None) + \
                 ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_D_B, ss_D_A])
         visuals = OrderedDict([('real_A', real_A.detach()), ('fake_B', self._nchw(fake_B, nB)),
@@ -1212,6 +1247,9 @@ class AugmentedCycleGAN(_Base):
             marg = self._marginal_terms(fake_A, A, fake_B, B)
             if marg is not None:
                 loss_G = loss_G + marg[2]
+            ssim = self._ssim_terms(rec_A, A, rec_B, B)
+            if ssim is not None:
+                loss_G = loss_G + ssim[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             mu_v, lv_v = mu_rB.detach()[:, :nl], lv_rB.detach()[:, :nl]
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_cycle_z_B, kld_z_B, loss_D_B, loss_G_B, loss_cycle_B,
@@ -1220,6 +1258,8 @@ class AugmentedCycleGAN(_Base):
                 sums += [spec[0], spec[1]]
             if marg is not None:
                 sums += [marg[0], marg[1]]
+            if ssim is not None:
+                sums += [ssim[0], ssim[1]]
             mins, maxs = [mu_v.min(), lv_v.min()], [mu_v.max(), lv_v.max()]
             # completion order of the G backward: E_B (its first call is the last of the three first-pass networks to have
             # been built), then G_B_A, then G_A_B — which therefore carries the scalar tail
@@ -1235,7 +1275,7 @@ class AugmentedCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B',
-                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + optional_loss_names(spec is not None, marg is not None) + [
+                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + optional_loss_names(spec is not None, marg is not None, ssim is not None) + [
                  'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_B', 'gnorm_D_z_B', 'gnorm_D_A',
                  'mu_min', 'logvar_min', 'mu_max', 'logvar_max']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, mins, maxs,
@@ -1294,8 +1334,13 @@ class AugmentedCycleGAN(_Base):
                 loss_G = loss_G + kld_z_B * o.lambda_z_B
             if o.z_gan and not o.stoch_enc:
                 loss_G = loss_G + loss_G_z_B
+            ssim = self._ssim_terms(pred_A, A, pred_B, B)
+            if ssim is not None:
+                loss_G = loss_G + ssim[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             sums = [loss_sup_A, loss_sup_B, kld_z_B, loss_D_z_B]
+            if ssim is not None:
+                sums += [ssim[0], ssim[1]]
             # backward order: G_B_A (built last), G_A_B, then the encoder behind post_z
             ex_G = self._backward(loss_G, "sup.G", [self.f_G_B_A, self.f_G_A_B, self.f_E_B], tail=(self.f_E_B, sums))
         finally:
@@ -1304,11 +1349,13 @@ class AugmentedCycleGAN(_Base):
         (ss_G_B_A,) = self.optimizer_G_A.clip_and_step(o.max_gnorm)
         self._wait(ex_G, self.f_G_A_B, self.f_E_B)
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
-        names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B', 'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
+        n_loss = len(sums)
+        names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B'] + (['S_ssim_A', 'S_ssim_B'] if ssim is not None else []) + \
+                ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
         vals = self._scalars(ex_G, self.f_E_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_E, ss_D_z])
 
         def finish(vals):
-            for k in names[4:]:
+            for k in names[n_loss:]:
                 vals[k] = math.sqrt(max(vals[k], 0.0))
             return vals                                                                         # model.py:596-604
         return self._report(vals, finish)

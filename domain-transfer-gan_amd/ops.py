@@ -1810,6 +1810,101 @@ def marginal_loss(x, y, C, layout):
 
 
 # ----------------------------------------------------------------------------------------------
+# structural similarity (model._ssim_terms, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, test.py --metric ssim)
+# ----------------------------------------------------------------------------------------------
+SSIM_WINDOW, SSIM_MAX_HW = 11, 1024
+
+
+def _ssim_size(what, H, W):
+    if not (SSIM_WINDOW <= H <= SSIM_MAX_HW and SSIM_WINDOW <= W <= SSIM_MAX_HW):
+        raise _lib.AcgError("%s: fields must be H x W with %d <= H, W <= %d (got %d x %d)" % (what, SSIM_WINDOW, SSIM_MAX_HW, H, W))
+    return int(H), int(W)
+
+
+def _ssim_range(what, data_range):
+    L = float(data_range)
+    if not 0.0 < L < float("inf"):
+        raise _lib.AcgError("%s: data_range must be positive and finite (got %r)" % (what, data_range))
+    return L
+
+
+def _ssim_call(x, y, sizes, sx, sy, x_per_y, L, out, maps):
+    rows, C, H, W = sizes
+    nbytes = _lib.query("acg_ssim_workspace_bytes", rows, C, H, W)
+    ws = workspace(nbytes, slot=2)
+    _lib.call("acg_ssim", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], ctypes.c_float(L),
+              _ptr(out), _ptr(maps), _ptr(ws), nbytes, _stream())
+
+
+def ssim(x, y, C, layout_x, layout_y, x_per_y=1, data_range=2.0, out=None):
+    """acg_ssim: the structural similarity of the C valid channels of x against y -> (rows, C, 2) float32 on the device: per
+    (row, channel) the mean of S and the mean of the contrast-structure factor cs over the (H - 10) x (W - 10) valid positions
+    of the separable 11 x 11 Gaussian window, sigma 1.5 (Wang et al. 2004; C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range, 2
+    for fields in [-1, 1]; tests/ssim_ref.py).  Row r of x pairs with row r / x_per_y of y.  Each operand has its own layout
+    ("nhwc" or "nchw", as radial_spectrum takes them; padded channels never reach a result).  11 <= H, W <= 1024.  Two
+    launches, the same bits for every layout; nothing is read back to the host.  Not differentiable (ssim_loss is)."""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "ssim")
+    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "ssim")
+    H, W = _ssim_size("ssim", H, W)
+    x_per_y = _check_pairing("ssim", x_per_y, rows, rows, rows_y, (H, W), (Hy, Wy))
+    L = _ssim_range("ssim", data_range)
+    if out is not None and (tuple(out.shape) != (rows, C, 2) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise _lib.AcgError("ssim: out %s %s is not a contiguous float32 (%d, %d, 2)" % (tuple(out.shape), out.dtype, rows, C))
+    _check(x, y, out)                                              # after the refusals that need no device
+    if out is None:
+        out = torch.empty((rows, C, 2), device=x.device, dtype=torch.float32)
+    _ssim_call(x, y, (rows, C, H, W), sx, sy, x_per_y, L, out, None)
+    return out
+
+
+class SsimLoss(torch.autograd.Function):
+    """ssim_loss with its data gradient in x: forward acg_ssim (storing the derivative maps a, b, c of every window position
+    only when x needs a gradient), backward acg_ssim_bwd: the maps through the window once more and the point-wise combine
+    with x and y, scaled by the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, C, layout, data_range):
+        x, y = x.detach().contiguous(), y.detach().contiguous()
+        rows, C, Cp, H, W, strides = _field_args(x, C, layout, "ssim_loss")
+        rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout, "ssim_loss")
+        H, W = _ssim_size("ssim_loss", H, W)
+        _check_pairing("ssim_loss", 1, 1, rows, rows_y, (H, W), (Hy, Wy))
+        L = _ssim_range("ssim_loss", data_range)
+        _check(x, y)
+        out = torch.empty((rows, C, 2), device=x.device, dtype=torch.float32)
+        maps = None
+        if ctx.needs_input_grad[0]:
+            maps = torch.empty((3, rows, C, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1), device=x.device, dtype=torch.float32)
+        _ssim_call(x, y, (rows, C, H, W), strides, sy, 1, L, out, maps)
+        ctx.cfg = (rows, C, Cp if layout == "nhwc" else C, H, W, strides, sy)
+        ctx.has_maps = maps is not None
+        if maps is not None:
+            ctx.save_for_backward(maps, x, y)
+        return 1.0 - out[:, :, 0].mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        maps, x, y = ctx.saved_tensors
+        rows, C, Cp, H, W, sx, sy = ctx.cfg
+        g = g.detach().to(torch.float32).contiguous()
+        gx = torch.empty_like(x)
+        _lib.call("acg_ssim_bwd", _ptr(maps), _ptr(x), _ptr(y), _ptr(g), rows, C, Cp, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2],
+                  _ptr(gx), _stream())
+        return gx, None, None, None, None
+
+
+def ssim_loss(x, y, C, layout, data_range=2.0):
+    """1 - the mean over the rows and the C valid channels of ssim's mean S -> device scalar, differentiable in x (y is
+    detached).  x and y share the layout and pair row by row.  With a = dS/d mu_x (total), b = dS/dE[x^2], c = dS/dE[xy] per
+    window position, d loss / d x(q) = -((w * a)(q) + 2 x(q) (w * b)(q) + y(q) (w * c)(q)) / (rows C (H - 10) (W - 10)), * the
+    full correlation with the window: gathers, deterministic.  NHWC: the padded channels of the gradient are 0.  No host
+    synchronisation.  Under torch.no_grad(), or for an x that needs no gradient, the derivative maps are neither computed nor
+    allocated."""
+    return SsimLoss.apply(x if torch.is_grad_enabled() else x.detach(), y, C, layout, data_range)
+
+
+# ----------------------------------------------------------------------------------------------
 # neighbourhood fractions skill scores (model.translate_fss, test.py --metric fss)
 # ----------------------------------------------------------------------------------------------
 FSS_MAX_HW, FSS_MAX_T, FSS_MAX_NW, FSS_MAX_M = 1024, 8, 8, 64

@@ -98,6 +98,10 @@ _T = [
                                   "of the two batches' mean quantile functions, per channel (ops.marginal_loss: every field is "
                                   "sorted); 0: off; needs --grid_size up to 1024"),
     ("lambda_marg_B", float, 0.0, "the same on fake_B against the real B"),
+    ("lambda_ssim_A", float, 0.0, "weight of the structural-similarity loss 1 - SSIM (ops.ssim_loss: 11 x 11 Gaussian window, "
+                                  "sigma 1.5, data range 2) on the cycle reconstruction rec_A against the real A, and with "
+                                  "--supervised on the paired prediction of A; 0: off; needs 11 <= --grid_size <= 1024"),
+    ("lambda_ssim_B", float, 0.0, "the same on rec_B (and the paired prediction of B) against the real B"),
     ("native_res", "flag", False, "keep the fields at their stored resolution (no resize to --grid_size; both extents must be at "
                                   "least --grid_size): every training step cuts a fresh random --grid_size window per sample on "
                                   "the device (ops.window_gather), dev and test are cut once to their centre windows; whole "
@@ -140,6 +144,12 @@ class TrainOptions(object):
         if (opt.lambda_marg_A > 0 or opt.lambda_marg_B > 0) and not 1 <= g <= 1024:
             self.parser.error("--lambda_marg_A / --lambda_marg_B: the marginal loss sorts fields of up to 1024 x 1024 "
                               "(--grid_size %d)" % g)
+        if opt.lambda_ssim_A < 0 or opt.lambda_ssim_B < 0:
+            self.parser.error("--lambda_ssim_A / --lambda_ssim_B must not be negative (got %r, %r)"
+                              % (opt.lambda_ssim_A, opt.lambda_ssim_B))
+        if (opt.lambda_ssim_A > 0 or opt.lambda_ssim_B > 0) and not 11 <= g <= 1024:
+            self.parser.error("--lambda_ssim_A / --lambda_ssim_B: the structural similarity slides an 11 x 11 window over "
+                              "fields of up to 1024 x 1024 (--grid_size %d)" % g)
         if opt.native_res and opt.synthetic:
             self.parser.error("--native_res cuts windows from stored fields; --synthetic fields are --grid_size already")
         if opt.window_flip and not opt.native_res:
@@ -174,7 +184,8 @@ class TestOptions(object):
     `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
     --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric);
     the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap; the metric
-    `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap)."""
+    `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap); the metric `ssim`
+    (structural similarity of the paired translations, reuses --n_samples)."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -184,10 +195,10 @@ class TestOptions(object):
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
                                  choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate',
-                                          'field_spectrum'])
+                                          'field_spectrum', 'ssim'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
         self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),

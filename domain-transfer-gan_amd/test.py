@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum|ssim
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -63,6 +63,14 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               <res_dir>/field_spectrum.npz.  Seams put power at the window pitch and its multiples, the blend ramp removes
               small-scale variance: neither shows in translate's RMSE.  Printed: LSD_B, LSD_A and the channel mean of k_eff
               of the members.  No plot
+  ssim        (new) the local structure: the structural similarity (Wang et al. 2004; 11 x 11 Gaussian window, sigma 1.5,
+              data range 2, valid positions; ops.ssim, HIP) on the aligned dev and test pairs, of the --n_samples translations
+              A -> B (members_B) and of their per-pixel mean (ens_mean_B) (model.translate_ssim) against the paired B, and
+              of B -> A (fake_A) against the paired A.  Per comparison k, float64: ssim_k and cs_k (C,), the split means of
+              the mean S and of the mean contrast-structure factor cs, and ssim_k_per_input, cs_k_per_input (N, C), the
+              members averaged per input -> <res_dir>/ssim.npz.  The mean of an ensemble is smoother than its members: a
+              higher luminance term, a lower cs; the file shows both.  Printed: the channel means.  11 <= H, W <= 1024.
+              No plot
 
 A run trained with --native_res (its saved options say so) is scored by every other metric on what it was trained on: the
 centre grid_size windows of the stored fields in place of resized ones.
@@ -398,6 +406,34 @@ def eval_coherence(dataset, model, n_samples, use_gpu=True):
     return _coherence_entries(sums, pairs)
 
 
+SSIM_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
+
+
+def eval_ssim(dataset, model, n_samples, use_gpu=True):
+    """structural similarity on an aligned split, one read of the (S, cs) pairs per batch.  A -> B: n_samples members per
+    input and their ensemble mean (model.translate_ssim) against the paired real B; B -> A: predict_A against the paired real
+    A.  -> dict, per comparison k of SSIM_PAIRS, float64: ssim_k, cs_k (C,), the means over the split (and the members), and
+    ssim_k_per_input, cs_k_per_input (N, C), the members averaged per input"""
+    parts = {k: [] for k in SSIM_PAIRS}
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        r = model.translate_ssim(real_A, n_samples, real_B)
+        with torch.no_grad():
+            fake_A = ops.ssim(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw")
+        got = _read_back((r['members'], r['ens_mean'], fake_A))
+        parts['members_B'].append(got[0].astype(np.float64).mean(1))
+        parts['ens_mean_B'].append(got[1].astype(np.float64))
+        parts['fake_A'].append(got[2].astype(np.float64))
+    res = {}
+    for k in SSIM_PAIRS:
+        v = np.concatenate(parts[k])                               # (N, C, 2)
+        res['ssim_' + k], res['cs_' + k] = v[..., 0].mean(0), v[..., 1].mean(0)
+        res['ssim_%s_per_input' % k], res['cs_%s_per_input' % k] = v[..., 0], v[..., 1]
+    return res
+
+
 FSS_PAIRS = ('members_B', 'ens_prob_B', 'ens_mean_B', 'fake_A')
 
 
@@ -695,6 +731,14 @@ def test_model(argv=None):
         print("DEV_LSD_B: %.4f, TEST_LSD_B: %.4f, DEV_LSD_A: %.4f, TEST_LSD_A: %.4f, DEV_K_EFF_B: %.4f, TEST_K_EFF_B: %.4f"
               % (dev['lsd_B'], test['lsd_B'], dev['lsd_A'], test['lsd_A'], dev['k_eff_members_B'].mean(),
                  test['k_eff_members_B'].mean()))
+    elif opt.metric == 'ssim':
+        dev, test = _eval_splits(opt, 'ssim', lambda d: eval_ssim(d, model, opt.n_samples), dev_dataset, test_dataset,
+                                 dict(n_samples=np.int64(opt.n_samples)), dtype=np.float64)
+        print("DEV_SSIM_B: %.4f, TEST_SSIM_B: %.4f, TEST_CS_B: %.4f, TEST_SSIM_MEAN_B: %.4f, TEST_CS_MEAN_B: %.4f, "
+              "TEST_SSIM_A: %.4f, TEST_CS_A: %.4f"
+              % (dev['ssim_members_B'].mean(), test['ssim_members_B'].mean(), test['cs_members_B'].mean(),
+                 test['ssim_ens_mean_B'].mean(), test['cs_ens_mean_B'].mean(), test['ssim_fake_A'].mean(),
+                 test['cs_fake_A'].mean()))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

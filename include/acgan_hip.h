@@ -568,6 +568,42 @@ int acg_marginal_loss_fwd(const float *sx, int rows_x, const float *sy, int rows
 int acg_marginal_loss_bwd(const float *d, const int *rank, const float *gscale, int rows, int C, int Cp, int H, int W,
                           long long row_stride, int pix_stride, long long chan_stride, float *gx, void *stream);
 
+/* ---- structural similarity (ops.ssim, ops.ssim_loss, --lambda_ssim_A / --lambda_ssim_B, test.py --metric ssim; no reference
+ *      call site: the reference compares pixels by L1 alone, tests/ssim_ref.py states the definition; Wang et al. 2004) ----
+ * x: rows x C fields of H x W fp32 pixels, y: rows / x_per_y x C paired fields; row r of x pairs with row r / x_per_y of y
+ * (x_per_y ensemble members share one truth).  The strides (in floats) mean what they mean in acg_cross_spectrum: NHWC with
+ * Cp stored channels is (H W Cp, Cp, 1) - padded channels never reach a result - and planar NCHW is (C H W, 1, H W); each
+ * operand has its own.  w: the separable 11 x 11 Gaussian, sigma = 1.5, each axis normalised to sum 1.  For every window
+ * position p of the (H - 10) x (W - 10) 'valid' region (the window covers pixels p .. p + 10 on both axes):
+ *   mu_x = sum w x, mu_y = sum w y, s_x = sum w x^2 - mu_x^2, s_y = sum w y^2 - mu_y^2, s_xy = sum w x y - mu_x mu_y,
+ *   A1 = 2 mu_x mu_y + C1, A2 = 2 s_xy + C2, B1 = mu_x^2 + mu_y^2 + C1, B2 = s_x + s_y + C2,
+ *   C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range (2 for fields in [-1, 1]),
+ *   S(p) = A1 A2 / (B1 B2), cs(p) = A2 / B2 (the contrast-structure factor); no clamping of the variances.
+ * out (rows, C, 2): the mean of S and the mean of cs over the valid region.  11 <= H, W <= 1024.
+ * dmaps (or NULL): 3 planes of (rows, C, H - 10, W - 10), fully written: a = dS/d mu_x (total: 2 mu_y A2 / (B1 B2) -
+ * 2 mu_x S / B1 - c mu_y - 2 b mu_x), b = dS/dE[x^2] = -S / B2, c = dS/dE[xy] = 2 A1 / (B1 B2): what acg_ssim_bwd reads.
+ * fp32 per window position, the moments taken about a per-tile pivot (x at the tile's first pixel; variances are
+ * shift-invariant, the means get it back), the sums over positions in double: per tile of 32 x 16 positions into the
+ * workspace (acg_ssim_workspace_bytes = 16 rows C tiles, 16-byte aligned), then one wave per (row, channel) in a fixed order.
+ * Two launches, no atomics, nothing read back; the same bits on every run and for every layout.  Refused before a launch
+ * (-1, acg_last_error starts with "acg_ssim"): a null x, y or out, rows < 1, C < 1, an extent outside 11 .. 1024, a stride
+ * < 1, rows % x_per_y != 0, data_range <= 0 or not finite, aliasing outputs, a misaligned workspace; a short workspace: -2.
+ * The size query is 0 for a refused size. */
+size_t acg_ssim_workspace_bytes(int rows, int C, int H, int W);
+int acg_ssim(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride, int x_pix_stride,
+             long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, float data_range,
+             float *out, float *dmaps, void *workspace, size_t ws_bytes, void *stream);
+/* The data gradient of loss = 1 - mean over rows and channels of the mean S, rows of x and y pairing one to one:
+ * gx(q) = -g[0] / (rows C (H - 10) (W - 10)) ((w * a)(q) + 2 x(q) (w * b)(q) + y(q) (w * c)(q)), * the full correlation of
+ * a map (zero outside the valid region) with the window, the result H x W.  g: the upstream gradient, one float on the
+ * device.  gx is written in x's layout; Cp: the channels stored per pixel of gx, channels C .. Cp - 1 are written as 0
+ * (NHWC: Cp = pix_stride; planar: Cp = C).  One workgroup per tile of 32 x 16 pixels, a gather: no atomics, deterministic,
+ * the same bits for every layout.  One launch.  Refused before a launch (-1): a null pointer, rows < 1, C < 1, C > Cp, an
+ * extent outside 11 .. 1024, a stride < 1, gx aliasing an input. */
+int acg_ssim_bwd(const float *dmaps, const float *x, const float *y, const float *g, int rows, int C, int Cp, int H, int W,
+                 long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                 long long y_chan_stride, float *gx, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
