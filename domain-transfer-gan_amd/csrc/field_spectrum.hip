@@ -28,6 +28,8 @@
 #include <math.h>
 #include <stdint.h>
 #include "common.h"
+#include "field.h"
+#include "spectrum_shared.h"
 
 #define FS_MIN 16
 #define FS_MAX 1024
@@ -52,17 +54,6 @@ __device__ __forceinline__ float2 fs_cmul(float2 a, float2 b)
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
 __device__ __forceinline__ float fs_dot2(float a, float b, float c, float d) { return fmaf(a, b, c * d); }
-
-// tw[Ns + k] = exp(-i pi k / Ns), 0 <= k < Ns, Ns = 1, 2, .. M/2: exact arguments
-__device__ __forceinline__ void fs_twiddles(float2 *tw, int M)
-{
-    for (int m = threadIdx.x + 1; m < M; m += blockDim.x) {
-        const int Ns = 1 << (31 - __clz(m)), k = m - Ns;
-        float s, c;
-        sincospif(-(float)k / (float)Ns, &s, &c);
-        tw[m] = make_float2(c, s);
-    }
-}
 
 // the M-point transform of a (M a power of two), radix-2 Stockham autosort between a and b; returns the buffer of the result
 __device__ __forceinline__ float2 *fs_fft(float2 *a, float2 *b, const float2 *tw, int M)
@@ -111,18 +102,6 @@ struct FsAxis {
     int N, M;
     long long chirp, filt;                                         // in float2 from the workspace's start
 };
-// one operand: where its fields lie; c4: a pixel's channels are one aligned 16-byte load
-struct FsField {
-    const float *x;
-    long long row, chan;
-    int pix, c4;
-};
-template <int NF>
-struct FsSrc {
-    FsField f[NF];
-    int C, x_per_y;
-};
-
 // blockIdx.x: the axis (0: W, 1: H).  Nothing to do for a power of two.
 __global__ __launch_bounds__(FS_THREADS) void field_spectrum_setup_kernel(FsAxis ax0, FsAxis ax1, float2 *__restrict__ head)
 {
@@ -132,7 +111,7 @@ __global__ __launch_bounds__(FS_THREADS) void field_spectrum_setup_kernel(FsAxis
     if (M == N) return;
     float2 *a = fs_lds, *b = a + M, *tw = b + M;
     float2 *chirp = head + ax.chirp, *filt = head + ax.filt;
-    fs_twiddles(tw, M);
+    spec_twiddles(tw, M);
     for (int n = threadIdx.x; n < M; n += blockDim.x) a[n] = make_float2(0.f, 0.f);
     __syncthreads();
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
@@ -150,31 +129,27 @@ __global__ __launch_bounds__(FS_THREADS) void field_spectrum_setup_kernel(FsAxis
     for (int k = threadIdx.x; k < M; k += blockDim.x) filt[k] = make_float2(r[k].x * inv, r[k].y * inv);
 }
 
-__device__ __forceinline__ float fs_pick(float4 v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
 // blockIdx.x: the field or pair p; blockIdx.y: operand i and row pair q.  half: [p][i][h][W/2 + 1]
 template <int NF>
-__global__ __launch_bounds__(FS_THREADS) void field_spectrum_rows_kernel(FsSrc<NF> src, int H, FsAxis ax, const float2 *__restrict__ head,
+__global__ __launch_bounds__(FS_THREADS) void field_spectrum_rows_kernel(FieldSrc<NF> src, int H, FsAxis ax, const float2 *__restrict__ head,
                                                                          float2 *__restrict__ half)
 {
     extern __shared__ __attribute__((aligned(16))) float2 fs_lds[];
     const int W = ax.N, M = ax.M, WH = W / 2 + 1, RP = (H + 1) / 2;
     const int p = blockIdx.x, i = NF == 1 ? 0 : blockIdx.y / RP, q = blockIdx.y - i * RP;
     float2 *a = fs_lds, *b = a + M, *tw = b + M;
-    const FsField &f = src.f[i];
-    int row = p / src.C;
-    const int c = p - row * src.C;
-    if (i == 1) row /= src.x_per_y;
-    const float *xf = f.x + (long long)row * f.row + (f.c4 ? 0 : (long long)c * f.chan);
+    const Field &f = src.f[i];
+    int c;
+    const float *xf = field_first(src, i, p, c);
     const bool two = 2 * q + 1 < H;
-    fs_twiddles(tw, M);
+    spec_twiddles(tw, M);
     for (int w = threadIdx.x; w < W; w += blockDim.x) {
         const long long p0 = (long long)(2 * q) * W + w, p1 = p0 + W;
         float v0, v1 = 0.f;
-        if (f.c4) {
+        if (f.mode == FIELD_C4) {
             const float4 *x4 = reinterpret_cast<const float4 *>(xf);
-            v0 = fs_pick(x4[p0], c);
-            if (two) v1 = fs_pick(x4[p1], c);
+            v0 = field_pick(x4[p0], c);
+            if (two) v1 = field_pick(x4[p1], c);
         } else {
             v0 = xf[p0 * f.pix];
             if (two) v1 = xf[p1 * f.pix];
@@ -202,7 +177,7 @@ __global__ __launch_bounds__(FS_THREADS) void field_spectrum_cols_kernel(const f
     const int H = ax.N, M = ax.M, WH = W / 2 + 1;
     const int p = blockIdx.x, kx = blockIdx.y;
     float2 *a = fs_lds, *b = a + M, *tw = b + M, *res = tw + M;    // res[NF][H]
-    fs_twiddles(tw, M);
+    spec_twiddles(tw, M);
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         const float2 *hf = half + ((long long)p * NF + i) * H * WH + kx;
@@ -222,14 +197,6 @@ __global__ __launch_bounds__(FS_THREADS) void field_spectrum_cols_kernel(const f
             pl[2ll * WH * H + ky] = fs_dot2(u.x, v.x, u.y, v.y) * scale;
         }
     }
-}
-
-__host__ __device__ inline int fs_isqrt(int n)                    // floor(sqrt(n)), 0 <= n < 2^24
-{
-    int r = (int)sqrtf((float)n);
-    while (r * r > n) --r;
-    while ((r + 1) * (r + 1) <= n) ++r;
-    return r;
 }
 
 // Ring b, rows of one sign of fy (neg: fy < 0; fy = 0 goes with the positive side): cell(ky, kx) for every stored cell
@@ -253,12 +220,12 @@ __host__ __device__ inline void fs_ring_cells(int b, bool neg, int H, int W, int
         const long long T = E * y * y;
         if (T > up0) break;
         const long long qu = (up0 - T) / D, lo = lo0 - T;
-        const int xh = qu >= (long long)xcap * xcap ? xcap : fs_isqrt((int)qu);
+        const int xh = qu >= (long long)xcap * xcap ? xcap : spec_isqrt((int)qu);
         int xl = 0;
         if (lo > 0) {
             const long long ql = (lo + D - 1) / D;                 // fx^2 >= ql
             if (ql > (long long)xcap * xcap) continue;
-            xl = fs_isqrt((int)ql - 1) + 1;
+            xl = spec_isqrt((int)ql - 1) + 1;
         }
         const int ky = neg ? H - y : y;
         for (int x = xl; x <= xh; ++x) {
@@ -316,36 +283,8 @@ static size_t fs_workspace_bytes(int rows, int C, int H, int W, int NF)
 extern "C" size_t acg_field_spectrum_workspace_bytes(int rows, int C, int H, int W) { return fs_workspace_bytes(rows, C, H, W, 1); }
 extern "C" size_t acg_field_cross_spectrum_workspace_bytes(int rows, int C, int H, int W) { return fs_workspace_bytes(rows, C, H, W, 2); }
 
-static FsField fs_operand(const float *x, long long row_stride, int pix_stride, long long chan_stride)
-{
-    FsField f;
-    f.x = x, f.row = row_stride, f.chan = chan_stride, f.pix = pix_stride, f.c4 = 0;
-    return f;
-}
-
-// what both entry points refuse before any launch, under their own name fn
-static int fs_refuse(const char *fn, int rows, int x_per_y, int C, int H, int W, const FsField *f, int nf, const void *ws,
-                     size_t ws_bytes, size_t need)
-{
-    ACG_REQUIRE(fs_extent_ok(H) && fs_extent_ok(W), "%s: fields must be H x W with both extents in %d..%d (got %d x %d)", fn, FS_MIN,
-                FS_MAX, H, W);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "%s: need rows >= 1 and C >= 1 (rows=%d, C=%d)", fn, rows, C);
-    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn, rows, C);
-    for (int i = 0; i < nf; ++i)
-        ACG_REQUIRE(f[i].row >= 1 && f[i].pix >= 1 && f[i].chan >= 1, "%s: strides must be positive (%s: row %lld, pixel %d, channel %lld)",
-                    fn, i ? "y" : "x", f[i].row, f[i].pix, f[i].chan);
-    ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0, "%s: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)", fn,
-                rows, x_per_y);
-    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-        acg_set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "%s: the workspace must be 16-byte aligned", fn);
-    return ACG_OK;
-}
-
 template <int NF>
-static void fs_launch(hipStream_t st, FsSrc<NF> src, int n, int H, int W, float *out, void *ws)
+static void fs_launch(hipStream_t st, FieldSrc<NF> src, int n, int H, int W, float *out, void *ws)
 {
     FsAxis aw, ah;
     aw.N = W, aw.M = fs_padded(W), aw.chirp = 0, aw.filt = W;
@@ -354,7 +293,7 @@ static void fs_launch(hipStream_t st, FsSrc<NF> src, int n, int H, int W, float 
     float2 *half = (float2 *)((char *)ws + fs_head_bytes(H, W));
     float *planes = (float *)((char *)half + fs_half_bytes(n, NF, H, W));
     const int Mmax = aw.M > ah.M ? aw.M : ah.M, WH = W / 2 + 1, RP = (H + 1) / 2;
-    for (FsField &f : src.f) f.c4 = f.pix == 4 && f.chan == 1 && src.C <= 4 && (uintptr_t)f.x % 16 == 0 && f.row % 4 == 0;
+    for (Field &f : src.f) f.mode = field_load_mode(f, src.C);
     if (aw.M != W || ah.M != H)
         hipLaunchKernelGGL(field_spectrum_setup_kernel, dim3(2), dim3(FS_THREADS), 3 * Mmax * sizeof(float2), st, aw, ah, head);
     hipLaunchKernelGGL(field_spectrum_rows_kernel<NF>, dim3(n, NF * RP), dim3(FS_THREADS), 3 * aw.M * sizeof(float2), st, src, H, aw,
@@ -366,15 +305,24 @@ static void fs_launch(hipStream_t st, FsSrc<NF> src, int n, int H, int W, float 
                     NF == 1 ? "field_spectrum" : "field_cross_spectrum", H, ah.M);
 }
 
+// what both entry points refuse first, under their own name fn: an extent they cannot serve, no rows or no channels
+static int fs_shape_refused(const char *fn, int H, int W, int rows, int C)
+{
+    ACG_REQUIRE(fs_extent_ok(H) && fs_extent_ok(W), "%s: fields must be H x W with both extents in %d..%d (got %d x %d)", fn, FS_MIN,
+                FS_MAX, H, W);
+    return field_refuse_operands(fn, rows, C, nullptr, 0);
+}
+
 extern "C" int acg_field_spectrum(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride,
                                   long long chan_stride, float *psd, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && psd != nullptr, "acg_field_spectrum: null tensor");
-    FsSrc<1> src;
-    src.f[0] = fs_operand(x, row_stride, pix_stride, chan_stride);
-    src.C = C, src.x_per_y = 1;
-    if (const int rc = fs_refuse("acg_field_spectrum", rows, 1, C, H, W, src.f, 1, ws, ws_bytes, fs_workspace_bytes(rows, C, H, W, 1)))
-        return rc;
+    const char *fn = "acg_field_spectrum";
+    ACG_REQUIRE(x != nullptr && psd != nullptr, "%s: null tensor", fn);
+    const FieldSrc<1> src = {{{x, row_stride, chan_stride, pix_stride, FIELD_SCALAR}}, C, 1};
+    FIELD_CHECK(fs_shape_refused(fn, H, W, rows, C));
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn, rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, 1));
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, fs_workspace_bytes(rows, C, H, W, 1)));
     if (fs_forwarded(H, W))                                        // nothing is left for it to refuse
         return acg_radial_spectrum(x, rows, C, H, row_stride, pix_stride, chan_stride, psd, ws, ws_bytes, stream);
     fs_launch<1>((hipStream_t)stream, src, rows * C, H, W, psd, ws);
@@ -386,14 +334,15 @@ extern "C" int acg_field_cross_spectrum(const float *x, const float *y, int rows
                                         long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride,
                                         int y_pix_stride, long long y_chan_stride, float *out, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_field_cross_spectrum: null tensor");
-    FsSrc<2> src;
-    src.f[0] = fs_operand(x, x_row_stride, x_pix_stride, x_chan_stride);
-    src.f[1] = fs_operand(y, y_row_stride, y_pix_stride, y_chan_stride);
-    src.C = C, src.x_per_y = x_per_y;
-    if (const int rc = fs_refuse("acg_field_cross_spectrum", rows, x_per_y, C, H, W, src.f, 2, ws, ws_bytes,
-                                 fs_workspace_bytes(rows, C, H, W, 2)))
-        return rc;
+    const char *fn = "acg_field_cross_spectrum";
+    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "%s: null tensor", fn);
+    const FieldSrc<2> src = {{{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}},
+                             C, x_per_y};
+    FIELD_CHECK(fs_shape_refused(fn, H, W, rows, C));
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn, rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, rows));
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, fs_workspace_bytes(rows, C, H, W, 2)));
     if (fs_forwarded(H, W))
         return acg_cross_spectrum(x, y, rows, x_per_y, C, H, x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride,
                                   y_chan_stride, out, ws, ws_bytes, stream);

@@ -21,6 +21,7 @@
 //           kernel with NS planes on its x side, one workgroup per (truth row, c, t) (fss_ens<lds> while NS + 1 planes fit:
 //           16 members at 256^2 take 63 KiB).  M = 1: e is the member's own plane, no slices.
 #include "common.h"
+#include "field.h"
 #include <stdint.h>
 
 #define FSS_MAX_HW 1024
@@ -46,11 +47,10 @@ static size_t fss_pref_bytes(size_t planes, int H, int W)
     return acg_round_up(planes * H * (fss_ww(W) + 1) * sizeof(unsigned short), 16);
 }
 
-// One wave per (field row f, image row i [, channel]): words and prefixes of the planes (f, c, t), all t.  C4: x is NHWC with 4
-// stored channels, 16-byte aligned, and the wave covers channels 0 .. C - 1 (C <= 4); otherwise blockIdx.y is the channel.
+// One wave per (field row f, image row i [, channel]): words and prefixes of the planes (f, c, t), all t.  C4: x is FIELD_C4
+// and the wave covers channels 0 .. C - 1 (C <= 4); otherwise blockIdx.y is the channel.
 template <bool C4>
-__global__ __launch_bounds__(FSS_EVENT_THREADS) void fss_events_kernel(const float *__restrict__ x, int rows, int C, int H, int W,
-                                                                     long long row_stride, int pix_stride, long long chan_stride,
+__global__ __launch_bounds__(FSS_EVENT_THREADS) void fss_events_kernel(Field x, int rows, int C, int H, int W,
                                                                      const float *__restrict__ thr, int T, FssPlanes pl)
 {
     constexpr int NC = C4 ? 4 : 1;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(FSS_EVENT_THREADS) void fss_events_kernel(const flo
     if (item >= (long long)rows * H) return;                       // whole waves leave: the ballots below see full waves
     const int f = (int)(item / H), i = (int)(item - (long long)f * H);
     const int c0 = C4 ? 0 : blockIdx.y, nc = C4 ? C : 1;
-    const float *xf = x + (long long)f * row_stride;
+    const float *__restrict__ xf = x.x + (long long)f * x.row;
     unsigned before = 0;                 // lane c FSS_MAX_T + t keeps the events of plane (c, t) in the words before w, and stores
     for (int w = 0; w <= WW; ++w) {
         const int j = w * 64 + lane;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(FSS_EVENT_THREADS) void fss_events_kernel(const flo
             const float4 q = in ? reinterpret_cast<const float4 *>(xf)[(long long)i * W + j] : make_float4(0.f, 0.f, 0.f, 0.f);
             v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
         } else {
-            v[0] = in ? xf[(long long)c0 * chan_stride + ((long long)i * W + j) * pix_stride] : 0.f;
+            v[0] = in ? xf[(long long)c0 * x.chan + ((long long)i * W + j) * x.pix] : 0.f;
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -259,21 +259,13 @@ extern "C" size_t acg_fss_workspace_bytes(int rows, int x_per_y, int C, int H, i
            fss_bits_bytes(ps, H, W) + fss_pref_bytes(ps, H, W);
 }
 
-static bool fss_c4(const float *x, int C, long long row_stride, int pix_stride, long long chan_stride)
-{
-    return pix_stride == 4 && chan_stride == 1 && C <= 4 && (uintptr_t)x % 16 == 0 && row_stride % 4 == 0;
-}
-
-static void fss_events(hipStream_t st, const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride,
-                       long long chan_stride, const float *thr, int T, FssPlanes pl)
+static void fss_events(hipStream_t st, const Field &x, int rows, int C, int H, int W, const float *thr, int T, FssPlanes pl)
 {
     const unsigned blocks = (unsigned)acg_cdiv((long)rows * H, FSS_EVENT_THREADS / 64);
-    if (fss_c4(x, C, row_stride, pix_stride, chan_stride))
-        hipLaunchKernelGGL(fss_events_kernel<true>, dim3(blocks), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, row_stride,
-                           pix_stride, chan_stride, thr, T, pl);
+    if (x.mode == FIELD_C4)
+        hipLaunchKernelGGL(fss_events_kernel<true>, dim3(blocks), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, thr, T, pl);
     else
-        hipLaunchKernelGGL(fss_events_kernel<false>, dim3(blocks, C), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, row_stride,
-                           pix_stride, chan_stride, thr, T, pl);
+        hipLaunchKernelGGL(fss_events_kernel<false>, dim3(blocks, C), dim3(FSS_EVENT_THREADS), 0, st, x, rows, C, H, W, thr, T, pl);
 }
 
 extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
@@ -281,21 +273,19 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
                        const float *thr, int T, const int *windows, int nw, long long *out, long long *ens_out, void *ws,
                        size_t ws_bytes, void *stream)
 {
+    const char *fn = "acg_fss";
     ACG_REQUIRE(x != nullptr && y != nullptr && thr != nullptr && windows != nullptr, "acg_fss: null tensor");
     ACG_REQUIRE(out != nullptr || ens_out != nullptr, "acg_fss: out and ens_out are both NULL");
+    Field f[2] = {{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}};
     ACG_REQUIRE(H >= 1 && W >= 1 && H <= FSS_MAX_HW && W <= FSS_MAX_HW, "acg_fss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)",
                 FSS_MAX_HW, H, W);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_fss: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, nullptr, 0));
     ACG_REQUIRE(T >= 1 && T <= FSS_MAX_T && nw >= 1 && nw <= FSS_MAX_NW, "acg_fss: need 1 <= T <= %d thresholds and 1 <= nw <= %d windows (T=%d, nw=%d)",
                 FSS_MAX_T, FSS_MAX_NW, T, nw);
     ACG_REQUIRE((long long)rows * C * T <= 0x7fffffffLL && (long long)rows * H <= 0x7fffffffLL,
                 "acg_fss: too many planes (rows=%d, C=%d, T=%d, H=%d)", rows, C, T, H);
-    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
-                    y_chan_stride >= 1,
-                "acg_fss: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, channel %lld)",
-                x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
-    ACG_REQUIRE(x_per_y >= 1 && x_per_y <= FSS_MAX_M && rows % x_per_y == 0,
-                "acg_fss: x_per_y must lie in 1..%d and divide the rows of x (rows=%d, x_per_y=%d)", FSS_MAX_M, rows, x_per_y);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, FSS_MAX_M));
     FssWindows win;
     win.n = nw;
     const int whole = H > W ? H : W;
@@ -309,12 +299,8 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
         ACG_REQUIRE(side * side * (unsigned)H * (unsigned)W < ((unsigned __int128)1 << 63),
                     "acg_fss: overflow: window %d on %d x %d with %d members per truth can reach 2^63", n, H, W, ens_out ? x_per_y : 1);
     }
-    const size_t need = acg_fss_workspace_bytes(rows, x_per_y, C, H, W, T, nw, ens_out != nullptr);
-    if (ws == nullptr || ws_bytes < need) {
-        acg_set_error("acg_fss: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_fss: the workspace must be 16-byte aligned");
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_fss_workspace_bytes(rows, x_per_y, C, H, W, T, nw, ens_out != nullptr)));
+    for (Field &o : f) o.mode = field_load_mode(o, C);
     hipStream_t st = (hipStream_t)stream;
     const int rows_y = rows / x_per_y, CT = C * T;
     const size_t npx = (size_t)rows * CT, npy = (size_t)rows_y * CT;
@@ -327,8 +313,8 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
     const int NS = fss_slices(x_per_y);
     ps.bits = (u64 *)w8, w8 += fss_bits_bytes(npy * NS, H, W);
     ps.pref = (unsigned short *)w8;
-    fss_events(st, x, rows, C, H, W, x_row_stride, x_pix_stride, x_chan_stride, thr, T, px);
-    fss_events(st, y, rows_y, C, H, W, y_row_stride, y_pix_stride, y_chan_stride, thr, T, py);
+    fss_events(st, f[0], rows, C, H, W, thr, T, px);
+    fss_events(st, f[1], rows_y, C, H, W, thr, T, py);
     const unsigned threads = (unsigned)acg_round_up(W, 64);
     const size_t plane = (size_t)H * fss_ww(W) * sizeof(u64) + (size_t)H * (fss_ww(W) + 1) * sizeof(unsigned short);
     auto box = [&](const FssPlanes &xs, int nx, size_t blocks, int per, long long *o) {   // -> whether the planes went into LDS
@@ -349,7 +335,7 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
                            px, ps, (long long)npy, CT, x_per_y, NS, H, W);
         len += snprintf(path + len, sizeof(path) - len, " + fss_slices + fss_ens<%s>", box(ps, NS, npy, 1, ens_out) ? "lds" : "global");
     }
-    acg_note_kernel("fss_events<%s>%s", fss_c4(x, C, x_row_stride, x_pix_stride, x_chan_stride) ? "c4" : "strided", path);
+    acg_note_kernel("fss_events<%s>%s", f[0].mode == FIELD_C4 ? "c4" : "strided", path);
     ACG_CHECK_LAUNCH("acg_fss");
     return ACG_OK;
 }

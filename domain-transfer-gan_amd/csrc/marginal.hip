@@ -22,6 +22,7 @@
 // (marginal_merge_global<2>) and an odd one left alone (marginal_merge_global<1>), and one marginal_sort<words, words> that
 // finishes the strides below MS_T in LDS; the last of them unpacks.
 #include "common.h"
+#include "field.h"
 
 typedef unsigned long long u64;
 
@@ -134,17 +135,11 @@ __device__ __forceinline__ void ms_merge(u64 *lds, u64 (&v)[MS_E], int t, int jh
     ms_tail(v, t, jhi >= 512 ? 64 : jhi, fi0, pmask, k);
 }
 
-struct MsField {
-    const float *x;
-    long long row, chan;                                           // strides in floats
-    int pix, C;
-};
-
 // FROM_X: the words are made from x and sorted from the start (stages 2 .. min(Ppad, MS_T)); else they are read from
 // `words` and only stage k is finished (strides MS_T / 2 .. 1).  UNPACK: the words leave as sorted / rank; else to `words`.
 // total: rows C Ppad words; a chunk beyond them (Ppad < MS_T only) is padding.
 template <bool FROM_X, bool UNPACK>
-__global__ __launch_bounds__(MS_THREADS) void marginal_sort_kernel(MsField f, u64 *__restrict__ words, long long total, int P,
+__global__ __launch_bounds__(MS_THREADS) void marginal_sort_kernel(Field f, int C, u64 *__restrict__ words, long long total, int P,
                                                                    int Ppad, unsigned k, float *__restrict__ sorted,
                                                                    int *__restrict__ rank)
 {
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(MS_THREADS) void marginal_sort_kernel(MsField f, u6
             const unsigned p = (unsigned)(g & pmask);
             u64 w = MS_PAD;
             if (g < total && p < (unsigned)P) {
-                const unsigned r = field / (unsigned)f.C, c = field - r * (unsigned)f.C;
+                const unsigned r = field / (unsigned)C, c = field - r * (unsigned)C;
                 w = ms_word(f.x[r * f.row + c * f.chan + (long long)p * f.pix], p);
             }
             v[e] = w;
@@ -257,33 +252,28 @@ extern "C" size_t acg_field_sort_workspace_bytes(int rows, int C, int H, int W)
 extern "C" int acg_field_sort(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride,
                               long long chan_stride, float *sorted, int *rank, void *ws, size_t ws_bytes, void *stream)
 {
+    const char *fn = "acg_field_sort";
     ACG_REQUIRE(x != nullptr && sorted != nullptr, "acg_field_sort: null tensor");
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_field_sort: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
+    const Field f = {x, row_stride, chan_stride, pix_stride, FIELD_SCALAR};
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, nullptr, 0));
     ACG_REQUIRE(ms_shape_ok(rows, C, H, W), "acg_field_sort: fields must hold 1 .. %d pixels (H=%d, W=%d)", MS_MAX_P, H, W);
-    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
-                "acg_field_sort: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride, chan_stride);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, &f, 1));
     ACG_REQUIRE((const void *)x != (const void *)sorted && (const void *)x != (const void *)rank && (void *)sorted != (void *)rank,
                 "acg_field_sort: sorted and rank must not alias x or each other");
     const int P = H * W, Ppad = ms_ppad(P);
     const long long total = (long long)rows * C * Ppad;
     const long long chunks = (total + MS_T - 1) / MS_T;
     ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL && chunks <= 0x7fffffffLL && total / 2 / 256 <= 0x7fffffffLL, "acg_field_sort: too many fields (rows=%d, C=%d)", rows, C);
-    const size_t need = acg_field_sort_workspace_bytes(rows, C, H, W);
-    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-        acg_set_error("acg_field_sort: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "acg_field_sort: the workspace must be 16-byte aligned");
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_field_sort_workspace_bytes(rows, C, H, W)));
     hipStream_t st = (hipStream_t)stream;
-    const MsField f = {x, row_stride, chan_stride, pix_stride, C};
     const dim3 grid((unsigned)chunks), block(MS_THREADS);
     if (Ppad <= MS_T) {
-        hipLaunchKernelGGL((marginal_sort_kernel<true, true>), grid, block, 0, st, f, (u64 *)nullptr, total, P, Ppad, 0u, sorted, rank);
+        hipLaunchKernelGGL((marginal_sort_kernel<true, true>), grid, block, 0, st, f, C, (u64 *)nullptr, total, P, Ppad, 0u, sorted, rank);
         acg_note_kernel("marginal_sort<x, unpack>");
     } else {
         u64 *words = (u64 *)ws;
         const unsigned pmask = (unsigned)Ppad - 1u;
-        hipLaunchKernelGGL((marginal_sort_kernel<true, false>), grid, block, 0, st, f, words, total, P, Ppad, 0u, (float *)nullptr,
+        hipLaunchKernelGGL((marginal_sort_kernel<true, false>), grid, block, 0, st, f, C, words, total, P, Ppad, 0u, (float *)nullptr,
                            (int *)nullptr);
         for (long long k = 2LL * MS_T; k <= Ppad; k <<= 1) {
             long long j = k >> 1;
@@ -294,10 +284,10 @@ extern "C" int acg_field_sort(const float *x, int rows, int C, int H, int W, lon
                 hipLaunchKernelGGL(marginal_merge_global_kernel<1>, dim3((unsigned)((total / 2 + 255) / 256)), dim3(256), 0, st, words,
                                    total / 2, (unsigned)j, (unsigned)k, pmask);
             if (k < Ppad)
-                hipLaunchKernelGGL((marginal_sort_kernel<false, false>), grid, block, 0, st, f, words, total, P, Ppad, (unsigned)k,
+                hipLaunchKernelGGL((marginal_sort_kernel<false, false>), grid, block, 0, st, f, C, words, total, P, Ppad, (unsigned)k,
                                    (float *)nullptr, (int *)nullptr);
             else
-                hipLaunchKernelGGL((marginal_sort_kernel<false, true>), grid, block, 0, st, f, words, total, P, Ppad, (unsigned)k, sorted,
+                hipLaunchKernelGGL((marginal_sort_kernel<false, true>), grid, block, 0, st, f, C, words, total, P, Ppad, (unsigned)k, sorted,
                                    rank);
         }
         acg_note_kernel("marginal_sort<x, words> + marginal_merge chain: %d launches", ms_launches(Ppad));
@@ -365,12 +355,7 @@ extern "C" int acg_marginal_loss_fwd(const float *sx, int rows_x, const float *s
                 rows_x, rows_y, C);
     ACG_REQUIRE(P >= 1 && P <= MS_MAX_P, "acg_marginal_loss_fwd: fields must hold 1 .. %d pixels (P=%lld)", MS_MAX_P, P);
     ACG_REQUIRE(d != sx && d != sy && loss != sx && loss != sy && loss != d, "acg_marginal_loss_fwd: d and loss must not alias an input");
-    const size_t need = acg_marginal_loss_workspace_bytes(C, P);
-    if (ws == nullptr || ws_bytes < need) {
-        acg_set_error("acg_marginal_loss_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_marginal_loss_fwd: the workspace must be 16-byte aligned");
+    FIELD_CHECK(field_refuse_workspace("acg_marginal_loss_fwd", ws, ws_bytes, acg_marginal_loss_workspace_bytes(C, P)));
     hipStream_t st = (hipStream_t)stream;
     const long long CP = (long long)C * P;
     hipLaunchKernelGGL(marginal_diff_kernel, dim3(ML_BLOCKS), dim3(ML_THREADS), 0, st, sx, rows_x, sy, rows_y, CP, d, (double *)ws);
@@ -413,16 +398,15 @@ extern "C" int acg_marginal_loss_bwd(const float *d, const int *rank, const floa
     ACG_REQUIRE(rows >= 1 && C >= 1 && C <= Cp,
                 "acg_marginal_loss_bwd: need rows >= 1 and 1 <= C <= Cp stored channels (rows=%d, C=%d, Cp=%d)", rows, C, Cp);
     ACG_REQUIRE(ms_shape_ok(rows, C, H, W), "acg_marginal_loss_bwd: fields must hold 1 .. %d pixels (H=%d, W=%d)", MS_MAX_P, H, W);
-    ACG_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1,
-                "acg_marginal_loss_bwd: strides must be positive (row %lld, pixel %d, channel %lld)", row_stride, pix_stride,
-                chan_stride);
+    const Field f = {gx, row_stride, chan_stride, pix_stride, FIELD_SCALAR};   // gx, in the layout of the x it is the gradient of
+    FIELD_CHECK(field_refuse_operands("acg_marginal_loss_bwd", rows, C, &f, 1));
     ACG_REQUIRE((const void *)gx != (const void *)d && (const void *)gx != (const void *)rank && (const void *)gx != (const void *)gscale,
                 "acg_marginal_loss_bwd: gx must not alias an input");
     const int P = H * W;
     const long long pixels = (long long)rows * P;
     ACG_REQUIRE((pixels + 255) / 256 <= 0x7fffffffLL, "acg_marginal_loss_bwd: too many pixels (rows=%d)", rows);
     const float coef = (float)(2.0 / ((double)C * (double)P * (double)rows));
-    const bool c4 = Cp == 4 && pix_stride == 4 && chan_stride == 1 && row_stride % 4 == 0 && (uintptr_t)gx % 16 == 0;
+    const bool c4 = Cp == 4 && field_load_mode(f, C) == FIELD_C4;
     const dim3 grid((unsigned)((pixels + 255) / 256));
     if (c4)
         hipLaunchKernelGGL(marginal_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d, rank, gscale, pixels, C, Cp, P,

@@ -33,9 +33,10 @@
 // Twiddles: sincospif on exact arguments, one table per stage laid out by butterfly index (unit-stride reads).
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <type_traits>
 #include "common.h"
+#include "field.h"
+#include "spectrum_shared.h"
 
 #define SPEC_TILE 4096                   // complex elements of one LDS buffer of the two-pass kernels (32 KiB)
 #define SPEC_MIN_S 16
@@ -59,20 +60,6 @@ static_assert(spec_field_threads(16, 1) == 64 && spec_field_threads(32, 1) == 25
 __host__ __device__ constexpr int spec_planes(int NF) { return NF == 1 ? 1 : 3; }   // |X|^2; with a second field |Y|^2 and Re(X conj Y)
 // slots of the kept rows of the column kx = S/2: row fy in slot fy & (slots - 1); fy^2 <= S/2 <= 512 lies well inside
 __host__ __device__ constexpr int spec_nyq(int S) { return S < 64 ? S : 64; }
-
-enum { SPEC_SCALAR = 0, SPEC_PLANAR = 1, SPEC_C4 = 2 };   // how a field's pixels are loaded
-
-// tw[Ns + k] = exp(-i pi k / Ns), 0 <= k < Ns, Ns = 1, 2, .. S/2: stage Ns reads tw[Ns + (j mod Ns)]
-template <int S>
-__device__ __forceinline__ void spec_twiddles(float2 *tw)
-{
-    for (int m = threadIdx.x + 1; m < S; m += blockDim.x) {
-        const int Ns = 1 << (31 - __clz(m)), k = m - Ns;
-        float s, c;
-        sincospif(-(float)k / (float)Ns, &s, &c);
-        tw[m] = make_float2(c, s);
-    }
-}
 
 __device__ __forceinline__ void spec_butterfly(float2 u, float2 v, float2 w, float2 &p, float2 &m)
 {
@@ -127,10 +114,8 @@ __device__ __forceinline__ float2 *spec_fft_cols(float2 *a, float2 *b, const flo
     return a;
 }
 
-__device__ __forceinline__ float spec_pick(float4 v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
 // z[q][w] = x[2 (rp0 + q)][w] + i x[2 (rp0 + q) + 1][w] for NRP row pairs; four pixels of both rows per work item.
-// xf: the field's first pixel (SPEC_C4: the image's, the channel picked from each pixel's 16 bytes).
+// xf: the field's first pixel (FIELD_C4: the image's, the channel picked from each pixel's 16 bytes).
 template <int S, int NRP>
 __device__ __forceinline__ void spec_load_rows(const float *__restrict__ xf, int pix_stride, int mode, int c, int rp0, float2 *z)
 {
@@ -138,13 +123,13 @@ __device__ __forceinline__ void spec_load_rows(const float *__restrict__ xf, int
         const int q = t / (S / 4), w = (t & (S / 4 - 1)) * 4;
         const long long p0 = (long long)(2 * (rp0 + q)) * S + w, p1 = p0 + S;
         float4 r0, r1;
-        if (mode == SPEC_PLANAR) {
+        if (mode == FIELD_PLANAR) {
             r0 = *reinterpret_cast<const float4 *>(xf + p0);
             r1 = *reinterpret_cast<const float4 *>(xf + p1);
-        } else if (mode == SPEC_C4) {
+        } else if (mode == FIELD_C4) {
             const float4 *x4 = reinterpret_cast<const float4 *>(xf);
-            r0 = make_float4(spec_pick(x4[p0], c), spec_pick(x4[p0 + 1], c), spec_pick(x4[p0 + 2], c), spec_pick(x4[p0 + 3], c));
-            r1 = make_float4(spec_pick(x4[p1], c), spec_pick(x4[p1 + 1], c), spec_pick(x4[p1 + 2], c), spec_pick(x4[p1 + 3], c));
+            r0 = make_float4(field_pick(x4[p0], c), field_pick(x4[p0 + 1], c), field_pick(x4[p0 + 2], c), field_pick(x4[p0 + 3], c));
+            r1 = make_float4(field_pick(x4[p1], c), field_pick(x4[p1 + 1], c), field_pick(x4[p1 + 2], c), field_pick(x4[p1 + 3], c));
         } else {
             r0 = make_float4(xf[p0 * pix_stride], xf[(p0 + 1) * pix_stride], xf[(p0 + 2) * pix_stride], xf[(p0 + 3) * pix_stride]);
             r1 = make_float4(xf[p1 * pix_stride], xf[(p1 + 1) * pix_stride], xf[(p1 + 2) * pix_stride], xf[(p1 + 3) * pix_stride]);
@@ -228,13 +213,6 @@ __device__ __forceinline__ void spec_products(const float2 *f, int kx0, float *p
     }
 }
 
-__device__ __forceinline__ int spec_isqrt(int n)                  // floor(sqrt(n)), n >= 0
-{
-    int r = (int)sqrtf((float)n);
-    while (r * r > n) --r;
-    while ((r + 1) * (r + 1) <= n) ++r;
-    return r;
-}
 __device__ __forceinline__ int spec_isqrt_ceil(int n) { return n <= 0 ? 0 : spec_isqrt(n - 1) + 1; }
 
 // Ring b, rows of one sign of fy (neg: fy < 0; fy = 0 goes with the positive side), inside the tile's columns: the row range and
@@ -335,29 +313,6 @@ struct RingBins {
     }
 };
 
-// one operand of a launch: where its fields lie and how their pixels are loaded
-struct SpecField {
-    const float *x;
-    long long row, chan;
-    int pix, mode;
-};
-// what a launch reads: field or pair p is channel c of row r of operand 0 and, of a pair, channel c of row r / x_per_y of operand 1
-template <int NF>
-struct SpecSrc {
-    SpecField f[NF];
-    int C, x_per_y;
-};
-// the first pixel of field or pair p in operand i (SPEC_C4: the image's; c: the channel to pick)
-template <int NF>
-__device__ __forceinline__ const float *spec_field(const SpecSrc<NF> &s, int i, int p, int &c)
-{
-    int row = p / s.C;
-    c = p - row * s.C;
-    if (i == 1) row /= s.x_per_y;
-    const SpecField &f = s.f[i];
-    return f.x + (long long)row * f.row + (f.mode == SPEC_C4 ? 0 : (long long)c * f.chan);
-}
-
 // 16-byte copies between the half spectra of a field or pair in the workspace, hf[ky][NF S/2], and a [ky][KT] LDS tile that
 // holds columns kx0 .. kx0 + KT / NF - 1 of every field, X's in front and Y's behind
 template <int S, int KT, int NF>
@@ -386,7 +341,7 @@ __device__ __forceinline__ void spec_store_tile(const float2 *tile, int kx0, flo
 
 // spec_one_wg(S, NF): one workgroup per field or pair; nothing but out is written
 template <int S, int NF>
-__global__ __launch_bounds__(spec_field_threads(S, NF)) void spectrum_field_kernel(SpecSrc<NF> src, float *__restrict__ out)
+__global__ __launch_bounds__(spec_field_threads(S, NF)) void spectrum_field_kernel(FieldSrc<NF> src, float *__restrict__ out)
 {
     constexpr int H = S / 2, K = spec_planes(NF);
     using Bins = RingBins<S, spec_field_threads(S, NF), K>;
@@ -394,11 +349,11 @@ __global__ __launch_bounds__(spec_field_threads(S, NF)) void spectrum_field_kern
     __shared__ __attribute__((aligned(16))) float2 buf1[NF * H * S];
     __shared__ float2 tw[S];
     static_assert(K * (S * H + spec_nyq(S)) * sizeof(float) <= sizeof(buf0) && Bins::LDS_BYTES <= sizeof(buf0), "LDS");
-    spec_twiddles<S>(tw);
+    spec_twiddles(tw, S);
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         int c;
-        const float *xf = spec_field(src, i, blockIdx.x, c);
+        const float *xf = field_first(src, i, blockIdx.x, c);
         spec_load_rows<S, H>(xf, src.f[i].pix, src.f[i].mode, c, 0, buf0 + i * H * S);
     }
     __syncthreads();
@@ -420,7 +375,7 @@ __global__ __launch_bounds__(spec_field_threads(S, NF)) void spectrum_field_kern
 // above, first pass: SPEC_TILE / S row pairs of one field per workgroup (blockIdx.y: x's tiles, then y's) -> their rows of that
 // field's side of the [ky][NF S/2] tile in the workspace
 template <int S, int NF>
-__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(SpecSrc<NF> src, float2 *__restrict__ half)
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(FieldSrc<NF> src, float2 *__restrict__ half)
 {
     constexpr int NRP = SPEC_TILE / S, TILES = (S / 2) / NRP, H = S / 2;
     __shared__ __attribute__((aligned(16))) float2 buf0[SPEC_TILE];
@@ -428,8 +383,8 @@ __global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_rows_kernel(SpecSr
     __shared__ float2 tw[S];
     const int i = NF == 1 ? 0 : blockIdx.y / TILES, rp0 = (blockIdx.y - i * TILES) * NRP;
     int c;
-    const float *xf = spec_field(src, i, blockIdx.x, c);
-    spec_twiddles<S>(tw);
+    const float *xf = field_first(src, i, blockIdx.x, c);
+    spec_twiddles(tw, S);
     spec_load_rows<S, NRP>(xf, src.f[i].pix, src.f[i].mode, c, rp0, buf0);
     __syncthreads();
     const float2 *z = spec_fft_rows<S, NRP>(buf0, buf1, tw);
@@ -447,7 +402,7 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const 
     __shared__ float2 tw[S];
     static_assert(K * (S * KH + spec_nyq(S)) * sizeof(float) <= sizeof(buf0) && Bins::LDS_BYTES <= sizeof(buf0), "LDS");
     const float2 *hf = half + (long long)blockIdx.x * S * (NF * H);
-    spec_twiddles<S>(tw);
+    spec_twiddles(tw, S);
     Bins bins;
     bins.clear();
     float2 *f = buf0;
@@ -466,55 +421,14 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_cols_kernel(const 
 
 static bool spec_size_ok(int S) { return S >= SPEC_MIN_S && S <= SPEC_MAX_S && (S & (S - 1)) == 0; }
 
-// an operand as the caller describes it; its load mode follows once the call has been let pass
-static SpecField spec_operand(const float *x, long long row_stride, int pix_stride, long long chan_stride)
-{
-    SpecField f;
-    f.x = x, f.row = row_stride, f.chan = chan_stride, f.pix = pix_stride, f.mode = SPEC_SCALAR;
-    return f;
-}
-
-// 16-byte accesses where the layout allows them: four pixels of a planar row, or a C4 pixel's channels; gx: a second tensor
-// of the same strides (the gradient), or null
-static int spec_load_mode(const SpecField &f, int C, const float *gx = nullptr)
-{
-    const bool aligned = (uintptr_t)f.x % 16 == 0 && (uintptr_t)gx % 16 == 0 && f.row % 4 == 0;
-    if (f.pix == 1 && f.chan % 4 == 0 && aligned) return SPEC_PLANAR;
-    if (f.pix == 4 && f.chan == 1 && C <= 4 && aligned) return SPEC_C4;
-    return SPEC_SCALAR;
-}
-
-// What every entry point refuses, under its own name fn: a size, a count (of `what`: fields or pairs) or a stride of one of its
-// nf operands it cannot serve, and a workspace of fewer than `need` bytes (ACG_ERR_WORKSPACE) or off the 16-byte grid.  An
-// entry point's own refusals keep their places among these: own(SPEC_SHAPE_OK) and own(SPEC_STRIDES_OK) return them
-enum { SPEC_SHAPE_OK, SPEC_STRIDES_OK };
-template <class Own>
-static int spec_refuse(const char *fn, const char *what, int S, int rows, int C, const SpecField *f, int nf, const void *ws,
-                       size_t ws_bytes, size_t need, Own own)
+// what every entry point here refuses first, under its own name fn: a size it cannot serve, no rows or no channels
+static int spec_shape_refused(const char *fn, int S, int rows, int C)
 {
     ACG_REQUIRE(spec_size_ok(S), "%s: fields must be S x S with S a power of two in %d..%d (S=%d)", fn, SPEC_MIN_S, SPEC_MAX_S, S);
-    ACG_REQUIRE(rows >= 1 && C >= 1, "%s: need rows >= 1 and C >= 1 (rows=%d, C=%d)", fn, rows, C);
-    if (const int rc = own(SPEC_SHAPE_OK)) return rc;
-    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many %s (rows=%d, C=%d)", fn, what, rows, C);
-    bool positive = true;
-    char strides[256];
-    int n = 0;
-    for (int i = 0; i < nf; ++i) {                                 // one operand: "row ..", two: "x: row ..; y: row .."
-        positive = positive && f[i].row >= 1 && f[i].pix >= 1 && f[i].chan >= 1;
-        n += snprintf(strides + n, sizeof(strides) - n, "%s%srow %lld, pixel %d, channel %lld", i ? "; " : "",
-                      nf == 1 ? "" : i ? "y: " : "x: ", f[i].row, f[i].pix, f[i].chan);
-    }
-    ACG_REQUIRE(positive, "%s: strides must be positive (%s)", fn, strides);
-    if (const int rc = own(SPEC_STRIDES_OK)) return rc;
-    if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-        acg_set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE(need == 0 || (uintptr_t)ws % 16 == 0, "%s: the workspace must be 16-byte aligned", fn);
-    return ACG_OK;
+    return field_refuse_operands(fn, rows, C, nullptr, 0);
 }
 
-// f(std::integral_constant<int, S>) for the size S of a call that spec_refuse has let pass
+// f(std::integral_constant<int, S>) for the size S of a call that spec_shape_refused has let pass
 template <class F>
 static void spec_for_size(int S, F f)
 {
@@ -539,7 +453,7 @@ extern "C" size_t acg_radial_spectrum_workspace_bytes(int rows, int C, int S) { 
 extern "C" size_t acg_cross_spectrum_workspace_bytes(int rows, int C, int S) { return spec_half_bytes(rows, C, S, 2); }
 
 template <int S, int NF>
-static void spec_launch(hipStream_t st, const SpecSrc<NF> &src, int n, float *out, float2 *half)
+static void spec_launch(hipStream_t st, const FieldSrc<NF> &src, int n, float *out, float2 *half)
 {
     if constexpr (spec_one_wg(S, NF)) {
         hipLaunchKernelGGL((spectrum_field_kernel<S, NF>), dim3(n), dim3(spec_field_threads(S, NF)), 0, st, src, out);
@@ -555,14 +469,14 @@ static void spec_launch(hipStream_t st, const SpecSrc<NF> &src, int n, float *ou
 extern "C" int acg_radial_spectrum(const float *x, int rows, int C, int S, long long row_stride, int pix_stride,
                                    long long chan_stride, float *psd, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && psd != nullptr, "acg_radial_spectrum: null tensor");
-    SpecSrc<1> src;
-    src.f[0] = spec_operand(x, row_stride, pix_stride, chan_stride);
-    src.C = C, src.x_per_y = 1;
-    if (const int rc = spec_refuse("acg_radial_spectrum", "fields", S, rows, C, src.f, 1, ws, ws_bytes,
-                                   acg_radial_spectrum_workspace_bytes(rows, C, S), [](int) { return (int)ACG_OK; }))
-        return rc;
-    src.f[0].mode = spec_load_mode(src.f[0], C);
+    const char *fn = "acg_radial_spectrum";
+    ACG_REQUIRE(x != nullptr && psd != nullptr, "%s: null tensor", fn);
+    FieldSrc<1> src = {{{x, row_stride, chan_stride, pix_stride, FIELD_SCALAR}}, C, 1};
+    FIELD_CHECK(spec_shape_refused(fn, S, rows, C));
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn, rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, 1));
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_radial_spectrum_workspace_bytes(rows, C, S)));
+    src.f[0].mode = field_load_mode(src.f[0], C, true);
     spec_for_size(S, [&](auto s) { spec_launch<decltype(s)::value, 1>((hipStream_t)stream, src, rows * C, psd, (float2 *)ws); });
     ACG_CHECK_LAUNCH("acg_radial_spectrum");
     return ACG_OK;
@@ -572,21 +486,16 @@ extern "C" int acg_cross_spectrum(const float *x, const float *y, int rows, int 
                                   int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                                   long long y_chan_stride, float *out, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_cross_spectrum: null tensor");
-    SpecSrc<2> src;
-    src.f[0] = spec_operand(x, x_row_stride, x_pix_stride, x_chan_stride);
-    src.f[1] = spec_operand(y, y_row_stride, y_pix_stride, y_chan_stride);
-    src.C = C, src.x_per_y = x_per_y;
-    const auto own = [&](int after) -> int {
-        if (after == SPEC_STRIDES_OK)
-            ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0,
-                        "acg_cross_spectrum: x_per_y must be at least 1 and divide the rows of x (rows=%d, x_per_y=%d)", rows, x_per_y);
-        return ACG_OK;
-    };
-    if (const int rc = spec_refuse("acg_cross_spectrum", "pairs", S, rows, C, src.f, 2, ws, ws_bytes,
-                                   acg_cross_spectrum_workspace_bytes(rows, C, S), own))
-        return rc;
-    for (SpecField &f : src.f) f.mode = spec_load_mode(f, C);
+    const char *fn = "acg_cross_spectrum";
+    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "%s: null tensor", fn);
+    FieldSrc<2> src = {{{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}},
+                       C, x_per_y};
+    FIELD_CHECK(spec_shape_refused(fn, S, rows, C));
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many pairs (rows=%d, C=%d)", fn, rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, rows));
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_cross_spectrum_workspace_bytes(rows, C, S)));
+    for (Field &f : src.f) f.mode = field_load_mode(f, C, true);
     spec_for_size(S, [&](auto s) { spec_launch<decltype(s)::value, 2>((hipStream_t)stream, src, rows * C, out, (float2 *)ws); });
     ACG_CHECK_LAUNCH("acg_cross_spectrum");
     return ACG_OK;
@@ -736,7 +645,7 @@ struct SpecDst {
     float *gf, *gi;
     int zero_from, zero_ch;
 };
-__device__ __forceinline__ SpecDst spec_dst(float *gx, const SpecSrc<1> &src, int f, int Cp)
+__device__ __forceinline__ SpecDst spec_dst(float *gx, const FieldSrc<1> &src, int f, int Cp)
 {
     const int row = f / src.C, c = f - row * src.C;
     SpecDst d;
@@ -749,7 +658,7 @@ __device__ __forceinline__ SpecDst spec_dst(float *gx, const SpecSrc<1> &src, in
 
 // S <= 128: one workgroup per field
 template <int S>
-__global__ __launch_bounds__(spec_field_threads(S, 1)) void spectrum_bwd_field_kernel(SpecSrc<1> src, const float *__restrict__ g,
+__global__ __launch_bounds__(spec_field_threads(S, 1)) void spectrum_bwd_field_kernel(FieldSrc<1> src, const float *__restrict__ g,
                                                                              const int *__restrict__ cnt, int Cp,
                                                                              float *__restrict__ gx)
 {
@@ -759,8 +668,8 @@ __global__ __launch_bounds__(spec_field_threads(S, 1)) void spectrum_bwd_field_k
     __shared__ float2 tw[S];
     __shared__ float gw[H + 1];
     int c;
-    const float *xf = spec_field(src, 0, blockIdx.x, c);
-    spec_twiddles<S>(tw);
+    const float *xf = field_first(src, 0, blockIdx.x, c);
+    spec_twiddles(tw, S);
     spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
     spec_load_rows<S, H>(xf, src.f[0].pix, src.f[0].mode, c, 0, buf0);
     __syncthreads();
@@ -778,7 +687,7 @@ __global__ __launch_bounds__(spec_field_threads(S, 1)) void spectrum_bwd_field_k
     __syncthreads();
     const float2 *r = spec_fft_rows<S, H>(o, t, tw);
     const SpecDst d = spec_dst(gx, src, blockIdx.x, Cp);
-    spec_store_rows<S, H>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == SPEC_PLANAR, 0, d.zero_from, d.zero_ch);
+    spec_store_rows<S, H>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == FIELD_PLANAR, 0, d.zero_from, d.zero_ch);
 }
 
 // S > 128, second pass: one workgroup per tile of SPEC_TILE / S columns of a field's half spectrum, in place
@@ -793,7 +702,7 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_bwd_cols_kernel(fl
     __shared__ float gw[H + 1];
     const int kx0 = blockIdx.y * KT;
     float2 *hf = half + (long long)blockIdx.x * S * H;
-    spec_twiddles<S>(tw);
+    spec_twiddles(tw, S);
     spec_ring_weights<S>(g + (long long)blockIdx.x * (H + 1), cnt, gw);
     spec_load_tile<S, KT, 1>(hf, kx0, buf0);
     __syncthreads();
@@ -806,7 +715,7 @@ __global__ __launch_bounds__(SPEC_COLS_THREADS) void spectrum_bwd_cols_kernel(fl
 
 // S > 128, third pass: SPEC_TILE / S row pairs of one field per workgroup, half spectra -> the real rows of gx
 template <int S>
-__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(const float2 *__restrict__ half, SpecSrc<1> src, int Cp,
+__global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(const float2 *__restrict__ half, FieldSrc<1> src, int Cp,
                                                                          float *__restrict__ gx)
 {
     constexpr int NRP = SPEC_TILE / S;
@@ -814,12 +723,12 @@ __global__ __launch_bounds__(SPEC_ROWS_THREADS) void spectrum_bwd_rows_kernel(co
     __shared__ __attribute__((aligned(16))) float2 buf1[SPEC_TILE];
     __shared__ float2 tw[S];
     const int rp0 = blockIdx.y * NRP;
-    spec_twiddles<S>(tw);
+    spec_twiddles(tw, S);
     spec_tangle_rows<S, NRP>(half + ((long long)blockIdx.x * S + 2 * rp0) * (S / 2), buf0);
     __syncthreads();
     const float2 *r = spec_fft_rows<S, NRP>(buf0, buf1, tw);
     const SpecDst d = spec_dst(gx, src, blockIdx.x, Cp);
-    spec_store_rows<S, NRP>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == SPEC_PLANAR, rp0, d.zero_from, d.zero_ch);
+    spec_store_rows<S, NRP>(r, d.gf, d.gi, src.f[0].pix, src.f[0].chan, src.f[0].mode == FIELD_PLANAR, rp0, d.zero_from, d.zero_ch);
 }
 
 extern "C" size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S)
@@ -829,7 +738,7 @@ extern "C" size_t acg_radial_spectrum_bwd_workspace_bytes(int rows, int C, int S
 }
 
 template <int S>
-static void spec_bwd_launch(hipStream_t st, const SpecSrc<1> &src, const float *g, int fields, int Cp, float *gx, int *cnt,
+static void spec_bwd_launch(hipStream_t st, const FieldSrc<1> &src, const float *g, int fields, int Cp, float *gx, int *cnt,
                             float2 *half)
 {
     hipLaunchKernelGGL(spectrum_ring_counts_kernel, dim3(S / 2 + 1), dim3(SPEC_COUNT_THREADS), 0, st, S, cnt);
@@ -851,21 +760,16 @@ static void spec_bwd_launch(hipStream_t st, const SpecSrc<1> &src, const float *
 extern "C" int acg_radial_spectrum_bwd(const float *x, const float *g, int rows, int C, int Cp, int S, long long row_stride,
                                        int pix_stride, long long chan_stride, float *gx, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && g != nullptr && gx != nullptr, "acg_radial_spectrum_bwd: null tensor");
-    SpecSrc<1> src;
-    src.f[0] = spec_operand(x, row_stride, pix_stride, chan_stride);
-    src.C = C, src.x_per_y = 1;
-    const auto own = [&](int after) -> int {
-        if (after == SPEC_SHAPE_OK)
-            ACG_REQUIRE(Cp >= C, "acg_radial_spectrum_bwd: the stored channels cannot be fewer than the valid ones (C=%d, Cp=%d)", C, Cp);
-        else
-            ACG_REQUIRE(x != gx, "acg_radial_spectrum_bwd: gx must not alias x");
-        return ACG_OK;
-    };
-    if (const int rc = spec_refuse("acg_radial_spectrum_bwd", "fields", S, rows, C, src.f, 1, ws, ws_bytes,
-                                   acg_radial_spectrum_bwd_workspace_bytes(rows, C, S), own))
-        return rc;
-    src.f[0].mode = spec_load_mode(src.f[0], C, gx);
+    const char *fn = "acg_radial_spectrum_bwd";
+    ACG_REQUIRE(x != nullptr && g != nullptr && gx != nullptr, "%s: null tensor", fn);
+    FieldSrc<1> src = {{{x, row_stride, chan_stride, pix_stride, FIELD_SCALAR}}, C, 1};
+    FIELD_CHECK(spec_shape_refused(fn, S, rows, C));
+    ACG_REQUIRE(Cp >= C, "%s: the stored channels cannot be fewer than the valid ones (C=%d, Cp=%d)", fn, C, Cp);
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn, rows, C);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, 1));
+    ACG_REQUIRE(x != gx, "%s: gx must not alias x", fn);
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_radial_spectrum_bwd_workspace_bytes(rows, C, S)));
+    src.f[0].mode = field_load_mode(src.f[0], C, true, gx);
     int *cnt = (int *)ws;
     float2 *half = (float2 *)((char *)ws + spec_counts_bytes(S));
     spec_for_size(S, [&](auto s) { spec_bwd_launch<decltype(s)::value>((hipStream_t)stream, src, g, rows * C, Cp, gx, cnt, half); });

@@ -25,6 +25,7 @@
 // The file is compiled without floating-point contraction; the tap loops call fmaf themselves.  Every instantiation then
 // evaluates the same expressions in the same order, whatever the layout.
 #include "common.h"
+#include "field.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -38,21 +39,14 @@ constexpr int SS_MIN_HW = SS_K, SS_MAX_HW = 1024;
 constexpr int SS_PER_THREAD = SS_TW * SS_TH / SS_THREADS;          // 2 outputs per thread
 static_assert(SS_TW == 32 && SS_TW * SS_TH % SS_THREADS == 0, "lane groups of 32 walk one tile row");
 
-struct SsField {
-    const float *p;
-    long long row, chan;                                           // strides in floats
-    int pix;
-};
 struct SsWin {
     float w[SS_K];
 };
 
-__device__ __forceinline__ float ss_comp(const float4 &q, int c) { return c == 0 ? q.x : (c == 1 ? q.y : (c == 2 ? q.z : q.w)); }
-
 // the tile's pixels (oy + r, ox + j), r < SS_IH, j < SS_IW, of row `base` -> planes; outside H x W: 0.  C4: channels 0 .. C - 1
 // into planes 0 .. C - 1 from one 16-byte load per pixel; else channel c into plane 0.
 template <bool C4>
-__device__ __forceinline__ void ss_stage(float *planes, const SsField &f, const float *base, int c, int C, int oy, int ox, int H, int W)
+__device__ __forceinline__ void ss_stage(float *planes, const Field &f, const float *base, int c, int C, int oy, int ox, int H, int W)
 {
     for (int p = threadIdx.x; p < SS_IH * SS_IW; p += SS_THREADS) {
         const int r = p / SS_IW, j = p - r * SS_IW;
@@ -61,7 +55,7 @@ __device__ __forceinline__ void ss_stage(float *planes, const SsField &f, const 
         const long long pixel = (long long)gy * W + gx;
         if (C4) {
             const float4 q = in ? *reinterpret_cast<const float4 *>(base + pixel * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int k = 0; k < C; ++k) planes[k * (SS_IH * SS_IW) + p] = ss_comp(q, k);
+            for (int k = 0; k < C; ++k) planes[k * (SS_IH * SS_IW) + p] = field_pick(q, k);
         } else {
             planes[p] = in ? base[c * f.chan + pixel * f.pix] : 0.f;
         }
@@ -93,7 +87,7 @@ __device__ __forceinline__ void ss_block_store(double a, double b, double (*red)
 // blockIdx.x = row r of x * tiles + tile.  part: (rows, C, tiles, 2) doubles; dmaps (or NULL): 3 planes of (rows, C, Hv, Wv),
 // `plane` floats apart.
 template <bool XC4, bool YC4>
-__global__ __launch_bounds__(SS_THREADS) void ssim_fwd_kernel(SsField x, SsField y, int C, int H, int W, int x_per_y, int ntx,
+__global__ __launch_bounds__(SS_THREADS) void ssim_fwd_kernel(Field x, Field y, int C, int H, int W, int x_per_y, int ntx,
                                                               int tiles, SsWin win, float c1, float c2, double *__restrict__ part,
                                                               float *__restrict__ dmaps, long long plane)
 {
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_fwd_kernel(SsField x, SsField
     const int ty = tile / ntx, tx = tile - ty * ntx;
     const int oy = ty * SS_TH, ox = tx * SS_TW;
     const int Hv = H - SS_HALO, Wv = W - SS_HALO;
-    const float *xb = x.p + r * x.row, *yb = y.p + (r / x_per_y) * y.row;
+    const float *xb = x.x + r * x.row, *yb = y.x + (r / x_per_y) * y.row;
     for (int c = 0; c < C; ++c) {
         if (!XC4 || c == 0) ss_stage<XC4>(sx, x, xb, c, C, oy, ox, H, W);
         if (!YC4 || c == 0) ss_stage<YC4>(sy, y, yb, c, C, oy, ox, H, W);
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(64) void ssim_fold_kernel(const double *__restrict_
 
 // blockIdx.x = row r * tiles + tile, a tile of SS_TW x SS_TH pixels.  gx in x's layout; channels C .. Cp - 1 leave as 0.
 template <bool XC4, bool YC4>
-__global__ __launch_bounds__(SS_THREADS) void ssim_bwd_kernel(const float *__restrict__ dmaps, long long plane, SsField x, SsField y,
+__global__ __launch_bounds__(SS_THREADS) void ssim_bwd_kernel(const float *__restrict__ dmaps, long long plane, Field x, Field y,
                                                               const float *__restrict__ g, int C, int Cp, int H, int W, int ntx, int tiles,
                                                               SsWin win, float coef, float *__restrict__ gx)
 {
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_bwd_kernel(const float *__res
     const int qy0 = ty * SS_TH, qx0 = tx * SS_TW;
     const int Hv = H - SS_HALO, Wv = W - SS_HALO;
     const float scale = coef * g[0];
-    const float *xb = x.p + r * x.row, *yb = y.p + r * y.row;
+    const float *xb = x.x + r * x.row, *yb = y.x + r * y.row;
     float *ob = gx + r * x.row;
     long long pixel[SS_PER_THREAD];
     bool in[SS_PER_THREAD];
@@ -229,8 +223,8 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_bwd_kernel(const float *__res
             for (int k = 0; k < SS_K; ++k)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) m[q] = fmaf(win.w[k], hb[q][(i + k) * SS_TW + j], m[q]);
-            const float xv = XC4 ? ss_comp(x4[e], c) : xb[c * x.chan + pixel[e] * x.pix];
-            const float yv = YC4 ? ss_comp(y4[e], c) : yb[c * y.chan + pixel[e] * y.pix];
+            const float xv = XC4 ? field_pick(x4[e], c) : xb[c * x.chan + pixel[e] * x.pix];
+            const float yv = YC4 ? field_pick(y4[e], c) : yb[c * y.chan + pixel[e] * y.pix];
             const float v = scale * (m[0] + 2.f * xv * m[1] + yv * m[2]);
             if (XC4) {
                 o4[e].x = c == 0 ? v : o4[e].x, o4[e].y = c == 1 ? v : o4[e].y;
@@ -266,11 +260,6 @@ static bool ss_shape_ok(int rows, int C, int H, int W)
 static int ss_tiles_x(int extent) { return (extent + SS_TW - 1) / SS_TW; }
 static int ss_tiles_y(int extent) { return (extent + SS_TH - 1) / SS_TH; }
 
-static bool ss_c4(const float *p, int C, long long row_stride, int pix_stride, long long chan_stride)
-{
-    return pix_stride == 4 && chan_stride == 1 && C <= 4 && (uintptr_t)p % 16 == 0 && row_stride % 4 == 0;
-}
-
 extern "C" size_t acg_ssim_workspace_bytes(int rows, int C, int H, int W)
 {
     if (!ss_shape_ok(rows, C, H, W)) return 0;
@@ -282,39 +271,31 @@ extern "C" int acg_ssim(const float *x, const float *y, int rows, int x_per_y, i
                         int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride,
                         float data_range, float *out, float *dmaps, void *ws, size_t ws_bytes, void *stream)
 {
-    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "acg_ssim: null tensor");
-    ACG_REQUIRE(rows >= 1 && C >= 1, "acg_ssim: need rows >= 1 and C >= 1 (rows=%d, C=%d)", rows, C);
-    ACG_REQUIRE(ss_shape_ok(rows, C, H, W), "acg_ssim: fields must be H x W with %d <= H, W <= %d (got %d x %d)", SS_MIN_HW, SS_MAX_HW,
-                H, W);
-    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
-                    y_chan_stride >= 1,
-                "acg_ssim: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, channel %lld)",
-                x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
-    ACG_REQUIRE(x_per_y >= 1 && rows % x_per_y == 0, "acg_ssim: x_per_y must be positive and divide the rows of x (rows=%d, x_per_y=%d)",
-                rows, x_per_y);
-    ACG_REQUIRE(data_range > 0.f && data_range <= 3.0e38f, "acg_ssim: data_range must be positive and finite (got %g)", (double)data_range);
+    const char *fn = "acg_ssim";
+    ACG_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "%s: null tensor", fn);
+    Field f[2] = {{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}};
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, nullptr, 0));
+    ACG_REQUIRE(ss_shape_ok(rows, C, H, W), "%s: fields must be H x W with %d <= H, W <= %d (got %d x %d)", fn, SS_MIN_HW, SS_MAX_HW, H, W);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, rows));
+    ACG_REQUIRE(data_range > 0.f && data_range <= 3.0e38f, "%s: data_range must be positive and finite (got %g)", fn, (double)data_range);
     ACG_REQUIRE((const void *)out != (const void *)x && (const void *)out != (const void *)y && (const void *)dmaps != (const void *)x &&
                     (const void *)dmaps != (const void *)y && (const void *)dmaps != (const void *)out,
-                "acg_ssim: out and dmaps must not alias an input or each other");
+                "%s: out and dmaps must not alias an input or each other", fn);
     const int Hv = H - SS_HALO, Wv = W - SS_HALO;
     const int ntx = ss_tiles_x(Wv), tiles = ntx * ss_tiles_y(Hv);
-    ACG_REQUIRE((long long)rows * tiles <= 0x7fffffffLL && (long long)rows * C <= 0x7fffffffLL, "acg_ssim: too many fields (rows=%d, C=%d)",
+    ACG_REQUIRE((long long)rows * tiles <= 0x7fffffffLL && (long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn,
                 rows, C);
-    const size_t need = acg_ssim_workspace_bytes(rows, C, H, W);
-    if (ws == nullptr || ws_bytes < need) {
-        acg_set_error("acg_ssim: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ACG_ERR_WORKSPACE;
-    }
-    ACG_REQUIRE((uintptr_t)ws % 16 == 0, "acg_ssim: the workspace must be 16-byte aligned");
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_ssim_workspace_bytes(rows, C, H, W)));
     hipStream_t st = (hipStream_t)stream;
-    const SsField fx = {x, x_row_stride, x_chan_stride, x_pix_stride}, fy = {y, y_row_stride, y_chan_stride, y_pix_stride};
     const SsWin win = ss_window();
     const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
     const long long plane = (long long)rows * C * Hv * Wv;
-    const bool xc4 = ss_c4(x, C, x_row_stride, x_pix_stride, x_chan_stride), yc4 = ss_c4(y, C, y_row_stride, y_pix_stride, y_chan_stride);
+    for (Field &o : f) o.mode = field_load_mode(o, C);
+    const bool xc4 = f[0].mode == FIELD_C4, yc4 = f[1].mode == FIELD_C4;
     const dim3 grid((unsigned)((long long)rows * tiles)), block(SS_THREADS);
-#define SS_FWD(XC, YC)                                                                                                             \
-    hipLaunchKernelGGL((ssim_fwd_kernel<XC, YC>), grid, block, 0, st, fx, fy, C, H, W, x_per_y, ntx, tiles, win, c1, c2, (double *)ws, \
+#define SS_FWD(XC, YC)                                                                                                                 \
+    hipLaunchKernelGGL((ssim_fwd_kernel<XC, YC>), grid, block, 0, st, f[0], f[1], C, H, W, x_per_y, ntx, tiles, win, c1, c2, (double *)ws, \
                        dmaps, plane)
     if (xc4 && yc4) SS_FWD(true, true);
     else if (xc4) SS_FWD(true, false);
@@ -332,32 +313,28 @@ extern "C" int acg_ssim_bwd(const float *dmaps, const float *x, const float *y, 
                             long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                             long long y_chan_stride, float *gx, void *stream)
 {
-    ACG_REQUIRE(dmaps != nullptr && x != nullptr && y != nullptr && g != nullptr && gx != nullptr, "acg_ssim_bwd: null tensor");
-    ACG_REQUIRE(rows >= 1 && C >= 1 && C <= Cp, "acg_ssim_bwd: need rows >= 1 and 1 <= C <= Cp stored channels (rows=%d, C=%d, Cp=%d)",
-                rows, C, Cp);
-    ACG_REQUIRE(ss_shape_ok(rows, C, H, W), "acg_ssim_bwd: fields must be H x W with %d <= H, W <= %d (got %d x %d)", SS_MIN_HW,
-                SS_MAX_HW, H, W);
-    ACG_REQUIRE(x_row_stride >= 1 && x_pix_stride >= 1 && x_chan_stride >= 1 && y_row_stride >= 1 && y_pix_stride >= 1 &&
-                    y_chan_stride >= 1,
-                "acg_ssim_bwd: strides must be positive (x: row %lld, pixel %d, channel %lld; y: row %lld, pixel %d, channel %lld)",
-                x_row_stride, x_pix_stride, x_chan_stride, y_row_stride, y_pix_stride, y_chan_stride);
+    const char *fn = "acg_ssim_bwd";
+    ACG_REQUIRE(dmaps != nullptr && x != nullptr && y != nullptr && g != nullptr && gx != nullptr, "%s: null tensor", fn);
+    Field f[2] = {{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}};
+    ACG_REQUIRE(rows >= 1 && C >= 1 && C <= Cp, "%s: need rows >= 1 and 1 <= C <= Cp stored channels (rows=%d, C=%d, Cp=%d)", fn, rows, C, Cp);
+    ACG_REQUIRE(ss_shape_ok(rows, C, H, W), "%s: fields must be H x W with %d <= H, W <= %d (got %d x %d)", fn, SS_MIN_HW, SS_MAX_HW, H, W);
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, f, 2));
     ACG_REQUIRE((const void *)gx != (const void *)dmaps && (const void *)gx != (const void *)x && (const void *)gx != (const void *)y &&
                     (const void *)gx != (const void *)g,
-                "acg_ssim_bwd: gx must not alias an input");
+                "%s: gx must not alias an input", fn);
     const int Hv = H - SS_HALO, Wv = W - SS_HALO;
     const int ntx = ss_tiles_x(W), tiles = ntx * ss_tiles_y(H);
-    ACG_REQUIRE((long long)rows * tiles <= 0x7fffffffLL && (long long)rows * C <= 0x7fffffffLL, "acg_ssim_bwd: too many fields (rows=%d, C=%d)",
+    ACG_REQUIRE((long long)rows * tiles <= 0x7fffffffLL && (long long)rows * C <= 0x7fffffffLL, "%s: too many fields (rows=%d, C=%d)", fn,
                 rows, C);
     hipStream_t st = (hipStream_t)stream;
-    const SsField fx = {x, x_row_stride, x_chan_stride, x_pix_stride}, fy = {y, y_row_stride, y_chan_stride, y_pix_stride};
     const SsWin win = ss_window();
     const float coef = (float)(-1.0 / ((double)rows * (double)C * (double)Hv * (double)Wv));
     const long long plane = (long long)rows * C * Hv * Wv;
-    const bool xc4 = Cp == 4 && ss_c4(x, C, x_row_stride, x_pix_stride, x_chan_stride) && (uintptr_t)gx % 16 == 0;
-    const bool yc4 = ss_c4(y, C, y_row_stride, y_pix_stride, y_chan_stride);
+    f[0].mode = field_load_mode(f[0], C, false, gx), f[1].mode = field_load_mode(f[1], C);
+    const bool xc4 = Cp == 4 && f[0].mode == FIELD_C4, yc4 = f[1].mode == FIELD_C4;   // x's pixels leave as they came: 16 bytes of gx
     const dim3 grid((unsigned)((long long)rows * tiles)), block(SS_THREADS);
 #define SS_BWD(XC, YC) \
-    hipLaunchKernelGGL((ssim_bwd_kernel<XC, YC>), grid, block, 0, st, dmaps, plane, fx, fy, g, C, Cp, H, W, ntx, tiles, win, coef, gx)
+    hipLaunchKernelGGL((ssim_bwd_kernel<XC, YC>), grid, block, 0, st, dmaps, plane, f[0], f[1], g, C, Cp, H, W, ntx, tiles, win, coef, gx)
     if (xc4 && yc4) SS_BWD(true, true);
     else if (xc4) SS_BWD(true, false);
     else if (yc4) SS_BWD(false, true);

@@ -1546,19 +1546,44 @@ def _check_pairing(what, x_per_y, max_per, rows, rows_y, hw, hw_y):
     return x_per_y
 
 
+def _paired_fields(what, x, y, C, layout_x, layout_y, size, x_per_y, max_per=None, size_y=False):
+    """The preamble of the paired wrappers: both operands detached and contiguous, described by _field_args, the caller's rule
+    size(H, W) -> the extents that must pair (of x; size_y: of y too), x_per_y in 1..max_per (None: the rows of x) and the
+    pairing -> (x, y, rows, rows_y, C, Cp of x, extents, strides of x, strides of y, x_per_y)"""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    rows, C, Cp, H, W, sx = _field_args(x, C, layout_x, what)
+    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, what)
+    hw = size(H, W)
+    hw_y = size(Hy, Wy) if size_y else (Hy, Wy)
+    x_per_y = _check_pairing(what, x_per_y, rows if max_per is None else max_per, rows, rows_y, hw, hw_y)
+    return x, y, rows, rows_y, C, Cp, hw, sx, sy, x_per_y
+
+
+def _out_tensor(what, out, shape, inputs, strict=False):
+    """`out` as the caller gave it, refused unless it has the shape (strict: and is contiguous float32), or a new float32
+    tensor beside inputs[0]; the inputs and out go through _check in between: after the refusals that need no device"""
+    if out is not None and strict and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise _lib.AcgError("%s: out %s %s is not a contiguous float32 %s" % (what, tuple(out.shape), out.dtype, shape))
+    if out is not None and tuple(out.shape) != shape:
+        raise _lib.AcgError("%s: out %s is not %s" % (what, tuple(out.shape), shape))
+    _check(*(tuple(inputs) + (out,)))
+    return torch.empty(shape, device=inputs[0].device, dtype=torch.float32) if out is None else out
+
+
+def _metric_workspace(query, *args):
+    """the workspace an entry point asks for -> (its pointer, None where it asks for none; its bytes)"""
+    nbytes = _lib.query(query, *args)
+    return _ptr(workspace(nbytes, slot=2) if nbytes else None), nbytes
+
+
 def _radial_spectrum(x, C, layout, out=None):
     x = x.contiguous()
     _check(x, out)
     rows, C, Cp, H, W, strides = _field_args(x, C, layout, "radial_spectrum")
     S = _spectrum_size(H, W)
-    nb = S // 2 + 1
-    if out is None:
-        out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, C, nb):
-        raise _lib.AcgError("radial_spectrum: out %s is not (%d, %d, %d)" % (tuple(out.shape), rows, C, nb))
-    nbytes = _lib.query("acg_radial_spectrum_workspace_bytes", rows, C, S)
-    ws = workspace(nbytes, slot=2) if nbytes else None
-    _lib.call("acg_radial_spectrum", _ptr(x), rows, C, S, strides[0], strides[1], strides[2], _ptr(out), _ptr(ws), nbytes, _stream())
+    out = _out_tensor("radial_spectrum", out, (rows, C, S // 2 + 1), (x,))
+    ws, nbytes = _metric_workspace("acg_radial_spectrum_workspace_bytes", rows, C, S)
+    _lib.call("acg_radial_spectrum", _ptr(x), rows, C, S, strides[0], strides[1], strides[2], _ptr(out), ws, nbytes, _stream())
     return out
 
 
@@ -1572,10 +1597,9 @@ def radial_spectrum_bwd(x, g, C, layout):
     if tuple(g.shape) != (rows, C, S // 2 + 1):
         raise _lib.AcgError("radial_spectrum_bwd: the cotangent %s is not (%d, %d, %d)" % (tuple(g.shape), rows, C, S // 2 + 1))
     gx = torch.empty_like(x)
-    nbytes = _lib.query("acg_radial_spectrum_bwd_workspace_bytes", rows, C, S)
-    ws = workspace(nbytes, slot=2)
+    ws, nbytes = _metric_workspace("acg_radial_spectrum_bwd_workspace_bytes", rows, C, S)
     _lib.call("acg_radial_spectrum_bwd", _ptr(x), _ptr(g), rows, C, Cp if layout == "nhwc" else C, S, strides[0], strides[1],
-              strides[2], _ptr(gx), _ptr(ws), nbytes, _stream())
+              strides[2], _ptr(gx), ws, nbytes, _stream())
     return gx
 
 
@@ -1627,21 +1651,12 @@ def cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
     x_per_y members of an ensemble share one truth.  Each operand has its own layout ("nhwc" or "nchw", as radial_spectrum
     takes them).  One launch up to S = 64, a row and a column pass above; nothing is read back to the host.  Not
     differentiable."""
-    x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "cross_spectrum")
-    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "cross_spectrum")
-    S, Sy = _spectrum_size(H, W), _spectrum_size(Hy, Wy)
-    x_per_y = _check_pairing("cross_spectrum", x_per_y, rows, rows, rows_y, (S, S), (Sy, Sy))
-    nb = S // 2 + 1
-    if out is not None and tuple(out.shape) != (rows, C, 3, nb):
-        raise _lib.AcgError("cross_spectrum: out %s is not (%d, %d, 3, %d)" % (tuple(out.shape), rows, C, nb))
-    _check(x, y, out)                                              # after the refusals that need no device
-    if out is None:
-        out = torch.empty((rows, C, 3, nb), device=x.device, dtype=torch.float32)
-    nbytes = _lib.query("acg_cross_spectrum_workspace_bytes", rows, C, S)
-    ws = workspace(nbytes, slot=2) if nbytes else None
+    x, y, rows, _, C, _, (S, _), sx, sy, x_per_y = _paired_fields("cross_spectrum", x, y, C, layout_x, layout_y,
+                                                                  lambda H, W: (_spectrum_size(H, W),) * 2, x_per_y, size_y=True)
+    out = _out_tensor("cross_spectrum", out, (rows, C, 3, S // 2 + 1), (x, y))
+    ws, nbytes = _metric_workspace("acg_cross_spectrum_workspace_bytes", rows, C, S)
     _lib.call("acg_cross_spectrum", _ptr(x), _ptr(y), rows, x_per_y, C, S, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(out),
-              _ptr(ws), nbytes, _stream())
+              ws, nbytes, _stream())
     return out
 
 
@@ -1671,16 +1686,9 @@ def field_spectrum(x, C, layout, out=None):
     x = x.detach().contiguous()
     rows, C, _, H, W, strides = _field_args(x, C, layout, "field_spectrum")
     H, W = _field_spectrum_size("field_spectrum", H, W)
-    nb = field_spectrum_bins(H, W)
-    if out is not None and tuple(out.shape) != (rows, C, nb):
-        raise _lib.AcgError("field_spectrum: out %s is not (%d, %d, %d)" % (tuple(out.shape), rows, C, nb))
-    _check(x, out)
-    if out is None:
-        out = torch.empty((rows, C, nb), device=x.device, dtype=torch.float32)
-    nbytes = _lib.query("acg_field_spectrum_workspace_bytes", rows, C, H, W)
-    ws = workspace(nbytes, slot=2) if nbytes else None
-    _lib.call("acg_field_spectrum", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(out), _ptr(ws), nbytes,
-              _stream())
+    out = _out_tensor("field_spectrum", out, (rows, C, field_spectrum_bins(H, W)), (x,))
+    ws, nbytes = _metric_workspace("acg_field_spectrum_workspace_bytes", rows, C, H, W)
+    _lib.call("acg_field_spectrum", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(out), ws, nbytes, _stream())
     return out
 
 
@@ -1689,21 +1697,13 @@ def field_cross_spectrum(x, y, C, layout_x, layout_y, x_per_y=1, out=None):
     (rows, C, 3, nb) float32 on the device: per ring of field_spectrum the means of Pxx, Pyy and Cxy = Re(X conj Y) / (H W).
     Pairing and layouts as cross_spectrum; Pxx has the bits of field_spectrum(x); H = W a power of two gives
     cross_spectrum's bits.  The triples go to coherence_summary as cross_spectrum's do.  Not differentiable."""
-    x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "field_cross_spectrum")
-    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "field_cross_spectrum")
-    H, W = _field_spectrum_size("field_cross_spectrum", H, W)
-    x_per_y = _check_pairing("field_cross_spectrum", x_per_y, rows, rows, rows_y, (H, W), (Hy, Wy))
-    nb = field_spectrum_bins(H, W)
-    if out is not None and tuple(out.shape) != (rows, C, 3, nb):
-        raise _lib.AcgError("field_cross_spectrum: out %s is not (%d, %d, 3, %d)" % (tuple(out.shape), rows, C, nb))
-    _check(x, y, out)                                              # after the refusals that need no device
-    if out is None:
-        out = torch.empty((rows, C, 3, nb), device=x.device, dtype=torch.float32)
-    nbytes = _lib.query("acg_field_cross_spectrum_workspace_bytes", rows, C, H, W)
-    ws = workspace(nbytes, slot=2) if nbytes else None
+    x, y, rows, _, C, _, (H, W), sx, sy, x_per_y = _paired_fields(
+        "field_cross_spectrum", x, y, C, layout_x, layout_y,
+        lambda H, W: _field_spectrum_size("field_cross_spectrum", H, W), x_per_y)
+    out = _out_tensor("field_cross_spectrum", out, (rows, C, 3, field_spectrum_bins(H, W)), (x, y))
+    ws, nbytes = _metric_workspace("acg_field_cross_spectrum_workspace_bytes", rows, C, H, W)
     _lib.call("acg_field_cross_spectrum", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2],
-              _ptr(out), _ptr(ws), nbytes, _stream())
+              _ptr(out), ws, nbytes, _stream())
     return out
 
 
@@ -1757,9 +1757,8 @@ def field_sort(x, C, layout, want_rank=True):
     _check(x)
     srt = torch.empty((rows, C, P), device=x.device, dtype=torch.float32)
     rank = torch.empty((rows, C, P), device=x.device, dtype=torch.int32) if want_rank else None
-    nbytes = _lib.query("acg_field_sort_workspace_bytes", rows, C, H, W)
-    ws = workspace(nbytes, slot=2) if nbytes else None
-    _lib.call("acg_field_sort", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(srt), _ptr(rank), _ptr(ws), nbytes,
+    ws, nbytes = _metric_workspace("acg_field_sort_workspace_bytes", rows, C, H, W)
+    _lib.call("acg_field_sort", _ptr(x), rows, C, H, W, strides[0], strides[1], strides[2], _ptr(srt), _ptr(rank), ws, nbytes,
               _stream())
     return srt, rank
 
@@ -1781,9 +1780,8 @@ class MarginalLoss(torch.autograd.Function):
         sy, _ = field_sort(y, C, layout, want_rank=False)
         d = torch.empty((C, P), device=x.device, dtype=torch.float32)
         loss = torch.empty((), device=x.device, dtype=torch.float32)
-        nbytes = _lib.query("acg_marginal_loss_workspace_bytes", C, P)
-        ws = workspace(nbytes, slot=2)
-        _lib.call("acg_marginal_loss_fwd", _ptr(sx), rows, _ptr(sy), rows_y, C, P, _ptr(d), _ptr(loss), _ptr(ws), nbytes, _stream())
+        ws, nbytes = _metric_workspace("acg_marginal_loss_workspace_bytes", C, P)
+        _lib.call("acg_marginal_loss_fwd", _ptr(sx), rows, _ptr(sy), rows_y, C, P, _ptr(d), _ptr(loss), ws, nbytes, _stream())
         ctx.cfg = (rows, C, Cp if layout == "nhwc" else C, H, W, strides, tuple(x.shape))
         if rank is not None:
             ctx.save_for_backward(d, rank)
@@ -1830,10 +1828,9 @@ def _ssim_range(what, data_range):
 
 def _ssim_call(x, y, sizes, sx, sy, x_per_y, L, out, maps):
     rows, C, H, W = sizes
-    nbytes = _lib.query("acg_ssim_workspace_bytes", rows, C, H, W)
-    ws = workspace(nbytes, slot=2)
+    ws, nbytes = _metric_workspace("acg_ssim_workspace_bytes", rows, C, H, W)
     _lib.call("acg_ssim", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], ctypes.c_float(L),
-              _ptr(out), _ptr(maps), _ptr(ws), nbytes, _stream())
+              _ptr(out), _ptr(maps), ws, nbytes, _stream())
 
 
 def ssim(x, y, C, layout_x, layout_y, x_per_y=1, data_range=2.0, out=None):
@@ -1843,17 +1840,10 @@ def ssim(x, y, C, layout_x, layout_y, x_per_y=1, data_range=2.0, out=None):
     for fields in [-1, 1]; tests/ssim_ref.py).  Row r of x pairs with row r / x_per_y of y.  Each operand has its own layout
     ("nhwc" or "nchw", as radial_spectrum takes them; padded channels never reach a result).  11 <= H, W <= 1024.  Two
     launches, the same bits for every layout; nothing is read back to the host.  Not differentiable (ssim_loss is)."""
-    x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "ssim")
-    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "ssim")
-    H, W = _ssim_size("ssim", H, W)
-    x_per_y = _check_pairing("ssim", x_per_y, rows, rows, rows_y, (H, W), (Hy, Wy))
+    x, y, rows, _, C, _, (H, W), sx, sy, x_per_y = _paired_fields("ssim", x, y, C, layout_x, layout_y,
+                                                                  lambda H, W: _ssim_size("ssim", H, W), x_per_y)
     L = _ssim_range("ssim", data_range)
-    if out is not None and (tuple(out.shape) != (rows, C, 2) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise _lib.AcgError("ssim: out %s %s is not a contiguous float32 (%d, %d, 2)" % (tuple(out.shape), out.dtype, rows, C))
-    _check(x, y, out)                                              # after the refusals that need no device
-    if out is None:
-        out = torch.empty((rows, C, 2), device=x.device, dtype=torch.float32)
+    out = _out_tensor("ssim", out, (rows, C, 2), (x, y), strict=True)
     _ssim_call(x, y, (rows, C, H, W), sx, sy, x_per_y, L, out, None)
     return out
 
@@ -1865,14 +1855,10 @@ class SsimLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, C, layout, data_range):
-        x, y = x.detach().contiguous(), y.detach().contiguous()
-        rows, C, Cp, H, W, strides = _field_args(x, C, layout, "ssim_loss")
-        rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout, "ssim_loss")
-        H, W = _ssim_size("ssim_loss", H, W)
-        _check_pairing("ssim_loss", 1, 1, rows, rows_y, (H, W), (Hy, Wy))
+        x, y, rows, _, C, Cp, (H, W), strides, sy, _ = _paired_fields("ssim_loss", x, y, C, layout, layout,
+                                                                      lambda H, W: _ssim_size("ssim_loss", H, W), 1, max_per=1)
         L = _ssim_range("ssim_loss", data_range)
-        _check(x, y)
-        out = torch.empty((rows, C, 2), device=x.device, dtype=torch.float32)
+        out = _out_tensor("ssim_loss", None, (rows, C, 2), (x, y))
         maps = None
         if ctx.needs_input_grad[0]:
             maps = torch.empty((3, rows, C, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1), device=x.device, dtype=torch.float32)
@@ -1920,6 +1906,12 @@ def check_windows(windows):
     return w
 
 
+def _fss_size(H, W):
+    if not (1 <= H <= FSS_MAX_HW and 1 <= W <= FSS_MAX_HW):
+        raise _lib.AcgError("fss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (FSS_MAX_HW, H, W))
+    return H, W
+
+
 def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=False, out=None):
     """acg_fss: the fractions-skill-score triples of the C valid channels of x against y -> (rows, C, T, nw, 3) int64 on the
     device: per threshold thresholds[c][t] and odd window n the sums over the H x W cells of cf^2, co^2 and cf co, cf / co the
@@ -1929,13 +1921,8 @@ def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=Fa
     (rows / x_per_y, C, T, nw, 3) the triples (sum E^2, sum co^2, sum E co) of E = the members' summed counts; with x_per_y = 1
     ens equals out.  `out`: the (rows, C, T, nw, 3) int64 tensor to write, or with ensemble=True the pair (out, ens).
     Sum the triples over a set of pairs, then ops.fss_summary.  Nothing is read back to the host.  Not differentiable."""
-    x, y = x.detach().contiguous(), y.detach().contiguous()
-    rows, C, _, H, W, sx = _field_args(x, C, layout_x, "fss")
-    rows_y, _, _, Hy, Wy, sy = _field_args(y, C, layout_y, "fss")
-    for h, w in ((H, W), (Hy, Wy)):
-        if not (1 <= h <= FSS_MAX_HW and 1 <= w <= FSS_MAX_HW):
-            raise _lib.AcgError("fss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (FSS_MAX_HW, h, w))
-    x_per_y = _check_pairing("fss", x_per_y, FSS_MAX_M, rows, rows_y, (H, W), (Hy, Wy))
+    x, y, rows, rows_y, C, _, (H, W), sx, sy, x_per_y = _paired_fields("fss", x, y, C, layout_x, layout_y, _fss_size, x_per_y,
+                                                                       max_per=FSS_MAX_M, size_y=True)
     try:
         win = check_windows(windows)
     except ValueError as e:
@@ -1963,10 +1950,9 @@ def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=Fa
         o = torch.empty(shapes[0], device=x.device, dtype=torch.int64)
     if ensemble and e is None:
         e = torch.empty(shapes[1], device=x.device, dtype=torch.int64)
-    nbytes = _lib.query("acg_fss_workspace_bytes", rows, x_per_y, C, H, W, T, nw, int(ensemble))
-    ws = workspace(nbytes, slot=2)
+    ws, nbytes = _metric_workspace("acg_fss_workspace_bytes", rows, x_per_y, C, H, W, T, nw, int(ensemble))
     _lib.call("acg_fss", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
-              (ctypes.c_int * nw)(*win), nw, _ptr(o), _ptr(e), _ptr(ws), nbytes, _stream())
+              (ctypes.c_int * nw)(*win), nw, _ptr(o), _ptr(e), ws, nbytes, _stream())
     return (o, e) if ensemble else o
 
 
