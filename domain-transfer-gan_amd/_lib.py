@@ -189,6 +189,8 @@ SIGNATURES = {
     "acg_marginal_loss_fwd": (c_int, [_P, c_int, _P, c_int, c_int, ctypes.c_longlong, _P, _P, _P, c_size_t, _P]),
     "acg_marginal_loss_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
                                       _P, _P]),
+    "acg_marginal_scores": (c_int, [_P, _P, c_int, c_int, c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double), c_int, _P,
+                                    c_int, _P, _P, _P, _P]),
     "acg_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "acg_ssim": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_longlong,
                          c_int, ctypes.c_longlong, c_float, _P, _P, _P, c_size_t, _P]),

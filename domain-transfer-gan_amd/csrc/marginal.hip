@@ -1,6 +1,7 @@
 // The marginal loss (ops.field_sort, ops.marginal_loss, --lambda_marg_A / --lambda_marg_B): a stable sort of every field with
 // its permutation, the squared distance of two batch-mean quantile functions on the sorted fields and its data gradient.
-// tests/marginal_ref.py states the definition.
+// tests/marginal_ref.py states the definition.  At the end of the file, the evaluator on the same sorted fields
+// (acg_marginal_scores: ops.sorted_scores, ops.marginal_scores, --metric marginal; tests/marginal_eval_ref.py).
 //
 // The sort is a bitonic network on 64-bit words (key << 32) | pixel: key is the order-preserving image of the float's bits
 // after -0.0 -> +0.0, so the words of a field are distinct and their order is the stable order of the values.  A field is
@@ -416,5 +417,124 @@ extern "C" int acg_marginal_loss_bwd(const float *d, const int *rank, const floa
                            row_stride, pix_stride, chan_stride, coef, gx);
     acg_note_kernel(c4 ? "marginal_bwd<c4>" : "marginal_bwd<scalar>");
     ACG_CHECK_LAUNCH("acg_marginal_loss_bwd");
+    return ACG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The evaluator on the sorted fields (ops.sorted_scores, ops.marginal_scores, --metric marginal; tests/marginal_eval_ref.py):
+// per (row, channel) the Wasserstein distances w1 = mean |sx - sy| and w2sq = mean (sx - sy)^2 against the paired sorted truth,
+// the order-statistic quantiles at L levels and the counts of values below E edges.  One workgroup per field streams sx and sy
+// once.  A thread sums the groups of four neighbouring pixels t, t + MQ_THREADS, .. in that order in double, then one of the
+// P % 4 last pixels; a shuffle tree per wave, the waves in order: the same bits on every call, whatever the alignment of the
+// operands.  The quantile is s[lo] + frac (s[hi] - s[lo]) in double without contraction, rounded once; a count
+// is a lower bound by bisection, at most 21 steps, every probe inside the field whatever the values are.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int MQ_THREADS = 1024, MQ_WAVES = MQ_THREADS / 64;
+constexpr int MQ_MAX_L = 16, MQ_MAX_E = 256;
+
+struct MqLevels {
+    double v[MQ_MAX_L];
+};
+
+__device__ __forceinline__ double mq_wave_sum(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(MQ_THREADS) void marginal_scores_kernel(FieldSrc<2> src, int P, bool paired, MqLevels levels, int L,
+                                                                     const float *__restrict__ edges, int E, double *__restrict__ w,
+                                                                     float *__restrict__ q, int *__restrict__ below)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[2][MQ_WAVES];
+    const int t = threadIdx.x, p = blockIdx.x;
+    int c;
+    const float *sx = field_first(src, 0, p, c);
+    if (paired) {
+        const float *sy = field_first(src, 1, p, c);
+        const int G = P >> 2;
+        double a = 0.0, b = 0.0;
+        for (int g = t; g < G; g += MQ_THREADS) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double d = (double)sx[4 * g + i] - (double)sy[4 * g + i];
+                a += fabs(d);
+                b += d * d;
+            }
+        }
+        if (4 * G + t < P) {
+            const double d = (double)sx[4 * G + t] - (double)sy[4 * G + t];
+            a += fabs(d);
+            b += d * d;
+        }
+        a = mq_wave_sum(a);
+        b = mq_wave_sum(b);
+        if ((t & 63) == 0) red[0][t >> 6] = a, red[1][t >> 6] = b;
+        __syncthreads();
+        if (t == 0) {
+            a = red[0][0], b = red[1][0];
+            for (int i = 1; i < MQ_WAVES; ++i) a += red[0][i], b += red[1][i];
+            w[2 * (long long)p] = a / (double)P;
+            w[2 * (long long)p + 1] = b / (double)P;
+        }
+    }
+    for (int l = t; l < L; l += MQ_THREADS) {
+        const double pos = levels.v[l] * (double)(P - 1);
+        int lo = (int)floor(pos);
+        lo = lo < 0 ? 0 : (lo > P - 1 ? P - 1 : lo);                   // a level lies in [0, 1]: never read outside the field
+        const int hi = lo + 1 < P ? lo + 1 : P - 1;
+        const double frac = pos - (double)lo, slo = (double)sx[lo], shi = (double)sx[hi];
+        q[(long long)p * L + l] = (float)(slo + frac * (shi - slo));
+    }
+    for (int e = t; e < E; e += MQ_THREADS) {
+        const float edge = edges[c * E + e];
+        int lo = 0, hi = P;                                            // the first position whose value is not below the edge
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (sx[mid] < edge) lo = mid + 1;
+            else hi = mid;
+        }
+        below[(long long)p * E + e] = lo;
+    }
+}
+
+extern "C" int acg_marginal_scores(const float *sx, const float *sy, int rows, int x_per_y, int C, long long P, const double *levels,
+                                   int L, const float *edges, int E, double *w, float *q, int *below, void *stream)
+{
+    const char *fn = "acg_marginal_scores";
+    ACG_REQUIRE(sx != nullptr, "acg_marginal_scores: null sx");
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, nullptr, 0));
+    ACG_REQUIRE(P >= 1 && P <= MS_MAX_P, "acg_marginal_scores: fields must hold 1 .. %d pixels (P=%lld)", MS_MAX_P, P);
+    ACG_REQUIRE(L >= 0 && L <= MQ_MAX_L && E >= 0 && E <= MQ_MAX_E,
+                "acg_marginal_scores: need 0 .. %d levels and 0 .. %d edges (L=%d, E=%d)", MQ_MAX_L, MQ_MAX_E, L, E);
+    ACG_REQUIRE(sy != nullptr || L > 0 || E > 0, "acg_marginal_scores: nothing to compute (no sy, no levels, no edges)");
+    ACG_REQUIRE((w != nullptr) == (sy != nullptr), "acg_marginal_scores: null or stray w: it is written exactly when sy is given");
+    ACG_REQUIRE((q != nullptr) == (L > 0) && (L == 0 || levels != nullptr),
+                "acg_marginal_scores: null or stray q or levels: q is written exactly when L > 0 (L=%d)", L);
+    ACG_REQUIRE((below != nullptr) == (E > 0) && (E == 0 || edges != nullptr),
+                "acg_marginal_scores: null or stray below or edges: below is written exactly when E > 0 (E=%d)", E);
+    FieldSrc<2> src = {};
+    src.f[0] = {sx, (long long)C * P, P, 1, FIELD_SCALAR};
+    src.f[1] = {sy, (long long)C * P, P, 1, FIELD_SCALAR};
+    src.C = C;
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, src.f, sy != nullptr ? 2 : 1));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, sy != nullptr ? x_per_y : 1, rows));
+    src.x_per_y = sy != nullptr ? x_per_y : 1;
+    MqLevels lv = {};
+    for (int l = 0; l < L; ++l) {
+        ACG_REQUIRE(levels[l] >= 0.0 && levels[l] <= 1.0, "acg_marginal_scores: level %d must lie in [0, 1] (got %g)", l, levels[l]);
+        lv.v[l] = levels[l];
+    }
+    const void *in[3] = {sx, sy, edges}, *out[3] = {w, q, below};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            ACG_REQUIRE(out[i] == nullptr || (out[i] != in[j] && (j <= i || out[i] != out[j])),
+                        "acg_marginal_scores: w, q and below must not alias an input or each other");
+    ACG_REQUIRE((long long)rows * C <= 0x7fffffffLL, "acg_marginal_scores: too many fields (rows=%d, C=%d)", rows, C);
+    hipLaunchKernelGGL(marginal_scores_kernel, dim3((unsigned)(rows * C)), dim3(MQ_THREADS), 0, (hipStream_t)stream, src, (int)P,
+                       sy != nullptr, lv, L, edges, E, w, q, below);
+    acg_note_kernel("marginal_scores<%s>", sy == nullptr ? "single" : "paired");
+    ACG_CHECK_LAUNCH("acg_marginal_scores");
     return ACG_OK;
 }

@@ -666,6 +666,48 @@ class _Base(object):
                 ops.ssim(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
         return out
 
+    def translate_marginal(self, real_A, n_samples, real_B, levels, edges, z=None, chunk=None):
+        """Whether A -> B has the right values: per channel the Wasserstein distances w1 and w2sq of the value distribution of
+        a field against that of its paired real_B, its quantiles at `levels` and its counts of values below `edges`
+        (ops.sorted_scores on ops.field_sort's sorted fields), of each of n_samples translations of every input, one truth per
+        M members, of their per-pixel mean (_ensemble_mean: smoother than any member, so its tails are short) and, without a
+        distance, of the truth itself.  Per group the truth is sorted once and shared by the member and the ensemble-mean call.
+        levels: at most 16 inside [0, 1] (ops.check_levels); edges: (C, E), E <= 256, moved to the device once; at least one
+        of each.  z, chunk and the refusals: plan_ensemble, real_B required; the members: ensemble_groups.  H W <= 2^20.
+        Returns device tensors, w float64, q float32, below int32: members = dict(w (N, M, C, 2), q (N, M, C, L), below
+        (N, M, C, E)), ens_mean = dict(w (N, C, 2), q (N, C, L), below (N, C, E)) and target = dict(q (N, C, L), below
+        (N, C, E)).  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_marginal", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
+        lv = ops.check_levels(levels)
+        e = edges
+        if not torch.is_tensor(e):
+            e = torch.tensor(e, dtype=torch.float32)
+        e = e.detach().to(device=real_A.device, dtype=torch.float32).contiguous()        # once, not per group
+        if not lv or e.dim() != 2 or e.size(0) != C or not 1 <= e.size(1) <= ops.MARG_MAX_EDGES:
+            raise ValueError("translate_marginal: need 1..%d levels and edges (C, E) with C=%d and 1 <= E <= %d (got %d levels, "
+                             "edges %s)" % (ops.MARG_MAX_LEVELS, C, ops.MARG_MAX_EDGES, len(lv), tuple(e.shape)))
+        L, E = len(lv), e.size(1)
+        dev = real_A.device
+
+        def outputs(lead, w):
+            o = dict(q=torch.empty(lead + (C, L), device=dev, dtype=torch.float32),
+                     below=torch.empty(lead + (C, E), device=dev, dtype=torch.int32))
+            if w:
+                o["w"] = torch.empty(lead + (C, 2), device=dev, dtype=torch.float64)
+            return o
+        out = dict(members=outputs((N, M), True), ens_mean=outputs((N,), True), target=outputs((N,), False))
+        real_B = real_B.detach().contiguous()
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                sb, _ = ops.field_sort(real_B[g0:g0 + n], C, "nchw", want_rank=False)
+                sm, _ = ops.field_sort(members, C, "nhwc", want_rank=False)
+                ops.sorted_scores(sm, sb, lv, e, x_per_y=M,
+                                  out={k: v[g0:g0 + n].view((n * M,) + tuple(v.shape[2:])) for k, v in out["members"].items()})
+                se, _ = ops.field_sort(_ensemble_mean(members, M, C), C, "nchw", want_rank=False)
+                ops.sorted_scores(se, sb, lv, e, out={k: v[g0:g0 + n] for k, v in out["ens_mean"].items()})
+                ops.sorted_scores(sb, None, lv, e, out={k: v[g0:g0 + n] for k, v in out["target"].items()})
+        return out
+
     def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
         """Whether A -> B puts its threshold exceedances close enough: the fractions-skill-score triples (ops.fss: per
         channel, threshold and window the sums of cf^2, co^2 and cf co of the window counts of the events, x the translation,

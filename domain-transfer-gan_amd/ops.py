@@ -1808,6 +1808,135 @@ def marginal_loss(x, y, C, layout):
 
 
 # ----------------------------------------------------------------------------------------------
+# the marginal evaluator (model.translate_marginal, test.py --metric marginal): Wasserstein distances, quantiles and counts
+# below thresholds from the sorted fields
+# ----------------------------------------------------------------------------------------------
+MARG_MAX_LEVELS, MARG_MAX_EDGES = 16, 256
+
+
+def check_levels(levels):
+    """-> the quantile levels as a tuple of floats; ValueError unless at most 16 of them, each inside [0, 1] (any order)"""
+    q = tuple(float(v) for v in levels)
+    if len(q) > MARG_MAX_LEVELS:
+        raise ValueError("need at most %d quantile levels (got %d)" % (MARG_MAX_LEVELS, len(q)))
+    if any(not 0.0 <= v <= 1.0 for v in q):
+        raise ValueError("quantile levels must lie inside [0, 1] (got %s)" % (q,))
+    return q
+
+
+def _marginal_edges(what, edges, C, device):
+    """edges as sorted_scores takes them -> a contiguous (C, E) float32 tensor on the device (a host array is copied), or None"""
+    if edges is None:
+        return None
+    if not torch.is_tensor(edges):
+        import numpy as np
+        edges = torch.from_numpy(np.array(edges, dtype=np.float32, order="C"))       # a copy: the caller's array may be read-only
+    if edges.dim() != 2 or edges.size(0) != C or edges.size(1) > MARG_MAX_EDGES or edges.dtype != torch.float32:
+        raise _lib.AcgError("%s: edges must be (C, E) float32 with C=%d and E <= %d (got %s %s)"
+                            % (what, C, MARG_MAX_EDGES, tuple(edges.shape), edges.dtype))
+    return edges.detach().to(device).contiguous() if edges.size(1) else None
+
+
+def sorted_scores(sx, sy, levels=(), edges=None, x_per_y=1, out=None):
+    """acg_marginal_scores on already sorted fields: sx (rows, C, P) float32, every field ascending (field_sort's first
+    result), sy (rows / x_per_y, C, P) the same of the paired truths, or None; row r of sx pairs with row r / x_per_y of sy.
+    -> dict of device tensors, holding only what was asked for:
+      w     (rows, C, 2) float64, with sy: w1 = mean_k |sx[k] - sy[k]| and w2sq = mean_k (sx[k] - sy[k])^2, the 1-Wasserstein
+            and the squared 2-Wasserstein distance of the two fields' value distributions, summed in double;
+      q     (rows, C, L) float32, with L = len(levels) > 0 (check_levels): np.quantile(field, level, method="linear"),
+            evaluated in double and rounded once;
+      below (rows, C, E) int32, with edges (C, E) float32 (device tensor or host array), E > 0: the number of values below
+            edges[c][e], exact; P - below counts fss's events [x >= thr].
+    `out`: such a dict to write instead (e.g. slices of larger tensors), with exactly those entries.  One launch, the same bits
+    on every call; nothing is read back to the host.  Not differentiable."""
+    what = "sorted_scores"
+    if sx.dim() != 3 or (sy is not None and sy.dim() != 3):
+        raise _lib.AcgError("%s: sorted fields are (rows, C, P) (got %s, %s)"
+                            % (what, tuple(sx.shape), None if sy is None else tuple(sy.shape)))
+    sx = sx.detach().contiguous()
+    rows, C, P = (int(v) for v in sx.shape)
+    if rows < 1 or C < 1 or not 1 <= P <= FIELD_SORT_MAX_P:
+        raise _lib.AcgError("%s: need rows >= 1, C >= 1 and fields of 1 .. %d pixels (got %s)" % (what, FIELD_SORT_MAX_P, tuple(sx.shape)))
+    if sy is not None:
+        sy = sy.detach().contiguous()
+        if sy.size(1) != C:
+            raise _lib.AcgError("%s: %d channels against %d" % (what, C, sy.size(1)))
+        x_per_y = _check_pairing(what, x_per_y, rows, rows, sy.size(0), (1, P), (1, sy.size(2)))
+    else:
+        x_per_y = 1
+    try:
+        lv = check_levels(levels)
+    except ValueError as e:
+        raise _lib.AcgError("%s: %s" % (what, e))
+    edges = _marginal_edges(what, edges, C, sx.device)
+    L, E = len(lv), 0 if edges is None else int(edges.size(1))
+    if sy is None and L == 0 and E == 0:
+        raise _lib.AcgError("%s: nothing to compute (no sy, no levels, no edges)" % what)
+    want = {}
+    if sy is not None:
+        want["w"] = ((rows, C, 2), torch.float64)
+    if L:
+        want["q"] = ((rows, C, L), torch.float32)
+    if E:
+        want["below"] = ((rows, C, E), torch.int32)
+    if out is not None:
+        if set(out) != set(want):
+            raise _lib.AcgError("%s: out holds %s, the call writes %s" % (what, sorted(out), sorted(want)))
+        for k, (shape, dtype) in want.items():
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+                raise _lib.AcgError("%s: out[%r] %s %s is not a contiguous %s %s on the device"
+                                    % (what, k, tuple(t.shape), t.dtype, dtype, shape))
+    _check(sx, sy, edges)                                          # after the refusals that need no device
+    if out is None:
+        out = {k: torch.empty(shape, device=sx.device, dtype=dtype) for k, (shape, dtype) in want.items()}
+    _lib.call("acg_marginal_scores", _ptr(sx), _ptr(sy), rows, x_per_y, C, P, (ctypes.c_double * max(L, 1))(*lv), L, _ptr(edges), E,
+              _ptr(out.get("w")), _ptr(out.get("q")), _ptr(out.get("below")), _stream())
+    return out
+
+
+def marginal_scores(x, y, C, layout_x, layout_y, levels=(), edges=None, x_per_y=1):
+    """The value distribution of the C valid channels of every field of x against its paired truth y (or None): field_sort of
+    both operands (no ranks), then sorted_scores -> its dict: w (rows, C, 2) float64 with y, q (rows, C, L) float32 with levels,
+    below (rows, C, E) int32 with edges.  Row r of x pairs with row r / x_per_y of y.  Each operand has its own layout ("nhwc"
+    or "nchw", as field_sort takes them; padded channels never reach a result).  H W <= 2^20.  Nothing is read back to the
+    host.  Not differentiable."""
+    what = "marginal_scores"
+    if y is None:
+        x = x.detach().contiguous()
+        rows, C, _, H, W, _ = _field_args(x, C, layout_x, what)
+        _field_sort_size(what, H, W)
+    else:
+        x, y, rows, _, C, _, _, _, _, x_per_y = _paired_fields(what, x, y, C, layout_x, layout_y,
+                                                              lambda H, W: (1, _field_sort_size(what, H, W)), x_per_y, size_y=True)
+    try:
+        lv = check_levels(levels)
+    except ValueError as e:
+        raise _lib.AcgError("%s: %s" % (what, e))
+    edges = _marginal_edges(what, edges, C, x.device)
+    if y is None and not lv and edges is None:                     # before the sorts are launched
+        raise _lib.AcgError("%s: nothing to compute (no y, no levels, no edges)" % what)
+    sx, _ = field_sort(x, C, layout_x, want_rank=False)
+    sy = None if y is None else field_sort(y, C, layout_y, want_rank=False)[0]
+    return sorted_scores(sx, sy, lv, edges, x_per_y)
+
+
+def marginal_summary(below, cells, below_real, cells_real):
+    """counts below the E edges summed over a set of fields (C, E) int64 with the number of cells they were counted in, of the
+    generated and of the real fields -> dict of float64 arrays on the host: cdf, cdf_real (C, E) = below / cells, the pooled
+    empirical distribution functions at the edges (strictly below), and ks (C,), the Kolmogorov-Smirnov distance at the edges:
+    the maximum over the edges of |cdf - cdf_real| (0 without edges)"""
+    import numpy as np
+    b, r = np.asarray(below, dtype=np.int64), np.asarray(below_real, dtype=np.int64)
+    if b.ndim != 2 or b.shape != r.shape or int(cells) < 1 or int(cells_real) < 1:
+        raise ValueError("marginal_summary: need two (C, E) count arrays and positive cell counts (got %s, %s, %s, %s)"
+                         % (b.shape, r.shape, cells, cells_real))
+    cdf, cdf_real = b.astype(np.float64) / float(int(cells)), r.astype(np.float64) / float(int(cells_real))
+    ks = np.abs(cdf - cdf_real).max(axis=1) if b.shape[1] else np.zeros(b.shape[0], dtype=np.float64)
+    return dict(cdf=cdf, cdf_real=cdf_real, ks=ks)
+
+
+# ----------------------------------------------------------------------------------------------
 # structural similarity (model._ssim_terms, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, test.py --metric ssim)
 # ----------------------------------------------------------------------------------------------
 SSIM_WINDOW, SSIM_MAX_HW = 11, 1024

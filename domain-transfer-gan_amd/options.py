@@ -185,7 +185,8 @@ class TestOptions(object):
     --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric);
     the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap; the metric
     `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap); the metric `ssim`
-    (structural similarity of the paired translations, reuses --n_samples)."""
+    (structural similarity of the paired translations, reuses --n_samples); the metric `marginal` (Wasserstein distances,
+    quantiles and distribution functions of the fields' values, reuses --n_samples) with --marg_levels and --marg_bins."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -195,10 +196,10 @@ class TestOptions(object):
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
                                  choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate',
-                                          'field_spectrum', 'ssim'])
+                                          'field_spectrum', 'ssim', 'marginal'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim / marginal: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
         self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),
@@ -210,6 +211,12 @@ class TestOptions(object):
         self.parser.add_argument('--fss_windows', type=_fss_windows, default=(1, 3, 5, 9, 17, 33),
                                  help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
                                       '(the cell itself: bias, CSI, base rate) is put in front if absent')
+        self.parser.add_argument('--marg_levels', type=_marg_levels, default=(0.0, 0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999, 1.0),
+                                 help='--metric marginal: comma-separated quantile levels inside [0, 1], at most 16')
+        self.parser.add_argument('--marg_bins', type=_marg_bins, default=100,
+                                 help='--metric marginal: B in 2..257; the distribution functions are compared at the B - 1 '
+                                      'quantiles k / B of the real training fields, per channel (trainB for A -> B, trainA for '
+                                      'B -> A)')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
@@ -252,13 +259,13 @@ def _split(name, s, kind, noun):
         raise argparse.ArgumentTypeError("%s: not a comma-separated list of %s: %r" % (name, noun, s))
 
 
-def _floats(name, ok, rule, ordered=False):
-    """the argparse type of a comma-separated list of 1 to 8 floats that each pass `ok`, ascending where `ordered`; `rule`
-    words the refusal"""
+def _floats(name, ok, rule, ordered=False, most=8):
+    """the argparse type of a comma-separated list of 1 to `most` floats that each pass `ok`, ascending where `ordered`;
+    `rule` words the refusal"""
     def parse(s):
         v = tuple(_split(name, s, float, "numbers"))
-        if not 1 <= len(v) <= 8 or not all(ok(x) for x in v) or (ordered and any(b < a for a, b in zip(v, v[1:]))):
-            raise argparse.ArgumentTypeError("%s: 1 to 8 %s (got %r)" % (name, rule, s))
+        if not 1 <= len(v) <= most or not all(ok(x) for x in v) or (ordered and any(b < a for a, b in zip(v, v[1:]))):
+            raise argparse.ArgumentTypeError("%s: 1 to %d %s (got %r)" % (name, most, rule, s))
         return v
     return parse
 
@@ -267,6 +274,14 @@ _level = lambda x: 0.0 <= x <= 1.0
 _quantiles = _floats("--quantiles", _level, "levels, sorted inside [0, 1]", ordered=True)
 _fss_quantiles = _floats("--fss_quantiles", _level, "levels inside [0, 1]")
 _fss_thresholds = _floats("--fss_thresholds", lambda x: x == x, "numbers")
+_marg_levels = _floats("--marg_levels", _level, "levels inside [0, 1]", most=16)
+
+
+def _marg_bins(s):
+    v = int(s)
+    if not 2 <= v <= 257:
+        raise argparse.ArgumentTypeError("--marg_bins must lie in 2..257 (got %d)" % v)
+    return v
 
 
 def _fss_windows(s):

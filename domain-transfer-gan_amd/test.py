@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum|ssim
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum|ssim|marginal
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -71,6 +71,21 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               members averaged per input -> <res_dir>/ssim.npz.  The mean of an ensemble is smoother than its members: a
               higher luminance term, a lower cs; the file shows both.  Printed: the channel means.  11 <= H, W <= 1024.
               No plot
+  marginal    (new) whether the values are right, wherever they lie: every field is sorted on the device (ops.field_sort, HIP)
+              and from the sorted fields (ops.sorted_scores, one launch) come, per channel, the 1-Wasserstein distance w1 =
+              mean_k |s_x[k] - s_y[k]| and the squared 2-Wasserstein distance w2sq = mean_k (s_x[k] - s_y[k])^2 of a field's
+              value distribution against that of its paired truth (in double), its quantiles at the --marg_levels
+              (np.quantile, method "linear") and its exact counts of values below the edges: per channel the quantiles k / B,
+              k = 1 .. B - 1, B = --marg_bins, of the real training fields (trainB for A -> B, trainA for B -> A; np.quantile in
+              float64, cast to float32).  Compared on the aligned dev and test pairs: the --n_samples translations A -> B
+              (members_B) and their per-pixel mean (ens_mean_B) (model.translate_marginal) against the paired B, and B -> A
+              (fake_A) against the paired A.  Per comparison k: w1_k, w2sq_k (C,), the split means, and w1_k_per_input,
+              w2sq_k_per_input (N, C), the members averaged per input; q_k (C, L), the mean over the fields of their
+              quantiles (q_real_B, q_real_A: of the truths: a Q-Q curve); below_k (C, E) int64, the counts summed over inputs
+              and members, in cells_k cells (below_real_*, cells_real_*: of the truths), and from them (ops.marginal_summary)
+              the pooled distribution function cdf_k at the edges and ks_k (C,), its Kolmogorov-Smirnov distance to that of
+              the truths, with levels, edges_B, edges_A -> <res_dir>/marginal.npz.  P - below is the count of fss's events.
+              Printed: the channel means of w1 and ks.  H W <= 2^20.  No plot
 
 A run trained with --native_res (its saved options say so) is scored by every other metric on what it was trained on: the
 centre grid_size windows of the stored fields in place of resized ones.
@@ -434,6 +449,91 @@ def eval_ssim(dataset, model, n_samples, use_gpu=True):
     return res
 
 
+MARGINAL_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
+
+
+def marginal_edges(train, bins):
+    """the edges the distribution functions of one domain are compared at -> (C, bins - 1) float32: per channel the quantiles
+    k / bins, k = 1 .. bins - 1, of its real training fields (N, C, H, W), np.quantile in float64 as fss_thresholds takes its
+    thresholds.  Repeated edges (a field with mass at one value) are kept: every count is independent"""
+    bins = int(bins)
+    if not 2 <= bins <= ops.MARG_MAX_EDGES + 1:
+        raise ValueError("marginal_edges: bins must lie in 2..%d (got %d)" % (ops.MARG_MAX_EDGES + 1, bins))
+    train = np.asarray(train)
+    C = train.shape[1]
+    x = train.astype(np.float64).transpose(1, 0, 2, 3).reshape(C, -1)
+    return np.quantile(x, np.arange(1, bins, dtype=np.float64) / bins, axis=1).T.astype(np.float32)
+
+
+def _marginal_entries(parts, real):
+    """eval_marginal's result from what its batches gave.  parts[k], per comparison k of MARGINAL_PAIRS: lists of w (n, C, 2)
+    float64 (the members averaged per input), q (C, L) float64 sums over the fields, below (C, E) int64 sums, and the numbers
+    of fields and of cells they run over; real['B'], real['A']: q, below, fields, cells of the paired real fields of that
+    direction"""
+    res = {}
+    for k in MARGINAL_PAIRS:
+        p, r = parts[k], real[k[-1]]
+        w = np.concatenate(p['w'])                                 # (N, C, 2)
+        res['w1_' + k], res['w2sq_' + k] = w[..., 0].mean(0), w[..., 1].mean(0)
+        res['w1_%s_per_input' % k], res['w2sq_%s_per_input' % k] = w[..., 0], w[..., 1]
+        res['q_' + k] = p['q'] / float(p['fields'])
+        res['below_' + k], res['cells_' + k] = np.asarray(p['below'], dtype=np.int64), np.int64(p['cells'])
+        summary = ops.marginal_summary(p['below'], p['cells'], r['below'], r['cells'])
+        res['cdf_' + k], res['ks_' + k] = summary['cdf'], summary['ks']
+    for d in ('B', 'A'):
+        r = real[d]
+        res['q_real_' + d] = r['q'] / float(r['fields'])
+        res['below_real_' + d], res['cells_real_' + d] = np.asarray(r['below'], dtype=np.int64), np.int64(r['cells'])
+    return res
+
+
+def eval_marginal(dataset, model, n_samples, levels, edges_B, edges_A, use_gpu=True):
+    """the value distributions on an aligned split, one read of the scores per batch.  A -> B: n_samples members per input and
+    their ensemble mean against the paired real B, and the real B itself (model.translate_marginal); B -> A: predict_A against
+    the paired real A, and the real A itself (ops.marginal_scores).  -> dict, per comparison k of MARGINAL_PAIRS: w1_k, w2sq_k
+    (C,) float64, the split means of the per-field Wasserstein distances, with w1_k_per_input, w2sq_k_per_input (N, C), the
+    members averaged per input; q_k (C, L), the mean over the fields of their quantiles; below_k (C, E) int64, the counts
+    below the edges summed over inputs and members, in cells_k cells; cdf_k (C, E) and ks_k (C,) of ops.marginal_summary
+    against the real fields of that direction.  For those: q_real_B, q_real_A, below_real_B, below_real_A, cells_real_B,
+    cells_real_A"""
+    zero = lambda: dict(w=[], q=0.0, below=0, fields=0, cells=0)
+    parts, real = {k: zero() for k in MARGINAL_PAIRS}, {d: zero() for d in ('B', 'A')}
+    e_B = e_A = None
+
+    def add(acc, q, below, cells_per_field):
+        """q (..., C, L) float32 and below (..., C, E) int32 of some fields, summed over the leading axes in float64 / int64"""
+        q, below = q.reshape((-1,) + q.shape[-2:]), below.reshape((-1,) + below.shape[-2:])
+        acc['q'] = acc['q'] + q.astype(np.float64).sum(0)
+        acc['below'] = acc['below'] + below.sum(0, dtype=np.int64)
+        acc['fields'] += q.shape[0]
+        acc['cells'] += q.shape[0] * cells_per_field
+
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        if e_B is None:
+            e_B = torch.from_numpy(np.ascontiguousarray(edges_B)).to(real_B.device)
+            e_A = torch.from_numpy(np.ascontiguousarray(edges_A)).to(real_A.device)
+        r = model.translate_marginal(real_A, n_samples, real_B, levels, e_B)
+        CA = real_A.size(1)
+        with torch.no_grad():
+            fake_A = ops.marginal_scores(model.predict_A(real_B), real_A, CA, "nchw", "nchw", levels, e_A)
+        tgt_A = ops.marginal_scores(real_A, None, CA, "nchw", None, levels, e_A)
+        groups = (r['members'], r['ens_mean'], fake_A)
+        # one copy: the doubles as they are, the float32 quantiles and the int32 counts widened exactly
+        host = _read_back([g['w'] for g in groups]
+                          + [t[k].double() for t in groups + (r['target'], tgt_A) for k in ('q', 'below')])
+        w, rest = host[:3], host[3:]
+        cells = (real_B.size(2) * real_B.size(3), real_B.size(2) * real_B.size(3), real_A.size(2) * real_A.size(3))
+        for i, k in enumerate(MARGINAL_PAIRS):
+            parts[k]['w'].append(w[i].mean(1) if k == 'members_B' else w[i])
+            add(parts[k], rest[2 * i], rest[2 * i + 1].astype(np.int64), cells[i])
+        add(real['B'], rest[6], rest[7].astype(np.int64), cells[0])
+        add(real['A'], rest[8], rest[9].astype(np.int64), cells[2])
+    return _marginal_entries(parts, real)
+
+
 FSS_PAIRS = ('members_B', 'ens_prob_B', 'ens_mean_B', 'fake_A')
 
 
@@ -586,7 +686,7 @@ def test_model(argv=None):
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
     for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles', 'fss_quantiles', 'fss_thresholds',
-              'fss_windows', 'ema', 'overlap'):
+              'fss_windows', 'ema', 'overlap', 'marg_levels', 'marg_bins'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -739,6 +839,17 @@ def test_model(argv=None):
               % (dev['ssim_members_B'].mean(), test['ssim_members_B'].mean(), test['cs_members_B'].mean(),
                  test['ssim_ens_mean_B'].mean(), test['cs_ens_mean_B'].mean(), test['ssim_fake_A'].mean(),
                  test['cs_fake_A'].mean()))
+    elif opt.metric == 'marginal':
+        edges_B = marginal_edges(trainB, opt.marg_bins)            # once: dev and test share the climatology
+        edges_A = marginal_edges(trainA, opt.marg_bins)
+        levels = tuple(opt.marg_levels)
+        header = dict(n_samples=np.int64(opt.n_samples), levels=np.array(levels, dtype=np.float64), edges_B=edges_B, edges_A=edges_A)
+        dev, test = _eval_splits(opt, 'marginal', lambda d: eval_marginal(d, model, opt.n_samples, levels, edges_B, edges_A),
+                                 dev_dataset, test_dataset, header)
+        print("DEV_W1_B: %.4f, TEST_W1_B: %.4f, TEST_W1_MEAN_B: %.4f, TEST_W1_A: %.4f, TEST_KS_B: %.4f, TEST_KS_MEAN_B: %.4f, "
+              "TEST_KS_A: %.4f"
+              % (dev['w1_members_B'].mean(), test['w1_members_B'].mean(), test['w1_ens_mean_B'].mean(), test['w1_fake_A'].mean(),
+                 test['ks_members_B'].mean(), test['ks_ens_mean_B'].mean(), test['ks_fake_A'].mean()))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

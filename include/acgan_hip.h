@@ -567,6 +567,28 @@ int acg_marginal_loss_fwd(const float *sx, int rows_x, const float *sy, int rows
  * outside 1 .. 2^20, a stride < 1, gx aliasing an input. */
 int acg_marginal_loss_bwd(const float *d, const int *rank, const float *gscale, int rows, int C, int Cp, int H, int W,
                           long long row_stride, int pix_stride, long long chan_stride, float *gx, void *stream);
+/* The evaluator on sorted fields (ops.sorted_scores, ops.marginal_scores, test.py --metric marginal; tests/marginal_eval_ref.py
+ * states the definition).  sx (rows, C, P) and sy (rows / x_per_y, C, P), or NULL: fp32, every field ascending and planar, as
+ * acg_field_sort writes them; row r of sx pairs with row r / x_per_y of sy (x_per_y ensemble members share one truth).  Per
+ * (row, channel):
+ *   w     (rows, C, 2) double, exactly when sy is given (else NULL): w1 = mean_k |sx[k] - sy[k]| and w2sq = mean_k (sx[k] -
+ *         sy[k])^2, the differences taken and summed in double: the 1-Wasserstein and the squared 2-Wasserstein distance of the
+ *         two fields' value distributions (equal sample sizes);
+ *   q     (rows, C, L) fp32, exactly when L > 0: the order-statistic quantile with linear interpolation (numpy.quantile,
+ *         method="linear") at levels[l]: pos = level (P - 1), lo = floor(pos), hi = min(lo + 1, P - 1), q = sx[lo] + (pos - lo)
+ *         (sx[hi] - sx[lo]) in double, not contracted, rounded once to fp32.  levels: L doubles in HOST memory, each in
+ *         [0, 1], read before the launch; 0 <= L <= 16;
+ *   below (rows, C, E) int32, exactly when E > 0: #{k : sx[k] < edges[c][e]}, exact, by bisection in the sorted field; P -
+ *         below is the count of acg_fss's events [x >= thr].  edges: (C, E) fp32 on the device in any order; 0 <= E <= 256.
+ * Every output element is written.  NaN in a field is outside the contract; the kernel still ends and reads and writes only
+ * inside its operands.  One launch (marginal_scores), one workgroup of 1024 threads per field: sx and sy are read once; a
+ * thread sums groups of four pixels in a fixed order, then a shuffle tree per wave and the waves in order: no atomics, the same
+ * bits on every call and for every alignment.  Nothing is read back; capturable in a HIP graph.  Refused before a launch (-1,
+ * acg_last_error starts with "acg_marginal_scores"): a null sx, rows < 1, C < 1, P outside 1 .. 2^20, L or E outside their
+ * ranges, nothing to compute (no sy, L = 0, E = 0), w given without sy or missing with it, q (or levels) and below (or edges)
+ * likewise against L and E, rows % x_per_y != 0, a level outside [0, 1] or NaN, an output aliasing an input or another output. */
+int acg_marginal_scores(const float *sx, const float *sy, int rows, int x_per_y, int C, long long P, const double *levels, int L,
+                        const float *edges, int E, double *w, float *q, int *below, void *stream);
 
 /* ---- structural similarity (ops.ssim, ops.ssim_loss, --lambda_ssim_A / --lambda_ssim_B, test.py --metric ssim; no reference
  *      call site: the reference compares pixels by L1 alone, tests/ssim_ref.py states the definition; Wang et al. 2004) ----
