@@ -740,6 +740,36 @@ class _Base(object):
                 ops.fss(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
         return out
 
+    def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None):
+        """The shape of what A -> B puts above a threshold: the counts behind the Minkowski functionals (ops.minkowski: per
+        channel and threshold nF, nE1, nE2, nV1, nV4 of the excursion set, from which ops.minkowski_summary takes area,
+        perimeter and the two Euler numbers) of each of n_samples translations of every input and of their per-pixel mean
+        (_ensemble_mean: smoother than any member, so it has fewer, rounder objects).  Unpaired: no real_B; the real fields
+        go through ops.minkowski themselves.  thresholds: (C, T), 1 <= T <= 255, per channel finite and non-decreasing; a
+        host array is checked (ops.check_thresholds) and moved to the device once, a device tensor is taken as it is.  z,
+        chunk and the refusals: plan_ensemble; the members: ensemble_groups.  1 <= H, W <= 1024.  Returns int64 device
+        tensors: members (N, M, C, T, 5) and ens_mean (N, C, T, 5), to be summed over a set of fields and handed to
+        ops.minkowski_summary.  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_minkowski", self.opt, real_A, n_samples, z, None, chunk)
+        thr = thresholds
+        if not torch.is_tensor(thr):
+            try:
+                thr = torch.from_numpy(ops.check_thresholds(thr, C))
+            except ValueError as e:
+                raise ValueError("translate_minkowski: %s" % e)
+        thr = thr.detach().to(device=real_A.device, dtype=torch.float32).contiguous()    # once, not per group
+        if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= ops.MINK_MAX_T:
+            raise ValueError("translate_minkowski: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)"
+                             % (C, ops.MINK_MAX_T, tuple(thr.shape)))
+        T = thr.size(1)
+        i64 = dict(device=real_A.device, dtype=torch.int64)
+        out = dict(members=torch.empty((N, M, C, T, 5), **i64), ens_mean=torch.empty((N, C, T, 5), **i64))
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+                ops.minkowski(members, C, "nhwc", thr, out=out["members"][g0:g0 + n].view(n * M, C, T, 5))
+                ops.minkowski(_ensemble_mean(members, M, C), C, "nchw", thr, out=out["ens_mean"][g0:g0 + n])
+        return out
+
     def _field_groups(self, who, G, x, copies, C, overlap, chunk, code=None):
         """What translate_field and translate_field_A share -> (copies*N, C, H, W): every (N, Cin, H, W) field of x, `copies`
         times in a row, through G in windows of grid_size (ops.window_plan) blended on canvases (ops.window_blend).  Groups

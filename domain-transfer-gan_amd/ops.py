@@ -2124,6 +2124,99 @@ def fss_summary(sums, windows, cells, members=1):
     return res
 
 
+# ----------------------------------------------------------------------------------------------
+# Minkowski functionals of excursion sets (model.translate_minkowski, test.py --metric minkowski)
+# ----------------------------------------------------------------------------------------------
+MINK_MAX_T, MINK_MAX_HW = 255, 1024
+MINK_FUNCTIONALS = ("area", "perimeter", "euler4", "euler8")
+
+
+def check_thresholds(thresholds, C):
+    """host thresholds as minkowski takes them -> a contiguous (C, T) float32 array; ValueError unless 1 <= T <= 255 and every
+    channel's thresholds are finite and non-decreasing (repeats allowed)"""
+    import numpy as np
+    thr = np.array(thresholds, dtype=np.float32, order="C")        # a copy: the caller's array may be read-only
+    if thr.ndim != 2 or thr.shape[0] != C or not 1 <= thr.shape[1] <= MINK_MAX_T:
+        raise ValueError("thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)" % (C, MINK_MAX_T, thr.shape))
+    if not np.all(np.isfinite(thr)) or np.any(thr[:, 1:] < thr[:, :-1]):
+        raise ValueError("thresholds must be finite and non-decreasing per channel")
+    return thr
+
+
+def minkowski(x, C, layout, thresholds, out=None):
+    """acg_minkowski: the counts behind the Minkowski functionals of the excursion sets {x >= thresholds[c][t]} of the C valid
+    channels of x -> (rows, C, T, 5) int64 on the device: (nF, nE1, nE2, nV1, nV4), the pixels in the set, the unit edges
+    with a pixel / both pixels in it and the vertices with a pixel / all four pixels in it, the field standing in a ring of
+    cells outside every set (x == threshold is inside, NaN outside, as in fss).  Exact integers, the same bits in every layout;
+    linear over fields: sum them over a set of fields, then ops.minkowski_summary.  layout "nhwc": x (rows, H, W, Cp) as
+    forward_nhwc / ToNHWC give it (padded channels never reach a result); "nchw": x (rows, C, H, W).  1 <= H, W <= 1024.
+    thresholds: (C, T), 1 <= T <= 255, per channel finite and non-decreasing (repeats allowed): a host array is checked
+    (check_thresholds) and copied to the device; a float32 device tensor is taken as it is - its order is the caller's
+    contract, nothing is read back to check it.  `out`: the contiguous int64 tensor to write.  One pass over x for all
+    thresholds, two launches; nothing is read back to the host.  Not differentiable."""
+    x = x.detach().contiguous()
+    rows, C, _, H, W, sx = _field_args(x, C, layout, "minkowski")
+    if not (1 <= H <= MINK_MAX_HW and 1 <= W <= MINK_MAX_HW):
+        raise _lib.AcgError("minkowski: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (MINK_MAX_HW, H, W))
+    thr = thresholds
+    if not torch.is_tensor(thr):
+        try:
+            thr = torch.from_numpy(check_thresholds(thr, C))
+        except ValueError as e:
+            raise _lib.AcgError("minkowski: %s" % e)
+    if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= MINK_MAX_T or thr.dtype != torch.float32:
+        raise _lib.AcgError("minkowski: thresholds must be (C, T) float32 with C=%d and 1 <= T <= %d (got %s %s)"
+                            % (C, MINK_MAX_T, tuple(thr.shape), thr.dtype))
+    T = int(thr.size(1))
+    shape = (rows, C, T, 5)
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.int64 or not out.is_contiguous()):
+        raise _lib.AcgError("minkowski: out %s %s is not a contiguous int64 %s" % (tuple(out.shape), out.dtype, shape))
+    if not torch.is_tensor(thresholds):
+        thr = thr.to(x.device)
+    thr = thr.detach().contiguous()
+    _check(x, thr)                                                 # after the refusals that need no device
+    if out is not None and not out.is_cuda:
+        raise _lib.AcgError("acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path" % out.device)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.int64)
+    ws, nbytes = _metric_workspace("acg_minkowski_workspace_bytes", rows, C, H, W, T)
+    _lib.call("acg_minkowski", _ptr(x), rows, C, H, W, sx[0], sx[1], sx[2], _ptr(thr), T, _ptr(out), ws, nbytes, _stream())
+    return out
+
+
+def minkowski_summary(counts, cells):
+    """(..., T, 5) int64 counts (nF, nE1, nE2, nV1, nV4) summed over a set of fields of `cells` cells in all -> dict of
+    float64 arrays (..., T) on the host:
+      area       nF, the cells inside the set;
+      perimeter  nE1 - nE2, the unit edges with exactly one side inside (the domain's border counts as outside);
+      euler8     nV1 - nE1 + nF, the 8-connected components minus their holes (pixels as closed squares);
+      euler4     nF - nE2 + nV4, the 4-connected components minus their holes;
+    and each per cell under area_density, perimeter_density, euler4_density, euler8_density."""
+    import numpy as np
+    n = np.asarray(counts)
+    if n.ndim < 2 or n.shape[-1] != 5 or int(cells) < 1:
+        raise ValueError("minkowski_summary: need (..., T, 5) counts and a positive cell count (got %s, %s)" % (n.shape, cells))
+    n = n.astype(np.int64)
+    nF, nE1, nE2, nV1, nV4 = (n[..., k] for k in range(5))
+    res = dict(area=nF, perimeter=nE1 - nE2, euler4=nF - nE2 + nV4, euler8=nV1 - nE1 + nF)
+    res = {k: v.astype(np.float64) for k, v in res.items()}
+    res.update([(k + "_density", v / float(int(cells))) for k, v in res.items()])
+    return res
+
+
+def minkowski_distance(a, b):
+    """two minkowski_summary dicts of the same thresholds -> dict of float64 arrays (...): per functional (area, perimeter,
+    euler4, euler8) the mean over the thresholds of |density_a - density_b|"""
+    import numpy as np
+    res = {}
+    for k in MINK_FUNCTIONALS:
+        da, db = np.asarray(a[k + "_density"], dtype=np.float64), np.asarray(b[k + "_density"], dtype=np.float64)
+        if da.shape != db.shape or da.ndim < 1:
+            raise ValueError("minkowski_distance: %s densities %s against %s" % (k, da.shape, db.shape))
+        res[k] = np.abs(da - db).mean(-1)
+    return res
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

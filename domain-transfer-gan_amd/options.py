@@ -186,7 +186,9 @@ class TestOptions(object):
     the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap; the metric
     `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap); the metric `ssim`
     (structural similarity of the paired translations, reuses --n_samples); the metric `marginal` (Wasserstein distances,
-    quantiles and distribution functions of the fields' values, reuses --n_samples) with --marg_levels and --marg_bins."""
+    quantiles and distribution functions of the fields' values, reuses --n_samples) with --marg_levels and --marg_bins; the
+    metric `minkowski` (area, perimeter and Euler characteristic of the excursion sets, unpaired, reuses --n_samples) with
+    --mink_bins."""
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -196,10 +198,10 @@ class TestOptions(object):
         self.parser.add_argument('--dataroot', required=True, type=str)
         self.parser.add_argument('--metric', required=True, type=str,
                                  choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate',
-                                          'field_spectrum', 'ssim', 'marginal'])
+                                          'field_spectrum', 'ssim', 'marginal', 'minkowski'])
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim / marginal: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim / marginal / minkowski: translations per input (1..64)')
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
         self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),
@@ -217,6 +219,9 @@ class TestOptions(object):
                                  help='--metric marginal: B in 2..257; the distribution functions are compared at the B - 1 '
                                       'quantiles k / B of the real training fields, per channel (trainB for A -> B, trainA for '
                                       'B -> A)')
+        self.parser.add_argument('--mink_bins', type=_mink_bins, default=32,
+                                 help='--metric minkowski: B in 2..256; the excursion sets are taken at the B - 1 quantiles '
+                                      'k / B of the real training fields, per channel (trainB for A -> B, trainA for B -> A)')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
@@ -281,6 +286,13 @@ def _marg_bins(s):
     v = int(s)
     if not 2 <= v <= 257:
         raise argparse.ArgumentTypeError("--marg_bins must lie in 2..257 (got %d)" % v)
+    return v
+
+
+def _mink_bins(s):
+    v = int(s)
+    if not 2 <= v <= 256:
+        raise argparse.ArgumentTypeError("--mink_bins must lie in 2..256 (got %d)" % v)
     return v
 
 

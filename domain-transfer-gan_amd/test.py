@@ -1,6 +1,6 @@
 """Offline evaluation of a trained checkpoint — Py3 counterpart of /root/reference/augmented_cyclegan/test.py.
 
-    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum|ssim|marginal
+    python -m dtgan_amd.test --chk_path <expr_dir>/latest --dataroot <npz dir> --metric bpp|mse|visual|noise_sens|mvgauss|ensemble|spectrum|coherence|fss|translate|field_spectrum|ssim|marginal|minkowski
 
 The saved options of the run are read from opt.pkl next to the checkpoint (or opt.txt, parse_opt_file), the model is rebuilt
 with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
@@ -86,6 +86,22 @@ with testing=True, seeded with 12345 and loaded.  Metrics (test.py:230-283):
               the pooled distribution function cdf_k at the edges and ks_k (C,), its Kolmogorov-Smirnov distance to that of
               the truths, with levels, edges_B, edges_A -> <res_dir>/marginal.npz.  P - below is the count of fss's events.
               Printed: the channel means of w1 and ks.  H W <= 2^20.  No plot
+  minkowski   (new) the shape of the threshold exceedances, which none of the above sees: the Minkowski functionals of the
+              excursion sets {x >= t} - area, perimeter and the Euler characteristic (components minus holes, for 4- and for
+              8-connectivity) - as curves over the thresholds t: per channel the quantiles k / B, k = 1 .. B - 1, B =
+              --mink_bins, of the real training fields (trainB for A -> B, trainA for B -> A; marginal_edges).  ops.minkowski
+              (HIP, exact integers, one pass over a field for all thresholds) gives the counts (nF, nE1, nE2, nV1, nV4) of
+              cells, edges and vertices touching / inside each set; they are summed in int64 over five SETS of fields - the
+              --n_samples translations A -> B (members_B), their per-pixel means (ens_mean_B) (model.translate_minkowski),
+              B -> A (fake_A) and the real fields of both domains (real_B, real_A) - before anything is divided.  Unpaired:
+              sets are compared with sets, as the model is trained.  Per set k: counts_k (C, T, 5) int64, cells_k, and
+              (ops.minkowski_summary, float64) area_k = nF, perimeter_k = nE1 - nE2, euler8_k = nV1 - nE1 + nF, euler4_k =
+              nF - nE2 + nV4 (C, T), each also per cell (*_density_k); per translated set k against the real set of its
+              domain (ops.minkowski_distance): dist_area_k, dist_perimeter_k, dist_euler4_k, dist_euler8_k (C,), the mean
+              over the thresholds of the absolute difference of the densities, with n_samples, bins, thresholds_B,
+              thresholds_A -> <res_dir>/minkowski.npz.  A blobby, a filamentary and a speckled field can share marginal,
+              spectrum and FSS and differ here; the mean of an ensemble loses objects and boundary.  Printed per split: the
+              four distances of members_B, ens_mean_B and fake_A, the channel means.  1 <= H, W <= 1024.  No plot
 
 A run trained with --native_res (its saved options say so) is scored by every other metric on what it was trained on: the
 centre grid_size windows of the stored fields in place of resized ones.
@@ -579,6 +595,50 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
     return res
 
 
+MINKOWSKI_SETS = ('members_B', 'ens_mean_B', 'fake_A', 'real_B', 'real_A')
+MINKOWSKI_PAIRS = (('members_B', 'real_B'), ('ens_mean_B', 'real_B'), ('fake_A', 'real_A'))
+
+
+def eval_minkowski(dataset, model, n_samples, thr_B, thr_A, use_gpu=True):
+    """the shape of the excursion sets on a split, one read of the counts per batch.  The counts of ops.minkowski, at the
+    thresholds thr_B (C_B, T) in domain B and thr_A (C_A, T) in domain A, are summed in int64 over the fields of five sets:
+    the n_samples translations A -> B of every input (members_B) and their per-pixel means (ens_mean_B)
+    (model.translate_minkowski), B -> A (fake_A, predict_A), and the real fields of both domains through the same kernel
+    (real_B, real_A).  Unpaired: the sets are compared as sets.  -> dict, per set k of MINKOWSKI_SETS: counts_k (C, T, 5)
+    int64, cells_k int64 and the float64 (C, T) arrays of ops.minkowski_summary, area_k, perimeter_k, euler4_k, euler8_k and
+    the same per cell under *_density_k; per translated set k, against the real set of its domain (MINKOWSKI_PAIRS):
+    dist_area_k, dist_perimeter_k, dist_euler4_k, dist_euler8_k (C,) of ops.minkowski_distance"""
+    sums = {k: 0 for k in MINKOWSKI_SETS}
+    cells = {k: 0 for k in MINKOWSKI_SETS}
+    t_B = t_A = None
+    for batch in dataset:
+        real_A, real_B = batch['A'], batch['B']
+        if use_gpu:
+            real_A, real_B = real_A.cuda(), real_B.cuda()
+        if t_B is None:
+            t_B = torch.from_numpy(ops.check_thresholds(thr_B, real_B.size(1))).to(real_B.device)
+            t_A = torch.from_numpy(ops.check_thresholds(thr_A, real_A.size(1))).to(real_A.device)
+        r = model.translate_minkowski(real_A, n_samples, t_B)
+        CA, CB = real_A.size(1), real_B.size(1)
+        with torch.no_grad():
+            fake_A = ops.minkowski(model.predict_A(real_B), CA, "nchw", t_A)
+        parts = (r['members'].flatten(0, 1), r['ens_mean'], fake_A, ops.minkowski(real_B, CB, "nchw", t_B),
+                 ops.minkowski(real_A, CA, "nchw", t_A))
+        fields = [p.size(0) for p in parts]
+        for k, n, v in zip(MINKOWSKI_SETS, fields, _read_back([p.sum(0).reshape(-1) for p in parts])):
+            side = real_A if k.endswith('_A') else real_B
+            sums[k] = sums[k] + v.reshape(side.size(1), -1, 5).astype(np.int64)
+            cells[k] += n * side.size(2) * side.size(3)
+    res, summary = {}, {}
+    for k in MINKOWSKI_SETS:
+        res['counts_' + k], res['cells_' + k] = np.asarray(sums[k], dtype=np.int64), np.int64(cells[k])
+        summary[k] = ops.minkowski_summary(sums[k], cells[k])
+        res.update(('%s_%s' % (name, k), v) for name, v in summary[k].items())
+    for k, real in MINKOWSKI_PAIRS:
+        res.update(('dist_%s_%s' % (name, k), v) for name, v in ops.minkowski_distance(summary[k], summary[real]).items())
+    return res
+
+
 def eval_translate(dataset, model, n_samples, overlap, use_gpu=True):
     """whole-field translation of an aligned split at its stored resolution (model.translate_field, translate_field_A), one
     read per batch -> dict of float32 arrays (N, C, H, W): mean_B and std_B over the members (torch on the canvases; std
@@ -686,7 +746,7 @@ def test_model(argv=None):
     expr_dir = os.path.dirname(os.path.abspath(args.chk_path))
     opt.__dict__.update(_saved_options(expr_dir))
     for k in ('chk_path', 'res_dir', 'train_logvar', 'dataroot', 'metric', 'ubo_steps', 'n_samples', 'quantiles', 'fss_quantiles', 'fss_thresholds',
-              'fss_windows', 'ema', 'overlap', 'marg_levels', 'marg_bins'):
+              'fss_windows', 'ema', 'overlap', 'marg_levels', 'marg_bins', 'mink_bins'):
         setattr(opt, k, getattr(args, k))
     opt.expr_dir = expr_dir
     opt.gpu_ids = [i for i in (int(tok) for tok in args.gpu_ids.split(",")) if i >= 0]
@@ -850,6 +910,16 @@ def test_model(argv=None):
               "TEST_KS_A: %.4f"
               % (dev['w1_members_B'].mean(), test['w1_members_B'].mean(), test['w1_ens_mean_B'].mean(), test['w1_fake_A'].mean(),
                  test['ks_members_B'].mean(), test['ks_ens_mean_B'].mean(), test['ks_fake_A'].mean()))
+    elif opt.metric == 'minkowski':
+        thr_B = marginal_edges(trainB, opt.mink_bins)              # once: dev and test share the climatology
+        thr_A = marginal_edges(trainA, opt.mink_bins)
+        header = dict(n_samples=np.int64(opt.n_samples), bins=np.int64(opt.mink_bins), thresholds_B=thr_B, thresholds_A=thr_A)
+        dev, test = _eval_splits(opt, 'minkowski', lambda d: eval_minkowski(d, model, opt.n_samples, thr_B, thr_A),
+                                 dev_dataset, test_dataset, header)
+        for name, res in (('DEV', dev), ('TEST', test)):
+            print("%s_MINK_B: %s, %s_MINK_MEAN_B: %s, %s_MINK_A: %s (area, perimeter, euler4, euler8)"
+                  % tuple(v for k in ('members_B', 'ens_mean_B', 'fake_A')
+                          for v in (name, " ".join("%.6f" % _chan_mean(res['dist_%s_%s' % (f, k)]) for f in ops.MINK_FUNCTIONALS))))
     else:
         raise NotImplementedError('wrong metric!')
     return opt

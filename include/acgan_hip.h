@@ -528,6 +528,38 @@ int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H,
             long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr, int T,
             const int *windows, int nw, long long *out, long long *ens_out, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- Minkowski functionals of excursion sets (ops.minkowski, model.translate_minkowski, test.py --metric minkowski; no
+ *      reference call site: the reference has no verification code, tests/minkowski_ref.py states the definition) ----
+ * x: rows x C fields of H x W fp32 cells; the strides (in floats) mean what they mean in acg_fss: NHWC with Cp stored channels
+ * is (H W Cp, Cp, 1) - padded channels never reach a result - and planar NCHW is (C H W, 1, H W).  thr: (C, T) thresholds on
+ * the device, per channel finite and non-decreasing (repeats allowed): the caller's contract, the kernel cannot refuse them
+ * (with others it still ends and reads and writes only inside its operands).
+ * Per field and channel c the level of a pixel is L = #{t : thr[c][t] <= x} in 0 .. T: x == thr is an event and NaN has level
+ * 0, as in acg_fss; +inf has level T, -inf level 0.  The excursion set at threshold t is {L >= t + 1}; the sets are nested.
+ * The field stands in a ring of level-0 cells (outside the domain there is no event, so an event pixel on the border
+ * contributes its border edges to the perimeter).  Five multisets of levels: F, the H W pixels; Emax / Emin, the max / min of
+ * the two pixels on either side of each of the H (W + 1) + (H + 1) W unit edges; Vmax / Vmin, the max / min of the four pixels
+ * around each of the (H + 1) (W + 1) vertices.  With n_X[t] = #{elements of X with level >= t + 1}:
+ *   out (rows, C, T, 5) int64: (nF, nE1, nE2, nV1, nV4) = (n_F, n_Emax, n_Emin, n_Vmax, n_Vmin)[t], fully written.
+ * They are linear over fields: sum them over a set of fields, then (ops.minkowski_summary) area = nF, perimeter = nE1 - nE2
+ * (edges with exactly one side in the set), euler8 = nV1 - nE1 + nF (pixels as closed squares: 8-connected components minus
+ * their holes), euler4 = nF - nE2 + nV4 (4-connected components minus their holes).  One pass over the field serves all T
+ * thresholds.  Integer after the comparison: exact, the same bits for every layout and launch order.  Nothing is read back;
+ * capturable in a HIP graph.
+ * Limits: 1 <= H, W <= 1024 (need not be equal), 1 <= T <= 255 (levels fit a byte).  Refused before a launch (-1,
+ * acg_last_error starts with "acg_minkowski"): a null x, thr or out, an extent or T out of range, rows < 1, C < 1, rows C
+ * ceil((H + 1) / 8) or rows C T above 2^31 - 1, a stride < 1, a misaligned workspace (16 bytes).  A workspace below
+ * acg_minkowski_workspace_bytes returns -2; the size query is 0 for a refused size.
+ * The workspace holds (rows, C, bands, 5, T) 32-bit bins, bands = ceil((H + 1) / 8), rounded up to 16 bytes.  Kernels:
+ * mink_hist, one workgroup per (row, band of 8 lattice rows) for NHWC with four stored channels (mink_hist<c4>: a pixel's
+ * channels from one 16-byte load) and per (row, channel, band) otherwise (mink_hist<strided>): levels by bisection into an
+ * LDS byte tile, histograms in LDS by integer adds aggregated over runs of equal levels, bins stored plainly; then
+ * mink_finish, one workgroup per (row, channel): the bands summed, the suffix sums, the int64 stores.  No global atomics;
+ * neither the workspace's nor out's earlier contents matter. */
+size_t acg_minkowski_workspace_bytes(int rows, int C, int H, int W, int T);
+int acg_minkowski(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
+                  const float *thr, int T, long long *out, void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- the marginal loss (ops.field_sort, ops.marginal_loss, --lambda_marg_A / --lambda_marg_B; no reference call site: the
  *      reference has no distributional loss, tests/marginal_ref.py states the definition) ----
  * acg_field_sort: a stable sort of each of the rows x C fields of H x W fp32 pixels of x, with its permutation.  The strides
