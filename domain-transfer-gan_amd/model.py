@@ -583,6 +583,15 @@ class _Base(object):
             x = ops.ToNHWC.apply(a.unsqueeze(1).expand(n, M, *a.shape[1:]).reshape(n * M, *a.shape[1:]), img_in)
             yield g0, n, G.forward_nhwc(x, as_latent(self._z(z[g0 * M:(g0 + n) * M])))
 
+    def _groups(self, real_A, z, M, per, real_B=None):
+        """ensemble_groups for the translate_* methods that write slices of whole-batch outputs -> (members, g), g the
+        _Group of the inputs the members belong to; the paired real_B is detached and made contiguous once, here.  Stateless
+        as ensemble_groups is: the caller holds eval_state and no_grad."""
+        if real_B is not None:
+            real_B = real_B.detach().contiguous()
+        for g0, n, members in self.ensemble_groups(real_A, z, M, per):
+            yield members, _Group(g0, n, M, real_B)
+
     def translate_ensemble(self, real_A, n_samples, z=None, real_B=None, quantiles=(0.05, 0.5, 0.95), chunk=None):
         """The distribution of A -> B: n_samples translations of every input, summarised per pixel on the device.
         z: (N*n_samples, nlatent, 1, 1) codes in generate_multi's order (input n takes rows n*M .. n*M + M - 1; default N(0, 1)
@@ -622,9 +631,9 @@ class _Base(object):
         f = dict(device=real_A.device, dtype=torch.float32)
         out = dict(members=torch.empty((N, M, C, nb), **f), ens_mean=torch.empty((N, C, nb), **f))
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                ops.radial_spectrum(members, C, "nhwc", out=out["members"][g0:g0 + n].view(n * M, C, nb))
-                ops.radial_spectrum(_ensemble_mean(members, M, C), C, "nchw", out=out["ens_mean"][g0:g0 + n])
+            for members, g in self._groups(real_A, z, M, per):
+                ops.radial_spectrum(members, C, "nhwc", out=g.flat(out["members"]))
+                ops.radial_spectrum(_ensemble_mean(members, M, C), C, "nchw", out=g.rows(out["ens_mean"]))
             if real_B is not None:
                 out["target"] = ops.radial_spectrum(real_B, C, "nchw")
         return out
@@ -640,12 +649,10 @@ class _Base(object):
         nb = ops._spectrum_size(H, W) // 2 + 1
         f = dict(device=real_A.device, dtype=torch.float32)
         out = dict(members=torch.empty((N, M, C, 3, nb), **f), ens_mean=torch.empty((N, C, 3, nb), **f))
-        real_B = real_B.detach().contiguous()
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                b = real_B[g0:g0 + n]
-                ops.cross_spectrum(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 3, nb))
-                ops.cross_spectrum(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
+            for members, g in self._groups(real_A, z, M, per, real_B):
+                ops.cross_spectrum(members, g.b, C, "nhwc", "nchw", x_per_y=M, out=g.flat(out["members"]))
+                ops.cross_spectrum(_ensemble_mean(members, M, C), g.b, C, "nchw", "nchw", out=g.rows(out["ens_mean"]))
         return out
 
     def translate_ssim(self, real_A, n_samples, real_B, z=None, chunk=None):
@@ -658,12 +665,10 @@ class _Base(object):
         M, N, C, H, W, z, per = plan_ensemble("translate_ssim", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         f = dict(device=real_A.device, dtype=torch.float32)
         out = dict(members=torch.empty((N, M, C, 2), **f), ens_mean=torch.empty((N, C, 2), **f))
-        real_B = real_B.detach().contiguous()
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                b = real_B[g0:g0 + n]
-                ops.ssim(members, b, C, "nhwc", "nchw", x_per_y=M, out=out["members"][g0:g0 + n].view(n * M, C, 2))
-                ops.ssim(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", out=out["ens_mean"][g0:g0 + n])
+            for members, g in self._groups(real_A, z, M, per, real_B):
+                ops.ssim(members, g.b, C, "nhwc", "nchw", x_per_y=M, out=g.flat(out["members"]))
+                ops.ssim(_ensemble_mean(members, M, C), g.b, C, "nchw", "nchw", out=g.rows(out["ens_mean"]))
         return out
 
     def translate_marginal(self, real_A, n_samples, real_B, levels, edges, z=None, chunk=None):
@@ -679,13 +684,9 @@ class _Base(object):
         (N, C, E)).  Nothing is read back to the host."""
         M, N, C, H, W, z, per = plan_ensemble("translate_marginal", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         lv = ops.check_levels(levels)
-        e = edges
-        if not torch.is_tensor(e):
-            e = torch.tensor(e, dtype=torch.float32)
-        e = e.detach().to(device=real_A.device, dtype=torch.float32).contiguous()        # once, not per group
-        if not lv or e.dim() != 2 or e.size(0) != C or not 1 <= e.size(1) <= ops.MARG_MAX_EDGES:
-            raise ValueError("translate_marginal: need 1..%d levels and edges (C, E) with C=%d and 1 <= E <= %d (got %d levels, "
-                             "edges %s)" % (ops.MARG_MAX_LEVELS, C, ops.MARG_MAX_EDGES, len(lv), tuple(e.shape)))
+        if not lv:
+            raise ValueError("translate_marginal: need 1..%d levels (got none)" % ops.MARG_MAX_LEVELS)
+        e = ops.channel_table("translate_marginal", ValueError, "edges", edges, C, ops.MARG_MAX_EDGES, real_A.device, cast=True)
         L, E = len(lv), e.size(1)
         dev = real_A.device
 
@@ -696,16 +697,14 @@ class _Base(object):
                 o["w"] = torch.empty(lead + (C, 2), device=dev, dtype=torch.float64)
             return o
         out = dict(members=outputs((N, M), True), ens_mean=outputs((N,), True), target=outputs((N,), False))
-        real_B = real_B.detach().contiguous()
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                sb, _ = ops.field_sort(real_B[g0:g0 + n], C, "nchw", want_rank=False)
+            for members, g in self._groups(real_A, z, M, per, real_B):
+                sb, _ = ops.field_sort(g.b, C, "nchw", want_rank=False)
                 sm, _ = ops.field_sort(members, C, "nhwc", want_rank=False)
-                ops.sorted_scores(sm, sb, lv, e, x_per_y=M,
-                                  out={k: v[g0:g0 + n].view((n * M,) + tuple(v.shape[2:])) for k, v in out["members"].items()})
+                ops.sorted_scores(sm, sb, lv, e, x_per_y=M, out={k: g.flat(v) for k, v in out["members"].items()})
                 se, _ = ops.field_sort(_ensemble_mean(members, M, C), C, "nchw", want_rank=False)
-                ops.sorted_scores(se, sb, lv, e, out={k: v[g0:g0 + n] for k, v in out["ens_mean"].items()})
-                ops.sorted_scores(sb, None, lv, e, out={k: v[g0:g0 + n] for k, v in out["target"].items()})
+                ops.sorted_scores(se, sb, lv, e, out={k: g.rows(v) for k, v in out["ens_mean"].items()})
+                ops.sorted_scores(sb, None, lv, e, out={k: g.rows(v) for k, v in out["target"].items()})
         return out
 
     def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
@@ -720,24 +719,16 @@ class _Base(object):
         read back to the host."""
         M, N, C, H, W, z, per = plan_ensemble("translate_fss", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         win = ops.check_windows(windows)
-        thr = thresholds
-        if not torch.is_tensor(thr):
-            thr = torch.tensor(thr, dtype=torch.float32)
-        thr = thr.detach().to(device=real_A.device, dtype=torch.float32).contiguous()    # once, not per group
-        if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= ops.FSS_MAX_T:
-            raise ValueError("translate_fss: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)"
-                             % (C, ops.FSS_MAX_T, tuple(thr.shape)))
+        thr = ops.channel_table("translate_fss", ValueError, "thresholds", thresholds, C, ops.FSS_MAX_T, real_A.device, cast=True)
         T, nw = thr.size(1), len(win)
         i64 = dict(device=real_A.device, dtype=torch.int64)
         out = dict(members=torch.empty((N, M, C, T, nw, 3), **i64), ens_prob=torch.empty((N, C, T, nw, 3), **i64),
                    ens_mean=torch.empty((N, C, T, nw, 3), **i64))
-        real_B = real_B.detach().contiguous()
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                b = real_B[g0:g0 + n]
-                ops.fss(members, b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
-                        out=(out["members"][g0:g0 + n].view(n * M, C, T, nw, 3), out["ens_prob"][g0:g0 + n]))
-                ops.fss(_ensemble_mean(members, M, C), b, C, "nchw", "nchw", thr, win, out=out["ens_mean"][g0:g0 + n])
+            for members, g in self._groups(real_A, z, M, per, real_B):
+                ops.fss(members, g.b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
+                        out=(g.flat(out["members"]), g.rows(out["ens_prob"])))
+                ops.fss(_ensemble_mean(members, M, C), g.b, C, "nchw", "nchw", thr, win, out=g.rows(out["ens_mean"]))
         return out
 
     def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None):
@@ -746,28 +737,20 @@ class _Base(object):
         perimeter and the two Euler numbers) of each of n_samples translations of every input and of their per-pixel mean
         (_ensemble_mean: smoother than any member, so it has fewer, rounder objects).  Unpaired: no real_B; the real fields
         go through ops.minkowski themselves.  thresholds: (C, T), 1 <= T <= 255, per channel finite and non-decreasing; a
-        host array is checked (ops.check_thresholds) and moved to the device once, a device tensor is taken as it is.  z,
+        host array is checked (ops.channel_table) and moved to the device once, a device tensor is taken as it is.  z,
         chunk and the refusals: plan_ensemble; the members: ensemble_groups.  1 <= H, W <= 1024.  Returns int64 device
         tensors: members (N, M, C, T, 5) and ens_mean (N, C, T, 5), to be summed over a set of fields and handed to
         ops.minkowski_summary.  Nothing is read back to the host."""
         M, N, C, H, W, z, per = plan_ensemble("translate_minkowski", self.opt, real_A, n_samples, z, None, chunk)
-        thr = thresholds
-        if not torch.is_tensor(thr):
-            try:
-                thr = torch.from_numpy(ops.check_thresholds(thr, C))
-            except ValueError as e:
-                raise ValueError("translate_minkowski: %s" % e)
-        thr = thr.detach().to(device=real_A.device, dtype=torch.float32).contiguous()    # once, not per group
-        if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= ops.MINK_MAX_T:
-            raise ValueError("translate_minkowski: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)"
-                             % (C, ops.MINK_MAX_T, tuple(thr.shape)))
+        thr = ops.channel_table("translate_minkowski", ValueError, "thresholds", thresholds, C, ops.MINK_MAX_T, real_A.device,
+                                ordered=True, cast=True)
         T = thr.size(1)
         i64 = dict(device=real_A.device, dtype=torch.int64)
         out = dict(members=torch.empty((N, M, C, T, 5), **i64), ens_mean=torch.empty((N, C, T, 5), **i64))
         with eval_state(self.netG_A_B), torch.no_grad():
-            for g0, n, members in self.ensemble_groups(real_A, z, M, per):
-                ops.minkowski(members, C, "nhwc", thr, out=out["members"][g0:g0 + n].view(n * M, C, T, 5))
-                ops.minkowski(_ensemble_mean(members, M, C), C, "nchw", thr, out=out["ens_mean"][g0:g0 + n])
+            for members, g in self._groups(real_A, z, M, per):
+                ops.minkowski(members, C, "nhwc", thr, out=g.flat(out["members"]))
+                ops.minkowski(_ensemble_mean(members, M, C), C, "nchw", thr, out=g.rows(out["ens_mean"]))
         return out
 
     def _field_groups(self, who, G, x, copies, C, overlap, chunk, code=None):
@@ -950,6 +933,22 @@ def eval_state(net):
     finally:
         for m, mode in modes:
             m.training = mode
+
+
+class _Group(object):
+    """Inputs g0 .. g0 + n - 1 of a batch, M members each, as a translate_* method addresses them: b, their rows of the
+    paired real_B (None without one); rows(t) = t[g0:g0 + n] of a per-input tensor (N, ...); flat(t), the same rows of a
+    per-member tensor (N, M, ...) as (n*M, ...), one row per member in ensemble_groups' order.  Views: kernels write into them."""
+
+    def __init__(self, g0, n, M, real_B):
+        self.g0, self.n, self.M = g0, n, M
+        self.b = None if real_B is None else self.rows(real_B)
+
+    def rows(self, t):
+        return t[self.g0:self.g0 + self.n]
+
+    def flat(self, t):
+        return self.rows(t).view((self.n * self.M,) + tuple(t.shape[2:]))
 
 
 def _ensemble_mean(members, M, C):

@@ -45,16 +45,46 @@ def _stream():
     return _VP(torch.cuda.current_stream().cuda_stream)
 
 
+_NO_CPU_PATH = "acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path"
+
+
 def _check(*ts):
     for t in ts:
         if t is None:
             continue
         if not t.is_cuda:
-            raise _lib.AcgError("acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path" % t.device)
+            raise _lib.AcgError(_NO_CPU_PATH % t.device)
         if t.dtype != torch.float32:
             raise _lib.AcgError("acgan_hip kernels are fp32 (got %s)" % t.dtype)
         if not t.is_contiguous():
             raise _lib.AcgError("non-contiguous tensor reached a kernel")
+
+
+def channel_table(what, error, noun, table, C, most, device, none_if_empty=False, ordered=False, cast=False):
+    """A per-channel table (C, T) - the thresholds of fss and minkowski, the edges of the marginal scores - as the kernels
+    take it -> a contiguous float32 tensor on `device`, moved there once (None: left where it is, so that an entry point which
+    takes host arrays or device tensors uploads the former itself and lets _check refuse a tensor on the host);
+    error("<what>: <noun> ...") unless it is (C, T) with 1 <= T <= most (none_if_empty: T = 0 passes and gives None).  A host
+    array is copied to float32 (the caller's may be read-only) and fully checked: where `ordered`, every channel finite and
+    non-decreasing (repeats allowed).  A tensor is checked for its shape and for float32 (cast: converted instead) and is
+    otherwise taken as it is: its order is the caller's contract, nothing is read back to inspect it."""
+    import numpy as np
+    host = None
+    if not torch.is_tensor(table):
+        host = np.array(table, dtype=np.float32, order="C")
+        table = torch.from_numpy(host)
+    elif cast:
+        table = table.to(torch.float32)
+    least = 0 if none_if_empty else 1
+    if table.dim() != 2 or table.size(0) != C or not least <= table.size(1) <= most or table.dtype != torch.float32:
+        raise error("%s: %s must be (C, T) float32 with C=%d and %d <= T <= %d (got %s %s)"
+                    % (what, noun, C, least, most, tuple(table.shape), table.dtype))
+    if ordered and host is not None and (not np.all(np.isfinite(host)) or np.any(host[:, 1:] < host[:, :-1])):
+        raise error("%s: %s must be finite and non-decreasing per channel" % (what, noun))
+    if not table.size(1):
+        return None
+    table = table.detach().contiguous()
+    return table if device is None else table.to(device)
 
 
 _WS = {}
@@ -1346,7 +1376,7 @@ def latent_bound_step(mu, logvar, sq_mu, sq_logvar, eps, dz, nll, npx, lr, trace
 
 
 # ----------------------------------------------------------------------------------------------
-# ensemble statistics of M translations per input (model.translate_ensemble, test.py --metric ensemble)
+# ensemble statistics of M translations per input (model.translate_ensemble, eval_metrics.py, --metric ensemble)
 # ----------------------------------------------------------------------------------------------
 ENSEMBLE_MAX_M, ENSEMBLE_MAX_Q = 64, 8
 
@@ -1489,9 +1519,9 @@ def window_blend(tiles, plan, rows, C, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
-# radially averaged power spectra (model.translate_spectrum, test.py --metric spectrum), the spectral loss on them and the
-# paired cross-spectra (model.translate_coherence, test.py --metric coherence); both again for whole fields of any H x W
-# (model.translate_field_spectrum, test.py --metric field_spectrum)
+# radially averaged power spectra (model.translate_spectrum, eval_metrics.py, --metric spectrum), the spectral loss on them and the
+# paired cross-spectra (model.translate_coherence, eval_metrics.py, --metric coherence); both again for whole fields of any H x W
+# (model.translate_field_spectrum, eval_metrics.py, --metric field_spectrum)
 # ----------------------------------------------------------------------------------------------
 SPECTRUM_MIN_S, SPECTRUM_MAX_S = 16, 1024
 
@@ -1559,15 +1589,34 @@ def _paired_fields(what, x, y, C, layout_x, layout_y, size, x_per_y, max_per=Non
     return x, y, rows, rows_y, C, Cp, hw, sx, sy, x_per_y
 
 
-def _out_tensor(what, out, shape, inputs, strict=False):
-    """`out` as the caller gave it, refused unless it has the shape (strict: and is contiguous float32), or a new float32
-    tensor beside inputs[0]; the inputs and out go through _check in between: after the refusals that need no device"""
-    if out is not None and strict and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise _lib.AcgError("%s: out %s %s is not a contiguous float32 %s" % (what, tuple(out.shape), out.dtype, shape))
+def _refuse_out(what, out, shape, dtype=torch.float32, name="out"):
+    """the refusal, on the host, of an `out` that is not a contiguous tensor of this shape and dtype (None passes)"""
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous()):
+        raise _lib.AcgError("%s: %s %s %s is not a contiguous %s %s"
+                            % (what, name, tuple(out.shape), out.dtype, str(dtype).replace("torch.", ""), shape))
+
+
+def _out_or_new(out, shape, dtype, device):
+    """once the inputs have passed _check: `out` through its own device check (float32: _check), or a new tensor on `device`"""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if dtype == torch.float32:
+        _check(out)
+    elif not out.is_cuda:
+        raise _lib.AcgError(_NO_CPU_PATH % out.device)
+    return out
+
+
+def _out_tensor(what, out, shape, inputs, strict=False, dtype=torch.float32):
+    """`out` as the caller gave it, refused unless it has the shape (strict: and is contiguous of the dtype, _refuse_out), or
+    a new tensor of the dtype beside inputs[0]; the inputs and out go through _check in between: after the refusals that
+    need no device.  A call with several outputs does the three steps itself: _refuse_out each, one _check, _out_or_new each"""
+    if strict:
+        _refuse_out(what, out, shape, dtype)
     if out is not None and tuple(out.shape) != shape:
         raise _lib.AcgError("%s: out %s is not %s" % (what, tuple(out.shape), shape))
-    _check(*(tuple(inputs) + (out,)))
-    return torch.empty(shape, device=inputs[0].device, dtype=torch.float32) if out is None else out
+    _check(*inputs)
+    return _out_or_new(out, shape, dtype, inputs[0].device)
 
 
 def _metric_workspace(query, *args):
@@ -1634,7 +1683,7 @@ def radial_spectrum(x, C, layout, out=None):
 def spectral_loss(x, y, C, layout, eps=1e-6):
     """The squared log-spectral distance (in nepers) of the batch-mean spectra of x and y -> device scalar, differentiable in
     x: p = radial_spectrum(x).mean(0), q the same of y (detached); mean over the C channels and bins 1 .. S/2 of
-    (ln(p + eps) - ln(q + eps))^2.  Bin 0 (the mean) takes no part, as in test.log_spectral_distance.  eps belongs to the
+    (ln(p + eps) - ln(q + eps))^2.  Bin 0 (the mean) takes no part, as in eval_metrics.log_spectral_distance.  eps belongs to the
     definition: above the forward's absolute floor in an empty bin (~2.8e-7 for fields in [-1, 1]), below any populated bin.
     x and y need not pair (nor hold the same number of rows)."""
     p = radial_spectrum(x, C, layout).mean(0)
@@ -1808,7 +1857,7 @@ def marginal_loss(x, y, C, layout):
 
 
 # ----------------------------------------------------------------------------------------------
-# the marginal evaluator (model.translate_marginal, test.py --metric marginal): Wasserstein distances, quantiles and counts
+# the marginal evaluator (model.translate_marginal, eval_metrics.py, --metric marginal): Wasserstein distances, quantiles and counts
 # below thresholds from the sorted fields
 # ----------------------------------------------------------------------------------------------
 MARG_MAX_LEVELS, MARG_MAX_EDGES = 16, 256
@@ -1825,16 +1874,10 @@ def check_levels(levels):
 
 
 def _marginal_edges(what, edges, C, device):
-    """edges as sorted_scores takes them -> a contiguous (C, E) float32 tensor on the device (a host array is copied), or None"""
+    """edges as sorted_scores takes them -> channel_table's (C, E) tensor on the device, E <= 256; None for none or for E = 0"""
     if edges is None:
         return None
-    if not torch.is_tensor(edges):
-        import numpy as np
-        edges = torch.from_numpy(np.array(edges, dtype=np.float32, order="C"))       # a copy: the caller's array may be read-only
-    if edges.dim() != 2 or edges.size(0) != C or edges.size(1) > MARG_MAX_EDGES or edges.dtype != torch.float32:
-        raise _lib.AcgError("%s: edges must be (C, E) float32 with C=%d and E <= %d (got %s %s)"
-                            % (what, C, MARG_MAX_EDGES, tuple(edges.shape), edges.dtype))
-    return edges.detach().to(device).contiguous() if edges.size(1) else None
+    return channel_table(what, _lib.AcgError, "edges", edges, C, MARG_MAX_EDGES, device, none_if_empty=True)
 
 
 def sorted_scores(sx, sy, levels=(), edges=None, x_per_y=1, out=None):
@@ -1883,13 +1926,9 @@ def sorted_scores(sx, sy, levels=(), edges=None, x_per_y=1, out=None):
         if set(out) != set(want):
             raise _lib.AcgError("%s: out holds %s, the call writes %s" % (what, sorted(out), sorted(want)))
         for k, (shape, dtype) in want.items():
-            t = out[k]
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
-                raise _lib.AcgError("%s: out[%r] %s %s is not a contiguous %s %s on the device"
-                                    % (what, k, tuple(t.shape), t.dtype, dtype, shape))
+            _refuse_out(what, out[k], shape, dtype, "out[%r]" % k)
     _check(sx, sy, edges)                                          # after the refusals that need no device
-    if out is None:
-        out = {k: torch.empty(shape, device=sx.device, dtype=dtype) for k, (shape, dtype) in want.items()}
+    out = {k: _out_or_new(None if out is None else out[k], shape, dtype, sx.device) for k, (shape, dtype) in want.items()}
     _lib.call("acg_marginal_scores", _ptr(sx), _ptr(sy), rows, x_per_y, C, P, (ctypes.c_double * max(L, 1))(*lv), L, _ptr(edges), E,
               _ptr(out.get("w")), _ptr(out.get("q")), _ptr(out.get("below")), _stream())
     return out
@@ -1937,7 +1976,7 @@ def marginal_summary(below, cells, below_real, cells_real):
 
 
 # ----------------------------------------------------------------------------------------------
-# structural similarity (model._ssim_terms, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, test.py --metric ssim)
+# structural similarity (model._ssim_terms, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, eval_metrics.py, --metric ssim)
 # ----------------------------------------------------------------------------------------------
 SSIM_WINDOW, SSIM_MAX_HW = 11, 1024
 
@@ -2020,7 +2059,7 @@ def ssim_loss(x, y, C, layout, data_range=2.0):
 
 
 # ----------------------------------------------------------------------------------------------
-# neighbourhood fractions skill scores (model.translate_fss, test.py --metric fss)
+# neighbourhood fractions skill scores (model.translate_fss, eval_metrics.py, --metric fss)
 # ----------------------------------------------------------------------------------------------
 FSS_MAX_HW, FSS_MAX_T, FSS_MAX_NW, FSS_MAX_M = 1024, 8, 8, 64
 
@@ -2056,29 +2095,18 @@ def fss(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, ensemble=Fa
         win = check_windows(windows)
     except ValueError as e:
         raise _lib.AcgError("fss: %s" % e)
-    thr = thresholds
-    if not torch.is_tensor(thr):
-        import numpy as np
-        thr = torch.from_numpy(np.ascontiguousarray(np.asarray(thr, dtype=np.float32)))
-    if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= FSS_MAX_T:
-        raise _lib.AcgError("fss: thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)" % (C, FSS_MAX_T, tuple(thr.shape)))
+    thr = channel_table("fss", _lib.AcgError, "thresholds", thresholds, C, FSS_MAX_T, None)
     T, nw = int(thr.size(1)), len(win)
     o, e = (out if ensemble else (out, None)) if out is not None else (None, None)
     shapes = ((rows, C, T, nw, 3), (rows_y, C, T, nw, 3))
-    for t, shape, name in ((o, shapes[0], "out"), (e, shapes[1], "ens")):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.int64 or not t.is_contiguous()):
-            raise _lib.AcgError("fss: %s %s %s is not a contiguous int64 %s" % (name, tuple(t.shape), t.dtype, shape))
-    if not torch.is_tensor(thresholds):
+    _refuse_out("fss", o, shapes[0], torch.int64)
+    _refuse_out("fss", e, shapes[1], torch.int64, "ens")
+    if not torch.is_tensor(thresholds):                            # a host array goes to the device; a tensor is where it has to be
         thr = thr.to(x.device)
-    thr = thr.detach().contiguous()
     _check(x, y, thr)                                              # after the refusals that need no device
-    for t in (o, e):
-        if t is not None and not t.is_cuda:
-            raise _lib.AcgError("acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path" % t.device)
-    if o is None:
-        o = torch.empty(shapes[0], device=x.device, dtype=torch.int64)
-    if ensemble and e is None:
-        e = torch.empty(shapes[1], device=x.device, dtype=torch.int64)
+    o = _out_or_new(o, shapes[0], torch.int64, x.device)
+    if ensemble:
+        e = _out_or_new(e, shapes[1], torch.int64, x.device)
     ws, nbytes = _metric_workspace("acg_fss_workspace_bytes", rows, x_per_y, C, H, W, T, nw, int(ensemble))
     _lib.call("acg_fss", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
               (ctypes.c_int * nw)(*win), nw, _ptr(o), _ptr(e), ws, nbytes, _stream())
@@ -2125,7 +2153,7 @@ def fss_summary(sums, windows, cells, members=1):
 
 
 # ----------------------------------------------------------------------------------------------
-# Minkowski functionals of excursion sets (model.translate_minkowski, test.py --metric minkowski)
+# Minkowski functionals of excursion sets (model.translate_minkowski, eval_metrics.py, --metric minkowski)
 # ----------------------------------------------------------------------------------------------
 MINK_MAX_T, MINK_MAX_HW = 255, 1024
 MINK_FUNCTIONALS = ("area", "perimeter", "euler4", "euler8")
@@ -2134,13 +2162,7 @@ MINK_FUNCTIONALS = ("area", "perimeter", "euler4", "euler8")
 def check_thresholds(thresholds, C):
     """host thresholds as minkowski takes them -> a contiguous (C, T) float32 array; ValueError unless 1 <= T <= 255 and every
     channel's thresholds are finite and non-decreasing (repeats allowed)"""
-    import numpy as np
-    thr = np.array(thresholds, dtype=np.float32, order="C")        # a copy: the caller's array may be read-only
-    if thr.ndim != 2 or thr.shape[0] != C or not 1 <= thr.shape[1] <= MINK_MAX_T:
-        raise ValueError("thresholds must be (C, T) with C=%d and 1 <= T <= %d (got %s)" % (C, MINK_MAX_T, thr.shape))
-    if not np.all(np.isfinite(thr)) or np.any(thr[:, 1:] < thr[:, :-1]):
-        raise ValueError("thresholds must be finite and non-decreasing per channel")
-    return thr
+    return channel_table("check_thresholds", ValueError, "thresholds", thresholds, C, MINK_MAX_T, None, ordered=True).numpy()
 
 
 def minkowski(x, C, layout, thresholds, out=None):
@@ -2151,34 +2173,19 @@ def minkowski(x, C, layout, thresholds, out=None):
     linear over fields: sum them over a set of fields, then ops.minkowski_summary.  layout "nhwc": x (rows, H, W, Cp) as
     forward_nhwc / ToNHWC give it (padded channels never reach a result); "nchw": x (rows, C, H, W).  1 <= H, W <= 1024.
     thresholds: (C, T), 1 <= T <= 255, per channel finite and non-decreasing (repeats allowed): a host array is checked
-    (check_thresholds) and copied to the device; a float32 device tensor is taken as it is - its order is the caller's
+    (channel_table) and copied to the device; a float32 device tensor is taken as it is - its order is the caller's
     contract, nothing is read back to check it.  `out`: the contiguous int64 tensor to write.  One pass over x for all
     thresholds, two launches; nothing is read back to the host.  Not differentiable."""
     x = x.detach().contiguous()
     rows, C, _, H, W, sx = _field_args(x, C, layout, "minkowski")
     if not (1 <= H <= MINK_MAX_HW and 1 <= W <= MINK_MAX_HW):
         raise _lib.AcgError("minkowski: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (MINK_MAX_HW, H, W))
-    thr = thresholds
-    if not torch.is_tensor(thr):
-        try:
-            thr = torch.from_numpy(check_thresholds(thr, C))
-        except ValueError as e:
-            raise _lib.AcgError("minkowski: %s" % e)
-    if thr.dim() != 2 or thr.size(0) != C or not 1 <= thr.size(1) <= MINK_MAX_T or thr.dtype != torch.float32:
-        raise _lib.AcgError("minkowski: thresholds must be (C, T) float32 with C=%d and 1 <= T <= %d (got %s %s)"
-                            % (C, MINK_MAX_T, tuple(thr.shape), thr.dtype))
+    thr = channel_table("minkowski", _lib.AcgError, "thresholds", thresholds, C, MINK_MAX_T, None, ordered=True)
     T = int(thr.size(1))
-    shape = (rows, C, T, 5)
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.int64 or not out.is_contiguous()):
-        raise _lib.AcgError("minkowski: out %s %s is not a contiguous int64 %s" % (tuple(out.shape), out.dtype, shape))
-    if not torch.is_tensor(thresholds):
+    _refuse_out("minkowski", out, (rows, C, T, 5), torch.int64)
+    if not torch.is_tensor(thresholds):                            # a host array goes to the device; a tensor is where it has to be
         thr = thr.to(x.device)
-    thr = thr.detach().contiguous()
-    _check(x, thr)                                                 # after the refusals that need no device
-    if out is not None and not out.is_cuda:
-        raise _lib.AcgError("acgan_hip kernels need tensors on a ROCm device (got %s); there is no CPU path" % out.device)
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.int64)
+    out = _out_tensor("minkowski", out, (rows, C, T, 5), (x, thr), dtype=torch.int64)
     ws, nbytes = _metric_workspace("acg_minkowski_workspace_bytes", rows, C, H, W, T)
     _lib.call("acg_minkowski", _ptr(x), rows, C, H, W, sx[0], sx[1], sx[2], _ptr(thr), T, _ptr(out), ws, nbytes, _stream())
     return out

@@ -177,6 +177,9 @@ class TrainOptions(object):
         return opt
 
 
+REFERENCE_METRICS = ('bpp', 'mse', 'visual', 'noise_sens', 'mvgauss')      # the project's own: eval_metrics.METRICS
+
+
 class TestOptions(object):
     """options.py:134-143 (the options of dtgan_amd.test).  Additions: the metric `mvgauss` (the reference's
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
@@ -191,17 +194,18 @@ class TestOptions(object):
     --mink_bins."""
 
     def __init__(self):
+        from .eval_metrics import METRICS      # here, not at the top: it imports train.py, which imports this module
+        own = [m.name for m in METRICS]
         self.parser = argparse.ArgumentParser()
         self.parser.add_argument('--chk_path', required=True, type=str)
         self.parser.add_argument('--res_dir', type=str, default='test_res')
         self.parser.add_argument('--train_logvar', type=int, default=1)
         self.parser.add_argument('--dataroot', required=True, type=str)
-        self.parser.add_argument('--metric', required=True, type=str,
-                                 choices=['bpp', 'mse', 'visual', 'noise_sens', 'mvgauss', 'ensemble', 'spectrum', 'coherence', 'fss', 'translate',
-                                          'field_spectrum', 'ssim', 'marginal', 'minkowski'])
+        self.parser.add_argument('--metric', required=True, type=str, choices=list(REFERENCE_METRICS) + own)
         self.parser.add_argument('--ubo_steps', type=int, default=500, help='iterates of the variational bound per test batch')
         self.parser.add_argument('--gpu_ids', type=str, default='0', help='the GPU to evaluate on (the first id given)')
-        self.parser.add_argument('--n_samples', type=_n_samples, default=16, help='--metric ensemble / spectrum / coherence / fss / translate / field_spectrum / ssim / marginal / minkowski: translations per input (1..64)')
+        self.parser.add_argument('--n_samples', type=_n_samples, default=16,
+                                 help='--metric %s: translations per input (1..64)' % ' / '.join(own))
         self.parser.add_argument('--quantiles', type=_quantiles, default=(0.05, 0.5, 0.95),
                                  help='--metric ensemble: comma-separated quantile levels, sorted inside [0, 1], at most 8')
         self.parser.add_argument('--fss_quantiles', type=_fss_quantiles, default=(0.5, 0.9, 0.99),

@@ -8,7 +8,7 @@ import pytest
 
 import dtgan_amd  # noqa: F401
 from dtgan_amd import options as O
-from dtgan_amd import test as T
+from dtgan_amd import eval_metrics as EM, test as T
 from golden_util import load
 
 
@@ -108,11 +108,11 @@ def test_read_back_returns_every_tensor_with_its_shape(dtype):
     g = torch.Generator().manual_seed(11)
     shapes = [(3, 2, 5), (), (7,), (2, 1, 3, 3), (1,)]
     ts = [(torch.randn(s, generator=g) * 100).to(getattr(torch, dtype)) for s in shapes]
-    got = T._read_back(ts)
+    got = EM._read_back(ts)
     assert len(got) == len(ts)
     for a, t in zip(got, ts):
         assert a.shape == tuple(t.shape) and a.dtype == np.dtype(dtype) and np.array_equal(a, t.numpy())
-    (only,) = T._read_back(iter(ts[:1]))                           # any iterable, a single tensor included
+    (only,) = EM._read_back(iter(ts[:1]))                           # any iterable, a single tensor included
     assert np.array_equal(only, ts[0].numpy())
 
 

@@ -73,8 +73,8 @@ def test_options_accept_the_metric():
     a = TestOptions().parse(["--chk_path", "x/latest", "--dataroot", "d", "--metric", "field_spectrum", "--n_samples", "3",
                              "--overlap", "5"])
     assert (a.metric, a.n_samples, a.overlap) == ("field_spectrum", 3, 5)
-    from dtgan_amd import test as T
-    assert "field_spectrum" in T.WHOLE_FIELD_METRICS and "translate" in T.WHOLE_FIELD_METRICS
+    from dtgan_amd import eval_metrics as EM
+    assert "field_spectrum" in EM.WHOLE_FIELD_METRICS and "translate" in EM.WHOLE_FIELD_METRICS
 
 
 def test_cross_reference_of_a_field_with_itself():

@@ -123,12 +123,12 @@ def test_the_fss_options():
 
 
 def test_thresholds_are_float64_quantiles_per_channel():
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM
     train = np.random.RandomState(1).uniform(0, 3, (6, 2, 8, 8)).astype(np.float32)
-    thr = T.fss_thresholds(train, (0.5, 0.9))
+    thr = EM.fss_thresholds(train, (0.5, 0.9))
     want = np.stack([np.quantile(train[:, c].astype(np.float64), [0.5, 0.9]) for c in range(2)]).astype(np.float32)
     assert thr.dtype == np.float32 and thr.shape == (2, 2) and np.array_equal(thr, want)
-    assert np.array_equal(T.fss_thresholds(train, (0.5,), (1.0, 2.5)), np.array([[1.0, 2.5], [1.0, 2.5]], np.float32))
+    assert np.array_equal(EM.fss_thresholds(train, (0.5,), (1.0, 2.5)), np.array([[1.0, 2.5], [1.0, 2.5]], np.float32))
 
 
 def test_the_header_declares_both_entries_and_the_binding_matches():

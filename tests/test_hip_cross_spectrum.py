@@ -278,7 +278,7 @@ def test_translate_coherence_host_syncs_do_not_grow_with_groups():
 def test_metric_coherence(experiment):
     from test_hip_eval_driver import S
     from dtgan_amd import ops
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM, test as T
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
     env = dict(os.environ, PYTHONPATH=ROOT)
     pat = (r"^DEV_KEFF_B: (\d+\.\d{4}), TEST_KEFF_B: (\d+\.\d{4}), TEST_KEFF_MEAN_B: (\d+\.\d{4}), TEST_KEFF_A: (\d+\.\d{4}), "
@@ -298,13 +298,13 @@ def test_metric_coherence(experiment):
     for k in arr:                                                  # two runs, the same file
         assert arr[k].dtype == arr2[k].dtype and np.array_equal(arr[k], arr2[k]), k
     nb = S // 2 + 1
-    want = {"n_samples", "bin_counts"} | {"%s_%s_%s" % (split, q, k) for split in ("dev", "test") for k in T.COHERENCE_PAIRS
+    want = {"n_samples", "bin_counts"} | {"%s_%s_%s" % (split, q, k) for split in ("dev", "test") for k in EM.COHERENCE_PAIRS
                                           for q in ("sums", "coh", "r", "perr", "k_eff")}
     assert set(arr) == want, set(arr) ^ want
     assert int(arr["n_samples"]) == 4 and np.array_equal(arr["bin_counts"], R.bin_counts(S))
     _, _, devA, devB, testA, testB = load_numpy_data(experiment["data"], grid_size=S)
     for split, A, B in (("dev", devA, devB), ("test", testA, testB)):
-        for k in T.COHERENCE_PAIRS:
+        for k in EM.COHERENCE_PAIRS:
             sums, coh, r = arr["%s_sums_%s" % (split, k)], arr["%s_coh_%s" % (split, k)], arr["%s_r_%s" % (split, k)]
             perr, k_eff = arr["%s_perr_%s" % (split, k)], arr["%s_k_eff_%s" % (split, k)]
             assert sums.shape == (3, 3, nb) and sums.dtype == np.float64 and np.all(np.isfinite(sums)), (split, k)
@@ -330,11 +330,11 @@ def test_metric_coherence(experiment):
         model, _ = T._build(opt)
         model.load(experiment["chk"])
         torch.manual_seed(12345)
-        T.eval_coherence(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
-        test = T.eval_coherence(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
+        EM.eval_coherence(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
+        test = EM.eval_coherence(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
     finally:
         ops.set_precision(prec)
-    for k in T.COHERENCE_PAIRS:
+    for k in EM.COHERENCE_PAIRS:
         assert np.allclose(arr["test_sums_" + k], test["sums_" + k], rtol=1e-6), k
         assert np.array_equal(arr["test_k_eff_" + k], test["k_eff_" + k]), k
 

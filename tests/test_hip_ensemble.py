@@ -208,7 +208,7 @@ def test_flags_and_grad_mode_survive_a_raising_consumer(which, monkeypatch):
 def test_metric_ensemble(experiment):
     from test_hip_eval_driver import _png_shape, S
     from dtgan_amd import ops
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM, test as T
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
     env = dict(os.environ, PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
@@ -240,8 +240,8 @@ def test_metric_ensemble(experiment):
         model.load(experiment["chk"])
         _, _, devA, devB, testA, testB = load_numpy_data(experiment["data"], grid_size=S)
         torch.manual_seed(12345)
-        T.eval_ensemble_B(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4, (0.05, 0.5, 0.95))
-        test, _ = T.eval_ensemble_B(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4, (0.05, 0.5, 0.95))
+        EM.eval_ensemble_B(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4, (0.05, 0.5, 0.95))
+        test, _ = EM.eval_ensemble_B(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4, (0.05, 0.5, 0.95))
     finally:
         ops.set_precision(prec)
     assert abs(float(mt.group(2)) - test["crps"].mean()) < 1e-4, (mt.group(2), test["crps"].mean())

@@ -353,7 +353,7 @@ def test_translate_fss_host_syncs_do_not_grow_with_groups():
 def test_metric_fss(experiment):
     from test_hip_eval_driver import S
     from dtgan_amd import ops
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM, test as T
     from dtgan_amd.dataloader import load_numpy_data
     env = dict(os.environ, PYTHONPATH=ROOT)
     num = r"(\d+\.\d{4}|nan)"
@@ -375,7 +375,7 @@ def test_metric_fss(experiment):
         assert arr[k].dtype == arr2[k].dtype and np.array_equal(arr[k], arr2[k], equal_nan=True), k
     win, M, C, Tn = (1, 3, 9, 17), 4, 3, 3
     want = {"n_samples", "windows", "thresholds_B", "thresholds_A"}
-    want |= {"%s_%s_%s" % (split, q, k) for split in ("dev", "test") for k in T.FSS_PAIRS
+    want |= {"%s_%s_%s" % (split, q, k) for split in ("dev", "test") for k in EM.FSS_PAIRS
              for q in ("sums", "fss", "bias", "csi", "base_rate", "useful_scale")}
     assert set(arr) == want, set(arr) ^ want
     assert int(arr["n_samples"]) == M and arr["windows"].dtype == np.int64 and tuple(arr["windows"]) == win     # 1 put in front
@@ -384,7 +384,7 @@ def test_metric_fss(experiment):
         q = np.quantile(np.asarray(train).astype(np.float64).transpose(1, 0, 2, 3).reshape(C, -1), [0.5, 0.9, 0.99], axis=1).T
         assert arr[name].dtype == np.float32 and arr[name].shape == (C, Tn) and np.array_equal(arr[name], q.astype(np.float32)), name
     for split, A, B in (("dev", np.asarray(devA), np.asarray(devB)), ("test", np.asarray(testA), np.asarray(testB))):
-        for k in T.FSS_PAIRS:
+        for k in EM.FSS_PAIRS:
             g = lambda q: arr["%s_%s_%s" % (split, q, k)]
             sums = g("sums")
             assert sums.shape == (C, Tn, 4, 3) and sums.dtype == np.int64 and np.all(sums >= 0), (split, k)

@@ -174,7 +174,7 @@ def experiment(tmp_path_factory):
 
 
 def test_metric_marginal_writes_its_file(experiment, capsys):
-    from dtgan_amd import ops, test as T
+    from dtgan_amd import eval_metrics as EM, ops, test as T
     prec = ops.get_precision()
     try:
         opt = T.test_model(["--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric", "marginal", "--n_samples",
@@ -186,7 +186,7 @@ def test_metric_marginal_writes_its_file(experiment, capsys):
     assert re.search(r"DEV_W1_B: \d+\.\d{4}, TEST_W1_B: \d+\.\d{4}, TEST_W1_MEAN_B: ", out) and "TEST_KS_A: " in out, out[-2000:]
     a = dict(np.load(os.path.join(experiment["expr"], "res_marg", "marginal.npz")))
     C, L, E, M, P = 3, 4, 9, 2, S * S
-    assert T.MARGINAL_PAIRS == ("members_B", "ens_mean_B", "fake_A")
+    assert EM.MARGINAL_PAIRS == ("members_B", "ens_mean_B", "fake_A")
     assert a["levels"].dtype == np.float64 and np.array_equal(a["levels"], [0.0, 0.5, 0.99, 1.0]) and int(a["n_samples"]) == M
     for d in "BA":
         e = a["edges_" + d]
@@ -197,7 +197,7 @@ def test_metric_marginal_writes_its_file(experiment, capsys):
         g = lambda name: a["%s_%s" % (split, name)]
         n = g("w1_members_B_per_input").shape[0] if n is None else n
         assert n >= 1
-        for k in T.MARGINAL_PAIRS:
+        for k in EM.MARGINAL_PAIRS:
             per_field = M if k == "members_B" else 1
             for name, shape, dtype in (("w1", (C,), np.float64), ("w2sq", (C,), np.float64), ("w1_%s_per_input", (n, C), np.float64),
                                        ("w2sq_%s_per_input", (n, C), np.float64), ("q", (C, L), np.float64),
@@ -232,12 +232,12 @@ def test_metric_marginal_writes_its_file(experiment, capsys):
 
 def test_the_real_fields_of_eval_marginal_are_numpys(experiment):
     """eval_marginal's truth entries against NumPy on the batches it was given, and ks of the truths against themselves is 0"""
-    from dtgan_amd import ops, test as T
+    from dtgan_amd import eval_metrics as EM, ops
     rs = np.random.RandomState(7)
     A = rs.uniform(-1, 1, (4, 3, S, S)).astype(np.float32)
     B = R.make_fields("masked", S, S, 4, 3)
     levels = (0.0, 0.25, 1.0)
-    edges_B, edges_A = T.marginal_edges(B, 5), T.marginal_edges(A, 5)
+    edges_B, edges_A = EM.marginal_edges(B, 5), EM.marginal_edges(A, 5)
 
     class Model(object):                                                      # B -> A and A -> B as identities of the truths
         def translate_marginal(self, real_A, n, real_B, lv, e):
@@ -255,11 +255,11 @@ def test_the_real_fields_of_eval_marginal_are_numpys(experiment):
         for b in batches:
             m.real_A = b["A"].cuda()
             yield b
-    res = T.eval_marginal(dataset(), m, 1, levels, edges_B, edges_A)
+    res = EM.eval_marginal(dataset(), m, 1, levels, edges_B, edges_A)
     for d, x, e in (("B", B, edges_B), ("A", A, edges_A)):
         ref = R.scores(x, None, levels, e)
         assert np.array_equal(res["below_real_" + d], ref["below"].sum(0, dtype=np.int64)) and int(res["cells_real_" + d]) == 4 * S * S
         assert np.allclose(res["q_real_" + d], ref["q"].astype(np.float64).mean(0), rtol=0, atol=1e-12)
-    for k in T.MARGINAL_PAIRS:                                                 # every comparison is a truth against itself
+    for k in EM.MARGINAL_PAIRS:                                                 # every comparison is a truth against itself
         assert np.all(res["ks_" + k] == 0.0) and np.all(res["w1_" + k] == 0.0) and np.all(res["w2sq_" + k] == 0.0), k
         assert res["w1_%s_per_input" % k].shape == (4, 3)

@@ -1,5 +1,5 @@
 """GPU tests of the Minkowski evaluator above the C ABI: model.translate_minkowski against tests/minkowski_ref.py on the
-members generate_multi gives for the same codes, test.eval_minkowski's real sets against the reference, and `--metric
+members generate_multi gives for the same codes, eval_metrics.eval_minkowski's real sets against the reference, and `--metric
 minkowski` on a saved tiny checkpoint (test_model, what `python -m dtgan_amd.test` runs)."""
 import os
 import re
@@ -64,17 +64,17 @@ def test_translate_minkowski_equals_the_reference_on_generate_multis_members(mod
 
 
 def test_the_real_sets_of_eval_minkowski_are_the_references(model):
-    from dtgan_amd import ops, test as T
+    from dtgan_amd import eval_metrics as EM, ops
     rs = np.random.RandomState(7)
     A = K.make_fields("smooth", 5, 3, S, S, np.zeros((3, 1), np.float32), seed=1)
     B = K.make_fields("smooth", 5, 3, S, S, np.zeros((3, 1), np.float32), seed=2)
     B[rs.uniform(size=B.shape) < 0.3] = -1.0                        # mass at one value: the octiles 1/8 and 2/8 coincide
-    thr_B, thr_A = T.marginal_edges(B, 8), T.marginal_edges(A, 8)
+    thr_B, thr_A = EM.marginal_edges(B, 8), EM.marginal_edges(A, 8)
     assert np.any(np.diff(thr_B, axis=1) == 0)
     batches = [dict(A=torch.from_numpy(A[:3]), B=torch.from_numpy(B[:3])), dict(A=torch.from_numpy(A[3:]), B=torch.from_numpy(B[3:]))]
     M = 2
     torch.manual_seed(11)
-    res = T.eval_minkowski(batches, model, M, thr_B, thr_A)
+    res = EM.eval_minkowski(batches, model, M, thr_B, thr_A)
     P = S * S
     for d, x, thr in (("B", B, thr_B), ("A", A, thr_A)):
         ref = K.counts(x, thr).sum(0)
@@ -88,7 +88,7 @@ def test_the_real_sets_of_eval_minkowski_are_the_references(model):
     with torch.no_grad():
         fake_A = model.predict_A(torch.from_numpy(B).cuda()).cpu().numpy()
     assert np.array_equal(res["counts_fake_A"], K.counts(fake_A, thr_A).sum(0))
-    for k, real in T.MINKOWSKI_PAIRS:
+    for k, real in EM.MINKOWSKI_PAIRS:
         d = ops.minkowski_distance(ops.minkowski_summary(res["counts_" + k], res["cells_" + k]),
                                    ops.minkowski_summary(res["counts_" + real], res["cells_" + real]))
         for f in FUNCTIONALS:
@@ -119,7 +119,7 @@ def experiment(tmp_path_factory):
 
 
 def test_metric_minkowski_writes_its_file(experiment, capsys):
-    from dtgan_amd import ops, test as T
+    from dtgan_amd import eval_metrics as EM, ops, test as T
     from dtgan_amd.dataloader import load_numpy_data
     prec = ops.get_precision()
     try:
@@ -141,11 +141,11 @@ def test_metric_minkowski_writes_its_file(experiment, capsys):
         q = np.quantile(np.asarray(train).astype(np.float64).transpose(1, 0, 2, 3).reshape(C, -1), np.arange(1, 6) / 6.0, axis=1).T
         assert a[name].dtype == np.float32 and a[name].shape == (C, Tn) and np.array_equal(a[name], q.astype(np.float32)), name
     want = {"n_samples", "bins", "thresholds_B", "thresholds_A"}
-    assert T.MINKOWSKI_SETS == ("members_B", "ens_mean_B", "fake_A", "real_B", "real_A")
+    assert EM.MINKOWSKI_SETS == ("members_B", "ens_mean_B", "fake_A", "real_B", "real_A")
     for split, fields in (("dev", (devA, devB)), ("test", (testA, testB))):
         g = lambda name: a["%s_%s" % (split, name)]
         n = len(fields[0])
-        for k in T.MINKOWSKI_SETS:
+        for k in EM.MINKOWSKI_SETS:
             want |= {"%s_counts_%s" % (split, k), "%s_cells_%s" % (split, k)}
             assert g("counts_" + k).shape == (C, Tn, 5) and g("counts_" + k).dtype == np.int64 and np.all(g("counts_" + k) >= 0)
             assert g("cells_" + k).dtype == np.int64 and int(g("cells_" + k)) == n * P * (M if k == "members_B" else 1)
@@ -155,7 +155,7 @@ def test_metric_minkowski_writes_its_file(experiment, capsys):
                 want |= {"%s_%s_%s" % (split, name, k), "%s_%s_density_%s" % (split, name, k)}
                 assert g("%s_%s" % (name, k)).dtype == np.float64 and np.array_equal(g("%s_%s" % (name, k)), f[name].astype(np.float64))
                 assert np.array_equal(g("%s_density_%s" % (name, k)), f[name] / float(g("cells_" + k)))
-        for (k, real), tag in zip(T.MINKOWSKI_PAIRS, ("MINK_B", "MINK_MEAN_B", "MINK_A")):
+        for (k, real), tag in zip(EM.MINKOWSKI_PAIRS, ("MINK_B", "MINK_MEAN_B", "MINK_A")):
             printed = re.search(r"%s_%s: (%s)" % (split.upper(), tag, four), out).group(1).split()
             for i, name in enumerate(FUNCTIONALS):
                 key = "dist_%s_%s" % (name, k)

@@ -226,7 +226,7 @@ def test_translate_spectrum_host_syncs_do_not_grow_with_groups():
 def test_metric_spectrum(experiment):
     from test_hip_eval_driver import S
     from dtgan_amd import ops
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM, test as T
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
     env = dict(os.environ, PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
@@ -265,8 +265,8 @@ def test_metric_spectrum(experiment):
         model, _ = T._build(opt)
         model.load(experiment["chk"])
         torch.manual_seed(12345)
-        T.eval_spectrum(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
-        test = T.eval_spectrum(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
+        EM.eval_spectrum(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
+        test = EM.eval_spectrum(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
     finally:
         ops.set_precision(prec)
     assert abs(float(mt.group(2)) - test["lsd_B"]) < 1e-4, (mt.group(2), test["lsd_B"])

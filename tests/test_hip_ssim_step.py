@@ -195,7 +195,7 @@ def experiment(tmp_path_factory):
 
 
 def test_metric_ssim_writes_its_file(experiment, capsys):
-    from dtgan_amd import ops, test as T
+    from dtgan_amd import eval_metrics as EM, ops, test as T
     prec = ops.get_precision()
     try:
         T.test_model(["--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric", "ssim", "--n_samples", "2",
@@ -207,7 +207,7 @@ def test_metric_ssim_writes_its_file(experiment, capsys):
     a = dict(np.load(os.path.join(experiment["expr"], "res_ssim", "ssim.npz")))
     want = {"n_samples"}
     for split, n in (("dev", None), ("test", 3)):
-        for k in T.SSIM_PAIRS:
+        for k in EM.SSIM_PAIRS:
             for q in ("ssim", "cs"):
                 mean, per = a["%s_%s_%s" % (split, q, k)], a["%s_%s_%s_per_input" % (split, q, k)]
                 want |= {"%s_%s_%s" % (split, q, k), "%s_%s_%s_per_input" % (split, q, k)}
@@ -215,7 +215,7 @@ def test_metric_ssim_writes_its_file(experiment, capsys):
                 assert mean.shape == (3,) and per.shape == (n_in, 3) and mean.dtype == np.float64 and per.dtype == np.float64
                 assert np.isfinite(mean).all() and np.isfinite(per).all() and np.abs(per).max() <= 1 and np.abs(mean).max() <= 1
                 assert np.allclose(per.mean(0), mean, rtol=0, atol=1e-12)
-    assert T.SSIM_PAIRS == ('members_B', 'ens_mean_B', 'fake_A') and set(a) == want and int(a["n_samples"]) == 2
+    assert EM.SSIM_PAIRS == ('members_B', 'ens_mean_B', 'fake_A') and set(a) == want and int(a["n_samples"]) == 2
 
 
 def test_train_driver_with_the_ssim_loss(tmp_path):

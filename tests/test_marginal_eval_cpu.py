@@ -10,7 +10,7 @@ import pytest
 import dtgan_amd  # noqa: F401
 from dtgan_amd import ops
 from dtgan_amd import options as O
-from dtgan_amd import test as T
+from dtgan_amd import eval_metrics as EM
 import marginal_eval_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,16 +98,16 @@ def test_scores_holds_only_what_was_asked_for():
 def test_marginal_edges_are_the_training_quantiles_per_channel():
     train = np.concatenate([R.make_fields("masked", 16, 16, 5, 2), R.make_fields("uniform", 16, 16, 4, 2, seed=3)])
     for bins in (2, 10, 100, 257):
-        e = T.marginal_edges(train, bins)
+        e = EM.marginal_edges(train, bins)
         assert e.dtype == np.float32 and e.shape == (2, bins - 1)
         for c in range(2):
             want = np.quantile(train[:, c].astype(np.float64).ravel(), np.arange(1, bins) / float(bins))
             assert np.array_equal(e[c], want.astype(np.float32))
         assert np.all(np.diff(e, axis=1) >= 0)
-    assert np.any(np.diff(T.marginal_edges(train, 100), axis=1) == 0)               # the mass at 0 repeats an edge
+    assert np.any(np.diff(EM.marginal_edges(train, 100), axis=1) == 0)               # the mass at 0 repeats an edge
     for bins in (1, 258):
         with pytest.raises(ValueError):
-            T.marginal_edges(train, bins)
+            EM.marginal_edges(train, bins)
 
 
 def test_marginal_summary_on_hand_made_counts():

@@ -156,12 +156,12 @@ def test_the_parser_takes_the_metric_and_its_bins():
 
 def test_the_thresholds_of_the_metric_are_the_training_quantiles():
     from dtgan_amd import ops
-    from dtgan_amd import test as T
+    from dtgan_amd import eval_metrics as EM, test as T
     train = np.random.RandomState(2).uniform(-1, 1, (5, 2, 8, 8)).astype(np.float32)
     for bins in (2, 32, 256):
-        thr = ops.check_thresholds(T.marginal_edges(train, bins), 2)
+        thr = ops.check_thresholds(EM.marginal_edges(train, bins), 2)
         assert thr.shape == (2, bins - 1)
-    assert "minkowski" in T.__doc__ and "mink_bins" in T.__doc__ and "eval_minkowski" in dir(T)
+    assert "minkowski" in T.__doc__ and "mink_bins" in T.__doc__ and "eval_minkowski" in dir(EM)
 
 
 def test_the_header_declares_both_entries_and_the_binding_matches():

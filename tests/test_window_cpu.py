@@ -123,8 +123,11 @@ def test_evaluator_options(capsys):
     for bad in (9, -1):
         with pytest.raises(ValueError, match="--overlap"):
             O.check_overlap(bad, 16)
-    src = open(os.path.join(ROOT, "domain-transfer-gan_amd", "test.py")).read()
-    assert re.search(r"for k in \([^)]*'overlap'[^)]*\):\s*setattr\(opt, k, getattr\(args, k\)\)", src)
+    from dtgan_amd import test as T                                # the parsed --overlap wins over a saved one, the default too
+    saved = {"overlap": 99, "grid_size": 64}
+    assert T._merged_options(saved, O.TestOptions().parse(base + ["--overlap", "3"])).overlap == 3
+    merged = T._merged_options(saved, args)
+    assert merged.overlap is None and merged.grid_size == 64
 
 
 def test_header_declares_both_entries_and_keeps_the_version():
