@@ -336,7 +336,7 @@ MINKOWSKI_SETS = ('members_B', 'ens_mean_B', 'fake_A', 'real_B', 'real_A')
 MINKOWSKI_PAIRS = (('members_B', 'real_B'), ('ens_mean_B', 'real_B'), ('fake_A', 'real_A'))
 
 
-def eval_minkowski(dataset, model, n_samples, thr_B, thr_A, use_gpu=True):
+def eval_minkowski(dataset, model, n_samples, thr_B, thr_A, use_gpu=True, components=0):
     """the shape of the excursion sets on a split, one read of the counts per batch.  The counts of ops.minkowski, at the
     thresholds thr_B (C_B, T) in domain B and thr_A (C_A, T) in domain A, are summed in int64 over the fields of five sets:
     the n_samples translations A -> B of every input (members_B) and their per-pixel means (ens_mean_B)
@@ -344,20 +344,30 @@ def eval_minkowski(dataset, model, n_samples, thr_B, thr_A, use_gpu=True):
     (real_B, real_A).  Unpaired: the sets are compared as sets.  -> dict, per set k of MINKOWSKI_SETS: counts_k (C, T, 5)
     int64, cells_k int64 and the float64 (C, T) arrays of ops.minkowski_summary, area_k, perimeter_k, euler4_k, euler8_k and
     the same per cell under *_density_k; per translated set k, against the real set of its domain (MINKOWSKI_PAIRS):
-    dist_area_k, dist_perimeter_k, dist_euler4_k, dist_euler8_k (C,) of ops.minkowski_distance"""
+    dist_area_k, dist_perimeter_k, dist_euler4_k, dist_euler8_k (C,) of ops.minkowski_distance.  components = 4 or 8: the
+    connected components of the same sets under that connectivity too (ops.components, summed like the counts): per set
+    comp_k (C, T, 25) int64 and the entries of ops.components_summary under <name>_k, per translated set dist_components_k,
+    dist_holes_k, dist_size_k (C,) of ops.components_distance; 0: none of them, and no launch more than before"""
     sums = {k: _Sum() for k in MINKOWSKI_SETS}
+    comp = {k: _Sum() for k in MINKOWSKI_SETS}
     thresholds = _domain_tables(thr_B, thr_A, check=ops.check_thresholds)
     for real_A, real_B in _batches(dataset, use_gpu):
         t_B, t_A = thresholds(real_B, real_A)
-        r = model.translate_minkowski(real_A, n_samples, t_B)
+        r = model.translate_minkowski(real_A, n_samples, t_B, components=components)
         CA, CB = real_A.size(1), real_B.size(1)
         with torch.no_grad():
-            fake_A = ops.minkowski(model.predict_A(real_B), CA, "nchw", t_A)
+            pred_A = model.predict_A(real_B)
+            fake_A = ops.minkowski(pred_A, CA, "nchw", t_A)
         parts = (r['members'].flatten(0, 1), r['ens_mean'], fake_A, ops.minkowski(real_B, CB, "nchw", t_B),
                  ops.minkowski(real_A, CA, "nchw", t_A))
         # the fields of a set are summed on the device: what is read is (1, C, T, 5) per set
         for k, p, v in zip(MINKOWSKI_SETS, parts, _read_back([p.sum(0, keepdim=True) for p in parts])):
             sums[k].add(v, _cells(real_A if k.endswith('_A') else real_B), rows=p.size(0))
+        if components:
+            parts = (r['members_comp'].flatten(0, 1), r['ens_mean_comp'], ops.components(pred_A, CA, "nchw", t_A, conn=components),
+                     ops.components(real_B, CB, "nchw", t_B, conn=components), ops.components(real_A, CA, "nchw", t_A, conn=components))
+            for k, p, v in zip(MINKOWSKI_SETS, parts, _read_back([p.sum(0, keepdim=True) for p in parts])):
+                comp[k].add(v, rows=p.size(0))
     res, summary = {}, {}
     for k in MINKOWSKI_SETS:
         res['counts_' + k], res['cells_' + k] = np.asarray(sums[k].total, dtype=np.int64), np.int64(sums[k].cells)
@@ -365,6 +375,13 @@ def eval_minkowski(dataset, model, n_samples, thr_B, thr_A, use_gpu=True):
         res.update(('%s_%s' % (name, k), v) for name, v in summary[k].items())
     for k, real in MINKOWSKI_PAIRS:
         res.update(('dist_%s_%s' % (name, k), v) for name, v in ops.minkowski_distance(summary[k], summary[real]).items())
+    if components:
+        for k in MINKOWSKI_SETS:
+            res['comp_' + k] = np.asarray(comp[k].total, dtype=np.int64)
+            summary[k] = ops.components_summary(comp[k].total, sums[k].total, sums[k].rows, sums[k].cells, components)
+            res.update(('%s_%s' % (name, k), v) for name, v in summary[k].items())
+        for k, real in MINKOWSKI_PAIRS:
+            res.update(('%s_%s' % (name, k), v) for name, v in ops.components_distance(summary[k], summary[real]).items())
     return res
 
 
@@ -641,14 +658,24 @@ def _minkowski_prepare(opt, model, arrays):
     thr_B = marginal_edges(arrays[1], opt.mink_bins)              # once: dev and test share the climatology
     thr_A = marginal_edges(arrays[0], opt.mink_bins)
     header = dict(n_samples=np.int64(opt.n_samples), bins=np.int64(opt.mink_bins), thresholds_B=thr_B, thresholds_A=thr_A)
-    return header, lambda d: eval_minkowski(d, model, opt.n_samples, thr_B, thr_A)
+    conn = int(getattr(opt, 'mink_components', 0))
+    if conn:
+        header['connectivity'] = np.int64(conn)
+    return header, lambda d: eval_minkowski(d, model, opt.n_samples, thr_B, thr_A, components=conn)
 
 
 def _minkowski_report(opt, dev, test):
-    return "\n".join("%s_MINK_B: %s, %s_MINK_MEAN_B: %s, %s_MINK_A: %s (area, perimeter, euler4, euler8)"
-                     % tuple(v for k in ('members_B', 'ens_mean_B', 'fake_A')
-                             for v in (name, " ".join("%.6f" % _chan_mean(res['dist_%s_%s' % (f, k)]) for f in ops.MINK_FUNCTIONALS)))
-                     for name, res in (('DEV', dev), ('TEST', test)))
+    lines = ["%s_MINK_B: %s, %s_MINK_MEAN_B: %s, %s_MINK_A: %s (area, perimeter, euler4, euler8)"
+             % tuple(v for k in ('members_B', 'ens_mean_B', 'fake_A')
+                     for v in (name, " ".join("%.6f" % _chan_mean(res['dist_%s_%s' % (f, k)]) for f in ops.MINK_FUNCTIONALS)))
+             for name, res in (('DEV', dev), ('TEST', test))]
+    if int(getattr(opt, 'mink_components', 0)):
+        lines += ["%s_COMP_B: %s, %s_COMP_MEAN_B: %s, %s_COMP_A: %s (components, holes, size; %d-connected)"
+                  % (tuple(v for k in ('members_B', 'ens_mean_B', 'fake_A')
+                           for v in (name, " ".join("%.6f" % _chan_mean(res['dist_%s_%s' % (f, k)]) for f in ('components', 'holes', 'size'))))
+                     + (int(opt.mink_components),))
+                  for name, res in (('DEV', dev), ('TEST', test))]
+    return "\n".join(lines)
 
 
 _MINKOWSKI = Metric('minkowski', False, 200, None, _minkowski_prepare, _minkowski_report, """\
@@ -667,7 +694,15 @@ _MINKOWSKI = Metric('minkowski', False, 200, None, _minkowski_prepare, _minkowsk
               over the thresholds of the absolute difference of the densities, with n_samples, bins, thresholds_B,
               thresholds_A -> <res_dir>/minkowski.npz.  A blobby, a filamentary and a speckled field can share marginal,
               spectrum and FSS and differ here; the mean of an ensemble loses objects and boundary.  Printed per split: the
-              four distances of members_B, ens_mean_B and fake_A, the channel means.  1 <= H, W <= 1024.  No plot""")
+              four distances of members_B, ens_mean_B and fake_A, the channel means.  1 <= H, W <= 1024.  No plot.
+              --mink_components 4 | 8 (default 0: off, file and output as without it) labels the connected components of
+              the same sets under that connectivity (ops.components, HIP union-find, exact integers) - the Euler numbers only
+              give components MINUS holes - and adds, per set k: comp_k (C, T, 25) int64 = n, area, sum of squared areas,
+              n_border and the 21 bins of floor(log2(area)) summed over the fields, and (ops.components_summary) components_k,
+              holes_k = components - euler, both per cell (*_density_k), mean_area_k, weighted_area_k, border_fraction_k
+              (C, T) and size_pdf_k (C, T, 21); per translated set (ops.components_distance) dist_components_k, dist_holes_k
+              and dist_size_k (C,), the total-variation distance of the size distributions; connectivity in the header; one
+              more printed line per split: the three distances, the channel means""")
 
 
 METRICS = (_ensemble_record(), _SPECTRUM, _COHERENCE, _FSS, _translate_record(), _FIELD_SPECTRUM, _SSIM, _MARGINAL, _MINKOWSKI)

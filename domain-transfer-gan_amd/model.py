@@ -731,7 +731,7 @@ class _Base(object):
                 ops.fss(_ensemble_mean(members, M, C), g.b, C, "nchw", "nchw", thr, win, out=g.rows(out["ens_mean"]))
         return out
 
-    def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None):
+    def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None, components=0):
         """The shape of what A -> B puts above a threshold: the counts behind the Minkowski functionals (ops.minkowski: per
         channel and threshold nF, nE1, nE2, nV1, nV4 of the excursion set, from which ops.minkowski_summary takes area,
         perimeter and the two Euler numbers) of each of n_samples translations of every input and of their per-pixel mean
@@ -740,17 +740,29 @@ class _Base(object):
         host array is checked (ops.channel_table) and moved to the device once, a device tensor is taken as it is.  z,
         chunk and the refusals: plan_ensemble; the members: ensemble_groups.  1 <= H, W <= 1024.  Returns int64 device
         tensors: members (N, M, C, T, 5) and ens_mean (N, C, T, 5), to be summed over a set of fields and handed to
-        ops.minkowski_summary.  Nothing is read back to the host."""
+        ops.minkowski_summary.  components: 0, or the connectivity 4 or 8: the connected components of the same sets
+        (ops.components: n, area, sum of squared areas, n_border and the 21 size bins) of the same members and of their mean,
+        in the same group loop, as members_comp (N, M, C, T, 25) and ens_mean_comp (N, C, T, 25), for
+        ops.components_summary; with 0 neither the entries nor their launches exist.  Nothing is read back to the host."""
+        if components not in (0, 4, 8):
+            raise ValueError("translate_minkowski: components must be 0, 4 or 8 (got %r)" % (components,))
         M, N, C, H, W, z, per = plan_ensemble("translate_minkowski", self.opt, real_A, n_samples, z, None, chunk)
         thr = ops.channel_table("translate_minkowski", ValueError, "thresholds", thresholds, C, ops.MINK_MAX_T, real_A.device,
                                 ordered=True, cast=True)
         T = thr.size(1)
         i64 = dict(device=real_A.device, dtype=torch.int64)
         out = dict(members=torch.empty((N, M, C, T, 5), **i64), ens_mean=torch.empty((N, C, T, 5), **i64))
+        if components:
+            out.update(members_comp=torch.empty((N, M, C, T, ops.COMP_STATS), **i64),
+                       ens_mean_comp=torch.empty((N, C, T, ops.COMP_STATS), **i64))
         with eval_state(self.netG_A_B), torch.no_grad():
             for members, g in self._groups(real_A, z, M, per):
                 ops.minkowski(members, C, "nhwc", thr, out=g.flat(out["members"]))
-                ops.minkowski(_ensemble_mean(members, M, C), C, "nchw", thr, out=g.rows(out["ens_mean"]))
+                mean = _ensemble_mean(members, M, C)
+                ops.minkowski(mean, C, "nchw", thr, out=g.rows(out["ens_mean"]))
+                if components:
+                    ops.components(members, C, "nhwc", thr, conn=components, out=g.flat(out["members_comp"]))
+                    ops.components(mean, C, "nchw", thr, conn=components, out=g.rows(out["ens_mean_comp"]))
         return out
 
     def _field_groups(self, who, G, x, copies, C, overlap, chunk, code=None):

@@ -2224,6 +2224,99 @@ def minkowski_distance(a, b):
     return res
 
 
+# ----------------------------------------------------------------------------------------------
+# Connected components of excursion sets (model.translate_minkowski(components=), --metric minkowski --mink_components)
+# ----------------------------------------------------------------------------------------------
+COMP_STATS, COMP_BINS = 25, 21
+
+
+def components(x, C, layout, thresholds, conn=8, out=None, labels=None):
+    """acg_components: the connected components of the excursion sets {x >= thresholds[c][t]} of the C valid channels of x,
+    under conn = 4 or 8 connectivity -> (rows, C, T, COMP_STATS) int64 on the device: n (the components), area (the cells in
+    the set, minkowski's nF), sum_sq (the sum of the components' squared areas), n_border (the components with a cell in the
+    first or last row or column) and hist[b], b = 0 .. 20 (the components with 2^b <= area < 2^(b + 1)).  x == threshold is
+    inside, NaN outside, as in minkowski.  Exact integers, the same bits in every layout and on every call; linear over
+    fields: sum them over a set of fields, then ops.components_summary.  x, C, layout, thresholds: as ops.minkowski takes
+    them (1 <= H, W <= 1024; a host table is checked and copied to the device, a float32 device tensor is taken as it is).
+    `out`: the contiguous int64 tensor to write.  labels: True, or a contiguous int32 (rows, C, T, H, W) tensor to write: the
+    canonical label planes are returned too, (out, labels): 0 outside the set, inside 1 + the row-major index of the first
+    cell of the cell's component.  Launches only, in passes over the planes when the workspace (256 MiB at most) does not
+    hold them all; nothing is read back to the host.  Not differentiable."""
+    x = x.detach().contiguous()
+    rows, C, _, H, W, sx = _field_args(x, C, layout, "components")
+    if not (1 <= H <= MINK_MAX_HW and 1 <= W <= MINK_MAX_HW):
+        raise _lib.AcgError("components: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (MINK_MAX_HW, H, W))
+    if conn not in (4, 8):
+        raise _lib.AcgError("components: connectivity must be 4 or 8 (got %r)" % (conn,))
+    thr = channel_table("components", _lib.AcgError, "thresholds", thresholds, C, MINK_MAX_T, None, ordered=True)
+    T = int(thr.size(1))
+    _refuse_out("components", out, (rows, C, T, COMP_STATS), torch.int64)
+    want_labels = labels is not None and labels is not False
+    lab = labels if torch.is_tensor(labels) else None
+    if want_labels:
+        if rows * C * T * H * W > 2 ** 31 - 1:
+            raise _lib.AcgError("components: labels of %d planes of %d x %d pass 2^31 - 1 cells" % (rows * C * T, H, W))
+        _refuse_out("components", lab, (rows, C, T, H, W), torch.int32, name="labels")
+    if not torch.is_tensor(thresholds):                            # a host array goes to the device; a tensor is where it has to be
+        thr = thr.to(x.device)
+    _check(x, thr)
+    out = _out_or_new(out, (rows, C, T, COMP_STATS), torch.int64, x.device)
+    if want_labels:
+        lab = _out_or_new(lab, (rows, C, T, H, W), torch.int32, x.device)
+    ws, nbytes = _metric_workspace("acg_components_workspace_bytes", rows, C, H, W, T)
+    _lib.call("acg_components", _ptr(x), rows, C, H, W, sx[0], sx[1], sx[2], _ptr(thr), T, int(conn), _ptr(out),
+              _ptr(lab) if want_labels else None, ws, nbytes, _stream())
+    return (out, lab) if want_labels else out
+
+
+def components_summary(stats, counts, fields, cells, conn):
+    """(..., T, COMP_STATS) int64 stats of ops.components and (..., T, 5) counts of ops.minkowski, both summed over the same
+    `fields` fields of `cells` cells in all -> dict of float64 arrays (..., T) on the host:
+      components, holes          n, and n minus minkowski_summary's euler8 (conn = 8) or euler4 (conn = 4);
+      components_density, holes_density   the two per cell;
+      mean_area                  area / n, NaN where there is no component;
+      weighted_area              sum_sq / area, the area of the component an inside cell lies in on average; NaN for an empty set;
+      border_fraction            n_border / n, NaN where there is no component;
+    and size_pdf (..., T, COMP_BINS) = hist / n (NaN where there is no component)."""
+    import numpy as np
+    s, n5 = np.asarray(stats), np.asarray(counts)
+    if (s.ndim < 2 or s.shape[-1] != COMP_STATS or n5.shape != s.shape[:-1] + (5,) or int(cells) < 1 or int(fields) < 1
+            or conn not in (4, 8)):
+        raise ValueError("components_summary: need (..., T, %d) stats, (..., T, 5) counts of the same fields, positive field and "
+                         "cell counts and conn 4 or 8 (got %s, %s, %s, %s, %r)" % (COMP_STATS, s.shape, n5.shape, fields, cells, conn))
+    s = s.astype(np.int64)
+    euler = minkowski_summary(n5, cells)["euler%d" % conn]
+    n, area = s[..., 0].astype(np.float64), s[..., 1].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res = dict(components=n, holes=n - euler, mean_area=np.where(n > 0, area / n, np.nan),
+                   weighted_area=np.where(area > 0, s[..., 2] / area, np.nan), border_fraction=np.where(n > 0, s[..., 3] / n, np.nan),
+                   size_pdf=np.where(n[..., None] > 0, s[..., 4:] / n[..., None], np.nan))
+    res["components_density"], res["holes_density"] = res["components"] / float(int(cells)), res["holes"] / float(int(cells))
+    return res
+
+
+def components_distance(a, b):
+    """two components_summary dicts of the same thresholds -> dict of float64 arrays (...): dist_components and dist_holes,
+    the mean over the thresholds of |density_a - density_b|; dist_size, the mean, over the thresholds where both sides have
+    a component, of the total-variation distance 0.5 sum_b |pdf_a - pdf_b| of the size distributions (NaN if none has)"""
+    import numpy as np
+    res = {}
+    for k in ("components", "holes"):
+        da, db = np.asarray(a[k + "_density"], dtype=np.float64), np.asarray(b[k + "_density"], dtype=np.float64)
+        if da.shape != db.shape or da.ndim < 1:
+            raise ValueError("components_distance: %s densities %s against %s" % (k, da.shape, db.shape))
+        res["dist_" + k] = np.abs(da - db).mean(-1)
+    pa, pb = np.asarray(a["size_pdf"], dtype=np.float64), np.asarray(b["size_pdf"], dtype=np.float64)
+    if pa.shape != pb.shape or pa.ndim < 2 or pa.shape[-1] != COMP_BINS:
+        raise ValueError("components_distance: size_pdf %s against %s" % (pa.shape, pb.shape))
+    tv = 0.5 * np.abs(pa - pb).sum(-1)                             # NaN where either side has no component
+    ok = ~np.isnan(tv)
+    cnt = ok.sum(-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res["dist_size"] = np.where(cnt > 0, np.where(ok, tv, 0.0).sum(-1) / cnt, np.nan)
+    return res
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

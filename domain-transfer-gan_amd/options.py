@@ -191,7 +191,7 @@ class TestOptions(object):
     (structural similarity of the paired translations, reuses --n_samples); the metric `marginal` (Wasserstein distances,
     quantiles and distribution functions of the fields' values, reuses --n_samples) with --marg_levels and --marg_bins; the
     metric `minkowski` (area, perimeter and Euler characteristic of the excursion sets, unpaired, reuses --n_samples) with
-    --mink_bins."""
+    --mink_bins, and --mink_components (the connected components of the same sets: objects, holes, object sizes)."""
 
     def __init__(self):
         from .eval_metrics import METRICS      # here, not at the top: it imports train.py, which imports this module
@@ -226,6 +226,9 @@ class TestOptions(object):
         self.parser.add_argument('--mink_bins', type=_mink_bins, default=32,
                                  help='--metric minkowski: B in 2..256; the excursion sets are taken at the B - 1 quantiles '
                                       'k / B of the real training fields, per channel (trainB for A -> B, trainA for B -> A)')
+        self.parser.add_argument('--mink_components', type=int, choices=[0, 4, 8], default=0,
+                                 help='--metric minkowski: 4 or 8 also labels the connected components of the excursion sets '
+                                      'under that connectivity (counts, holes, sizes); 0: off')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')

@@ -560,6 +560,39 @@ size_t acg_minkowski_workspace_bytes(int rows, int C, int H, int W, int T);
 int acg_minkowski(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
                   const float *thr, int T, long long *out, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- Connected components of excursion sets (ops.components, model.translate_minkowski(components=), test.py --metric
+ *      minkowski --mink_components; no reference call site, tests/components_ref.py states the definition) ----
+ * x, its strides and thr (C, T): as in acg_minkowski.  A plane is one (row, channel c, threshold t); its set is
+ * [x >= thr[c][t]]: x == thr is inside, NaN outside, cells beyond the field outside (acg_minkowski's conventions; for
+ * non-decreasing thresholds the sets are the same).  conn = 4: cells sharing an edge are connected; conn = 8: cells sharing an
+ * edge or a corner.  Per plane, with the components of the set:
+ *   out (rows, C, T, 25) int64, fully written: [0] n, the number of components; [1] area, the cells in the set (acg_minkowski's
+ *   nF); [2] sum_sq, the sum over the components of area^2 (at most 2^40); [3] n_border, the components with a cell in the first
+ *   or last row or column; [4 + b], b = 0 .. 20, the components with 2^b <= area < 2^(b + 1).
+ *   labels (rows, C, T, H, W) int32, or NULL: 0 outside the set, inside 1 + the row-major index of the first cell of the cell's
+ *   component: canonical, so comparable for equality.
+ * All are linear over fields: sum them, then ops.components_summary (holes = n - euler of acg_minkowski's counts).  Exact
+ * integers, the same bits on every call, in every layout and whatever the workspace held.  Launches only: nothing is read back,
+ * no host synchronisation, capturable in a HIP graph.
+ * Limits: 1 <= H, W <= 1024, 1 <= T <= 255, conn in {4, 8}.  Refused before a launch (-1, acg_last_error starts with
+ * "acg_components"): a null x, thr or out, an extent, T or conn out of range, rows < 1, C < 1, rows C T above 2^31 - 1, labels
+ * given with rows C T H W above 2^31 - 1, a stride < 1, a misaligned workspace (16 bytes).  A workspace below ONE plane returns -2.
+ * The workspace holds whole planes of 8 H W bytes rounded up to 16 (int32 parents, uint32 areas); the call runs in passes of as
+ * many planes as ws_bytes holds.  acg_components_workspace_bytes: the bytes of all rows C T planes, capped at the whole planes
+ * that fit 256 MiB, never below one plane; 0 for a refused size.
+ * Kernels, per pass: comp_label, one workgroup per (row [, channel], 32 x 64 tile) - NHWC with four stored channels: a
+ * pixel's channels from one 16-byte load (comp_label<c4>), otherwise comp_label<strided> - keeps its cells in registers and, for
+ * every plane of its row that the pass holds, builds the tile's union-find forest in LDS, flattens it, reduces area and border
+ * flag per tile root in LDS and stores parents (global indices) and areas; comp_merge, a thread per cell of a tile's first row
+ * and column, joins trees across the seams (and tile corners) with agent-scope atomic loads, min and compare-and-swap only;
+ * comp_root points every tile root at its root and adds its area and flag there (integer atomics); comp_stats writes the labels
+ * and adds each root's bins, reduced per workgroup in LDS, to the plane's out (integer atomics; comp_label zeroed it).  A
+ * parent index is always below its child's, a union hooks the larger root under the smaller by compare-and-swap: every chase
+ * descends, a failed swap means another lane hooked that root, nothing waits.  Fields of one tile skip comp_merge and comp_root. */
+size_t acg_components_workspace_bytes(int rows, int C, int H, int W, int T);
+int acg_components(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
+                   const float *thr, int T, int conn, long long *out, int *labels, void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- the marginal loss (ops.field_sort, ops.marginal_loss, --lambda_marg_A / --lambda_marg_B; no reference call site: the
  *      reference has no distributional loss, tests/marginal_ref.py states the definition) ----
  * acg_field_sort: a stable sort of each of the rows x C fields of H x W fp32 pixels of x, with its permutation.  The strides
