@@ -183,6 +183,9 @@ SIGNATURES = {
     "acg_fss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "acg_fss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_longlong,
                         c_int, ctypes.c_longlong, _P, c_int, ctypes.POINTER(c_int), c_int, _P, _P, _P, c_size_t, _P]),
+    "acg_fss_scales_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "acg_fss_scales": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
+                               ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "acg_minkowski_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "acg_minkowski": (c_int, [_P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, _P, _P, c_size_t, _P]),
     "acg_components_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -20,6 +20,14 @@
 //           of e in plane k), so the row count of e is sum_k 2^k (row count of plane k) and the ensemble's walk is the box
 //           kernel with NS planes on its x side, one workgroup per (truth row, c, t) (fss_ens<lds> while NS + 1 planes fit:
 //           16 members at 256^2 take 63 KiB).  M = 1: e is the member's own plane, no slices.
+// The intensity-scale triples of the same events (ops.fss_scales, --fss_scales; tests/fss_scales_ref.py; Casati et al. 2004):
+//   scales  acg_fss_scales shares events and slices.  Level l = 0 .. L = ceil(log2(max(H, W))) cuts the plane into blocks of
+//           2^l x 2^l cells anchored at cell (0, 0), the last ones cut by the domain; bf, bo are the events of a block and the
+//           triple is (sum bf^2, sum bo^2, sum bf bo) over the blocks of a level.  One workgroup per (x row, c, t) (the ensemble:
+//           per (truth row, c, t), bf the slices' sum_k 2^k count), a wave per 64 x 64 tile at a time: lane r holds the words
+//           of tile row r, level 0 is popcounts, level 1 the 2-bit fields of x - ((x >> 1) & 0x55..), and each further level
+//           adds neighbouring blocks in the lane and then the lane 2^(l-1) away (6 levels: 63 exchanges per side), the first
+//           lane of every 2^l squaring.  The tile totals go to LDS; one thread per block forms levels 7 .. 10 from them.
 #include "common.h"
 #include "field.h"
 #include <stdint.h>
@@ -32,6 +40,9 @@
 #define FSS_MAX_NS 7                       // bit_width(FSS_MAX_M)
 #define FSS_SLICE_THREADS 256
 #define FSS_EVENT_THREADS 256
+#define FSS_SCALE_THREADS 256
+#define FSS_TILE_LEVELS 7                  // levels 0 .. 6 lie inside a 64 x 64 tile: one word per lane of a wave
+#define FSS_MAX_TILES 256                  // (FSS_MAX_HW / 64)^2
 
 typedef unsigned long long u64;
 
@@ -234,6 +245,85 @@ __global__ __launch_bounds__(FSS_SLICE_THREADS) void fss_slices_kernel(FssPlanes
     }
 }
 
+// The intensity-scale triples of one workgroup: blockIdx.x = (x row f, c, t) picks its planes as in fss_box_kernel (nx = 1: a
+// member's events; nx = NS <= NX: the bit planes of an exceedance count, x_per_y = 1), out + blockIdx.x nl 3 takes the triples
+// of levels 0 .. nl - 1.  Bits of a word past W and rows past H are masked here, whatever the workspace holds there.
+template <int NX>
+__global__ __launch_bounds__(FSS_SCALE_THREADS) void fss_scales_kernel(FssPlanes px, FssPlanes py, int nx, int CT, int x_per_y, int H,
+                                                                      int W, int nl, long long *__restrict__ out)
+{
+    __shared__ unsigned tile_x[FSS_MAX_TILES], tile_o[FSS_MAX_TILES];      // the events of every 64 x 64 tile
+    __shared__ u64 red[48];
+    const int lane = threadIdx.x & 63, WW = (W + 63) >> 6, TH = (H + 63) >> 6;
+    const long long p = blockIdx.x, f = p / CT, q = (f / x_per_y) * CT + (p - f * CT);
+    const long long nb = (long long)H * WW;
+    const u64 *xb = px.bits + p * nx * nb, *yb = py.bits + q * nb;
+    u64 acc[FSS_TILE_LEVELS][3];
+#pragma unroll
+    for (int l = 0; l < FSS_TILE_LEVELS; ++l) acc[l][0] = acc[l][1] = acc[l][2] = 0;
+    for (int tile = threadIdx.x >> 6; tile < TH * WW; tile += FSS_SCALE_THREADS / 64) {
+        const int ti = tile / WW, tj = tile - ti * WW, i = ti * 64 + lane, left = W - tj * 64;
+        const u64 keep = i >= H ? 0ull : left >= 64 ? ~0ull : (1ull << left) - 1ull;
+        const u64 O = keep ? yb[(long long)i * WW + tj] & keep : 0ull;
+        u64 F[NX];
+#pragma unroll
+        for (int k = 0; k < NX; ++k) F[k] = keep && k < nx ? xb[k * nb + (long long)i * WW + tj] & keep : 0ull;
+        // level 0: the cells themselves, e = sum_k 2^k F[k]: e^2 = sum_k 4^k F[k] + 2 sum_{k < k'} 2^(k + k') F[k] F[k']
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            acc[0][0] += (u64)__popcll(F[k]) << (2 * k);
+            acc[0][2] += (u64)__popcll(F[k] & O) << k;
+#pragma unroll
+            for (int k2 = k + 1; k2 < NX; ++k2) acc[0][0] += (u64)__popcll(F[k] & F[k2]) << (k + k2 + 1);
+        }
+        acc[0][1] += __popcll(O);
+        // level 1 inside the lane: the events of the 32 column pairs of its row
+        const u64 odd = 0x5555555555555555ull;
+        unsigned cx[32], co[32];
+        const u64 ho = O - ((O >> 1) & odd);
+#pragma unroll
+        for (int s = 0; s < 32; ++s) co[s] = (unsigned)(ho >> (2 * s)) & 3u, cx[s] = 0;
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            const u64 hx = F[k] - ((F[k] >> 1) & odd);
+#pragma unroll
+            for (int s = 0; s < 32; ++s) cx[s] += ((unsigned)(hx >> (2 * s)) & 3u) << k;
+        }
+        // level l: cx[s], co[s] become the events of block (lane >> l, s) of the tile in every lane of its 2^l rows
+#pragma unroll
+        for (int l = 1; l < FSS_TILE_LEVELS; ++l) {
+#pragma unroll
+            for (int s = 0; s < (64 >> l); ++s) {
+                if (l > 1) cx[s] = cx[2 * s] + cx[2 * s + 1], co[s] = co[2 * s] + co[2 * s + 1];
+                cx[s] += __shfl_xor(cx[s], 1 << (l - 1));
+                co[s] += __shfl_xor(co[s], 1 << (l - 1));
+                if ((lane & ((1 << l) - 1)) == 0) {
+                    acc[l][0] += (u64)cx[s] * cx[s];
+                    acc[l][1] += (u64)co[s] * co[s];
+                    acc[l][2] += (u64)cx[s] * co[s];
+                }
+            }
+        }
+        if (lane == 0) tile_x[tile] = cx[0], tile_o[tile] = co[0];
+    }
+#pragma unroll
+    for (int l = 0; l < FSS_TILE_LEVELS; ++l)
+        if (l < nl) fss_block_store(acc[l][0], acc[l][1], acc[l][2], red, out + (p * nl + l) * 3);
+    __syncthreads();                                               // the tile totals of all waves
+    for (int l = FSS_TILE_LEVELS; l < nl; ++l) {                   // blocks of tb x tb tiles: at most 8 x 8 of them
+        const int tb = 1 << (l - FSS_TILE_LEVELS + 1), bw = (WW + tb - 1) / tb, bh = (TH + tb - 1) / tb;
+        u64 ff = 0, oo = 0, fo = 0;
+        if ((int)threadIdx.x < bh * bw) {
+            const int bi = threadIdx.x / bw, bj = threadIdx.x - bi * bw;
+            unsigned sx = 0, so = 0;                               // at most 64 * 2^20 events
+            for (int ti = bi * tb; ti < min((bi + 1) * tb, TH); ++ti)
+                for (int tj = bj * tb; tj < min((bj + 1) * tb, WW); ++tj) sx += tile_x[ti * WW + tj], so += tile_o[ti * WW + tj];
+            ff = (u64)sx * sx, oo = (u64)so * so, fo = (u64)sx * so;
+        }
+        fss_block_store(ff, oo, fo, red, out + (p * nl + l) * 3);
+    }
+}
+
 static int fss_slices(int M)             // bit_width(M): the planes of a count in 0 .. M; none of their own for M = 1
 {
     int ns = 0;
@@ -250,13 +340,32 @@ static bool fss_shape_ok(int rows, int x_per_y, int C, int H, int W, int T, int 
 
 // x's planes (words, prefixes), then y's, then with want_ens and x_per_y > 1 the bit_width(x_per_y) slices of every truth plane:
 // about 10 bits per cell and plane, whatever the windows
-extern "C" size_t acg_fss_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int nw, int want_ens)
+static size_t fss_planes_bytes(int rows, int x_per_y, int C, int H, int W, int T, int want_ens)
 {
-    if (!fss_shape_ok(rows, x_per_y, C, H, W, T, nw)) return 0;
     const size_t px = (size_t)rows * C * T, py = (size_t)(rows / x_per_y) * C * T;
     const size_t ps = want_ens && x_per_y > 1 ? py * fss_slices(x_per_y) : 0;
     return fss_bits_bytes(px, H, W) + fss_pref_bytes(px, H, W) + fss_bits_bytes(py, H, W) + fss_pref_bytes(py, H, W) +
            fss_bits_bytes(ps, H, W) + fss_pref_bytes(ps, H, W);
+}
+extern "C" size_t acg_fss_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int nw, int want_ens)
+{
+    return fss_shape_ok(rows, x_per_y, C, H, W, T, nw) ? fss_planes_bytes(rows, x_per_y, C, H, W, T, want_ens) : 0;
+}
+
+struct FssSpace {                        // the workspace of a call: the planes of x, of y and the slices of every truth plane
+    FssPlanes px, py, ps;
+};
+static FssSpace fss_carve(void *ws, size_t npx, size_t npy, int NS, int H, int W)
+{
+    unsigned char *w8 = (unsigned char *)ws;
+    FssSpace s;
+    s.px.bits = (u64 *)w8, w8 += fss_bits_bytes(npx, H, W);
+    s.px.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npx, H, W);
+    s.py.bits = (u64 *)w8, w8 += fss_bits_bytes(npy, H, W);
+    s.py.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npy, H, W);
+    s.ps.bits = (u64 *)w8, w8 += fss_bits_bytes(npy * NS, H, W);
+    s.ps.pref = (unsigned short *)w8;
+    return s;
 }
 
 static void fss_events(hipStream_t st, const Field &x, int rows, int C, int H, int W, const float *thr, int T, FssPlanes pl)
@@ -304,15 +413,9 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
     hipStream_t st = (hipStream_t)stream;
     const int rows_y = rows / x_per_y, CT = C * T;
     const size_t npx = (size_t)rows * CT, npy = (size_t)rows_y * CT;
-    unsigned char *w8 = (unsigned char *)ws;
-    FssPlanes px, py, ps;
-    px.bits = (u64 *)w8, w8 += fss_bits_bytes(npx, H, W);
-    px.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npx, H, W);
-    py.bits = (u64 *)w8, w8 += fss_bits_bytes(npy, H, W);
-    py.pref = (unsigned short *)w8, w8 += fss_pref_bytes(npy, H, W);
     const int NS = fss_slices(x_per_y);
-    ps.bits = (u64 *)w8, w8 += fss_bits_bytes(npy * NS, H, W);
-    ps.pref = (unsigned short *)w8;
+    const FssSpace space = fss_carve(ws, npx, npy, NS, H, W);
+    const FssPlanes &px = space.px, &py = space.py, &ps = space.ps;
     fss_events(st, f[0], rows, C, H, W, thr, T, px);
     fss_events(st, f[1], rows_y, C, H, W, thr, T, py);
     const unsigned threads = (unsigned)acg_round_up(W, 64);
@@ -337,5 +440,60 @@ extern "C" int acg_fss(const float *x, const float *y, int rows, int x_per_y, in
     }
     acg_note_kernel("fss_events<%s>%s", f[0].mode == FIELD_C4 ? "c4" : "strided", path);
     ACG_CHECK_LAUNCH("acg_fss");
+    return ACG_OK;
+}
+
+static int fss_scale_levels(int H, int W)  // L + 1, L = ceil(log2(max(H, W)))
+{
+    int nl = 1;
+    while ((1 << (nl - 1)) < (H > W ? H : W)) ++nl;
+    return nl;
+}
+
+// acg_fss's workspace without the windows: the planes of x and y and, with want_ens and x_per_y > 1, the slices
+extern "C" size_t acg_fss_scales_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int want_ens)
+{
+    return fss_shape_ok(rows, x_per_y, C, H, W, T, 1) ? fss_planes_bytes(rows, x_per_y, C, H, W, T, want_ens) : 0;
+}
+
+extern "C" int acg_fss_scales(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
+                              int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                              long long y_chan_stride, const float *thr, int T, long long *out, long long *ens_out, void *ws,
+                              size_t ws_bytes, void *stream)
+{
+    const char *fn = "acg_fss_scales";
+    ACG_REQUIRE(x != nullptr && y != nullptr && thr != nullptr, "acg_fss_scales: null tensor");
+    Field f[2] = {{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}};
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, FSS_MAX_M));
+    ACG_REQUIRE(out != nullptr || ens_out != nullptr, "acg_fss_scales: out and ens_out are both NULL");
+    ACG_REQUIRE(H >= 1 && W >= 1 && H <= FSS_MAX_HW && W <= FSS_MAX_HW,
+                "acg_fss_scales: fields must be H x W with 1 <= H, W <= %d (got %d x %d)", FSS_MAX_HW, H, W);
+    ACG_REQUIRE(T >= 1 && T <= FSS_MAX_T, "acg_fss_scales: need 1 <= T <= %d thresholds (T=%d)", FSS_MAX_T, T);
+    ACG_REQUIRE((long long)rows * C * T <= 0x7fffffffLL && (long long)rows * H <= 0x7fffffffLL,
+                "acg_fss_scales: too many planes (rows=%d, C=%d, T=%d, H=%d)", rows, C, T, H);
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_fss_scales_workspace_bytes(rows, x_per_y, C, H, W, T, ens_out != nullptr)));
+    for (Field &o : f) o.mode = field_load_mode(o, C);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_y = rows / x_per_y, CT = C * T, NS = fss_slices(x_per_y), nl = fss_scale_levels(H, W);
+    const size_t npx = (size_t)rows * CT, npy = (size_t)rows_y * CT;
+    const FssSpace space = fss_carve(ws, npx, npy, NS, H, W);
+    fss_events(st, f[0], rows, C, H, W, thr, T, space.px);
+    fss_events(st, f[1], rows_y, C, H, W, thr, T, space.py);
+    if (out != nullptr)
+        hipLaunchKernelGGL(fss_scales_kernel<1>, dim3((unsigned)npx), dim3(FSS_SCALE_THREADS), 0, st, space.px, space.py, 1, CT, x_per_y,
+                           H, W, nl, out);
+    if (ens_out != nullptr && x_per_y == 1) {                      // the member's own plane is the count plane
+        hipLaunchKernelGGL(fss_scales_kernel<1>, dim3((unsigned)npy), dim3(FSS_SCALE_THREADS), 0, st, space.px, space.py, 1, CT, 1, H,
+                           W, nl, ens_out);
+    } else if (ens_out != nullptr) {
+        hipLaunchKernelGGL(fss_slices_kernel, dim3((unsigned)acg_cdiv((long)npy * H, FSS_SLICE_THREADS)), dim3(FSS_SLICE_THREADS), 0, st,
+                           space.px, space.ps, (long long)npy, CT, x_per_y, NS, H, W);
+        hipLaunchKernelGGL(fss_scales_kernel<FSS_MAX_NS>, dim3((unsigned)npy), dim3(FSS_SCALE_THREADS), 0, st, space.ps, space.py, NS, CT,
+                           1, H, W, nl, ens_out);
+    }
+    acg_note_kernel("fss_events<%s>%s%s", f[0].mode == FIELD_C4 ? "c4" : "strided", out != nullptr ? " + fss_scales" : "",
+                    ens_out == nullptr ? "" : x_per_y == 1 ? " + fss_scales_ens" : " + fss_slices + fss_scales_ens");
+    ACG_CHECK_LAUNCH("acg_fss_scales");
     return ACG_OK;
 }

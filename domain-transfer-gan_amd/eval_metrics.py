@@ -308,27 +308,44 @@ def fss_thresholds(train, quantiles, explicit=None):
     return np.quantile(x, np.asarray(quantiles, dtype=np.float64), axis=1).T.astype(np.float32)
 
 
-def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use_gpu=True):
+def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use_gpu=True, scales=False):
     """fractions-skill-score triples on an aligned split, one read of the sums per batch.  A -> B: n_samples members per
     input, the ensemble as a probability and the ensemble mean (model.translate_fss) against the paired real B; B -> A:
     predict_A against the paired real A.  The int64 triples of every comparison are summed over the split (over the members
     too) before anything is divided.  -> dict, per comparison k of FSS_PAIRS: sums_k (C, T, nw, 3) int64 and fss_k (C, T, nw),
-    bias_k, csi_k, base_rate_k (C, T), useful_scale_k (C, T) int64 of ops.fss_summary (ens_prob_B with members=n_samples)"""
+    bias_k, csi_k, base_rate_k (C, T), useful_scale_k (C, T) int64 of ops.fss_summary (ens_prob_B with members=n_samples).
+    scales: the intensity-scale triples of the same events too (ops.fss_scales; nl dyadic levels), summed like the others: per
+    k scale_sums_k (C, T, nl, 3) int64 and mse_scale_k, iss_k, en_rel_k (C, T, nl), mse_random_k (C, T), skill_scale_k (C, T)
+    int64 of ops.fss_scale_summary (ens_prob_B with members=n_samples and the members' events); False: none of them, and no
+    launch more than before"""
     sums = {k: _Sum() for k in FSS_PAIRS}
+    scale = {k: _Sum() for k in FSS_PAIRS}
     thresholds = _domain_tables(thresholds_B, thresholds_A)
     for real_A, real_B in _batches(dataset, use_gpu):
         thr_B, thr_A = thresholds(real_B, real_A)
-        r = model.translate_fss(real_A, n_samples, real_B, thr_B, windows)
+        r = model.translate_fss(real_A, n_samples, real_B, thr_B, windows, scales=scales)
         with torch.no_grad():
-            fake_A = ops.fss(model.predict_A(real_B), real_A, real_A.size(1), "nchw", "nchw", thr_A, windows)
+            pred_A = model.predict_A(real_B)
+            fake_A = ops.fss(pred_A, real_A, real_A.size(1), "nchw", "nchw", thr_A, windows)
         parts = (r['members'].flatten(0, 1), r['ens_prob'], r['ens_mean'], fake_A)
         for k, v in zip(FSS_PAIRS, _read_back(parts)):
             sums[k].add(v, _cells(real_B))
+        if scales:
+            parts = (r['members_scale'].flatten(0, 1), r['ens_prob_scale'], r['ens_mean_scale'],
+                     ops.fss_scales(pred_A, real_A, real_A.size(1), "nchw", "nchw", thr_A))
+            for k, v in zip(FSS_PAIRS, _read_back(parts)):
+                scale[k].add(v)
     res = {}
     for k in FSS_PAIRS:
         res['sums_' + k] = np.asarray(sums[k].total, dtype=np.int64)
         summary = ops.fss_summary(sums[k].total, windows, sums[k].cells, members=n_samples if k == 'ens_prob_B' else 1)
         res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
+    if scales:
+        for k in FSS_PAIRS:
+            res['scale_sums_' + k] = np.asarray(scale[k].total, dtype=np.int64)
+            ens = dict(members=n_samples, forecast_events=scale['members_B'].total[..., 0, 0]) if k == 'ens_prob_B' else {}
+            summary = ops.fss_scale_summary(scale[k].total, sums[k].cells, **ens)
+            res.update(('%s_%s' % ('mse_scale' if name == 'mse' else name, k), v) for name, v in summary.items())
     return res
 
 
@@ -513,17 +530,26 @@ def _fss_prepare(opt, model, arrays):
     thr_A = fss_thresholds(arrays[0], opt.fss_quantiles, opt.fss_thresholds)
     win = tuple(opt.fss_windows)
     header = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
-    return header, lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win)
+    scales = bool(getattr(opt, 'fss_scales', 0))
+    if scales:                                                     # 2^j, j = 0 .. L, of the fields the splits hold
+        header['scales'] = 2 ** np.arange(ops.fss_scale_levels(*np.shape(arrays[3])[-2:]), dtype=np.int64)
+    return header, lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win, scales=scales)
 
 
 def _fss_report(opt, dev, test):
     levels = opt.fss_thresholds if opt.fss_thresholds is not None else opt.fss_quantiles
     t, w = int(np.argmax(levels)), len(opt.fss_windows) // 2     # the highest threshold, the median listed window
-    return ("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "
+    line = ("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "
             "TEST_USEFUL_SCALE_B: %.4f"
             % (_chan_mean(dev['fss_members_B'][:, t, w]), _chan_mean(test['fss_members_B'][:, t, w]),
                _chan_mean(test['fss_ens_prob_B'][:, t, w]), _chan_mean(test['fss_ens_mean_B'][:, t, w]),
                _chan_mean(test['fss_fake_A'][:, t, w]), float(test['useful_scale_members_B'][:, t].mean())))
+    if int(getattr(opt, 'fss_scales', 0)):
+        line += ("\nDEV_ISS_B: %.4f, TEST_ISS_B: %.4f, TEST_SKILL_SCALE_B: %.4f, TEST_SKILL_SCALE_PROB_B: %.4f, "
+                 "TEST_SKILL_SCALE_MEAN_B: %.4f, TEST_SKILL_SCALE_A: %.4f"
+                 % ((_chan_mean(dev['iss_members_B'][:, t, 0]), _chan_mean(test['iss_members_B'][:, t, 0]))
+                    + tuple(float(test['skill_scale_' + k][:, t].mean()) for k in FSS_PAIRS)))
+    return line
 
 
 _FSS = Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
@@ -539,7 +565,22 @@ _FSS = Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
               over the split in int64, then (ops.fss_summary, float64 on the host) FSS = 2 sum cf co / (sum cf^2 + sum co^2),
               and from the window 1 the frequency bias, the CSI, the observed base rate f0 and the useful scale: the smallest
               listed window with FSS >= 0.5 + f0 / 2 (0: none).  Printed: FSS at the median listed window and the highest
-              threshold, the mean over the channels -> <res_dir>/fss.npz.  Any H x W up to 1024.  No plot""")
+              threshold, the mean over the channels -> <res_dir>/fss.npz.  Any H x W up to 1024.  No plot.
+              --fss_scales 1 (default 0: off, file and output as without it) says at which scale the error of the same
+              events sits: the intensity-scale skill score (Casati et al. 2004, Casati 2010).  The binary error field
+              [x >= t] - [y >= t] (the ensemble: the exceedance probability minus [y >= t]) is split into 2-D Haar
+              components on the dyadic blocks of 2^l x 2^l cells anchored at cell (0, 0), l = 0 .. L = ceil(log2(max(H, W))),
+              edge blocks cut by the domain (the planes zero-padded to 2^L x 2^L; one tiling, not Casati's average over
+              tilings; no bias recalibration, no dithering).  ops.fss_scales (HIP, exact) gives per level the integer triples
+              (sum bf^2, sum bo^2, sum bf bo) of the blocks' event counts; summed over the split they are scale_sums_k
+              (C, T, nl, 3) int64 per comparison k, and (ops.fss_scale_summary, float64) mse_scale_k (C, T, nl): the MSE of
+              the component at scale 2^j, j < L, and of the mean term at j = L, which add up to the plain MSE; mse_random_k
+              (C, T): the MSE of the same events placed at random; iss_k = 1 - mse_scale (L + 1) / mse_random (NaN where
+              mse_random is 0; L + 1 equal shares are a convention on a padded canvas); en_rel_k: the relative difference of
+              the forecast's and the truth's component energies; skill_scale_k (C, T) int64: the smallest 2^j with iss > 0
+              at every mother scale from j up (2^L: none); the header gains scales = 2^j.  One more line is printed: ISS of
+              members_B at the highest threshold and the finest scale on dev and test, and the test skill scales of
+              members_B, ens_prob_B, ens_mean_B and fake_A, channel means""")
 
 
 def _translate_record():

@@ -707,7 +707,7 @@ class _Base(object):
                 ops.sorted_scores(sb, None, lv, e, out={k: g.rows(v) for k, v in out["target"].items()})
         return out
 
-    def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None):
+    def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None, scales=False):
         """Whether A -> B puts its threshold exceedances close enough: the fractions-skill-score triples (ops.fss: per
         channel, threshold and window the sums of cf^2, co^2 and cf co of the window counts of the events, x the translation,
         y the paired real_B) of each of n_samples translations of every input, of the ensemble as a probability (the summed
@@ -715,8 +715,11 @@ class _Base(object):
         (_ensemble_mean).  thresholds: (C, T), moved to the device once; windows: odd widths, as ops.fss takes them.  z,
         chunk and the refusals: plan_ensemble, real_B required; the members: ensemble_groups.  Any H x W the generator
         accepts.  Returns int64 device tensors: members (N, M, C, T, nw, 3), ens_prob (N, C, T, nw, 3) and ens_mean
-        (N, C, T, nw, 3), to be summed over a set of pairs and handed to ops.fss_summary (ens_prob with members=M).  Nothing is
-        read back to the host."""
+        (N, C, T, nw, 3), to be summed over a set of pairs and handed to ops.fss_summary (ens_prob with members=M).
+        scales=True: the intensity-scale triples of the same events too (ops.fss_scales, nl = ops.fss_scale_levels(H, W)
+        dyadic levels in place of the windows), of the same members in the same group loop, as members_scale
+        (N, M, C, T, nl, 3), ens_prob_scale and ens_mean_scale (N, C, T, nl, 3), for ops.fss_scale_summary; with False
+        neither the entries nor their launches exist.  Nothing is read back to the host."""
         M, N, C, H, W, z, per = plan_ensemble("translate_fss", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         win = ops.check_windows(windows)
         thr = ops.channel_table("translate_fss", ValueError, "thresholds", thresholds, C, ops.FSS_MAX_T, real_A.device, cast=True)
@@ -724,11 +727,20 @@ class _Base(object):
         i64 = dict(device=real_A.device, dtype=torch.int64)
         out = dict(members=torch.empty((N, M, C, T, nw, 3), **i64), ens_prob=torch.empty((N, C, T, nw, 3), **i64),
                    ens_mean=torch.empty((N, C, T, nw, 3), **i64))
+        if scales:
+            nl = ops.fss_scale_levels(H, W)
+            out.update(members_scale=torch.empty((N, M, C, T, nl, 3), **i64), ens_prob_scale=torch.empty((N, C, T, nl, 3), **i64),
+                       ens_mean_scale=torch.empty((N, C, T, nl, 3), **i64))
         with eval_state(self.netG_A_B), torch.no_grad():
             for members, g in self._groups(real_A, z, M, per, real_B):
                 ops.fss(members, g.b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
                         out=(g.flat(out["members"]), g.rows(out["ens_prob"])))
-                ops.fss(_ensemble_mean(members, M, C), g.b, C, "nchw", "nchw", thr, win, out=g.rows(out["ens_mean"]))
+                mean = _ensemble_mean(members, M, C)
+                ops.fss(mean, g.b, C, "nchw", "nchw", thr, win, out=g.rows(out["ens_mean"]))
+                if scales:
+                    ops.fss_scales(members, g.b, C, "nhwc", "nchw", thr, x_per_y=M, ensemble=True,
+                                   out=(g.flat(out["members_scale"]), g.rows(out["ens_prob_scale"])))
+                    ops.fss_scales(mean, g.b, C, "nchw", "nchw", thr, out=g.rows(out["ens_mean_scale"]))
         return out
 
     def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None, components=0):

@@ -2152,6 +2152,93 @@ def fss_summary(sums, windows, cells, members=1):
     return res
 
 
+def fss_scale_levels(H, W):
+    """nl = L + 1 levels of fss_scales on H x W cells, L = ceil(log2(max(H, W))): 1 x 1 has one, 1024 eleven"""
+    H, W = _fss_size(int(H), int(W))
+    return (max(H, W) - 1).bit_length() + 1
+
+
+def fss_scales(x, y, C, layout_x, layout_y, thresholds, x_per_y=1, ensemble=False, out=None):
+    """acg_fss_scales: the intensity-scale triples (Casati et al. 2004) of the events of ops.fss -> (rows, C, T, nl, 3) int64
+    on the device, nl = fss_scale_levels(H, W): per threshold and level l = 0 .. nl - 1 the sums of bf^2, bo^2 and bf bo over
+    the blocks of 2^l x 2^l cells anchored at cell (0, 0) (edge blocks cut by the domain), bf / bo the events [x >= t] /
+    [y >= t] in a block.  Level 0 is ops.fss's window-1 triple, bit for bit.  Operands, thresholds, x_per_y, ensemble (ens:
+    bf is the block's events of all members of a truth) and `out` as in ops.fss.  Exact integers, the same bits in every
+    layout.  Sum the triples over a set of pairs, then ops.fss_scale_summary.  Nothing is read back to the host.  Not
+    differentiable."""
+    x, y, rows, rows_y, C, _, (H, W), sx, sy, x_per_y = _paired_fields("fss_scales", x, y, C, layout_x, layout_y, _fss_size, x_per_y,
+                                                                       max_per=FSS_MAX_M, size_y=True)
+    thr = channel_table("fss_scales", _lib.AcgError, "thresholds", thresholds, C, FSS_MAX_T, None)
+    T, nl = int(thr.size(1)), fss_scale_levels(H, W)
+    o, e = (out if ensemble else (out, None)) if out is not None else (None, None)
+    shapes = ((rows, C, T, nl, 3), (rows_y, C, T, nl, 3))
+    _refuse_out("fss_scales", o, shapes[0], torch.int64)
+    _refuse_out("fss_scales", e, shapes[1], torch.int64, "ens")
+    if not torch.is_tensor(thresholds):
+        thr = thr.to(x.device)
+    _check(x, y, thr)
+    o = _out_or_new(o, shapes[0], torch.int64, x.device)
+    if ensemble:
+        e = _out_or_new(e, shapes[1], torch.int64, x.device)
+    ws, nbytes = _metric_workspace("acg_fss_scales_workspace_bytes", rows, x_per_y, C, H, W, T, int(ensemble))
+    _lib.call("acg_fss_scales", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
+              _ptr(o), _ptr(e), ws, nbytes, _stream())
+    return (o, e) if ensemble else o
+
+
+def fss_scale_summary(sums, cells, members=1, forecast_events=None):
+    """(..., T, nl, 3) int64 triples of ops.fss_scales, (sum bf^2, sum bo^2, sum bf bo) per level, summed over a set of pairs
+    of `cells` cells in all (H W per pair) -> dict of arrays on the host, float64 unless said.  L = nl - 1; D_l = ff_l / M^2 +
+    oo_l - 2 fo_l / M is the sum over the blocks of level l of the squared block sums of the error field b_x / M - b_y.
+      mse (..., T, nl)      j < L: the energy of the Haar component "mean over 2^j blocks minus mean over 2^(j+1) blocks" of
+                            the error field on the canvas zero-padded to 2^L x 2^L, (4 D_j - D_{j+1}) / 4^(j+1) / cells (for
+                            M = 1 the numerator is formed in int64: exact, never negative); j = L: the mean term
+                            D_L / 4^L / cells.  They sum to the plain MSE of the event (or probability) field.
+      mse_random (..., T)   the MSE of a forecast with the same events placed at random: ff_0 / (M^2 cells) - 2 e_f e_o + e_o,
+                            e_f = n_f / (M cells), e_o = n_o / cells (M = 1: Casati 2010's B e (1 - e) + e (1 - B e)).
+      iss (..., T, nl)      1 - mse_j (L + 1) / mse_random: the random error split into L + 1 equal shares; NaN where
+                            mse_random is 0.
+      en_rel (..., T, nl)   (en_f - en_o) / (en_f + en_o), the component formula applied to ff / M^2 and to oo alone; NaN
+                            where the denominator is 0.
+      skill_scale (..., T)  int64: the smallest 2^j with iss > 0 at every mother scale j' >= j (j' < L); 2^L if there is none.
+    members = M > 1: the triples are an ensemble's (sum E^2, sum bo^2, sum E bo).  Their level 0 no longer holds the forecast
+    events n_f = sum E, so forecast_events (..., T) has to give them, summed over the same pairs (the level-0 sum bf^2 of the
+    members' own triples); with M = 1 it defaults to ff_0.  ValueError: a last axis that is not 3, cells < 1, members < 1, or
+    members > 1 without forecast_events."""
+    import numpy as np
+    t = np.asarray(sums)
+    if t.ndim < 3 or t.shape[-1] != 3:
+        raise ValueError("fss_scale_summary: need (..., T, nl, 3) triples (got %s)" % (t.shape,))
+    if int(cells) < 1:
+        raise ValueError("fss_scale_summary: cells must be at least 1 (got %s)" % (cells,))
+    M = int(members)
+    if M < 1:
+        raise ValueError("fss_scale_summary: members must be at least 1 (got %s)" % (members,))
+    if M > 1 and forecast_events is None:
+        raise ValueError("fss_scale_summary: members > 1 needs forecast_events, the members' events summed over the same pairs")
+    L, cells = t.shape[-2] - 1, float(int(cells))
+    quarter = 0.25 ** np.arange(1, L + 2)                          # 4^-(j+1); the mean term takes 4^-L
+
+    def components(s):                                             # s_l (..., nl), summed squared block sums -> energies
+        num = np.concatenate([4 * s[..., :-1] - s[..., 1:], 4 * s[..., -1:]], -1)
+        return num.astype(np.float64) * quarter / cells
+
+    exact = M == 1 and t.dtype.kind in "iu"
+    t = t.astype(np.int64 if exact else np.float64)
+    ff, oo, fo = t[..., 0], t[..., 1], t[..., 2]
+    res = dict(mse=components(ff + oo - 2 * fo if exact else ff / (M * M) + oo - 2.0 * fo / M))
+    n_f = ff[..., 0] if forecast_events is None else np.asarray(forecast_events)
+    e_f, e_o = n_f.astype(np.float64) / (M * cells), oo[..., 0].astype(np.float64) / cells
+    res["mse_random"] = ff[..., 0].astype(np.float64) / (M * M * cells) - 2.0 * e_f * e_o + e_o
+    en_f, en_o = components(ff.astype(np.float64) / (M * M)), components(oo)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        res["iss"] = np.where(res["mse_random"][..., None] != 0, 1.0 - res["mse"] * (L + 1) / res["mse_random"][..., None], np.nan)
+        res["en_rel"] = np.where(en_f + en_o != 0, (en_f - en_o) / (en_f + en_o), np.nan)
+    ok = np.logical_and.accumulate((res["iss"][..., :L] > 0)[..., ::-1], -1)      # NaN compares false; from the largest scale down
+    res["skill_scale"] = np.left_shift(np.int64(1), L - ok.sum(-1).astype(np.int64))
+    return res
+
+
 # ----------------------------------------------------------------------------------------------
 # Minkowski functionals of excursion sets (model.translate_minkowski, eval_metrics.py, --metric minkowski)
 # ----------------------------------------------------------------------------------------------

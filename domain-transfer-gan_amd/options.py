@@ -185,7 +185,8 @@ class TestOptions(object):
     compute_bpp_MVGauss_B, test.py:143-153, reachable only by editing its source), --ubo_steps (test.py:246 hard-codes
     500) and --gpu_ids (test.py:214 hard-codes [0]); the metric `ensemble` with --n_samples and --quantiles; the metric
     `spectrum` and the metric `coherence` (both reuse --n_samples); the metric `fss` (reuses --n_samples) with
-    --fss_quantiles, --fss_thresholds and --fss_windows; --ema 1 evaluates the checkpoint's averaged weights (every metric);
+    --fss_quantiles, --fss_thresholds, --fss_windows and --fss_scales (the intensity-scale skill of the same events: the
+    error split by dyadic scale); --ema 1 evaluates the checkpoint's averaged weights (every metric);
     the metric `translate` (whole fields at their stored resolution, reuses --n_samples) with --overlap; the metric
     `field_spectrum` (radial and cross spectra of those whole fields, reuses --n_samples and --overlap); the metric `ssim`
     (structural similarity of the paired translations, reuses --n_samples); the metric `marginal` (Wasserstein distances,
@@ -217,6 +218,9 @@ class TestOptions(object):
         self.parser.add_argument('--fss_windows', type=_fss_windows, default=(1, 3, 5, 9, 17, 33),
                                  help='--metric fss: comma-separated odd neighbourhood widths in cells, at most 8; sorted, and 1 '
                                       '(the cell itself: bias, CSI, base rate) is put in front if absent')
+        self.parser.add_argument('--fss_scales', type=int, choices=[0, 1], default=0,
+                                 help='--metric fss: 1 also splits the error of the events by dyadic scale (intensity-scale skill '
+                                      'score: MSE, skill and energy bias per threshold and scale 2^j); 0: off')
         self.parser.add_argument('--marg_levels', type=_marg_levels, default=(0.0, 0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999, 1.0),
                                  help='--metric marginal: comma-separated quantile levels inside [0, 1], at most 16')
         self.parser.add_argument('--marg_bins', type=_marg_bins, default=100,

@@ -528,6 +528,31 @@ int acg_fss(const float *x, const float *y, int rows, int x_per_y, int C, int H,
             long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr, int T,
             const int *windows, int nw, long long *out, long long *ens_out, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- intensity-scale triples of the same events (ops.fss_scales, model.translate_fss(scales=True), test.py --metric fss
+ *      --fss_scales 1; tests/fss_scales_ref.py states the definition; Casati et al. 2004, Casati 2010) ----
+ * x, y, the strides, x_per_y, thr and the events are acg_fss's.  With L = ceil(log2(max(H, W))) and nl = L + 1, level
+ * l = 0 .. L cuts the plane into blocks of 2^l x 2^l cells anchored at cell (0, 0); the blocks at the right and bottom edge
+ * are cut by the domain (the same as zero-padding the event planes to 2^L x 2^L).  With bf, bo the events of x and of its
+ * truth in a block
+ *   out     (rows, C, T, nl, 3) int64: sum bf^2, sum bo^2, sum bf bo over the blocks of level l;
+ *   ens_out (rows / x_per_y, C, T, nl, 3) int64: sum E^2, sum bo^2, sum E bo, E the events of a truth's x_per_y members in
+ *           the block.  With x_per_y = 1 it equals out.
+ * Either may be NULL, not both; both are fully written.  Level 0 is (n_f, n_o, hits), bit for bit acg_fss's window-1 triple;
+ * level L is (n_f^2, n_o^2, n_f n_o).  The largest value is (64 * 2^20)^2 = 2^52: nothing is refused for its size.  The Haar
+ * component energies, the skill against a random forecast and the energy bias follow on the host from the summed triples
+ * (ops.fss_scale_summary).  Integer after the comparison, no atomics, the same bits in every layout and launch order; nothing
+ * is read back; capturable in a HIP graph.  Limits: 1 <= H, W <= 1024, 1 <= T <= 8, 1 <= x_per_y <= 64.  Refused before a
+ * launch (-1, acg_last_error starts with "acg_fss_scales"), in this order: rows or C < 1, a stride < 1, x_per_y outside
+ * 1..64 or not dividing rows, both outputs NULL, H or W outside 1..1024, T outside 1..8, a misaligned workspace (16 bytes); a
+ * workspace below acg_fss_scales_workspace_bytes returns -2.  The workspace is acg_fss's (it never depended on the windows):
+ * the planes of x, of y and, with want_ens and x_per_y > 1, the slices; nothing it held before the call, nor its padded bits,
+ * reach a result.  Kernels: fss_events and fss_slices as in acg_fss, then fss_scales, one workgroup of four waves per
+ * (row, c, t): a wave per 64 x 64 tile, levels 0..6 by popcounts and lane exchanges, levels 7..10 from the tiles' totals. */
+size_t acg_fss_scales_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int want_ens);
+int acg_fss_scales(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
+                   int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride,
+                   const float *thr, int T, long long *out, long long *ens_out, void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- Minkowski functionals of excursion sets (ops.minkowski, model.translate_minkowski, test.py --metric minkowski; no
  *      reference call site: the reference has no verification code, tests/minkowski_ref.py states the definition) ----
  * x: rows x C fields of H x W fp32 cells; the strides (in floats) mean what they mean in acg_fss: NHWC with Cp stored channels

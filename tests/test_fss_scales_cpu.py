@@ -1,0 +1,213 @@
+"""CPU tests of the intensity-scale skill of the fss events: the numpy reference (tests/fss_scales_ref.py) against an explicit
+Haar decomposition on the padded canvas and against closed forms, ops.fss_scale_summary against the reference, the level
+count, the option parser, the documentation and the header."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import fss_ref as F
+import fss_scales_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HAAR_SIZES = ((1, 1), (1, 7), (5, 1), (2, 2), (3, 5), (63, 65), (64, 64), (65, 64), (100, 37), (321, 321))
+
+
+def _planes(H, W, seed=0, p=0.3, n=2):
+    return (np.random.RandomState(seed + 31 * H + W).uniform(size=(n, H, W)) < p).astype(np.int64)
+
+
+@pytest.mark.parametrize("H,W", HAAR_SIZES)
+def test_the_block_sums_give_the_explicit_haar_decomposition(H, W):
+    """every term is a dyadic rational far below 2^53, so both sides are exact in float64: equality, not closeness"""
+    bx, by = _planes(H, W)
+    t = R.triples_of_planes(bx, by)
+    assert t.shape == (R.levels(H, W), 3) and t.dtype == np.int64
+    D = t[:, 0] + t[:, 1] - 2 * t[:, 2]
+    assert np.all(4 * D[:-1] - D[1:] >= 0)
+    got, want = R.component_energies(D, 1), R.haar_mse((bx - by).astype(np.float64))
+    assert np.array_equal(got, want), (got, want)
+    s = R.summary(t, H * W)
+    assert np.allclose(s["mse"], want / (H * W), rtol=1e-15, atol=0)
+    assert abs(s["mse"].sum() - ((bx - by) ** 2).mean()) <= 1e-14                    # the components add up to the plain MSE
+    for side, b in ((0, bx), (1, by)):                             # and each field's own energies, which en_rel compares
+        assert np.array_equal(R.component_energies(t[:, side], 1), R.haar_mse(b.astype(np.float64)))
+
+
+@pytest.mark.parametrize("H,W", ((1, 1), (1, 7), (5, 1), (2, 2), (33, 31), (64, 64), (65, 130)))
+def test_level_zero_is_the_window_one_triple_and_level_L_the_squared_totals(H, W):
+    for kind in F.KINDS:
+        x, y, thr = F.make_pair(kind, H, W)
+        t = R.triples(x, y, thr)
+        assert t.shape == (2, 3, 3, R.levels(H, W), 3)
+        assert np.array_equal(t[..., 0, :], F.triples(x, y, thr, (1,))[..., 0, :]), kind
+        n_f, n_o = F.events(x, thr).sum((-2, -1)), F.events(y, thr).sum((-2, -1))
+        assert np.array_equal(t[..., -1, :], np.stack([n_f * n_f, n_o * n_o, n_f * n_o], -1)), kind
+        brute = np.array([[sum(F.events(x, thr)[0, 0, 0, i:i + s, j:j + s].sum() ** 2 for i in range(0, H, s) for j in range(0, W, s))]
+                          for s in (1 << l for l in range(R.levels(H, W)))]).ravel()
+        assert np.array_equal(t[0, 0, 0, :, 0], brute), kind       # blocks by slicing: anchored at (0, 0), cut by the domain
+
+
+def test_identical_fields_have_no_error_at_any_scale():
+    from dtgan_amd import ops
+    x, _, thr = F.make_pair("noise", 33, 31)
+    s = ops.fss_scale_summary(R.triples(x, x, thr).sum(0), 2 * 33 * 31)
+    assert s["mse"].shape == (3, 3, 7) and np.all(s["mse"] == 0.0)
+    assert np.all(s["mse_random"][:, 0] > 0) and np.all(s["iss"][:, 0] == 1.0) and np.all(s["skill_scale"][:, 0] == 1)
+    assert np.all(s["mse_random"][:, 1:] == 0) and np.all(np.isnan(s["iss"][:, 1:]))      # no event, and every cell an event
+    assert np.all(s["en_rel"][:, 0] == 0.0) and np.all(np.isnan(s["en_rel"][:, 1]))       # nothing on either side: 0 / 0
+    assert np.all(s["skill_scale"][:, 1:] == 64)                   # NaN is no skill: 2^L
+
+
+def test_a_checkerboard_against_nothing_errs_at_the_finest_scale_and_in_the_mean():
+    from dtgan_amd import ops
+    b = (np.add.outer(np.arange(64), np.arange(64)) % 2).astype(np.int64)
+    t = R.triples_of_planes(b, np.zeros_like(b))
+    for s in (R.summary(t[None], 4096), ops.fss_scale_summary(t[None], 4096)):
+        assert np.array_equal(s["mse"][0], [0.25, 0, 0, 0, 0, 0, 0.25]) and s["mse_random"][0] == 0.5
+        assert np.array_equal(s["iss"][0], [-2.5, 1, 1, 1, 1, 1, -2.5]) and s["skill_scale"][0] == 2
+        assert np.all(s["en_rel"][0][[0, 6]] == 1.0) and np.all(np.isnan(s["en_rel"][0][1:6]))
+
+
+@pytest.mark.parametrize("H,W", ((64, 64), (5, 7), (100, 37)))
+def test_everything_against_nothing_is_the_mean_term_alone(H, W):
+    from dtgan_amd import ops
+    one = np.ones((H, W), dtype=np.int64)
+    t = R.triples_of_planes(one, 0 * one)
+    s = ops.fss_scale_summary(t[None], H * W)
+    L = R.levels(H, W) - 1
+    assert abs(s["mse"][0].sum() - 1.0) <= 1e-15 and s["mse_random"][0] == 1.0
+    if (H, W) == (64, 64):                                         # a dyadic field: nothing but the mean
+        assert np.array_equal(s["mse"][0], [0] * L + [1.0]) and s["skill_scale"][0] == 1
+    else:                                                          # the cut blocks put the domain's edge into every scale
+        assert s["mse"][0, L] == H * W / 4.0 ** L and np.all(s["mse"][0] > 0)
+
+
+@pytest.mark.parametrize("k", (0, 2, 3, 5))
+def test_a_block_displaced_by_its_width_errs_at_its_own_scale(k):
+    from dtgan_amd import ops
+    s = 1 << k
+    f, o = np.zeros((2, 64, 64), dtype=np.int64)
+    f[0:s, 0:s], o[0:s, s:2 * s] = 1, 1                            # neighbours inside one 2^(k+1) block
+    got = ops.fss_scale_summary(R.triples_of_planes(f, o)[None], 4096)
+    want = np.zeros(7)
+    want[k] = 2.0 * s * s / 4096
+    assert np.array_equal(got["mse"][0], want)
+    e = s * s / 4096.0
+    assert abs(got["mse_random"][0] - 2 * e * (1 - e)) <= 1e-15
+    assert got["iss"][0, k] < 0 and got["skill_scale"][0] == 2 * s and np.all(np.delete(got["iss"][0], k) == 1.0)
+    assert np.all(got["en_rel"][0, k:] == 0.0) and np.all(np.isnan(got["en_rel"][0, :k]))    # the same object on both sides
+
+
+@pytest.mark.parametrize("H,W,M", ((33, 31, 5), (64, 64, 16), (5, 7, 64)))
+def test_an_ensemble_is_its_exceedance_probability_against_the_truth(H, W, M):
+    from dtgan_amd import ops
+    rs = np.random.RandomState(M)
+    x, y = rs.standard_normal((M, 1, H, W)).astype(np.float32), rs.standard_normal((1, 1, H, W)).astype(np.float32)
+    thr = np.array([[0.2]], dtype=np.float32)
+    t = R.ens_triples(x, y, thr, M)[0, 0]                          # (T, nl, 3)
+    bx, by = F.events(x, thr)[:, 0, 0], F.events(y, thr)[0, 0, 0]
+    assert np.array_equal(t[0], R.triples_of_planes(bx.sum(0), by))
+    err = bx.mean(0) - by
+    n_f = R.triples(x, y, thr, M).sum(0)[0, :, 0, 0]               # the members' own level 0
+    assert n_f[0] == bx.sum()
+    for s in (R.summary(t, H * W, M, n_f), ops.fss_scale_summary(t, H * W, M, n_f)):
+        # M is no power of two, so neither side is exact: a few roundings of terms that are at most 1 per cell
+        assert np.allclose(s["mse"][0], R.haar_mse(err) / (H * W), rtol=1e-12, atol=1e-14)
+        assert abs(s["mse"][0].sum() - (err ** 2).mean()) <= 1e-13
+        p = bx.mean(0)
+        assert abs(s["mse_random"][0] - ((p ** 2).mean() - 2 * p.mean() * by.mean() + by.mean())) <= 1e-13
+    with pytest.raises(ValueError, match="forecast_events"):      # an ensemble's level 0 is sum E^2, not the events
+        ops.fss_scale_summary(t, H * W, M)
+
+
+def test_the_summary_equals_the_reference_and_refuses_what_it_cannot_read():
+    from dtgan_amd import ops
+    for kind in F.KINDS:
+        for H, W in ((1, 1), (5, 7), (64, 64), (65, 130)):
+            x, y, thr = F.make_pair(kind, H, W)
+            t = R.triples(x, y, thr).sum(0)
+            got, want = ops.fss_scale_summary(t, 2 * H * W), R.summary(t, 2 * H * W)
+            assert set(got) == set(want) == {"mse", "iss", "en_rel", "mse_random", "skill_scale"}
+            nl = R.levels(H, W)
+            for k in got:
+                assert got[k].shape == ((3, 3) if k in ("mse_random", "skill_scale") else (3, 3, nl)), k
+                assert got[k].dtype == (np.int64 if k == "skill_scale" else np.float64), k
+                assert np.allclose(got[k], want[k], rtol=1e-14, atol=0, equal_nan=True), (kind, H, W, k)
+            assert np.all(got["mse"] >= 0) and np.all(np.isin(got["skill_scale"], 2 ** np.arange(nl)))
+            D = t[..., 0] + t[..., 1] - 2 * t[..., 2]
+            assert np.allclose(got["mse"].sum(-1), D[..., 0] / (2.0 * H * W), rtol=1e-13, atol=1e-15)   # n_f + n_o - 2 hits
+    assert ops.fss_scale_summary(np.zeros((1, 1, 3), np.int64), 1)["skill_scale"][0] == 1     # 1 x 1: no mother scale, 2^L = 1
+    for bad in ((np.zeros((2, 3, 4)), 10), (np.zeros((3,)), 10), (np.zeros((2, 3, 3)), 0), (np.zeros((2, 3, 3)), -5)):
+        with pytest.raises(ValueError, match="fss_scale_summary"):
+            ops.fss_scale_summary(*bad)
+    with pytest.raises(ValueError, match="members"):
+        ops.fss_scale_summary(np.zeros((2, 3, 3)), 10, members=0)
+
+
+def test_skill_scale_needs_skill_at_every_larger_scale():
+    from dtgan_amd import ops
+    # iss is 1 - mse (L + 1) / mse_random: block sums D whose components have the listed energies, at L = 4
+    cells, L = 256, 4
+
+    def sums_of(mse):                                              # triples with oo = fo = 0 whose components are mse
+        D = np.zeros(L + 1)
+        D[L] = mse[L] * 4.0 ** L * cells
+        for j in range(L - 1, -1, -1):
+            D[j] = (mse[j] * 4.0 ** (j + 1) * cells + D[j + 1]) / 4
+        t = np.zeros((1, L + 1, 3))
+        t[0, :, 0] = D
+        return t
+    for mse, want in (([0.1, 0.3, 0.1, 0.1, 0.4], 4), ([0.3, 0.1, 0.1, 0.3, 0.2], 16), ([0.1, 0.1, 0.1, 0.1, 0.6], 1),
+                      ([0.1, 0.1, 0.25, 0.1, 0.45], 8)):           # skill is mse_j below the share 1 / (L + 1) = 0.2
+        t = sums_of(np.array(mse))
+        s = ops.fss_scale_summary(t, cells)
+        assert abs(s["mse_random"][0] - 1.0) < 1e-12 and np.allclose(s["mse"][0], mse, rtol=1e-12)
+        assert s["skill_scale"][0] == want == R.summary(t, cells)["skill_scale"][0], (mse, s["iss"])
+
+
+def test_fss_scale_levels():
+    from dtgan_amd import _lib, ops
+    for n, nl in ((1, 1), (2, 2), (3, 3), (64, 7), (65, 8), (1024, 11)):
+        assert ops.fss_scale_levels(n, n) == ops.fss_scale_levels(1, n) == ops.fss_scale_levels(n, 1) == R.levels(n, 1) == nl, n
+    assert ops.fss_scale_levels(100, 37) == 8 and ops.fss_scale_levels(321, 321) == 10
+    for bad in ((0, 5), (5, 1025)):
+        with pytest.raises(_lib.AcgError):
+            ops.fss_scale_levels(*bad)
+
+
+def _parse(*extra):
+    from dtgan_amd import options as O
+    return O.TestOptions().parse(["--chk_path", "c", "--dataroot", "d", "--metric", "fss"] + list(extra))
+
+
+def test_the_parser_takes_the_option_and_the_documents_name_it():
+    from dtgan_amd import eval_metrics as EM, model, ops, options as O, test as T
+    assert _parse().fss_scales == 0 and _parse("--fss_scales", "1").fss_scales == 1
+    assert _parse("--fss_scales", "0", "--fss_windows", "3,9").fss_scales == 0
+    for bad in ("2", "-1", "x", "1.0"):
+        with pytest.raises(SystemExit):
+            _parse("--fss_scales", bad)
+    assert "--fss_scales" in O.TestOptions.__doc__
+    doc = [m.doc for m in EM.METRICS if m.name == "fss"][0]
+    assert doc.startswith("  fss ") and "--fss_scales 1" in doc and "ops.fss_scale_summary" in doc and "Casati" in doc
+    assert doc in T.__doc__
+    assert "scales=True" in model._Base.translate_fss.__doc__ and "members_scale" in model._Base.translate_fss.__doc__
+    assert "acg_fss_scales" in ops.fss_scales.__doc__ and "skill_scale" in ops.fss_scale_summary.__doc__
+
+
+def test_the_header_declares_both_entries_and_the_binding_matches():
+    from dtgan_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
+    for name, nargs in (("acg_fss_scales_workspace_bytes", 7), ("acg_fss_scales", 20)):
+        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
+        assert m, name
+        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]) == nargs, name
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert "`acg_fss_scales`" in doc and "acg_fss_scales_workspace_bytes" in doc and "ops.fss_scale_summary" in doc
+    lib = _lib.load()
+    for args in ((4, 2, 3, 65, 130, 3, 1), (4, 2, 3, 65, 130, 3, 0), (16, 16, 1, 1024, 1024, 1, 1), (2, 1, 1, 1, 1, 8, 1)):
+        assert lib.acg_fss_scales_workspace_bytes(*args) == lib.acg_fss_workspace_bytes(*(args[:6] + (1,) + args[6:])) > 0, args
+    for args in ((0, 1, 1, 8, 8, 1, 0), (3, 2, 1, 8, 8, 1, 0), (2, 1, 1, 8, 1025, 1, 0), (2, 1, 1, 8, 8, 9, 0), (65, 65, 1, 8, 8, 1, 1)):
+        assert lib.acg_fss_scales_workspace_bytes(*args) == 0, args

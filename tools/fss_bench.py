@@ -10,6 +10,11 @@ members held as planar NCHW: per threshold the comparison as float32, per window
 fractions), the three products summed per field, and the same on the members' mean event plane for the ensemble.  Its float
 sums depend on the pooling order; the integer triples do not.  The two are compared as FSS values.  One JSON line.
 
+Beside it the intensity-scale triples of the same events (ops.fss_scales, what --fss_scales 1 adds per group: events, scales,
+slices and the ensemble's scales kernels) on the same tensors, as scales_ms in that line, and a second JSON line for one
+1024 x 1024 pair of one channel and one threshold, the largest field either call takes: fss_ms at the same windows and
+scales_ms.  Both calls begin with the same events pass; a kernel trace of this tool splits their times by kernel.
+
     python tools/fss_bench.py [--reps 10] [--case 256x3:32x16] [--windows 1,3,5,9,17,33]
 """
 import argparse
@@ -58,6 +63,9 @@ def main():
     def hip():
         return ops.fss(x, y, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True)
 
+    def hip_scales():
+        return ops.fss_scales(x, y, C, "nhwc", "nchw", thr, x_per_y=M, ensemble=True)
+
     def composed():
         """-> member triples (N M, C, T, nw, 3) and ensemble triples (N, C, T, nw, 3) of FRACTIONS, float32"""
         mem, ens = [], []
@@ -78,6 +86,8 @@ def main():
     with torch.no_grad():
         hip_ms = timed(hip)
         kernel = _lib.query("acg_last_kernel").decode()
+        scales_ms = timed(hip_scales)
+        scales_kernel = _lib.query("acg_last_kernel").decode()
         torch_ms = timed(composed)
         (o, e), (om, em) = hip(), composed()
         fss = lambda t: 2 * t[..., 2].sum(0).double() / (t[..., 0].sum(0).double() + t[..., 1].sum(0).double())
@@ -85,9 +95,18 @@ def main():
         diff = float(torch.nan_to_num(fss(o) - fss(om)).abs().max())
         diff_prob = float(torch.nan_to_num(fss_prob - fss(em)).abs().max())
     print(json.dumps(dict(tool="fss_bench", S=S, C=C, N=N, M=M, T=T, windows=list(win), reps=a.reps, kernel=kernel,
-                          hip_ms=round(hip_ms, 3), torch_ms=round(torch_ms, 3), torch_over_hip=round(torch_ms / hip_ms, 2),
+                          hip_ms=round(hip_ms, 3), scales_ms=round(scales_ms, 3), scales_kernel=scales_kernel, torch_ms=round(torch_ms, 3), torch_over_hip=round(torch_ms / hip_ms, 2),
                           workspace_MiB=round(_lib.query("acg_fss_workspace_bytes", N * M, M, C, S, S, T, len(win), 1) / 2 ** 20, 1),
                           max_fss_difference=float("%.3e" % diff), max_fss_prob_difference=float("%.3e" % diff_prob))), flush=True)
+    big = torch.rand(2, 1, 1024, 1024, device="cuda", generator=gen) * 2 - 1
+    half = torch.zeros(1, 1, device="cuda")
+    with torch.no_grad():
+        pair_ms = timed(lambda: ops.fss(big[:1], big[1:], 1, "nchw", "nchw", half, win))
+        pair_kernel = _lib.query("acg_last_kernel").decode()
+        pair_scales_ms = timed(lambda: ops.fss_scales(big[:1], big[1:], 1, "nchw", "nchw", half))
+    print(json.dumps(dict(tool="fss_bench", S=1024, C=1, N=1, M=1, T=1, windows=list(win), reps=a.reps, kernel=pair_kernel,
+                          fss_ms=round(pair_ms, 3), scales_ms=round(pair_scales_ms, 3),
+                          scales_kernel=_lib.query("acg_last_kernel").decode())), flush=True)
 
 
 if __name__ == "__main__":
