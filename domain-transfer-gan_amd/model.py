@@ -261,7 +261,8 @@ class StepGraph(object):
         baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
                                                         "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
                                                         "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B",
-                                                        "lambda_ssim_A", "lambda_ssim_B"))
+                                                        "lambda_ssim_A", "lambda_ssim_B", "lambda_crps_B", "crps_members",
+                                                        "crps_alpha"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -1397,6 +1398,33 @@ class AugmentedCycleGAN(_Base):
         with _in_train_step():
             return self._supervised_train_instance(real_A, real_B, prior_z_B)
 
+    def _crps_term(self, A, B, z):
+        """S_crps_B, S_pair_B under --lambda_crps_B: None when the weight is 0 (the default: no launch is issued), else (the
+        almost fair CRPS of Me = min(crps_members, batch) translations of every paired input against its B, the members' mean
+        pair distance, the weighted term for loss_G).  The members are one more pass of G_A_B, in the step's train state, over
+        every input repeated Me times in a row; member m of input n is coded with z[(n + m) % batch]: prior draws the step
+        already has, independent of the inputs and distinct per input, so no new random number enters the step and a captured
+        step replays it.  Neither the encoder nor G_B_A is on the term's path."""
+        o = self.opt
+        lam = float(getattr(o, 'lambda_crps_B', 0.0) or 0.0)
+        if lam <= 0:
+            return None
+        bs = z.shape[0]
+        members = int(getattr(o, 'crps_members', 4))
+        if not 2 <= members <= ops.CRPS_MAX_M:
+            raise ValueError("crps_members must lie in 2..%d (got %d)" % (ops.CRPS_MAX_M, members))
+        Me = min(members, bs)
+        most = ensemble_chunk(o.ngf, A.shape[1], A.shape[2])
+        if bs * Me > most:
+            raise ValueError("lambda_crps_B: %d inputs x %d members are more than the %d images one generator pass holds at "
+                             "%d x %d with ngf %d" % (bs, Me, most, A.shape[1], A.shape[2], o.ngf))
+        inputs = A.unsqueeze(1).expand((bs, Me) + tuple(A.shape[1:])).reshape((bs * Me,) + tuple(A.shape[1:]))
+        codes = torch.stack([torch.roll(z, -m, 0) for m in range(Me)], 1).reshape(bs * Me, z.shape[1])
+        fakes = self.netG_A_B.forward_nhwc(inputs, codes)
+        loss, _, pair = ops.crps_loss(fakes, B, o.output_nc, "nhwc", "nhwc", Me,
+                                      alpha=float(getattr(o, 'crps_alpha', 0.95)), parts=True)
+        return loss, pair, loss * lam
+
     def _supervised_train_instance(self, real_A, real_B, prior_z_B):
         o = self.opt
         nA, nB, nl = o.input_nc, o.output_nc, o.nlatent
@@ -1432,11 +1460,18 @@ class AugmentedCycleGAN(_Base):
             ssim = self._ssim_terms(pred_A, A, pred_B, B)
             if ssim is not None:
                 loss_G = loss_G + ssim[2]
+            crps = self._crps_term(A, B, z)
+            if crps is not None:
+                loss_G = loss_G + crps[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             sums = [loss_sup_A, loss_sup_B, kld_z_B, loss_D_z_B]
             if ssim is not None:
                 sums += [ssim[0], ssim[1]]
-            # backward order: G_B_A (built last), G_A_B, then the encoder behind post_z
+            if crps is not None:
+                sums += [crps[0], crps[1]]
+            # the order in which the networks' gradients complete: G_B_A (its only pass hangs on nothing else), G_A_B, then
+            # the encoder behind post_z.  With the CRPS term G_A_B's member pass is built last and runs backward first, but
+            # G_A_B is complete only after its first pass, which still finishes after G_B_A's and before the encoder's
             ex_G = self._backward(loss_G, "sup.G", [self.f_G_B_A, self.f_G_A_B, self.f_E_B], tail=(self.f_E_B, sums))
         finally:
             self.f_D_z_B.set_requires_grad(True)
@@ -1446,6 +1481,7 @@ class AugmentedCycleGAN(_Base):
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
         n_loss = len(sums)
         names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B'] + (['S_ssim_A', 'S_ssim_B'] if ssim is not None else []) + \
+                (['S_crps_B', 'S_pair_B'] if crps is not None else []) + \
                 ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
         vals = self._scalars(ex_G, self.f_E_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_E, ss_D_z])
 

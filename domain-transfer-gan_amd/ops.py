@@ -2059,6 +2059,88 @@ def ssim_loss(x, y, C, layout, data_range=2.0):
 
 
 # ----------------------------------------------------------------------------------------------
+# the CRPS training loss of M translations per input (the paired step under --lambda_crps_B; tests/crps_ref.py)
+# ----------------------------------------------------------------------------------------------
+CRPS_MAX_HW, CRPS_MAX_M = 1024, 16
+
+
+def crps_weight(M, alpha):
+    """w of the score e1 - w e2 of M members, e2 the sum of |x_i - x_j| over the pairs i < j: alpha / (M (M - 1)) +
+    (1 - alpha) / M^2, 0 for M = 1.  alpha = 1: the fair CRPS (Ferro 2014), alpha = 0: the ensemble CRPS, between them the
+    almost fair score (Lang et al. 2024).  ValueError for M outside 1..16 or alpha outside [0, 1]."""
+    M, a = int(M), float(alpha)
+    if not 1 <= M <= CRPS_MAX_M:
+        raise ValueError("members must lie in 1..%d (got %d)" % (CRPS_MAX_M, M))
+    if not 0.0 <= a <= 1.0:
+        raise ValueError("alpha must lie in [0, 1] (got %r)" % (alpha,))
+    return 0.0 if M == 1 else a / (M * (M - 1)) + (1.0 - a) / (M * M)
+
+
+def _crps_size(H, W):
+    if not (1 <= H <= CRPS_MAX_HW and 1 <= W <= CRPS_MAX_HW):
+        raise _lib.AcgError("crps_loss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (CRPS_MAX_HW, H, W))
+    return int(H), int(W)
+
+
+def _crps_call(x, y, sizes, sx, sy, M, out):
+    rows, C, H, W = sizes
+    ws, nbytes = _metric_workspace("acg_crps_workspace_bytes", rows, M, C, H, W)
+    _lib.call("acg_crps_fwd", _ptr(x), _ptr(y), rows, M, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(out), ws, nbytes,
+              _stream())
+
+
+class CrpsLoss(torch.autograd.Function):
+    """crps_loss with its data gradient in x: forward acg_crps_fwd (the sums of e1 and e2 per input and channel, in double)
+    and the scalar combine on the device; backward acg_crps_bwd, which recomputes the signs from x and y (nothing but the two
+    operands is kept, and those only when x needs a gradient) and scales by the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, C, layout_x, layout_y, members, alpha):
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise _lib.AcgError("crps_loss: alpha must lie in [0, 1] (got %r)" % (alpha,))
+        x, y, rows, N, C, Cp, (H, W), sx, sy, M = _paired_fields("crps_loss", x, y, C, layout_x, layout_y, _crps_size, members,
+                                                                 max_per=CRPS_MAX_M, size_y=True)
+        w = crps_weight(M, alpha)
+        out = _out_tensor("crps_loss", None, (N, C, 2), (x, y), dtype=torch.float64)
+        _crps_call(x, y, (rows, C, H, W), sx, sy, M, out)
+        cells = N * C * H * W
+        tot = out.sum((0, 1))
+        loss = ((tot[0] - w * tot[1]) / cells).float()
+        e1 = (tot[0] / cells).float()
+        pair = (tot[1] * (2.0 / (M * (M - 1) * cells))).float() if M > 1 else torch.zeros_like(e1)
+        ctx.mark_non_differentiable(e1, pair)
+        if ctx.needs_input_grad[0]:
+            ctx.cfg = (rows, M, C, Cp, H, W, sx, sy, 1.0 / (M * cells), w / cells)
+            ctx.save_for_backward(x, y)
+        return loss, e1, pair
+
+    @staticmethod
+    def backward(ctx, g, _e1, _pair):
+        x, y = ctx.saved_tensors
+        rows, M, C, Cp, H, W, sx, sy, coef_y, coef_pair = ctx.cfg
+        g = g.detach().to(torch.float32).contiguous()
+        dx = torch.empty_like(x)
+        _lib.call("acg_crps_bwd", _ptr(x), _ptr(y), _ptr(g), rows, M, C, Cp, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2],
+                  ctypes.c_double(coef_y), ctypes.c_double(coef_pair), _ptr(dx), _stream())
+        return dx, None, None, None, None, None, None
+
+
+def crps_loss(x, y, C, layout_x, layout_y, members, alpha=0.95, parts=False):
+    """The almost fair CRPS of `members` translations per input against their truth -> float32 device scalar, differentiable in
+    x (y is detached).  x holds rows = N members fields, member m of input n at row n members + m (ensemble_stats's order); y
+    the N truths; each operand has its own layout ("nhwc" or "nchw").  Per cell (input, valid channel, pixel)
+    s = (1/M) sum_i |x_i - y| - w sum_{i<j} |x_i - x_j|, w = crps_weight(M, alpha); the loss is the mean of s over N, the C
+    valid channels and the H W pixels (M = 1: the mean absolute error).  alpha = 1 equals ensemble_stats's fair CRPS, alpha = 0
+    its crps.  d loss / d x_i = g (sign(x_i - y) / M - w sum_{j != i} sign(x_i - x_j)) / (N C H W) with sign(0) = 0; NHWC: the
+    padded channels of the gradient are 0.  parts=True: (loss, e1, pair), the detached scalars e1 = the mean of (1/M) sum_i
+    |x_i - y| and pair = the mean over cells of the mean |x_i - x_j| over i != j (0 for M = 1).  1 <= H, W <= 1024, members in
+    1..16.  acg_crps_fwd sums in double in a fixed order (the same bits in every layout), acg_crps_bwd recomputes the signs; no
+    host synchronisation.  Under torch.no_grad(), or for an x that needs no gradient, nothing is saved."""
+    loss, e1, pair = CrpsLoss.apply(x if torch.is_grad_enabled() else x.detach(), y, C, layout_x, layout_y, members, alpha)
+    return (loss, e1, pair) if parts else loss
+
+
+# ----------------------------------------------------------------------------------------------
 # neighbourhood fractions skill scores (model.translate_fss, eval_metrics.py, --metric fss)
 # ----------------------------------------------------------------------------------------------
 FSS_MAX_HW, FSS_MAX_T, FSS_MAX_NW, FSS_MAX_M = 1024, 8, 8, 64

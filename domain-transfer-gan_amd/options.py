@@ -102,6 +102,18 @@ _T = [
                                   "sigma 1.5, data range 2) on the cycle reconstruction rec_A against the real A, and with "
                                   "--supervised on the paired prediction of A; 0: off; needs 11 <= --grid_size <= 1024"),
     ("lambda_ssim_B", float, 0.0, "the same on rec_B (and the paired prediction of B) against the real B"),
+    ("lambda_crps_B", float, 0.0, "weight of the CRPS loss of the paired step (needs --supervised): G_A_B translates every paired "
+                                  "input --crps_members times with codes from the step's prior draws, and the almost fair CRPS "
+                                  "of those members against the paired B (ops.crps_loss) joins the generator loss, so that the "
+                                  "ensemble's spread is trained and not only its median; 0: off; needs --norm instance and "
+                                  "--grid_size up to 1024.  There is no lambda_crps_A: B -> A is deterministic, an ensemble of "
+                                  "one, whose CRPS is the L1 term the step already has"),
+    ("crps_members", int, 4, "members per paired input under --lambda_crps_B, 2..16 (at most the paired batch: member m of "
+                             "input n is coded with the prior draw (n + m) mod batch); batch x members images go through G_A_B "
+                             "in one pass and must fit it (255 images at 256 x 256 with --ngf 32)"),
+    ("crps_alpha", float, 0.95, "under --lambda_crps_B: 1 is the fair CRPS (Ferro 2014), 0 the ensemble CRPS, between them the "
+                                "almost fair score (Lang et al. 2024), which keeps a member from being sent away when the others "
+                                "sit on the truth; inside [0, 1]"),
     ("native_res", "flag", False, "keep the fields at their stored resolution (no resize to --grid_size; both extents must be at "
                                   "least --grid_size): every training step cuts a fresh random --grid_size window per sample on "
                                   "the device (ops.window_gather), dev and test are cut once to their centre windows; whole "
@@ -150,6 +162,29 @@ class TrainOptions(object):
         if (opt.lambda_ssim_A > 0 or opt.lambda_ssim_B > 0) and not 11 <= g <= 1024:
             self.parser.error("--lambda_ssim_A / --lambda_ssim_B: the structural similarity slides an 11 x 11 window over "
                               "fields of up to 1024 x 1024 (--grid_size %d)" % g)
+        if opt.lambda_crps_B < 0:
+            self.parser.error("--lambda_crps_B must not be negative (got %r)" % opt.lambda_crps_B)
+        if not 2 <= opt.crps_members <= 16:
+            self.parser.error("--crps_members must lie in 2..16 (got %d)" % opt.crps_members)
+        if not 0.0 <= opt.crps_alpha <= 1.0:
+            self.parser.error("--crps_alpha must lie in [0, 1] (got %r)" % opt.crps_alpha)
+        if opt.lambda_crps_B > 0:
+            if not opt.supervised:
+                self.parser.error("--lambda_crps_B is a term of the paired step: it requires --supervised")
+            if opt.model != "aug_cycle_gan":
+                self.parser.error("--lambda_crps_B: --model %s has no paired step (aug_cycle_gan has)" % opt.model)
+            if opt.norm != "instance":
+                self.parser.error("--lambda_crps_B needs --norm instance: under batch statistics the members of one input "
+                                  "would see each other (--norm %s)" % opt.norm)
+            if not 1 <= g <= 1024:
+                self.parser.error("--lambda_crps_B: the CRPS loss takes fields of up to 1024 x 1024 (--grid_size %d)" % g)
+            from .model import ensemble_chunk              # the step's own limit, met here before any data is loaded
+            per_rank = max(opt.batchSize // max(int(os.environ.get("WORLD_SIZE", "1")), 1), 1)
+            images, most = per_rank * min(opt.crps_members, per_rank), ensemble_chunk(opt.ngf, g, g)
+            if images > most:
+                self.parser.error("--lambda_crps_B: a paired batch of %d x %d members is %d images, more than the %d one pass of "
+                                  "G_A_B holds at --grid_size %d with --ngf %d; lower --crps_members or --batchSize"
+                                  % (per_rank, min(opt.crps_members, per_rank), images, most, g, opt.ngf))
         if opt.native_res and opt.synthetic:
             self.parser.error("--native_res cuts windows from stored fields; --synthetic fields are --grid_size already")
         if opt.window_flip and not opt.native_res:

@@ -716,6 +716,42 @@ int acg_ssim_bwd(const float *dmaps, const float *x, const float *y, const float
                  long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                  long long y_chan_stride, float *gx, void *stream);
 
+/* ---- the CRPS training loss (ops.crps_loss, train.py --lambda_crps_B; no reference call site: the reference's paired step
+ *      penalises one translation per input by L1, tests/crps_ref.py states the definition; Ferro 2014, Lang et al. 2024) ----
+ * x: rows = N M fields of C channels of H x W fp32 pixels, member m of input n at row n M + m (acg_ensemble_stats's order),
+ * M = x_per_y; y: the N truths, row n.  Each operand has its own three strides (in floats), meaning what they mean in
+ * acg_fss.  1 <= H, W <= 1024, 1 <= M <= 16, any C >= 1.  Per cell (n, c, pixel) with members x_1 .. x_M and truth y:
+ *   e1 = (1/M) sum_i |x_i - y|,  e2 = sum_{i<j} |x_i - x_j|,  s = e1 - w e2,
+ *   w = alpha / (M (M - 1)) + (1 - alpha) / M^2 (0 for M = 1): alpha = 1 the fair CRPS, alpha = 0 the ensemble CRPS e1 - e2 / M^2.
+ * acg_crps_fwd writes out (N, C, 2) in DOUBLE: per input and channel the sums over the pixels of e1 and of e2; the loss is
+ * (sum out[.., 0] - w sum out[.., 1]) / (N C H W), the caller's to form.  Differences and sums in double (float -> double is
+ * exact); a workgroup of 256 threads owns 1024 consecutive pixels, thread t the pixels t, t + 256, t + 512, t + 768 of them,
+ * added in that order, the threads by a fixed tree into the workspace (acg_crps_workspace_bytes = 16 N C ceil(H W / 1024),
+ * 16-byte aligned), one wave per (n, c) folds them in a fixed order.  A thread holds the M values of a cell in registers and
+ * walks the M (M - 1) / 2 pairs there.  A C4 pixel's channels come from one 16-byte load per member, everything else value by
+ * value (a planar row is read 256 bytes per wave and load as it is); the order of every sum is the same: the same bits on
+ * every call and in every layout.  Two launches, no atomics, out fully written whatever it and the workspace held, nothing
+ * read back, capturable in a HIP graph.  acg_last_kernel(): "crps_fwd<x, y> + crps_fold", x and y each c4 or strided.  Refused before a launch (-1, acg_last_error starts with
+ * "acg_crps_fwd"), in this order: a null x, y or out; an extent outside 1 .. 1024; rows < 1 or C < 1; too many fields for a
+ * grid; a stride < 1; x_per_y outside 1 .. 16 or not dividing rows; out aliasing an input; a misaligned workspace; a short
+ * workspace: -2.  The size query is 0 for a refused size. */
+size_t acg_crps_workspace_bytes(int rows, int x_per_y, int C, int H, int W);
+int acg_crps_fwd(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride, int x_pix_stride,
+                 long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, double *out,
+                 void *workspace, size_t ws_bytes, void *stream);
+/* The data gradient of that loss in x.  The signs are recomputed from x and y (sign(0) = 0, what torch.abs propagates; no maps
+ * are kept between the passes): per member i of a cell the integers sy = sign(x_i - y), sp = sum_{j != i} sign(x_i - x_j), and
+ *   dx_i = (float)(g[0] (coef_y sy - coef_pair sp)),  coef_y = 1 / (M N C H W),  coef_pair = w / (N C H W),
+ * the two coefficients formed by the caller in double, the combine in double without contraction, rounded once.  g: the
+ * upstream gradient, one float on the device.  dx is written in x's layout; Cp: the channels stored per pixel of dx,
+ * channels C .. Cp - 1 are written as 0 (NHWC: Cp = pix_stride; planar: the stored planes).  y gets no gradient.  One launch,
+ * no workspace, nothing read back, capturable.  acg_last_kernel(): "crps_bwd<x, y>".  Refused before a launch (-1), in this
+ * order: a null pointer; an extent outside 1 .. 1024; rows < 1, C < 1 or C > Cp; too many fields; a stride < 1; x_per_y
+ * outside 1 .. 16 or not dividing rows; a coefficient that is not finite; dx aliasing an input. */
+int acg_crps_bwd(const float *x, const float *y, const float *g, int rows, int x_per_y, int C, int Cp, int H, int W,
+                 long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                 long long y_chan_stride, double coef_y, double coef_pair, float *dx, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
