@@ -121,6 +121,7 @@ SIGNATURES = {
     "acg_conv_transpose2d_bwd_weight": (c_int, [_D, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "acg_norm_workspace_bytes": (c_size_t, [c_int, c_size_t, c_int]),
     "acg_conv2d_fwd_stats_supported": (c_int, [_P]),
+    "acg_conv2d_fwd_stats_per_tile": (c_int, [_P]),
     "acg_conv2d_bwd_data_add_supported": (c_int, [_P]),
     "acg_conv2d_bwd_data_add": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "acg_pack_conv_weights_multi_supported": (c_int, [c_int, c_int, c_int]),

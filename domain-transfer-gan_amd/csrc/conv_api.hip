@@ -307,6 +307,22 @@ extern "C" int acg_conv2d_fwd_stats_supported(const acg_conv_desc *d)
     return ((long long)d->Ho * d->Wo) % 128 == 0 ? 1 : 0;
 }
 
+// Are the statistics acg_conv2d_fwd_stats emits for d those of each 128-pixel tile on its own (1), or may entries be the joint
+// statistics of several tiles (0)?  The row pipeline (conv_rows.hip) writes the joint (mean, M2) of the rows a workgroup owns,
+// and that count follows the batch: the merged mean / rstd of an image then depend, in their last bits, on how many images
+// share the launch.  A caller that needs a pass to be bit-identical across batch sizes (the ensemble groups of the evaluator)
+// asks here and leaves the statistics to the norm's own pass (acg_norm_stats: fixed chunks per image) where the answer is 0.
+extern "C" int acg_conv2d_fwd_stats_per_tile(const acg_conv_desc *d)
+{
+    if (!acg_conv2d_fwd_stats_supported(d)) return 0;
+    if (thin_in(d)) return 1;   // the thin-row stem: one entry per 8 x 16 tile
+    Geom g; Taps t;
+    static float probe;   // (only compared with nullptr)
+    fwd_geom(d, &g, &t, ACG_ACT_NONE);
+    g.stats = &probe; g.stats_chunk0 = 0; g.stats_cpi = (int)(((long long)d->Ho * d->Wo) / 128);
+    return !acg_igemm_uses_ws(g) && acg_conv_rows_ok(g, t) ? 0 : 1;   // (the dispatch order of acg_igemm_bf16_launch)
+}
+
 extern "C" int acg_conv2d_fwd_stats(const acg_conv_desc *d, const float *x, const float *wf, const float *bias, float *y,
                                     float *stats, void *stream)
 {

@@ -111,6 +111,8 @@ class Conv2d(nn.Conv2d, _Cached):
     def forward_nhwc(self, x, act=ACT_NONE, reflect_pad=0, fusion=None):
         pad, mode = (reflect_pad, PAD_REFLECT) if reflect_pad else (self.padding[0], PAD_ZERO)
         x = restore_width(x, self.packed().Cis)
+        if fusion is not None and not torch.is_grad_enabled():
+            fusion = fusion._replace(no_grad=True)
         return ops.Conv2dFn.apply(x, self.weight, self.bias, self.packed(), self.stride[0], pad, mode, act, fusion)
 
     def dgrad_sums_ok(self, x):

@@ -517,11 +517,12 @@ class S16Encode(torch.autograd.Function):
 
 
 # What a Conv2d shares with its neighbours (None in place of the record = a plain convolution): the slots documented at
-# ConvStats (want_stats), SkipGrad, ReluLink (link_out / link_in), S16Plan (s16) and NormSums.  want_identity: also return x
+# ConvStats (want_stats), SkipGrad, ReluLink (link_out / link_in), S16Plan (s16) and NormSums; no_grad: the grad mode was off
+# at the call (Conv2d.forward_nhwc fills it in: inside Function.forward it is always off).  want_identity: also return x
 # itself as a second output; a ResnetBlock feeds that alias to its skip connection, so the skip gradient arrives at the
 # convolution and is added inside the data-gradient epilogue (acg_conv2d_bwd_data_add) instead of by an autograd accumulation.
-ConvFusion = collections.namedtuple("ConvFusion", "want_stats want_identity link_out link_in skip_grad s16 norm_sums",
-                                    defaults=(None, False, None, None, None, None, None))
+ConvFusion = collections.namedtuple("ConvFusion", "want_stats want_identity link_out link_in skip_grad s16 norm_sums no_grad",
+                                    defaults=(None, False, None, None, None, None, None, False))
 
 
 def _weight_grad(ctx, entry, x, g, nbias, st, timed=True):
@@ -560,7 +561,7 @@ class Conv2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed, stride, pad, pad_mode, act, fusion=None):
-        want_stats, want_identity, link_out, link_in, skip_grad, s16, norm_sums = fusion or ConvFusion()
+        want_stats, want_identity, link_out, link_in, skip_grad, s16, norm_sums, no_grad = fusion or ConvFusion()
         x = x.contiguous()
         _check(x)
         N, Hi, Wi, Ci = x.shape
@@ -589,7 +590,11 @@ class Conv2dFn(torch.autograd.Function):
                 _lib.call("acg_conv2d_fwd_s16", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), act, _ptr(part),
                           1 if s16.y else 0, _stream())
         elif want_stats is not None and CONV_STATS_ENABLED and act == ACT_NONE and \
-                _lib.query("acg_conv2d_fwd_stats_supported", ctypes.byref(d)):
+                _lib.query("acg_conv2d_fwd_stats_supported", ctypes.byref(d)) and \
+                (not no_grad or _lib.query("acg_conv2d_fwd_stats_per_tile", ctypes.byref(d))):
+            # (no_grad: the caller ran under torch.no_grad() - the evaluator's ensemble groups - and such a forward must not
+            # depend on how many images share the launch: where the epilogue's entries are joint statistics whose grouping
+            # follows the batch, the norm's own pass takes them instead.  A training step keeps the fused statistics.)
             part = torch.empty((N, (d.Ho * d.Wo) // STATS_ROWS, 2, packed.Co), device=x.device, dtype=torch.float32)
             _fused("conv_fwd_tile_stats")
             _lib.call("acg_conv2d_fwd_stats", ctypes.byref(d), _ptr(x), _ptr(packed.wf), pbias, _ptr(y), _ptr(part), _stream())

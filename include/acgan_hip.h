@@ -134,6 +134,10 @@ int acg_conv2d_fwd(const acg_conv_desc *d, const float *x, const float *wf, cons
  * over tiles of 128 consecutive output pixels, to be merged by acg_norm_stats_from_partials(rows_per_chunk = 128).
  * Supported (query first) for the bf16x3 128-column tile: Co >= 128, Ci % 32 == 0, Ho*Wo % 128 == 0. */
 int acg_conv2d_fwd_stats_supported(const acg_conv_desc *d);
+/* 1: every entry acg_conv2d_fwd_stats writes for d is the (mean, M2) of its own 128-pixel tile; 0: entries may be joint
+ * statistics of several tiles whose grouping follows the batch (the row pipeline), so an image's merged statistics are not
+ * bit-identical across batch sizes.  model.py:606-733's translations run group by group and must not depend on the grouping. */
+int acg_conv2d_fwd_stats_per_tile(const acg_conv_desc *d);
 int acg_conv2d_fwd_stats(const acg_conv_desc *d, const float *x, const float *wf, const float *bias, float *y,
                          float *stats, void *stream);
 /* data gradient of the above (autograd of nn.Conv2d / ReflectionPad2d): dy -> dx.

@@ -388,3 +388,54 @@ def test_phase_exchange_async_handles_complete_out_of_order(monkeypatch):
         assert torch.equal(b1.g[:7], torch.full((7,), 6.0)) and torch.equal(b2.g[:5], torch.full((5,), 6.0))
         ex.wait(b1)                                # a second wait is a no-op (handle dropped): the marker is not re-applied
         assert torch.equal(b1.g[:7], torch.full((7,), 6.0))
+
+
+def test_large_operand_cases_straddle_2_gib_and_stay_inside_the_launchers_limit():
+    """the case generators of tests/test_hip_large_operands.py (no GPU): every size puts the 64-channel tensor past byte 2^31 and
+    under 2^32, the middle one is ensemble_chunk itself, both operands of every convolution pass are inside the launchers' 4 GiB
+    ACG_REQUIRE, the baseline size is below 2^31, and the image classes have the period the wrap argument needs"""
+    import test_hip_large_operands as L
+    from dtgan_amd.model import ensemble_chunk
+    from dtgan_amd.ops import cpad
+    assert cpad(2 * L.NGF) == L.C_LARGE == 64
+    assert [L.nbytes(s + (L.C_LARGE,)) for s in L.SIZES] == [2 ** 31 + 2 ** 24, 2 ** 32 - 2 ** 24, 131 * 250 * 262 * 256]
+    for N, H, W in L.SIZES:
+        assert 2 ** 31 < L.nbytes((N, H, W, L.C_LARGE)) < 2 ** 32
+        assert (N - 1) * H * W * L.C_LARGE * 4 >= 2 ** 31            # the last image lies wholly past the signed limit
+        for layer in L.LAYERS:
+            x, y = L.layer_shapes(layer, (N, H, W))
+            large = y if L.LAYERS[layer][4] == "out" else x
+            assert large == (N, H, W, L.C_LARGE)
+            assert 0 < L.nbytes(x) < 2 ** 32 and 0 < L.nbytes(y) < 2 ** 32   # gathered and written tensor of all three passes
+    assert L.SIZES[1][0] == ensemble_chunk(L.NGF, 256, 256) == 255
+    assert L.nbytes(L.BASE_SIZE + (L.C_LARGE,)) < 2 ** 31
+    N, H, W = L.SIZES[2]
+    assert W % 128 and (H * W) % 128 and H % 2 == 0 and W % 2 == 0
+    # 12 classes; a wrap by 2^31 or 2^32 bytes is 128 or 256 images of 256 x 256 and always lands on another base image
+    assert len(set(L.image_class(i) for i in range(12))) == 12 == L.PERIOD and L.image_class(12) == L.image_class(0)
+    for wrap in (128, 256):
+        assert all(L.image_class(i)[0] != L.image_class(i + wrap)[0] for i in range(12))
+    ids = [L.conv_id(c) for c in L.CONV_CASES] + [L.norm_id(c) for c in L.NORM_CASES]
+    assert len(set(ids)) == len(ids) == 4 * 3 * 3 * 2 + 2 * 3 * 3
+    assert all(L.expected_kernel(l, w, s, p) in L.KERNELS for l, w, s, p in L.CONV_CASES)
+    # the fast paths are expected exactly where W is a multiple of 128 in the bf16x3 arithmetic
+    assert L.expected_kernel("conv32to64", "fwd", L.SIZES[0], "bf16x3") == "rows"
+    assert L.expected_kernel("conv32to64", "fwd", L.SIZES[2], "bf16x3") == "bf16tile"
+    assert L.expected_kernel("conv32to64", "fwd", L.SIZES[0], "f32") == "f32tile"
+
+
+def test_stats_per_tile_query_names_the_row_pipeline():
+    """acg_conv2d_fwd_stats_per_tile (host only): 0 exactly where the forward statistics come from the row pipeline, whose
+    entries are joint over a workgroup's rows (the 32 -> 64 layer at widths of whole 128-pixel bands, bf16x3), 1 for the
+    per-tile epilogues, 0 where no statistics are emitted at all"""
+    import ctypes
+    from dtgan_amd import ops
+    q = lambda *a: _lib.query("acg_conv2d_fwd_stats_per_tile", ctypes.byref(ops.conv_desc(*a)))   # noqa: E731
+    assert ops.get_precision() == "bf16x3"
+    assert q(255, 256, 256, 32, 64, 3, 1, 1, ops.PAD_ZERO, 32, 64) == 0          # row pipeline
+    assert q(2, 16, 128, 32, 64, 3, 1, 1, ops.PAD_ZERO, 32, 64) == 0
+    assert q(2, 16, 64, 32, 64, 3, 1, 1, ops.PAD_ZERO, 32, 64) == 1              # width 64: the generic tile
+    assert q(2, 16, 128, 64, 32, 3, 1, 1, ops.PAD_ZERO, 64, 32) == 1             # 64 -> 32: the row-patch tile
+    assert q(2, 32, 128, 64, 128, 3, 2, 1, ops.PAD_ZERO, 64, 128) == 1           # wave-specialised
+    assert q(2, 16, 32, 4, 32, 7, 1, 3, ops.PAD_REFLECT, 3, 32) == 1             # thin-row stem
+    assert q(2, 9, 13, 32, 64, 3, 1, 1, ops.PAD_ZERO, 32, 64) == 0               # no whole tiles: no statistics
