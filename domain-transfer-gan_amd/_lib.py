@@ -210,6 +210,12 @@ SIGNATURES = {
                              c_int, ctypes.c_longlong, _P, _P, c_size_t, _P]),
     "acg_crps_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
                              ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "acg_fss_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "acg_fss_loss_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_longlong,
+                                 c_int, ctypes.c_longlong, _P, c_int, ctypes.POINTER(c_int), c_int, c_float, _P, _P, c_size_t, _P]),
+    "acg_fss_loss_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
+                                 ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, ctypes.POINTER(c_int), c_int, c_float, _P, _P,
+                                 _P, c_size_t, _P]),
     "acg_window_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "acg_window_blend": (c_int, [_P, ctypes.POINTER(WindowPlan), _P, c_int, c_int, c_int, _P]),
     "acg_comm_unique_id": (c_int, [_P]),

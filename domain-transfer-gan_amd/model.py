@@ -258,11 +258,12 @@ class StepGraph(object):
         lrs = tuple(opt.param_groups[0]['lr'] for opt in m._optimizers().values())
         # everything a captured launch bakes in as an argument: shapes, learning rates, train/eval mode, the kernel
         # configuration (precision / implementation switch) and the scalar options of the step
-        baked = tuple(getattr(m.opt, k, None) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
+        baked = tuple(_hashable(getattr(m.opt, k, None)) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
                                                         "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
                                                         "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B",
                                                         "lambda_ssim_A", "lambda_ssim_B", "lambda_crps_B", "crps_members",
-                                                        "crps_alpha"))
+                                                        "crps_alpha", "lambda_fss_A", "lambda_fss_B", "fss_tau",
+                                                        "fss_loss_windows", "fss_loss_thr_A", "fss_loss_thr_B"))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -352,6 +353,11 @@ class StepGraph(object):
         return deferred if deferred is not None else self.pending.resolve()
 
 
+def _hashable(v):
+    """an option's value as a key: lists (the windows and the nested threshold tables of the fss loss) become tuples"""
+    return tuple(_hashable(x) for x in v) if isinstance(v, (list, tuple)) else v
+
+
 def optional_loss_names(spec_on, marg_on, ssim_on=False):
     """the names of the optional loss scalars a step appends to its fixed ones, in the order of its sums: the spectral pair
     (--lambda_spec_A/B), then the marginal pair (--lambda_marg_A/B), then the structural-similarity pair (--lambda_ssim_A/B),
@@ -385,18 +391,20 @@ class _Base(object):
     def _optional_terms(self, loss, lams, fake_A, A, fake_B, B):
         """An optional loss family on the first-pass outputs against the real batches (`loss(fake, real, C, "nhwc")` on the
         internal NHWC tensors; unpaired: batch statistics): None when both weights are 0 (the default: no launch is issued),
-        else (term_A, term_B, weighted sum for loss_G).  A term of weight 0 is a monitor without gradient."""
+        else (term_A, term_B, weighted sum for loss_G).  A term of weight 0 is a monitor without gradient.  `loss` may be a
+        pair (loss of the A side, loss of the B side) where the sides differ in more than their operands."""
         lam_A, lam_B = lams
         if lam_A <= 0 and lam_B <= 0:
             return None
+        loss_A, loss_B = loss if isinstance(loss, tuple) else (loss, loss)
 
-        def term(fake, real, C, lam):
+        def term(loss, fake, real, C, lam):
             if lam > 0:
                 return loss(fake, real, C, "nhwc")
             with torch.no_grad():
                 return loss(fake.detach(), real, C, "nhwc")
-        t_A = term(fake_A, A, self.opt.input_nc, lam_A)
-        t_B = term(fake_B, B, self.opt.output_nc, lam_B)
+        t_A = term(loss_A, fake_A, A, self.opt.input_nc, lam_A)
+        t_B = term(loss_B, fake_B, B, self.opt.output_nc, lam_B)
         add = None
         for v, lam in ((t_A, lam_A), (t_B, lam_B)):
             if lam > 0:
@@ -417,6 +425,36 @@ class _Base(object):
         them, of the pairs a step has: the CYCLE reconstructions against their real batches in an unpaired step, the
         predictions against their paired fields in the paired one"""
         return _Base._optional_terms(self, ops.ssim_loss, self._ssim_lambdas(), rec_A, A, rec_B, B)
+
+    def _fss_terms(self, pred_A, A, pred_B, B):
+        """S_fss_A, S_fss_B (ops.fss_loss: 1 - the fractions skill score of soft threshold exceedances, pooled over the
+        batch) under --lambda_fss_A/B, as _optional_terms gives them, of the paired step's predictions against their paired
+        fields.  Each side has its own thresholds, opt.fss_loss_thr_A / _B ((C, T) nested lists, the climatology train.py
+        resolves at start), uploaded once; the windows (fss_loss_windows) and the temperature (fss_tau) are shared.  Under the
+        data-parallel exchange every rank pools its own batch, as the marginal loss does, and the reported scalars are the
+        ranks' average."""
+        lams = _Base._lambda_pair(self, 'fss')
+        if lams[0] <= 0 and lams[1] <= 0:
+            return None
+        o = self.opt
+        windows, tau = tuple(getattr(o, 'fss_loss_windows', (3, 9, 17))), float(getattr(o, 'fss_tau', 0.05))
+
+        def side(name):
+            thr = getattr(o, 'fss_loss_thr_' + name, None)
+            if thr is None:
+                raise ValueError("lambda_fss_A / lambda_fss_B: the options hold no thresholds: fss_loss_thr_A and fss_loss_thr_B "
+                                 "must be (C, T) nested lists (train.py resolves them from fss_loss_quantiles / "
+                                 "fss_loss_thresholds)")
+            cache = self.__dict__.setdefault('_fss_thr_dev', {})
+            key = (name, _hashable(thr))
+            if key not in cache:                                   # once; device fills, no host copy: a capture can record them
+                flat = [float(v) for row in thr for v in row]
+                table = torch.empty(len(flat), dtype=torch.float32, device=pred_A.device)
+                for i, v in enumerate(flat):
+                    table[i].fill_(v)
+                cache[key] = table.reshape(len(thr), -1)
+            return lambda fake, real, C, layout: ops.fss_loss(fake, real, C, layout, cache[key], windows, tau)
+        return _Base._optional_terms(self, (side('A'), side('B')), lams, pred_A, A, pred_B, B)
 
     def _nchw(self, x, C):
         return ops.ToNCHW.apply(x, C).detach()
@@ -1463,12 +1501,17 @@ class AugmentedCycleGAN(_Base):
             crps = self._crps_term(A, B, z)
             if crps is not None:
                 loss_G = loss_G + crps[2]
+            fss = self._fss_terms(pred_A, A, pred_B, B)
+            if fss is not None:
+                loss_G = loss_G + fss[2]
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             sums = [loss_sup_A, loss_sup_B, kld_z_B, loss_D_z_B]
             if ssim is not None:
                 sums += [ssim[0], ssim[1]]
             if crps is not None:
                 sums += [crps[0], crps[1]]
+            if fss is not None:
+                sums += [fss[0], fss[1]]
             # the order in which the networks' gradients complete: G_B_A (its only pass hangs on nothing else), G_A_B, then
             # the encoder behind post_z.  With the CRPS term G_A_B's member pass is built last and runs backward first, but
             # G_A_B is complete only after its first pass, which still finishes after G_B_A's and before the encoder's
@@ -1481,7 +1524,7 @@ class AugmentedCycleGAN(_Base):
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
         n_loss = len(sums)
         names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B'] + (['S_ssim_A', 'S_ssim_B'] if ssim is not None else []) + \
-                (['S_crps_B', 'S_pair_B'] if crps is not None else []) + \
+                (['S_crps_B', 'S_pair_B'] if crps is not None else []) + (['S_fss_A', 'S_fss_B'] if fss is not None else []) + \
                 ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
         vals = self._scalars(ex_G, self.f_E_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_E, ss_D_z])
 

@@ -2327,6 +2327,106 @@ def fss_scale_summary(sums, cells, members=1, forecast_events=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# the fractions-skill-score training loss (the paired step under --lambda_fss_A / --lambda_fss_B; tests/fss_loss_ref.py)
+# ----------------------------------------------------------------------------------------------
+FSS_LOSS_MAX_WINDOW = 65
+
+
+def check_fss_loss_windows(windows):
+    """check_windows with the loss's cap -> the widths as a tuple of ints; ValueError unless 1..8 odd widths in 1..65"""
+    w = check_windows(windows)
+    if max(w) > FSS_LOSS_MAX_WINDOW:
+        raise ValueError("windows of the loss must not exceed %d (got %s)" % (FSS_LOSS_MAX_WINDOW, w))
+    return w
+
+
+def fss_loss_inv_tau(tau):
+    """1 / tau as the float the kernels take (formed in double, rounded once); ValueError unless both are positive and finite"""
+    import numpy as np
+    t = float(tau)
+    with np.errstate(over="ignore", under="ignore"):
+        inv = float(np.float32(1.0 / t)) if 0.0 < t < float("inf") else 0.0
+    if not 0.0 < inv < float("inf"):
+        raise ValueError("tau must be positive and finite, and so must 1 / tau in float32 (got %r)" % (tau,))
+    return inv
+
+
+def _fss_loss_size(H, W):
+    if not (1 <= H <= FSS_MAX_HW and 1 <= W <= FSS_MAX_HW):
+        raise _lib.AcgError("fss_loss: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (FSS_MAX_HW, H, W))
+    return int(H), int(W)
+
+
+class FssLoss(torch.autograd.Function):
+    """fss_loss with its data gradient in x: forward acg_fss_loss_fwd (num and den per row, channel, threshold and window, in
+    double) and the pooled combine on the device; backward acg_fss_loss_bwd, which recomputes the soft events from x and y
+    (nothing but the two operands, the thresholds and the small pooled tensors is kept, and those only when x needs a
+    gradient) and takes the coefficients a, b, scaled by the upstream gradient, from the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, C, layout, thresholds, windows, tau):
+        x, y, rows, _, C, Cp, (H, W), sx, sy, _ = _paired_fields("fss_loss", x, y, C, layout, layout, _fss_loss_size, 1, max_per=1,
+                                                                 size_y=True)
+        try:
+            win = check_fss_loss_windows(windows)
+            inv_tau = fss_loss_inv_tau(tau)
+        except ValueError as e:
+            raise _lib.AcgError("fss_loss: %s" % e)
+        thr = channel_table("fss_loss", _lib.AcgError, "thresholds", thresholds, C, FSS_MAX_T, None)
+        T, nw = int(thr.size(1)), len(win)
+        if not torch.is_tensor(thresholds):                        # a host array goes to the device; a tensor is where it has to be
+            thr = thr.to(x.device)
+        out = _out_tensor("fss_loss", None, (rows, C, T, nw, 2), (x, y, thr), dtype=torch.float64)
+        cwin = (ctypes.c_int * nw)(*win)
+        ws, nbytes = _metric_workspace("acg_fss_loss_workspace_bytes", rows, C, H, W, T, nw)
+        _lib.call("acg_fss_loss_fwd", _ptr(x), _ptr(y), rows, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T, cwin, nw,
+                  ctypes.c_float(inv_tau), _ptr(out), ws, nbytes, _stream())
+        tot = out.sum(0)                                           # pooled over the batch before dividing, as fss_summary pools a split
+        num, den = tot[..., 0], tot[..., 1]
+        some = den != 0                                            # a NaN denominator stays: a diverged run shows
+        R = torch.where(some, num / torch.where(some, den, torch.ones_like(den)), torch.zeros_like(den))
+        loss = R.mean().float()
+        ctx.mark_non_differentiable(R)
+        if ctx.needs_input_grad[0]:
+            ctx.cfg = (rows, C, Cp, H, W, sx, sy, T, win, inv_tau)
+            ctx.save_for_backward(x, y, thr, R, den)
+        return loss, R
+
+    @staticmethod
+    def backward(ctx, g, _R):
+        x, y, thr, R, den = ctx.saved_tensors
+        rows, C, Cp, H, W, sx, sy, T, win, inv_tau = ctx.cfg
+        nw = len(win)
+        some = den != 0
+        inv = torch.where(some, 1.0 / torch.where(some, den, torch.ones_like(den)), torch.zeros_like(den))
+        inv = inv * (g.detach().to(torch.float64) / (C * T * nw))
+        coef = torch.stack((2.0 * (1.0 - R) * inv, 2.0 * inv), -1).contiguous()
+        dx = torch.empty_like(x)
+        ws, nbytes = _metric_workspace("acg_fss_loss_workspace_bytes", rows, C, H, W, T, nw)
+        _lib.call("acg_fss_loss_bwd", _ptr(x), _ptr(y), rows, C, Cp, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
+                  (ctypes.c_int * nw)(*win), nw, ctypes.c_float(inv_tau), _ptr(coef), _ptr(dx), ws, nbytes, _stream())
+        return dx, None, None, None, None, None, None
+
+
+def fss_loss(x, y, C, layout, thresholds, windows, tau, parts=False):
+    """1 - the pooled fractions skill score of soft events, averaged over the C valid channels, the T thresholds and the nw
+    windows -> float32 device scalar, differentiable in x (y is detached).  x and y share the layout ("nhwc" or "nchw") and
+    pair row by row.  p = 1 / (1 + exp(-(x - thresholds[c][t]) / tau)) in fp32 (q of y), cf / co their sums over the centred
+    n x n window of each cell inside the domain (fp32; cells outside count 0), Num = sum over rows and cells of (cf - co)^2,
+    Den = of cf^2 + co^2 (double), R = Num / Den = 1 - FSS, 0 where Den == 0 exactly; loss = mean R.  Pooling the batch before
+    dividing, as ops.fss_summary pools a split, keeps a rare threshold usable.  NaN is not masked.  With every value at
+    least 200 tau from every threshold the events are exactly 0 or 1 and Num, Den equal ff + oo - 2 fo, ff + oo of ops.fss.
+    d loss / d x(q) = g / (C T nw) sum_t p_t (1 - p_t) / tau sum_w B_n(a cf - b co)(q), a = 2 (1 - R) / Den, b = 2 / Den (0
+    where Den == 0), B_n the window sum over the domain's cells; NHWC: the padded channels of the gradient are 0.
+    thresholds: (C, T) float32 on the device, or a host array (copied to the device), 1 <= T <= 8; windows: 1..8 odd widths of
+    at most 65; tau > 0; 1 <= H, W <= 1024.  parts=True: (loss, R) with the detached R (C, T, nw) in double.  Sums in a fixed
+    order, the same bits in every layout; no host synchronisation.  Under torch.no_grad(), or for an x that needs no
+    gradient, nothing is saved."""
+    loss, R = FssLoss.apply(x if torch.is_grad_enabled() else x.detach(), y, C, layout, thresholds, windows, tau)
+    return (loss, R) if parts else loss
+
+
+# ----------------------------------------------------------------------------------------------
 # Minkowski functionals of excursion sets (model.translate_minkowski, eval_metrics.py, --metric minkowski)
 # ----------------------------------------------------------------------------------------------
 MINK_MAX_T, MINK_MAX_HW = 255, 1024

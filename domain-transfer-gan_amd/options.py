@@ -2,7 +2,8 @@
 `import cPickle`, options.py:4).  Same flags, defaults, `opt.txt` format, `opt.pkl`, sub-directory creation
 (options.py:7-12, 20-131).  Additions (not in the reference): --n_blocks, --precision, --synthetic, --dist,
 --step_graph, --defer_scalars, --lambda_spec_A, --lambda_spec_B, --ema_decay, --ema_eval,
---lambda_marg_A, --lambda_marg_B, --native_res, --window_flip."""
+--lambda_marg_A, --lambda_marg_B, --native_res, --window_flip, --lambda_fss_A, --lambda_fss_B (with --fss_loss_quantiles,
+--fss_loss_thresholds, --fss_loss_windows, --fss_tau)."""
 import argparse
 import os
 import pickle
@@ -185,6 +186,18 @@ class TrainOptions(object):
                 self.parser.error("--lambda_crps_B: a paired batch of %d x %d members is %d images, more than the %d one pass of "
                                   "G_A_B holds at --grid_size %d with --ngf %d; lower --crps_members or --batchSize"
                                   % (per_rank, min(opt.crps_members, per_rank), images, most, g, opt.ngf))
+        if opt.lambda_fss_A < 0 or opt.lambda_fss_B < 0:
+            self.parser.error("--lambda_fss_A / --lambda_fss_B must not be negative (got %r, %r)" % (opt.lambda_fss_A, opt.lambda_fss_B))
+        if not 0.0 < opt.fss_tau < float("inf"):
+            self.parser.error("--fss_tau must be positive and finite (got %r)" % opt.fss_tau)
+        if opt.lambda_fss_A > 0 or opt.lambda_fss_B > 0:
+            if not opt.supervised:
+                self.parser.error("--lambda_fss_A / --lambda_fss_B are terms of the paired step: they require --supervised")
+            if opt.model != "aug_cycle_gan":
+                self.parser.error("--lambda_fss_A / --lambda_fss_B: --model %s has no paired step (aug_cycle_gan has)" % opt.model)
+            if not 1 <= g <= 1024:
+                self.parser.error("--lambda_fss_A / --lambda_fss_B: the fss loss takes fields of up to 1024 x 1024 "
+                                  "(--grid_size %d)" % g)
         if opt.native_res and opt.synthetic:
             self.parser.error("--native_res cuts windows from stored fields; --synthetic fields are --grid_size already")
         if opt.window_flip and not opt.native_res:
@@ -351,3 +364,31 @@ def _fss_windows(s):
     if len(w) > 8:
         raise argparse.ArgumentTypeError("--fss_windows: at most 8 widths, 1 included (got %r)" % s)
     return tuple(w)
+
+
+def _fss_loss_windows(s):
+    w = tuple(_split("--fss_loss_windows", s, int, "integers"))
+    if not 1 <= len(w) <= 8 or any(v < 1 or v % 2 == 0 or v > 65 for v in w):
+        raise argparse.ArgumentTypeError("--fss_loss_windows: 1 to 8 odd widths of at most 65 cells (got %r)" % s)
+    return w
+
+
+# the fractions-skill-score loss of the paired step; here because its list types are the helpers above
+_T += [
+    ("lambda_fss_A", float, 0.0, "weight of the fractions-skill-score loss of the paired step (needs --supervised) on the paired "
+                                 "prediction of A against the real A: 1 - FSS of soft threshold exceedances (ops.fss_loss: "
+                                 "sigmoid((x - threshold) / --fss_tau), summed over --fss_loss_windows, pooled over the batch), "
+                                 "which rewards putting a rare event nearly in the right place; 0: off (with --lambda_fss_B on, "
+                                 "this side is reported as S_fss_A without a gradient); needs --grid_size up to 1024"),
+    ("lambda_fss_B", float, 0.0, "the same on the paired prediction of B against the real B"),
+    ("fss_loss_quantiles", _floats("--fss_loss_quantiles", _level, "levels inside [0, 1]"), (0.9, 0.99),
+     "under --lambda_fss_A / --lambda_fss_B: the event thresholds as quantile levels of the real training fields, per channel "
+     "(the climatology --metric fss uses); comma-separated, inside [0, 1], at most 8"),
+    ("fss_loss_thresholds", _floats("--fss_loss_thresholds", lambda x: x == x and abs(x) != float("inf"), "finite numbers"), None,
+     "explicit event thresholds of the loss in data units, the same for every channel (comma-separated, at most 8); overrides "
+     "--fss_loss_quantiles"),
+    ("fss_loss_windows", _fss_loss_windows, (3, 9, 17), "comma-separated odd neighbourhood widths of the loss in cells, each at "
+                                                       "most 65, at most 8 of them"),
+    ("fss_tau", float, 0.05, "the temperature of the soft events in data units (fields in [-1, 1]): smaller is closer to the "
+                             "evaluator's hard events and gives a gradient to fewer cells; must be positive"),
+]

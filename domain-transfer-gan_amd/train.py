@@ -181,6 +181,30 @@ class Trainer(object):
             n_sup = int(len(trainA) * o.sup_frac)
             self.sup_it = itertools.cycle(AlignedIterator(trainA[:n_sup], trainB[:n_sup], batch_size=o.batchSize))
             self.log('#supervised images = %d' % n_sup)
+        if getattr(o, "lambda_fss_A", 0.0) > 0 or getattr(o, "lambda_fss_B", 0.0) > 0:
+            self._fss_loss_thresholds(trainA, trainB)
+
+    def _fss_loss_thresholds(self, trainA, trainB):
+        """--lambda_fss_A / --lambda_fss_B: the event thresholds of the loss, once, from the real training fields - the
+        climatology --metric fss uses (eval_metrics.fss_thresholds) - as (C, T) nested lists on the options, so that the
+        model finds them and opt.pkl carries them to whoever reloads the run"""
+        from .eval_metrics import fss_thresholds
+        o = self.opt
+        for name, train in (("A", trainA), ("B", trainB)):
+            thr = fss_thresholds(train, o.fss_loss_quantiles, o.fss_loss_thresholds)
+            setattr(o, "fss_loss_thr_" + name, [[float(v) for v in row] for row in thr])
+            self.log("fss loss thresholds %s (%s): %s" % (name, "explicit" if o.fss_loss_thresholds is not None else
+                                                          "quantiles %s" % (tuple(o.fss_loss_quantiles),),
+                                                          "; ".join("channel %d: %s" % (c, ", ".join("%.6g" % v for v in row))
+                                                                    for c, row in enumerate(thr))))
+        if self.rank == 0:                                         # the options on disk were written before the data was read
+            import pickle
+            path = os.path.join(o.expr_dir, "opt.pkl")
+            with open(path, "rb") as f:
+                saved = pickle.load(f)
+            saved.update(fss_loss_thr_A=o.fss_loss_thr_A, fss_loss_thr_B=o.fss_loss_thr_B)
+            with open(path, "wb") as f:
+                pickle.dump(saved, f)
 
     def _model(self):
         o = self.opt

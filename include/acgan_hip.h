@@ -756,6 +756,54 @@ int acg_crps_bwd(const float *x, const float *y, const float *g, int rows, int x
                  long long x_row_stride, int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
                  long long y_chan_stride, double coef_y, double coef_pair, float *dx, void *stream);
 
+/* ---- the fractions-skill-score training loss (ops.fss_loss, train.py --lambda_fss_A / --lambda_fss_B; no reference call site,
+ *      tests/fss_loss_ref.py states the definition; Roberts & Lean 2008, Ebert-Uphoff et al. 2021) ----
+ * x: rows forecasts of C channels of H x W fp32 pixels, y: the paired truths, row for row.  Each operand has its own three
+ * strides (in floats), meaning what they mean in acg_fss.  thr: (C, T) fp32 on the device; windows: nw odd widths in host
+ * memory, read during the call.  1 <= H, W <= 1024 (need not be equal), 1 <= T <= 8, 1 <= nw <= 8, odd 1 <= n <= 65, any C >= 1.
+ *   soft events  p = 1 / (1 + exp(-(x - thr[c][t]) inv_tau)), q the same of y: fp32 in exactly this form, so they saturate to
+ *                exactly 0 and 1 (exp overflows to inf, underflows to 0).  NaN is not masked: it reaches the sums.
+ *   window sums  cf(i, j) = sum of p over the cells |i' - i| <= n/2, |j' - j| <= n/2 inside the domain (cells outside count 0,
+ *                / n^2 is never formed), co of q: fp32, n terms along the row, then n row sums down the column, each in
+ *                ascending order.  Window sums of 0/1 planes are exact integers.
+ *   per (row, c, t, window)  num = sum over cells (cf - co)^2, den = sum over cells (cf^2 + co^2), differences, squares and sums
+ *                in double.  With saturated events they equal ff + oo - 2 fo and ff + oo of acg_fss's triples exactly.
+ * acg_fss_loss_fwd writes out (rows, C, T, nw, 2) in DOUBLE, (num, den); the pooled ratio R = sum_rows num / sum_rows den
+ * (0 where the denominator is 0) and loss = mean of R over C, T, nw are the caller's to form.  A workgroup of 256 threads owns
+ * a tile of 32 x 32 cells of one (row, c, t) and walks the windows: the (32 + 2 (n/2))^2 events around the tile go to LDS (dynamic,
+ * sized by the call's largest window: 21 KiB at n = 17, 60 KiB at n = 65), are summed along rows and then down columns; thread k adds its cells k, k + 256, k + 512, k + 768 of the tile in
+ * that order, the threads by a fixed tree, one partial pair per tile into the workspace, one wave per (row, c, t, window) folds
+ * the tiles in a fixed order.  Every layout is read value by value through its strides: the same bits on every call and in
+ * every layout.  Two launches, no atomics, out fully written whatever it and the workspace held, nothing read back,
+ * capturable in a HIP graph.  acg_last_kernel(): "fss_loss_fwd + fss_loss_fold".  acg_fss_loss_workspace_bytes serves both
+ * passes: the larger of 16 rows C T nw ceil(H/32) ceil(W/32) and 4 rows C T nw H W bytes, 16-byte aligned; 0 for a refused size.
+ * Refused before a launch (-1, acg_last_error starts with "acg_fss_loss_fwd"), in this order: a null x, y, thr, windows or
+ * out; an extent outside 1 .. 1024; rows < 1 or C < 1; T or nw outside 1 .. 8; a window that is even, not positive or above
+ * 65; a stride < 1; inv_tau not finite or not positive; too many fields for a grid; out aliasing an input; a short
+ * workspace: -2; a misaligned workspace. */
+size_t acg_fss_loss_workspace_bytes(int rows, int C, int H, int W, int T, int nw);
+int acg_fss_loss_fwd(const float *x, const float *y, int rows, int C, int H, int W, long long x_row_stride, int x_pix_stride,
+                     long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr,
+                     int T, const int *windows, int nw, float inv_tau, double *out, void *workspace, size_t ws_bytes, void *stream);
+/* The data gradient of that loss in x.  coef: (C, T, nw, 2) DOUBLE on the device, the caller's a = 2 (1 - R) / Den and
+ * b = 2 / Den, already multiplied by the upstream gradient and by 1 / (C T nw) and 0 where Den == 0: no host synchronisation.
+ * B_n, the window sum, is symmetric:
+ *   dx(q) = sum_t p_t (1 - p_t) inv_tau sum_w B_n( a cf - b co )(q),
+ * the inner plane living on the domain's cells only (cells outside contribute 0 to the second sum; not a padded convolution
+ * of a padded convolution).  p and q are recomputed, no maps are kept between the passes.  a cf - b co = B_n u with the one
+ * plane u = (float)(a p - b q), combined in double and rounded once: "fss_loss_g" window-sums u with the forward's code and
+ * writes one fp32 plane per (row, c, t, window) into the workspace, "fss_loss_dx" (a workgroup per 32 x 32 tile of (row, c))
+ * window-sums those planes, adds the windows and then the thresholds in ascending order in fp32; p (1 - p) is exactly 0 where
+ * p is saturated.  A gather: no atomics, deterministic, the same bits in every layout.  dx is written in x's layout; Cp: the
+ * channels stored per pixel of dx, channels C .. Cp - 1 are written as 0 (NHWC: Cp = pix_stride; planar: the stored planes).
+ * y gets no gradient.  Two launches, nothing read back, capturable.  acg_last_kernel(): "fss_loss_g + fss_loss_dx".  Refused
+ * before a launch (-1) as the forward and in its order, with a null coef or dx among the null pointers, then C > Cp, dx
+ * aliasing an input, a short workspace (-2), a misaligned workspace. */
+int acg_fss_loss_bwd(const float *x, const float *y, int rows, int C, int Cp, int H, int W, long long x_row_stride, int x_pix_stride,
+                     long long x_chan_stride, long long y_row_stride, int y_pix_stride, long long y_chan_stride, const float *thr,
+                     int T, const int *windows, int nw, float inv_tau, const double *coef, float *dx, void *workspace,
+                     size_t ws_bytes, void *stream);
+
 /* ---- optimiser: torch.nn.utils.clip_grad_norm + torch.optim.Adam.step (model.py:447-452, 510-515)
  *      on one flat fp32 buffer per network. ---- */
 int acg_sumsq(const float *g, size_t n, float *out, void *workspace, size_t ws_bytes, void *stream);
