@@ -192,6 +192,9 @@ SIGNATURES = {
     "acg_components_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "acg_components": (c_int, [_P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, c_int, _P, _P, _P,
                                c_size_t, _P]),
+    "acg_sal_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "acg_sal": (c_int, [_P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, c_int, ctypes.c_float,
+                        _P, _P, _P, _P, c_size_t, _P]),
     "acg_field_sort_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "acg_field_sort": (c_int, [_P, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, _P, _P, _P, c_size_t, _P]),
     "acg_marginal_loss_workspace_bytes": (c_size_t, [c_int, ctypes.c_longlong]),

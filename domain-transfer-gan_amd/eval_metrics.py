@@ -349,6 +349,60 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
     return res
 
 
+SAL_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
+SAL_SCORES = ('S', 'A', 'L1', 'L2', 'L')
+
+
+def _nan_reduce(fn, v):
+    """fn (np.nanmedian, np.nanmean) over the leading axis of v; NaN, silently, where nothing is defined"""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        return fn(v, axis=0)
+
+
+def eval_sal(dataset, model, n_samples, thresholds_B, thresholds_A, floor=-1.0, conn=8, use_gpu=True):
+    """the SAL scores (Wernli et al. 2008) on an aligned split, one read of the integers and one of the doubles per batch.
+    A -> B: n_samples members per input and their ensemble mean against the paired real B (model.translate_sal); B -> A:
+    predict_A against the paired real A (ops.sal on both).  Every pair is scored on its own (ops.sal_scores, float64 on the
+    host).  -> dict, per comparison k of SAL_PAIRS: the per-input arrays S_k, L2_k, L_k (N, [M,] C, T) and A_k, L1_k
+    (N, [M,] C) (M: members_B only); over the pairs of the split (and the members), NaN-aware: median_S_k, median_L_k,
+    mean_abs_S_k, mean_L_k (C, T) and median_A_k, mean_abs_A_k (C,); defined_k (C, T): the fraction of pairs whose S and L
+    are not NaN"""
+    parts = {k: {s: [] for s in SAL_SCORES} for k in SAL_PAIRS}
+    thresholds = _domain_tables(thresholds_B, thresholds_A, check=ops.check_thresholds)
+    kw = dict(floor=floor, conn=conn)
+    names = ('field', 'obj', 'shape')
+    for real_A, real_B in _batches(dataset, use_gpu):
+        thr_B, thr_A = thresholds(real_B, real_A)
+        r = model.translate_sal(real_A, n_samples, real_B, thr_B, **kw)
+        CA = real_A.size(1)
+        with torch.no_grad():
+            fake_A = ops.sal(model.predict_A(real_B), CA, "nchw", thr_A, **kw)
+        true_A = ops.sal(real_A, CA, "nchw", thr_A, **kw)
+        sets = [tuple(r['%s_%s' % (who, n)] for n in names) for who in ('members', 'ens_mean', 'target')] + [fake_A, true_A]
+        ints = _read_back([t for s in sets for t in s[:2]])
+        dbls = _read_back([s[2] for s in sets])
+        mem, mean, tgt, fa, ta = [(ints[2 * i], ints[2 * i + 1], dbls[i]) for i in range(len(sets))]
+        H, W = real_B.shape[-2:]
+        pairs = (ops.sal_scores(mem, tuple(a[:, None] for a in tgt), H, W), ops.sal_scores(mean, tgt, H, W),
+                 ops.sal_scores(fa, ta, *real_A.shape[-2:]))
+        for k, sc in zip(SAL_PAIRS, pairs):
+            for s in SAL_SCORES:
+                parts[k][s].append(sc[s])
+    res = {}
+    for k in SAL_PAIRS:
+        p = {s: np.concatenate(v) for s, v in parts[k].items()}
+        res.update(('%s_%s' % (s, k), v) for s, v in p.items())
+        flat = {s: v.reshape((-1,) + v.shape[(2 if k == 'members_B' else 1):]) for s, v in p.items()}
+        for s in ('S', 'A', 'L'):
+            res['median_%s_%s' % (s, k)] = _nan_reduce(np.nanmedian, flat[s])
+        res['mean_abs_S_' + k], res['mean_abs_A_' + k] = (_nan_reduce(np.nanmean, np.abs(flat[s])) for s in ('S', 'A'))
+        res['mean_L_' + k] = _nan_reduce(np.nanmean, flat['L'])
+        res['defined_' + k] = (~np.isnan(flat['S']) & ~np.isnan(flat['L'])).mean(0)
+    return res
+
+
 MINKOWSKI_SETS = ('members_B', 'ens_mean_B', 'fake_A', 'real_B', 'real_A')
 MINKOWSKI_PAIRS = (('members_B', 'real_B'), ('ens_mean_B', 'real_B'), ('fake_A', 'real_A'))
 
@@ -525,34 +579,66 @@ _COHERENCE = Metric('coherence', False, 200, None, _plain_prepare(eval_coherence
               <res_dir>/coherence.npz.  Sizes as for spectrum.  No plot""")
 
 
-def _fss_prepare(opt, model, arrays):
-    thr_B = fss_thresholds(arrays[1], opt.fss_quantiles, opt.fss_thresholds)     # once: dev and test share the climatology
-    thr_A = fss_thresholds(arrays[0], opt.fss_quantiles, opt.fss_thresholds)
-    win = tuple(opt.fss_windows)
-    header = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
-    scales = bool(getattr(opt, 'fss_scales', 0))
-    if scales:                                                     # 2^j, j = 0 .. L, of the fields the splits hold
-        header['scales'] = 2 ** np.arange(ops.fss_scale_levels(*np.shape(arrays[3])[-2:]), dtype=np.int64)
-    return header, lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win, scales=scales)
+def _fss_record():
+    sal = []          # prepare -> report, with --fss_sal: the header of sal.npz, then what eval_sal gave on dev and on test
 
+    def _fss_prepare(opt, model, arrays):
+        thr_B = fss_thresholds(arrays[1], opt.fss_quantiles, opt.fss_thresholds)     # once: dev and test share the climatology
+        thr_A = fss_thresholds(arrays[0], opt.fss_quantiles, opt.fss_thresholds)
+        win = tuple(opt.fss_windows)
+        header = dict(n_samples=np.int64(opt.n_samples), windows=np.array(win, dtype=np.int64), thresholds_B=thr_B, thresholds_A=thr_A)
+        scales = bool(getattr(opt, 'fss_scales', 0))
+        if scales:                                                     # 2^j, j = 0 .. L, of the fields the splits hold
+            header['scales'] = 2 ** np.arange(ops.fss_scale_levels(*np.shape(arrays[3])[-2:]), dtype=np.int64)
+        evaluate = lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win, scales=scales)
+        if not int(getattr(opt, 'fss_sal', 0)):
+            return header, evaluate
+        del sal[:]
+        explicit = getattr(opt, 'sal_thresholds', None)               # ascending, whoever built the options
+        quantiles, explicit = sorted(opt.sal_quantiles), None if explicit is None else sorted(explicit)
+        sal_B = fss_thresholds(arrays[1], quantiles, explicit)
+        sal_A = fss_thresholds(arrays[0], quantiles, explicit)
+        floor, conn = float(opt.sal_floor), int(opt.sal_conn)
+        sal.append(dict(n_samples=np.int64(opt.n_samples), thresholds_B=sal_B, thresholds_A=sal_A, floor=np.float64(floor),
+                        conn=np.int64(conn)))
 
-def _fss_report(opt, dev, test):
-    levels = opt.fss_thresholds if opt.fss_thresholds is not None else opt.fss_quantiles
-    t, w = int(np.argmax(levels)), len(opt.fss_windows) // 2     # the highest threshold, the median listed window
-    line = ("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "
-            "TEST_USEFUL_SCALE_B: %.4f"
-            % (_chan_mean(dev['fss_members_B'][:, t, w]), _chan_mean(test['fss_members_B'][:, t, w]),
-               _chan_mean(test['fss_ens_prob_B'][:, t, w]), _chan_mean(test['fss_ens_mean_B'][:, t, w]),
-               _chan_mean(test['fss_fake_A'][:, t, w]), float(test['useful_scale_members_B'][:, t].mean())))
-    if int(getattr(opt, 'fss_scales', 0)):
-        line += ("\nDEV_ISS_B: %.4f, TEST_ISS_B: %.4f, TEST_SKILL_SCALE_B: %.4f, TEST_SKILL_SCALE_PROB_B: %.4f, "
-                 "TEST_SKILL_SCALE_MEAN_B: %.4f, TEST_SKILL_SCALE_A: %.4f"
-                 % ((_chan_mean(dev['iss_members_B'][:, t, 0]), _chan_mean(test['iss_members_B'][:, t, 0]))
-                    + tuple(float(test['skill_scale_' + k][:, t].mean()) for k in FSS_PAIRS)))
-    return line
+        def with_sal(dataset):
+            res = evaluate(dataset)
+            dev = [torch.cuda.current_device()] if torch.cuda.is_available() else []
+            with torch.random.fork_rng(devices=dev):                   # its own members; the codes of the fss entries stay what they were
+                sal.append(eval_sal(dataset, model, opt.n_samples, sal_B, sal_A, floor=floor, conn=conn))
+            return res
+        return header, with_sal
 
+    def _fss_report(opt, dev, test):
+        levels = opt.fss_thresholds if opt.fss_thresholds is not None else opt.fss_quantiles
+        t, w = int(np.argmax(levels)), len(opt.fss_windows) // 2     # the highest threshold, the median listed window
+        line = ("DEV_FSS_B: %.4f, TEST_FSS_B: %.4f, TEST_FSS_PROB_B: %.4f, TEST_FSS_MEAN_B: %.4f, TEST_FSS_A: %.4f, "
+                "TEST_USEFUL_SCALE_B: %.4f"
+                % (_chan_mean(dev['fss_members_B'][:, t, w]), _chan_mean(test['fss_members_B'][:, t, w]),
+                   _chan_mean(test['fss_ens_prob_B'][:, t, w]), _chan_mean(test['fss_ens_mean_B'][:, t, w]),
+                   _chan_mean(test['fss_fake_A'][:, t, w]), float(test['useful_scale_members_B'][:, t].mean())))
+        if int(getattr(opt, 'fss_scales', 0)):
+            line += ("\nDEV_ISS_B: %.4f, TEST_ISS_B: %.4f, TEST_SKILL_SCALE_B: %.4f, TEST_SKILL_SCALE_PROB_B: %.4f, "
+                     "TEST_SKILL_SCALE_MEAN_B: %.4f, TEST_SKILL_SCALE_A: %.4f"
+                     % ((_chan_mean(dev['iss_members_B'][:, t, 0]), _chan_mean(test['iss_members_B'][:, t, 0]))
+                        + tuple(float(test['skill_scale_' + k][:, t].mean()) for k in FSS_PAIRS)))
+        if int(getattr(opt, 'fss_sal', 0)):
+            header, sal_dev, sal_test = sal
+            arrays = dict(header)
+            for split, res in (('dev', sal_dev), ('test', sal_test)):
+                arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
+            np.savez(os.path.join(opt.res_dir, 'sal.npz'), **arrays)
 
-_FSS = Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
+            def medians(res, k):                                       # the highest threshold: the last, they are sorted
+                return tuple(_chan_mean(v) for v in (res['median_S_' + k][:, -1], res['median_A_' + k], res['median_L_' + k][:, -1]))
+            line += ("\nDEV_SAL_B: %.4f %.4f %.4f, TEST_SAL_B: %.4f %.4f %.4f, TEST_SAL_MEAN_B: %.4f %.4f %.4f, "
+                     "TEST_SAL_A: %.4f %.4f %.4f (S, A, L)"
+                     % (medians(sal_dev, 'members_B') + medians(sal_test, 'members_B') + medians(sal_test, 'ens_mean_B')
+                        + medians(sal_test, 'fake_A')))
+        return line
+
+    return Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
   fss         (new) whether threshold exceedances are put close enough: the fractions skill score (Roberts & Lean 2008) per
               channel, threshold and neighbourhood width.  Events are [x >= t]; per odd window n the events around every cell
               are counted (cells outside the domain count 0) for prediction (cf) and truth (co), and the integer triples
@@ -580,7 +666,28 @@ _FSS = Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
               the forecast's and the truth's component energies; skill_scale_k (C, T) int64: the smallest 2^j with iss > 0
               at every mother scale from j up (2^L: none); the header gains scales = 2^j.  One more line is printed: ISS of
               members_B at the highest threshold and the finest scale on dev and test, and the test skill scales of
-              members_B, ens_prob_B, ens_mean_B and fake_A, channel means""")
+              members_B, ens_prob_B, ens_mean_B and fake_A, channel means.
+              --fss_sal 1 (default 0: off, fss.npz and the output as without it) adds the object-based partner of the FSS,
+              the SAL score (Wernli et al. 2008): what a forecaster asks first of a paired translation, object by object.
+              The objects of a field are the connected components (--sal_conn 4 | 8, default 8) of its excursion set
+              {x >= t}; thresholds: per channel the --sal_quantiles (default 0.9) of the real training fields (trainB for
+              A -> B, trainA for B -> A; fss_thresholds), or the --sal_thresholds in data units, sorted ascending.  The mass of
+              a cell is its amount above --sal_floor (default -1, the lower end of the data range) as the fixed-point integer
+              q = clamp(rint((x - floor) 2^20), 0, 2^24), so every sum is exact; ops.sal (HIP: the union-find forest of
+              ops.components with the mass, the peak and the centre of mass reduced per object) gives per field Q, QY, QX and
+              per threshold n, area, Robj, Rmax and the double sums SV = sum R (R / P), SR = sum R |c_object - c_field|.  Per
+              PAIR (ops.sal_scores, float64 on the host): A = (Q_f - Q_o) / (0.5 (Q_f + Q_o)), the amplitude: too much or too
+              little overall; S = (V_f - V_o) / (0.5 (V_f + V_o)), V = SV / Robj, the structure: > 0 for objects too large
+              or too flat, < 0 for too small or too peaked; L = L1 + L2, the location: the distance of the centres of mass
+              and the difference of the objects' spread about them, over the diagonal.  S, A in [-2, 2], L in [0, 2]; S and
+              L are NaN where either side has no mass above the threshold.  Compared on the same aligned pairs, with members
+              of its own (model.translate_sal; a forked generator, so the codes of the fss entries stay what they were):
+              members_B and ens_mean_B against the paired B, fake_A against the paired A.  Per comparison k: S_k, L2_k, L_k
+              (N, [M,] C, T), A_k, L1_k (N, [M,] C) per input; median_S_k, median_A_k, median_L_k (NaN-aware), mean_abs_S_k,
+              mean_abs_A_k, mean_L_k and defined_k, the fraction of pairs whose S and L exist, with n_samples, thresholds_B,
+              thresholds_A, floor, conn -> <res_dir>/sal.npz, a file of its own.  The mean of an ensemble is smoother than
+              its members: a positive S.  One more line is printed: the medians of S, A and L at the highest threshold, the
+              channel means, for the members on dev and test, the ensemble mean and B -> A.  1 <= H, W <= 1024""")
 
 
 def _translate_record():
@@ -746,5 +853,5 @@ _MINKOWSKI = Metric('minkowski', False, 200, None, _minkowski_prepare, _minkowsk
               more printed line per split: the three distances, the channel means""")
 
 
-METRICS = (_ensemble_record(), _SPECTRUM, _COHERENCE, _FSS, _translate_record(), _FIELD_SPECTRUM, _SSIM, _MARGINAL, _MINKOWSKI)
+METRICS = (_ensemble_record(), _SPECTRUM, _COHERENCE, _fss_record(), _translate_record(), _FIELD_SPECTRUM, _SSIM, _MARGINAL, _MINKOWSKI)
 WHOLE_FIELD_METRICS = tuple(m.name for m in METRICS if m.whole_field)

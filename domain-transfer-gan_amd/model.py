@@ -816,6 +816,34 @@ class _Base(object):
                     ops.components(mean, C, "nchw", thr, conn=components, out=g.rows(out["ens_mean_comp"]))
         return out
 
+    def translate_sal(self, real_A, n_samples, real_B, thresholds, floor=-1.0, conn=8, z=None, chunk=None):
+        """Whether the objects of A -> B are too large and flat or too small and peaked, carry too much of the quantity, or lie
+        in the wrong place: the weighted moments behind the SAL score (ops.sal: per channel the mass sums Q, QY, QX of the
+        field and, per threshold, n, area, Robj, Rmax and the double sums SV, SR of the objects of the excursion set) of each
+        of n_samples translations of every input, of their per-pixel mean (_ensemble_mean: smoother than any member, so its
+        structure score is positive) and of the paired real_B.  thresholds: (C, T), 1 <= T <= 255, per channel finite and
+        non-decreasing; a host array is checked (ops.channel_table) and moved to the device once.  floor: finite, the lower end
+        of the data range; conn: 4 or 8.  z, chunk and the refusals: plan_ensemble, real_B required; the members:
+        ensemble_groups.  1 <= H, W <= 1024.  Returns device tensors, * = field (.., C, 3) int64, obj (.., C, T, 4) int64 and
+        shape (.., C, T, 2) float64: members_* (N, M, ..), ens_mean_* (N, ..) and target_* (N, ..), for ops.sal_scores
+        (members (N, M, ..) against target[:, None]).  Nothing is read back to the host."""
+        M, N, C, H, W, z, per = plan_ensemble("translate_sal", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
+        thr = ops.channel_table("translate_sal", ValueError, "thresholds", thresholds, C, ops.MINK_MAX_T, real_A.device,
+                                ordered=True, cast=True)
+        T = thr.size(1)
+        parts = (("field", (C, 3), torch.int64), ("obj", (C, T, 4), torch.int64), ("shape", (C, T, 2), torch.float64))
+        out = {}
+        for who, lead in (("members", (N, M)), ("ens_mean", (N,)), ("target", (N,))):
+            for name, shape, dtype in parts:
+                out["%s_%s" % (who, name)] = torch.empty(lead + shape, device=real_A.device, dtype=dtype)
+        triple = lambda who, view: tuple(view(out["%s_%s" % (who, name)]) for name, _, _ in parts)
+        with eval_state(self.netG_A_B), torch.no_grad():
+            for members, g in self._groups(real_A, z, M, per, real_B):
+                ops.sal(members, C, "nhwc", thr, floor=floor, conn=conn, out=triple("members", g.flat))
+                ops.sal(_ensemble_mean(members, M, C), C, "nchw", thr, floor=floor, conn=conn, out=triple("ens_mean", g.rows))
+                ops.sal(g.b, C, "nchw", thr, floor=floor, conn=conn, out=triple("target", g.rows))
+        return out
+
     def _field_groups(self, who, G, x, copies, C, overlap, chunk, code=None):
         """What translate_field and translate_field_A share -> (copies*N, C, H, W): every (N, Cin, H, W) field of x, `copies`
         times in a row, through G in windows of grid_size (ops.window_plan) blended on canvases (ops.window_blend).  Groups

@@ -2591,6 +2591,95 @@ def components_distance(a, b):
     return res
 
 
+# ----------------------------------------------------------------------------------------------
+# SAL: structure, amplitude and location of the objects (model.translate_sal, eval_metrics.py, --metric fss --fss_sal 1)
+# ----------------------------------------------------------------------------------------------
+def sal(x, C, layout, thresholds, floor=-1.0, conn=8, out=None):
+    """acg_sal: the weighted moments behind the SAL score (Wernli et al. 2008) of the C valid channels of x -> (field, obj,
+    shape) on the device.  The mass of a cell is the integer q = clamp(rint((x - floor) 2^20), 0, 2^24) in fp32 (NaN: 0), the
+    objects of a plane are the components of {x >= thresholds[c][t]} under conn = 4 or 8 connectivity, as ops.components
+    labels them.  field (rows, C, 3) int64: Q, QY, QX, the sums of q, q h, q w over all cells; obj (rows, C, T, 4) int64: n,
+    area, Robj (the mass in the set), Rmax (the largest mass of an object); shape (rows, C, T, 2) float64: SV, the sum over the
+    objects of R (R / P) with R the mass and P the peak of an object, and SR, the sum of R times the distance of the object's
+    centre of mass from the field's.  Exact integers, and doubles summed in a fixed order: the same bits in every layout and
+    on every call.  ops.sal_scores turns two triples into scores.  x, C, layout, thresholds: as ops.components takes them
+    (1 <= H, W <= 1024; a host table is checked and copied to the device, a float32 device tensor is taken as it is).  floor:
+    finite, the lower end of the data range.  `out`: a triple of contiguous tensors to write.  Launches only, in passes over
+    the planes when the workspace (256 MiB at most) does not hold them all; nothing is read back.  Not differentiable."""
+    import math
+    import numbers
+    x = x.detach().contiguous()
+    rows, C, _, H, W, sx = _field_args(x, C, layout, "sal")
+    if not (1 <= H <= MINK_MAX_HW and 1 <= W <= MINK_MAX_HW):
+        raise _lib.AcgError("sal: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (MINK_MAX_HW, H, W))
+    if conn not in (4, 8):
+        raise _lib.AcgError("sal: connectivity must be 4 or 8 (got %r)" % (conn,))
+    if isinstance(floor, bool) or not isinstance(floor, numbers.Real) or not math.isfinite(floor):
+        raise _lib.AcgError("sal: the floor must be a finite number (got %r)" % (floor,))
+    thr = channel_table("sal", _lib.AcgError, "thresholds", thresholds, C, MINK_MAX_T, None, ordered=True)
+    T = int(thr.size(1))
+    shapes = ((rows, C, 3), torch.int64, "field"), ((rows, C, T, 4), torch.int64, "obj"), ((rows, C, T, 2), torch.float64, "shape")
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+        raise _lib.AcgError("sal: out must be the triple (field, obj, shape)")
+    outs = list(out) if out is not None else [None] * 3
+    for o, (shape, dtype, name) in zip(outs, shapes):
+        if o is not None and not torch.is_tensor(o):
+            raise _lib.AcgError("sal: out must be the triple (field, obj, shape) of tensors")
+        _refuse_out("sal", o, shape, dtype, name=name)
+    if not torch.is_tensor(thresholds):                            # a host array goes to the device; a tensor is where it has to be
+        thr = thr.to(x.device)
+    _check(x, thr)
+    outs = [_out_or_new(o, shape, dtype, x.device) for o, (shape, dtype, _) in zip(outs, shapes)]
+    ws, nbytes = _metric_workspace("acg_sal_workspace_bytes", rows, C, H, W, T)
+    _lib.call("acg_sal", _ptr(x), rows, C, H, W, sx[0], sx[1], sx[2], _ptr(thr), T, int(conn), ctypes.c_float(floor), _ptr(outs[0]),
+              _ptr(outs[1]), _ptr(outs[2]), ws, nbytes, _stream())
+    return tuple(outs)
+
+
+def sal_scores(f, o, H, W):
+    """two triples (field, obj, shape) of ops.sal on the host, the forecast's and the observation's, of H x W fields and the
+    same thresholds, that broadcast against each other (members (N, M, ...) against truth (N, 1, ...)) -> dict of float64
+    arrays, with d = sqrt((H - 1)^2 + (W - 1)^2):
+      A  (..., C)     (Q_f - Q_o) / (0.5 (Q_f + Q_o)), the amplitude; NaN when Q_f + Q_o = 0;
+      L1 (..., C)     |c_f - c_o| / d with c = (QY / Q, QX / Q), the centres of mass; NaN when either Q is 0; 0 when d = 0;
+      S  (..., C, T)  (V_f - V_o) / (0.5 (V_f + V_o)) with V = SV / Robj, the structure: > 0 for objects too large or too flat;
+      L2 (..., C, T)  2 |r_f - r_o| / d with r = SR / Robj, the spread of the objects about the centre; 0 when d = 0;
+      L  (..., C, T)  L1 + L2, the location.
+    S, L2 and L are NaN when either side has Robj = 0.  S and A lie in [-2, 2], L in [0, 2]."""
+    import numpy as np
+
+    def triple(t, who):
+        if not isinstance(t, (tuple, list)) or len(t) != 3:
+            raise ValueError("sal_scores: %s must be the triple (field, obj, shape)" % who)
+        fld, obj, shp = (np.asarray(a) for a in t)
+        if (fld.ndim < 2 or fld.shape[-1] != 3 or obj.ndim != fld.ndim + 1 or obj.shape[-1] != 4 or obj.shape[:-2] != fld.shape[:-1]
+                or shp.shape != obj.shape[:-1] + (2,)):
+            raise ValueError("sal_scores: %s must be field (..., C, 3), obj (..., C, T, 4), shape (..., C, T, 2) (got %s, %s, %s)"
+                             % (who, fld.shape, obj.shape, shp.shape))
+        return fld.astype(np.float64), obj[..., 2].astype(np.float64), shp.astype(np.float64)
+
+    if int(H) < 1 or int(W) < 1:
+        raise ValueError("sal_scores: fields must be H x W with H, W >= 1 (got %s x %s)" % (H, W))
+    (ff, rf, sf), (fo, ro, so) = triple(f, "f"), triple(o, "o")
+    try:
+        np.broadcast_shapes(ff.shape, fo.shape), np.broadcast_shapes(sf.shape, so.shape)
+    except ValueError:
+        raise ValueError("sal_scores: %s and %s fields with %s and %s planes do not broadcast" % (ff.shape, fo.shape, sf.shape, so.shape))
+    d = float(np.sqrt(float((int(H) - 1) ** 2 + (int(W) - 1) ** 2)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        qf, qo = ff[..., 0], fo[..., 0]
+        A = (qf - qo) / (0.5 * (qf + qo))
+        cf, co = ff[..., 1:] / qf[..., None], fo[..., 1:] / qo[..., None]
+        dist = np.sqrt(((cf - co) ** 2).sum(-1))
+        L1 = np.where(np.isnan(dist), np.nan, dist / d if d > 0 else 0.0)
+        both = (rf > 0) & (ro > 0)
+        vf, vo = sf[..., 0] / rf, so[..., 0] / ro
+        S = np.where(both, (vf - vo) / (0.5 * (vf + vo)), np.nan)
+        spread = np.abs(sf[..., 1] / rf - so[..., 1] / ro)
+        L2 = np.where(both, 2.0 * spread / d if d > 0 else 0.0, np.nan)
+    return dict(S=S, A=A, L1=L1, L2=L2, L=L1[..., None] + L2)
+
+
 def mean_valid(x, C, out=None):
     """mean over the C valid channels of a C16 tensor -> device scalar (no grad)."""
     x = x.detach().contiguous()

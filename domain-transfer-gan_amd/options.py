@@ -240,7 +240,9 @@ class TestOptions(object):
     (structural similarity of the paired translations, reuses --n_samples); the metric `marginal` (Wasserstein distances,
     quantiles and distribution functions of the fields' values, reuses --n_samples) with --marg_levels and --marg_bins; the
     metric `minkowski` (area, perimeter and Euler characteristic of the excursion sets, unpaired, reuses --n_samples) with
-    --mink_bins, and --mink_components (the connected components of the same sets: objects, holes, object sizes)."""
+    --mink_bins, and --mink_components (the connected components of the same sets: objects, holes, object sizes); --fss_sal (with
+    the metric `fss`: the SAL score, structure, amplitude and location of the objects of the same paired translations, into a
+    file of its own) with --sal_quantiles, --sal_thresholds, --sal_floor and --sal_conn."""
 
     def __init__(self):
         from .eval_metrics import METRICS      # here, not at the top: it imports train.py, which imports this module
@@ -281,6 +283,21 @@ class TestOptions(object):
         self.parser.add_argument('--mink_components', type=int, choices=[0, 4, 8], default=0,
                                  help='--metric minkowski: 4 or 8 also labels the connected components of the excursion sets '
                                       'under that connectivity (counts, holes, sizes); 0: off')
+        self.parser.add_argument('--fss_sal', type=int, choices=[0, 1], default=0,
+                                 help='--metric fss: 1 also scores structure, amplitude and location of the objects of the '
+                                      'paired translations (SAL) -> sal.npz; 0: off')
+        self.parser.add_argument('--sal_quantiles', type=_sal_quantiles, default=(0.9,),
+                                 help='--metric fss --fss_sal 1: the object thresholds as quantile levels of the real training fields, per '
+                                      'channel (trainB for A -> B, trainA for B -> A); comma-separated, inside [0, 1], at most 8; '
+                                      'sorted ascending before use')
+        self.parser.add_argument('--sal_thresholds', type=_sal_thresholds, default=None,
+                                 help='--metric fss --fss_sal 1: explicit object thresholds in data units, the same for every channel '
+                                      '(comma-separated, finite, at most 8; sorted ascending); overrides --sal_quantiles')
+        self.parser.add_argument('--sal_floor', type=_sal_floor, default=-1.0,
+                                 help='--metric fss --fss_sal 1: the lower end of the data range; the mass of a cell is its amount above it '
+                                      '(finite, default -1)')
+        self.parser.add_argument('--sal_conn', type=int, choices=[4, 8], default=8,
+                                 help='--metric fss --fss_sal 1: the connectivity of the objects, 4 (shared edges) or 8 (edges or corners)')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
@@ -339,6 +356,22 @@ _quantiles = _floats("--quantiles", _level, "levels, sorted inside [0, 1]", orde
 _fss_quantiles = _floats("--fss_quantiles", _level, "levels inside [0, 1]")
 _fss_thresholds = _floats("--fss_thresholds", lambda x: x == x, "numbers")
 _marg_levels = _floats("--marg_levels", _level, "levels inside [0, 1]", most=16)
+_finite = lambda x: x - x == 0.0
+
+
+def _sorted(parse):
+    return lambda s: tuple(sorted(parse(s)))
+
+
+_sal_quantiles = _sorted(_floats("--sal_quantiles", _level, "levels inside [0, 1]"))
+_sal_thresholds = _sorted(_floats("--sal_thresholds", _finite, "finite numbers"))
+
+
+def _sal_floor(s):
+    v = float(s)
+    if not _finite(v):
+        raise argparse.ArgumentTypeError("--sal_floor must be finite (got %r)" % s)
+    return v
 
 
 def _marg_bins(s):

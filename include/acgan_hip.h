@@ -622,6 +622,40 @@ size_t acg_components_workspace_bytes(int rows, int C, int H, int W, int T);
 int acg_components(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
                    const float *thr, int T, int conn, long long *out, int *labels, void *workspace, size_t ws_bytes, void *stream);
 
+/* ---- SAL: structure, amplitude and location of the objects of a field (Wernli et al. 2008; ops.sal, ops.sal_scores,
+ *      model.translate_sal, test.py --metric fss --fss_sal 1; no reference call site, tests/sal_ref.py states the definition) ----
+ * x, its strides, thr (C, T), conn, the planes and their sets: as in acg_components.  The mass of a cell is the fixed-point
+ * integer q = clamp(rint((x - floor) 2^20), 0, 2^24), in fp32 with every operation rounded on its own (subtract, multiply,
+ * round to nearest even); a NaN cell has q = 0, -inf 0, +inf 2^24.  floor: the lower end of the data range, so that mass is
+ * "amount above the floor".  Every sum of masses is an exact integer below 2^54 and independent of its order.
+ *   field (rows, C, 3) int64, fully written: Q, QY, QX = the sums of q, q h and q w over ALL H W cells (h the row, w the column).
+ *   obj (rows, C, T, 4) int64, fully written: [0] n, the components of the plane's set; [1] area, the cells in the set (both as
+ *   acg_components gives them); [2] Robj, the mass in the set; [3] Rmax, the largest mass of a component (0 without one).
+ *   shape (rows, C, T, 2) double, fully written: with R_n, Y_n, X_n the sums of q, q h, q w and P_n the maximum of q over the
+ *   cells of component n, every integer converted to double first and every operation rounded on its own, over the
+ *   components with R_n > 0: [0] SV = sum R_n (R_n / P_n), the mass-weighted scaled volume; [1] SR = sum R_n
+ *   sqrt((Y_n / R_n - QY / Q)^2 + (X_n / R_n - QX / Q)^2), the mass-weighted distance of the objects from the field's centre of
+ *   mass.  0.0 where no component has mass.  The terms are summed per thread of a fixed partition in index order of the
+ *   components' first cells, then by a fixed tree: within (n + 8) 2^-52 of any other order, relatively.
+ * ops.sal_scores turns two such triples into S, A, L1, L2, L on the host.  The same bits on every call, in every layout, for
+ * every workspace size and whatever the workspace held: integer atomics only, no floating-point atomics.  Launches only:
+ * nothing is read back, no host synchronisation, capturable in a HIP graph.
+ * Limits: 1 <= H, W <= 1024, 1 <= T <= 255, conn in {4, 8}, floor finite.  Refused before a launch (-1, acg_last_error starts
+ * with "acg_sal"): a null x, thr, field, obj or shape, an extent, T or conn out of range, a floor that is not finite, rows < 1,
+ * C < 1, rows C T above 2^31 - 1, a stride < 1, a misaligned workspace (16 bytes).  A workspace below ONE plane returns -2.
+ * The workspace holds whole planes of 32 H W bytes (int32 parents, uint32 peaks, three uint64 sums), each rounded up to 16;
+ * the call runs in passes of as many planes as ws_bytes holds.  acg_sal_workspace_bytes: the bytes of all rows C T planes,
+ * capped at the whole planes that fit 256 MiB, never below one plane; 0 for a refused size.
+ * Kernels: once per call sal_zero and sal_field, one workgroup per chunk of 8192 cells of a field row (NHWC with four stored
+ * channels, sal_field<c4>) or of a (row, channel) (sal_field<strided>), which adds its sums to field (64-bit integer atomics);
+ * then per pass sal_label, comp_label's walk that reduces the three sums and the peak per
+ * tile root in LDS (64 KiB per workgroup); comp_merge; sal_root, which adds every tile root's sums and peak to its root's
+ * (64-bit add, 32-bit max, agent scope); sal_finish, one workgroup per plane.  Fields of one tile skip comp_merge and sal_root. */
+size_t acg_sal_workspace_bytes(int rows, int C, int H, int W, int T);
+int acg_sal(const float *x, int rows, int C, int H, int W, long long row_stride, int pix_stride, long long chan_stride,
+            const float *thr, int T, int conn, float floor, long long *field, long long *obj, double *shape, void *workspace,
+            size_t ws_bytes, void *stream);
+
 /* ---- the marginal loss (ops.field_sort, ops.marginal_loss, --lambda_marg_A / --lambda_marg_B; no reference call site: the
  *      reference has no distributional loss, tests/marginal_ref.py states the definition) ----
  * acg_field_sort: a stable sort of each of the rows x C fields of H x W fp32 pixels of x, with its permutation.  The strides
