@@ -19,6 +19,7 @@
 // The file is compiled without floating-point contraction: the combine is the reference's expression, term by term.
 #include "common.h"
 #include "field.h"
+#include "pair_sum.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -76,28 +77,6 @@ __device__ __forceinline__ void cr_load_y4(const Field &fy, const float *yb, int
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = k < C ? yb[k * fy.chan + (long long)p * fy.pix] : 0.f;
-    }
-}
-
-__device__ __forceinline__ double cr_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// sums of the workgroup's threads -> out[0], out[1] by thread 0: the waves' shuffle trees, then the four waves in order
-__device__ __forceinline__ void cr_block_store(double a, double b, double (*red)[CR_THREADS / 64], double *out)
-{
-    a = cr_wave_sum(a), b = cr_wave_sum(b);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                                               // red is reused channel after channel
-    if ((threadIdx.x & 63) == 0) red[0][wave] = a, red[1][wave] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int w = 0; w < CR_THREADS / 64; ++w) s0 += red[0][w], s1 += red[1][w];
-        out[0] = s0, out[1] = s1;
     }
 }
 
@@ -161,21 +140,17 @@ __global__ __launch_bounds__(CR_THREADS) void crps_fwd_kernel(FieldSrc<2> s, int
     for (int a = 0; a < 4; ++a) {
         if (a >= nacc) continue;                                   // uniform over the workgroup
         const int c = fx.mode == FIELD_C4 ? a : who.cg;
-        cr_block_store(acc[a][0], acc[a][1], red, part + ((who.n * C + c) * nblk + who.blk) * 2);
+        pair_block_store<CR_THREADS>(acc[a][0], acc[a][1], red, part + ((who.n * C + c) * nblk + who.blk) * 2);
     }
 }
 
 // one wave per (input, channel): its workgroups' partial pairs in a fixed order -> (sum of e1, sum of e2)
 __global__ __launch_bounds__(64) void crps_fold_kernel(const double *__restrict__ part, int nblk, double M, double *__restrict__ out)
 {
-    const double *p = part + (long long)blockIdx.x * nblk * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 64) s0 += p[2 * i], s1 += p[2 * i + 1];
-    s0 = cr_wave_sum(s0), s1 = cr_wave_sum(s1);
-    if (threadIdx.x == 0) {
+    pair_fold(part, nblk, [=](double s0, double s1) {
         out[(long long)blockIdx.x * 2] = s0 / M;
         out[(long long)blockIdx.x * 2 + 1] = s1;
-    }
+    });
 }
 
 // dx in x's layout; the stored channels C .. Cp - 1 leave as 0

@@ -30,6 +30,7 @@
 // The file is compiled without floating-point contraction: the expressions are the reference's, term by term.
 #include "common.h"
 #include "field.h"
+#include "pair_sum.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -88,27 +89,6 @@ __device__ __forceinline__ float fl_vsum(const float *B, int i, int j, int r)
     return s;
 }
 
-__device__ __forceinline__ double fl_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-// sums of the workgroup's threads -> out[0], out[1] by thread 0: the waves' shuffle trees, then the four waves in order
-__device__ __forceinline__ void fl_block_store(double a, double b, double (*red)[FL_THREADS / 64], double *out)
-{
-    a = fl_wave_sum(a), b = fl_wave_sum(b);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                                               // red is reused window after window
-    if ((threadIdx.x & 63) == 0) red[0][wave] = a, red[1][wave] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int w = 0; w < FL_THREADS / 64; ++w) s0 += red[0][w], s1 += red[1][w];
-        out[0] = s0, out[1] = s1;
-    }
-}
-
 // part: (rows, C, T, nw, ntiles, 2) doubles; blockIdx.x = ((row * C + c) * T + t) * ntiles + tile
 __global__ __launch_bounds__(FL_THREADS) void fss_loss_fwd_kernel(Field fx, Field fy, int C, int H, int W, const float *__restrict__ thr,
                                                                   int T, FlWindows win, float inv_tau, int tw, int ntiles,
@@ -144,18 +124,14 @@ __global__ __launch_bounds__(FL_THREADS) void fss_loss_fwd_kernel(Field fx, Fiel
                 den += cf * cf + co * co;
             }
         }
-        fl_block_store(num, den, red, part + ((who.field * win.n + w) * ntiles + who.tile) * 2);
+        pair_block_store<FL_THREADS>(num, den, red, part + ((who.field * win.n + w) * ntiles + who.tile) * 2);
     }
 }
 
 // one wave per (row, c, t, window): its tiles' partial pairs in a fixed order -> (num, den)
 __global__ __launch_bounds__(64) void fss_loss_fold_kernel(const double *__restrict__ part, int ntiles, double *__restrict__ out)
 {
-    const double *p = part + (long long)blockIdx.x * ntiles * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < ntiles; i += 64) s0 += p[2 * i], s1 += p[2 * i + 1];
-    s0 = fl_wave_sum(s0), s1 = fl_wave_sum(s1);
-    if (threadIdx.x == 0) out[(long long)blockIdx.x * 2] = s0, out[(long long)blockIdx.x * 2 + 1] = s1;
+    pair_fold(part, ntiles, [=](double s0, double s1) { out[(long long)blockIdx.x * 2] = s0, out[(long long)blockIdx.x * 2 + 1] = s1; });
 }
 
 // g: (rows, C, T, nw, H, W) floats, B_n of u = a p - b q on the domain's cells; blockIdx.x as in the forward

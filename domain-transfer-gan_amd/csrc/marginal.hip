@@ -24,6 +24,7 @@
 // finishes the strides below MS_T in LDS; the last of them unpacks.
 #include "common.h"
 #include "field.h"
+#include "pair_sum.h"
 
 typedef unsigned long long u64;
 
@@ -436,12 +437,6 @@ struct MqLevels {
     double v[MQ_MAX_L];
 };
 
-__device__ __forceinline__ double mq_wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
 __global__ __launch_bounds__(MQ_THREADS) void marginal_scores_kernel(FieldSrc<2> src, int P, bool paired, MqLevels levels, int L,
                                                                      const float *__restrict__ edges, int E, double *__restrict__ w,
                                                                      float *__restrict__ q, int *__restrict__ below)
@@ -468,16 +463,11 @@ __global__ __launch_bounds__(MQ_THREADS) void marginal_scores_kernel(FieldSrc<2>
             a += fabs(d);
             b += d * d;
         }
-        a = mq_wave_sum(a);
-        b = mq_wave_sum(b);
-        if ((t & 63) == 0) red[0][t >> 6] = a, red[1][t >> 6] = b;
-        __syncthreads();
-        if (t == 0) {
-            a = red[0][0], b = red[1][0];
-            for (int i = 1; i < MQ_WAVES; ++i) a += red[0][i], b += red[1][i];
-            w[2 * (long long)p] = a / (double)P;
-            w[2 * (long long)p + 1] = b / (double)P;
-        }
+        // (sums of |d| and of d d are never -0.0: adding the waves from 0.0 gives the bits of starting from the first wave)
+        pair_block_sum<MQ_THREADS>(a, b, red, [=](double s0, double s1) {
+            w[2 * (long long)p] = s0 / (double)P;
+            w[2 * (long long)p + 1] = s1 / (double)P;
+        });
     }
     for (int l = t; l < L; l += MQ_THREADS) {
         const double pos = levels.v[l] * (double)(P - 1);

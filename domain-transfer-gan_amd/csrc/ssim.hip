@@ -26,6 +26,7 @@
 // evaluates the same expressions in the same order, whatever the layout.
 #include "common.h"
 #include "field.h"
+#include "pair_sum.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -59,28 +60,6 @@ __device__ __forceinline__ void ss_stage(float *planes, const Field &f, const fl
         } else {
             planes[p] = in ? base[c * f.chan + pixel * f.pix] : 0.f;
         }
-    }
-}
-
-__device__ __forceinline__ double ss_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// sums of the workgroup's threads -> out[0], out[1] by thread 0: the waves' shuffle trees, then the four waves in order
-__device__ __forceinline__ void ss_block_store(double a, double b, double (*red)[SS_THREADS / 64], double *out)
-{
-    a = ss_wave_sum(a), b = ss_wave_sum(b);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                                               // red is reused channel after channel; the row sums are read
-    if ((threadIdx.x & 63) == 0) red[0][wave] = a, red[1][wave] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int w = 0; w < SS_THREADS / 64; ++w) s0 += red[0][w], s1 += red[1][w];
-        out[0] = s0, out[1] = s1;
     }
 }
 
@@ -146,21 +125,17 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_fwd_kernel(Field x, Field y, 
                 d[0] = da, d[plane] = db, d[2 * plane] = dc;
             }
         }
-        ss_block_store(sum_s, sum_cs, red, part + ((r * C + c) * tiles + tile) * 2);
+        pair_block_store<SS_THREADS>(sum_s, sum_cs, red, part + ((r * C + c) * tiles + tile) * 2);
     }
 }
 
 // one wave per (row, channel): its tiles' partial pairs in a fixed order -> the means over the count window positions
 __global__ __launch_bounds__(64) void ssim_fold_kernel(const double *__restrict__ part, int tiles, double count, float *__restrict__ out)
 {
-    const double *p = part + (long long)blockIdx.x * tiles * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < tiles; i += 64) s0 += p[2 * i], s1 += p[2 * i + 1];
-    s0 = ss_wave_sum(s0), s1 = ss_wave_sum(s1);
-    if (threadIdx.x == 0) {
+    pair_fold(part, tiles, [=](double s0, double s1) {
         out[(long long)blockIdx.x * 2] = (float)(s0 / count);
         out[(long long)blockIdx.x * 2 + 1] = (float)(s1 / count);
-    }
+    });
 }
 
 // blockIdx.x = row r * tiles + tile, a tile of SS_TW x SS_TH pixels.  gx in x's layout; channels C .. Cp - 1 leave as 0.

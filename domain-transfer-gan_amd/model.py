@@ -22,7 +22,8 @@ import numpy as np  # noqa: F401
 import torch
 
 from . import dist as acg_dist
-from . import networks, ops
+from . import losses, networks, ops
+from .losses import hashable as _hashable
 from .modules import _starts_with_conv, as_latent, mark_dirty, packed_of, repack
 from .ops import cpad
 
@@ -257,13 +258,11 @@ class StepGraph(object):
         m = self.model
         lrs = tuple(opt.param_groups[0]['lr'] for opt in m._optimizers().values())
         # everything a captured launch bakes in as an argument: shapes, learning rates, train/eval mode, the kernel
-        # configuration (precision / implementation switch) and the scalar options of the step
-        baked = tuple(_hashable(getattr(m.opt, k, None)) for k in ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A",
-                                                        "lambda_sup_B", "stoch_enc", "z_gan", "beta1", "lambda_spec_A",
-                                                        "lambda_spec_B", "ema_decay", "lambda_marg_A", "lambda_marg_B",
-                                                        "lambda_ssim_A", "lambda_ssim_B", "lambda_crps_B", "crps_members",
-                                                        "crps_alpha", "lambda_fss_A", "lambda_fss_B", "fss_tau",
-                                                        "fss_loss_windows", "fss_loss_thr_A", "fss_loss_thr_B"))
+        # configuration (precision / implementation switch) and the scalar options of the step: those of no loss family
+        # here, every family's own from its record
+        own = ("max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A", "lambda_sup_B", "stoch_enc", "z_gan", "beta1",
+               "ema_decay")
+        baked = tuple(_hashable(getattr(m.opt, k, None)) for k in own + tuple(losses.key_options()))
         return (tuple(a.shape), tuple(b.shape), tuple(z.shape), lrs, m.netG_A_B.training, ops.CONFIG_EPOCH, baked)
 
     def _capture(self, key, real_A, real_B, prior_z_B):
@@ -353,19 +352,6 @@ class StepGraph(object):
         return deferred if deferred is not None else self.pending.resolve()
 
 
-def _hashable(v):
-    """an option's value as a key: lists (the windows and the nested threshold tables of the fss loss) become tuples"""
-    return tuple(_hashable(x) for x in v) if isinstance(v, (list, tuple)) else v
-
-
-def optional_loss_names(spec_on, marg_on, ssim_on=False):
-    """the names of the optional loss scalars a step appends to its fixed ones, in the order of its sums: the spectral pair
-    (--lambda_spec_A/B), then the marginal pair (--lambda_marg_A/B), then the structural-similarity pair (--lambda_ssim_A/B),
-    each present when one of its weights is positive"""
-    return (['Spec_A', 'Spec_B'] if spec_on else []) + (['Marg_A', 'Marg_B'] if marg_on else []) + \
-           (['Ssim_A', 'Ssim_B'] if ssim_on else [])
-
-
 class _Base(object):
     def _gan_loss(self, pred_c16, target_is_real):
         """the model's criterionGAN on an internal prediction map: LSGAN, or BCE under --no_lsgan"""
@@ -373,20 +359,6 @@ class _Base(object):
 
     def _dev(self):
         return next(self.netG_A_B.parameters()).device
-
-    def _lambda_pair(self, name):
-        """(lambda_<name>_A, lambda_<name>_B); 0 for options written before that loss existed (opt.pkl)"""
-        o = self.opt
-        return float(getattr(o, 'lambda_%s_A' % name, 0.0) or 0.0), float(getattr(o, 'lambda_%s_B' % name, 0.0) or 0.0)
-
-    def _spec_lambdas(self):
-        return _Base._lambda_pair(self, 'spec')
-
-    def _marg_lambdas(self):
-        return _Base._lambda_pair(self, 'marg')
-
-    def _ssim_lambdas(self):
-        return _Base._lambda_pair(self, 'ssim')
 
     def _optional_terms(self, loss, lams, fake_A, A, fake_B, B):
         """An optional loss family on the first-pass outputs against the real batches (`loss(fake, real, C, "nhwc")` on the
@@ -410,51 +382,6 @@ class _Base(object):
             if lam > 0:
                 add = v * lam if add is None else add + v * lam
         return t_A, t_B, add
-
-    def _spectral_terms(self, fake_A, A, fake_B, B):
-        """Spec_A, Spec_B (ops.spectral_loss: batch-mean radial spectra) under --lambda_spec_A/B, as _optional_terms gives them"""
-        return _Base._optional_terms(self, ops.spectral_loss, self._spec_lambdas(), fake_A, A, fake_B, B)
-
-    def _marginal_terms(self, fake_A, A, fake_B, B):
-        """Marg_A, Marg_B (ops.marginal_loss: the distance of the two batches' mean quantile functions) under
-        --lambda_marg_A/B, as _optional_terms gives them"""
-        return _Base._optional_terms(self, ops.marginal_loss, self._marg_lambdas(), fake_A, A, fake_B, B)
-
-    def _ssim_terms(self, rec_A, A, rec_B, B):
-        """Ssim_A, Ssim_B (ops.ssim_loss: 1 - the mean structural similarity) under --lambda_ssim_A/B, as _optional_terms gives
-        them, of the pairs a step has: the CYCLE reconstructions against their real batches in an unpaired step, the
-        predictions against their paired fields in the paired one"""
-        return _Base._optional_terms(self, ops.ssim_loss, self._ssim_lambdas(), rec_A, A, rec_B, B)
-
-    def _fss_terms(self, pred_A, A, pred_B, B):
-        """S_fss_A, S_fss_B (ops.fss_loss: 1 - the fractions skill score of soft threshold exceedances, pooled over the
-        batch) under --lambda_fss_A/B, as _optional_terms gives them, of the paired step's predictions against their paired
-        fields.  Each side has its own thresholds, opt.fss_loss_thr_A / _B ((C, T) nested lists, the climatology train.py
-        resolves at start), uploaded once; the windows (fss_loss_windows) and the temperature (fss_tau) are shared.  Under the
-        data-parallel exchange every rank pools its own batch, as the marginal loss does, and the reported scalars are the
-        ranks' average."""
-        lams = _Base._lambda_pair(self, 'fss')
-        if lams[0] <= 0 and lams[1] <= 0:
-            return None
-        o = self.opt
-        windows, tau = tuple(getattr(o, 'fss_loss_windows', (3, 9, 17))), float(getattr(o, 'fss_tau', 0.05))
-
-        def side(name):
-            thr = getattr(o, 'fss_loss_thr_' + name, None)
-            if thr is None:
-                raise ValueError("lambda_fss_A / lambda_fss_B: the options hold no thresholds: fss_loss_thr_A and fss_loss_thr_B "
-                                 "must be (C, T) nested lists (train.py resolves them from fss_loss_quantiles / "
-                                 "fss_loss_thresholds)")
-            cache = self.__dict__.setdefault('_fss_thr_dev', {})
-            key = (name, _hashable(thr))
-            if key not in cache:                                   # once; device fills, no host copy: a capture can record them
-                flat = [float(v) for row in thr for v in row]
-                table = torch.empty(len(flat), dtype=torch.float32, device=pred_A.device)
-                for i, v in enumerate(flat):
-                    table[i].fill_(v)
-                cache[key] = table.reshape(len(thr), -1)
-            return lambda fake, real, C, layout: ops.fss_loss(fake, real, C, layout, cache[key], windows, tau)
-        return _Base._optional_terms(self, (side('A'), side('B')), lams, pred_A, A, pred_B, B)
 
     def _nchw(self, x, C):
         return ops.ToNCHW.apply(x, C).detach()
@@ -1144,24 +1071,11 @@ class StochCycleGAN(_Base):
             p_fA = self.netD_A.forward_nhwc(fake_A); loss_G_A = self._gan_loss(p_fA, True)
             p_fB = self.netD_B.forward_nhwc(fake_B); loss_G_B = self._gan_loss(p_fB, True)
             loss_G = loss_G_A + loss_G_B + loss_cycle_A * o.lambda_A + loss_cycle_B * o.lambda_B
-            spec = self._spectral_terms(fake_A, A, fake_B, B)
-            if spec is not None:
-                loss_G = loss_G + spec[2]
-            marg = self._marginal_terms(fake_A, A, fake_B, B)
-            if marg is not None:
-                loss_G = loss_G + marg[2]
-            ssim = self._ssim_terms(rec_A, A, rec_B, B)
-            if ssim is not None:
-                loss_G = loss_G + ssim[2]
+            loss_G, opt_sums, opt_names = losses.add_terms(self, losses.UNPAIRED, loss_G, A, B, z,
+                                                           fake=(fake_A, fake_B), rec=(rec_A, rec_B))
             self.optimizer_G.zero_grad()
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_D_B, loss_G_B, loss_cycle_B,
-                    m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
-            if spec is not None:
-                sums += [spec[0], spec[1]]
-            if marg is not None:
-                sums += [marg[0], marg[1]]
-            if ssim is not None:
-                sums += [ssim[0], ssim[1]]
+                    m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)] + opt_sums
             ex_G = self._backward(loss_G, "stoch.G", [self.f_G_B_A, self.f_G_A_B], tail=(self.f_G_A_B, sums))
         finally:
             self.f_D_A.set_requires_grad(True); self.f_D_B.set_requires_grad(True)
@@ -1170,8 +1084,7 @@ class StochCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + \
-                optional_loss_names(spec is not None, marg is not None, ssim is not None) + \
-                ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
+                opt_names + ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_D_B', 'gnorm_D_A']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_D_B, ss_D_A])
         visuals = OrderedDict([('real_A', real_A.detach()), ('fake_B', self._nchw(fake_B, nB)),
                                ('rec_A', self._nchw(rec_A, nA)), ('real_B', real_B.detach()),
@@ -1403,25 +1316,12 @@ class AugmentedCycleGAN(_Base):
                 loss_G = loss_G + kld_z_B * o.lambda_z_B
             if z_gan:
                 loss_G = loss_G + loss_G_z_B
-            spec = self._spectral_terms(fake_A, A, fake_B, B)
-            if spec is not None:
-                loss_G = loss_G + spec[2]
-            marg = self._marginal_terms(fake_A, A, fake_B, B)
-            if marg is not None:
-                loss_G = loss_G + marg[2]
-            ssim = self._ssim_terms(rec_A, A, rec_B, B)
-            if ssim is not None:
-                loss_G = loss_G + ssim[2]
+            loss_G, opt_sums, opt_names = losses.add_terms(self, losses.UNPAIRED, loss_G, A, B, z,
+                                                           fake=(fake_A, fake_B), rec=(rec_A, rec_B))
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
             mu_v, lv_v = mu_rB.detach()[:, :nl], lv_rB.detach()[:, :nl]
             sums = [loss_D_A, loss_G_A, loss_cycle_A, loss_cycle_z_B, kld_z_B, loss_D_B, loss_G_B, loss_cycle_B,
-                    loss_D_z_B, m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)]
-            if spec is not None:
-                sums += [spec[0], spec[1]]
-            if marg is not None:
-                sums += [marg[0], marg[1]]
-            if ssim is not None:
-                sums += [ssim[0], ssim[1]]
+                    loss_D_z_B, m_tA, ops.mean_valid(p_fA, 1), m_tB, ops.mean_valid(p_fB, 1)] + opt_sums
             mins, maxs = [mu_v.min(), lv_v.min()], [mu_v.max(), lv_v.max()]
             # completion order of the G backward: E_B (its first call is the last of the three first-pass networks to have
             # been built), then G_B_A, then G_A_B — which therefore carries the scalar tail
@@ -1437,7 +1337,7 @@ class AugmentedCycleGAN(_Base):
 
         n_loss = len(sums)
         names = ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B',
-                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + optional_loss_names(spec is not None, marg is not None, ssim is not None) + [
+                 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'] + opt_names + [
                  'gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_B', 'gnorm_D_z_B', 'gnorm_D_A',
                  'mu_min', 'logvar_min', 'mu_max', 'logvar_max']
         vals = self._scalars(ex_G, self.f_G_A_B, names, sums, mins, maxs,
@@ -1463,33 +1363,6 @@ class AugmentedCycleGAN(_Base):
             return self._sup_step_graph(real_A, real_B, prior_z_B)
         with _in_train_step():
             return self._supervised_train_instance(real_A, real_B, prior_z_B)
-
-    def _crps_term(self, A, B, z):
-        """S_crps_B, S_pair_B under --lambda_crps_B: None when the weight is 0 (the default: no launch is issued), else (the
-        almost fair CRPS of Me = min(crps_members, batch) translations of every paired input against its B, the members' mean
-        pair distance, the weighted term for loss_G).  The members are one more pass of G_A_B, in the step's train state, over
-        every input repeated Me times in a row; member m of input n is coded with z[(n + m) % batch]: prior draws the step
-        already has, independent of the inputs and distinct per input, so no new random number enters the step and a captured
-        step replays it.  Neither the encoder nor G_B_A is on the term's path."""
-        o = self.opt
-        lam = float(getattr(o, 'lambda_crps_B', 0.0) or 0.0)
-        if lam <= 0:
-            return None
-        bs = z.shape[0]
-        members = int(getattr(o, 'crps_members', 4))
-        if not 2 <= members <= ops.CRPS_MAX_M:
-            raise ValueError("crps_members must lie in 2..%d (got %d)" % (ops.CRPS_MAX_M, members))
-        Me = min(members, bs)
-        most = ensemble_chunk(o.ngf, A.shape[1], A.shape[2])
-        if bs * Me > most:
-            raise ValueError("lambda_crps_B: %d inputs x %d members are more than the %d images one generator pass holds at "
-                             "%d x %d with ngf %d" % (bs, Me, most, A.shape[1], A.shape[2], o.ngf))
-        inputs = A.unsqueeze(1).expand((bs, Me) + tuple(A.shape[1:])).reshape((bs * Me,) + tuple(A.shape[1:]))
-        codes = torch.stack([torch.roll(z, -m, 0) for m in range(Me)], 1).reshape(bs * Me, z.shape[1])
-        fakes = self.netG_A_B.forward_nhwc(inputs, codes)
-        loss, _, pair = ops.crps_loss(fakes, B, o.output_nc, "nhwc", "nhwc", Me,
-                                      alpha=float(getattr(o, 'crps_alpha', 0.95)), parts=True)
-        return loss, pair, loss * lam
 
     def _supervised_train_instance(self, real_A, real_B, prior_z_B):
         o = self.opt
@@ -1523,23 +1396,9 @@ class AugmentedCycleGAN(_Base):
                 loss_G = loss_G + kld_z_B * o.lambda_z_B
             if o.z_gan and not o.stoch_enc:
                 loss_G = loss_G + loss_G_z_B
-            ssim = self._ssim_terms(pred_A, A, pred_B, B)
-            if ssim is not None:
-                loss_G = loss_G + ssim[2]
-            crps = self._crps_term(A, B, z)
-            if crps is not None:
-                loss_G = loss_G + crps[2]
-            fss = self._fss_terms(pred_A, A, pred_B, B)
-            if fss is not None:
-                loss_G = loss_G + fss[2]
+            loss_G, opt_sums, opt_names = losses.add_terms(self, losses.PAIRED, loss_G, A, B, z, pred=(pred_A, pred_B))
             self.optimizer_G_A.zero_grad(); self.optimizer_G_B.zero_grad()
-            sums = [loss_sup_A, loss_sup_B, kld_z_B, loss_D_z_B]
-            if ssim is not None:
-                sums += [ssim[0], ssim[1]]
-            if crps is not None:
-                sums += [crps[0], crps[1]]
-            if fss is not None:
-                sums += [fss[0], fss[1]]
+            sums = [loss_sup_A, loss_sup_B, kld_z_B, loss_D_z_B] + opt_sums
             # the order in which the networks' gradients complete: G_B_A (its only pass hangs on nothing else), G_A_B, then
             # the encoder behind post_z.  With the CRPS term G_A_B's member pass is built last and runs backward first, but
             # G_A_B is complete only after its first pass, which still finishes after G_B_A's and before the encoder's
@@ -1551,9 +1410,7 @@ class AugmentedCycleGAN(_Base):
         self._wait(ex_G, self.f_G_A_B, self.f_E_B)
         ss_G_A_B, ss_E = self.optimizer_G_B.clip_and_step(o.max_gnorm)
         n_loss = len(sums)
-        names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B'] + (['S_ssim_A', 'S_ssim_B'] if ssim is not None else []) + \
-                (['S_crps_B', 'S_pair_B'] if crps is not None else []) + (['S_fss_A', 'S_fss_B'] if fss is not None else []) + \
-                ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
+        names = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B'] + opt_names + ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
         vals = self._scalars(ex_G, self.f_E_B, names, sums, local=[ss_G_A_B, ss_G_B_A, ss_E, ss_D_z])
 
         def finish(vals):

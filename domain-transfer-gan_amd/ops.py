@@ -1787,7 +1787,7 @@ def coherence_summary(sums):
 
 
 # ----------------------------------------------------------------------------------------------
-# the marginal loss (model._marginal_terms, --lambda_marg_A / --lambda_marg_B): sorted fields and the distance of two
+# the marginal loss (the marg record of losses.py, --lambda_marg_A / --lambda_marg_B): sorted fields and the distance of two
 # batches' mean quantile functions
 # ----------------------------------------------------------------------------------------------
 FIELD_SORT_MAX_P = 1 << 20
@@ -1981,7 +1981,7 @@ def marginal_summary(below, cells, below_real, cells_real):
 
 
 # ----------------------------------------------------------------------------------------------
-# structural similarity (model._ssim_terms, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, eval_metrics.py, --metric ssim)
+# structural similarity (the ssim record of losses.py, --lambda_ssim_A / --lambda_ssim_B; model.translate_ssim, eval_metrics.py, --metric ssim)
 # ----------------------------------------------------------------------------------------------
 SSIM_WINDOW, SSIM_MAX_HW = 11, 1024
 
@@ -2064,7 +2064,7 @@ def ssim_loss(x, y, C, layout, data_range=2.0):
 
 
 # ----------------------------------------------------------------------------------------------
-# the CRPS training loss of M translations per input (the paired step under --lambda_crps_B; tests/crps_ref.py)
+# the CRPS training loss of M translations per input (losses._crps_term: the paired step under --lambda_crps_B; tests/crps_ref.py)
 # ----------------------------------------------------------------------------------------------
 CRPS_MAX_HW, CRPS_MAX_M = 1024, 16
 

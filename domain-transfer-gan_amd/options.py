@@ -10,6 +10,8 @@ import pickle
 
 import torch
 
+from .losses import BY_STEM, FAMILIES
+
 
 def create_sub_dirs(opt, sub_dirs):
     """options.py:7-12"""
@@ -148,37 +150,27 @@ class TrainOptions(object):
         if opt.defer_scalars and not opt.step_graph:
             self.parser.error("--defer_scalars requires --step_graph")
         g = opt.grid_size
-        if (opt.lambda_spec_A > 0 or opt.lambda_spec_B > 0) and (not 16 <= g <= 1024 or g & (g - 1)):
-            self.parser.error("--lambda_spec_A / --lambda_spec_B: the spectral loss needs fields of S x S with S a power of two "
-                              "in 16..1024 (--grid_size %d)" % g)
-        if opt.lambda_marg_A < 0 or opt.lambda_marg_B < 0:
-            self.parser.error("--lambda_marg_A / --lambda_marg_B must not be negative (got %r, %r)"
-                              % (opt.lambda_marg_A, opt.lambda_marg_B))
-        if (opt.lambda_marg_A > 0 or opt.lambda_marg_B > 0) and not 1 <= g <= 1024:
-            self.parser.error("--lambda_marg_A / --lambda_marg_B: the marginal loss sorts fields of up to 1024 x 1024 "
-                              "(--grid_size %d)" % g)
-        if opt.lambda_ssim_A < 0 or opt.lambda_ssim_B < 0:
-            self.parser.error("--lambda_ssim_A / --lambda_ssim_B must not be negative (got %r, %r)"
-                              % (opt.lambda_ssim_A, opt.lambda_ssim_B))
-        if (opt.lambda_ssim_A > 0 or opt.lambda_ssim_B > 0) and not 11 <= g <= 1024:
-            self.parser.error("--lambda_ssim_A / --lambda_ssim_B: the structural similarity slides an 11 x 11 window over "
-                              "fields of up to 1024 x 1024 (--grid_size %d)" % g)
-        if opt.lambda_crps_B < 0:
-            self.parser.error("--lambda_crps_B must not be negative (got %r)" % opt.lambda_crps_B)
+        for fam in FAMILIES:                      # what every family refuses, from its record
+            weights = [getattr(opt, o) for o in fam.options()]
+            if not fam.negative_ok and any(w < 0 for w in weights):
+                self.parser.error("%s must not be negative (got %s)" % (fam.flags(), ", ".join("%r" % w for w in weights)))
+            if not fam.on(opt):
+                continue
+            if fam.paired_only and not opt.supervised:
+                self.parser.error("%s: a term of the paired step, which requires --supervised" % fam.flags())
+            if fam.paired_only and opt.model != "aug_cycle_gan":
+                self.parser.error("%s: --model %s has no paired step (aug_cycle_gan has)" % (fam.flags(), opt.model))
+            lo, hi, pow2, phrase = fam.grid
+            if not lo <= g <= hi or (pow2 and g & (g - 1)):
+                self.parser.error("%s: %s (--grid_size %d)" % (fam.flags(), phrase, g))
         if not 2 <= opt.crps_members <= 16:
             self.parser.error("--crps_members must lie in 2..16 (got %d)" % opt.crps_members)
         if not 0.0 <= opt.crps_alpha <= 1.0:
             self.parser.error("--crps_alpha must lie in [0, 1] (got %r)" % opt.crps_alpha)
-        if opt.lambda_crps_B > 0:
-            if not opt.supervised:
-                self.parser.error("--lambda_crps_B is a term of the paired step: it requires --supervised")
-            if opt.model != "aug_cycle_gan":
-                self.parser.error("--lambda_crps_B: --model %s has no paired step (aug_cycle_gan has)" % opt.model)
+        if BY_STEM["crps"].on(opt):
             if opt.norm != "instance":
                 self.parser.error("--lambda_crps_B needs --norm instance: under batch statistics the members of one input "
                                   "would see each other (--norm %s)" % opt.norm)
-            if not 1 <= g <= 1024:
-                self.parser.error("--lambda_crps_B: the CRPS loss takes fields of up to 1024 x 1024 (--grid_size %d)" % g)
             from .model import ensemble_chunk              # the step's own limit, met here before any data is loaded
             per_rank = max(opt.batchSize // max(int(os.environ.get("WORLD_SIZE", "1")), 1), 1)
             images, most = per_rank * min(opt.crps_members, per_rank), ensemble_chunk(opt.ngf, g, g)
@@ -186,18 +178,8 @@ class TrainOptions(object):
                 self.parser.error("--lambda_crps_B: a paired batch of %d x %d members is %d images, more than the %d one pass of "
                                   "G_A_B holds at --grid_size %d with --ngf %d; lower --crps_members or --batchSize"
                                   % (per_rank, min(opt.crps_members, per_rank), images, most, g, opt.ngf))
-        if opt.lambda_fss_A < 0 or opt.lambda_fss_B < 0:
-            self.parser.error("--lambda_fss_A / --lambda_fss_B must not be negative (got %r, %r)" % (opt.lambda_fss_A, opt.lambda_fss_B))
         if not 0.0 < opt.fss_tau < float("inf"):
             self.parser.error("--fss_tau must be positive and finite (got %r)" % opt.fss_tau)
-        if opt.lambda_fss_A > 0 or opt.lambda_fss_B > 0:
-            if not opt.supervised:
-                self.parser.error("--lambda_fss_A / --lambda_fss_B are terms of the paired step: they require --supervised")
-            if opt.model != "aug_cycle_gan":
-                self.parser.error("--lambda_fss_A / --lambda_fss_B: --model %s has no paired step (aug_cycle_gan has)" % opt.model)
-            if not 1 <= g <= 1024:
-                self.parser.error("--lambda_fss_A / --lambda_fss_B: the fss loss takes fields of up to 1024 x 1024 "
-                                  "(--grid_size %d)" % g)
         if opt.native_res and opt.synthetic:
             self.parser.error("--native_res cuts windows from stored fields; --synthetic fields are --grid_size already")
         if opt.window_flip and not opt.native_res:

@@ -20,7 +20,7 @@ from shutil import copyfile
 import numpy as np
 import torch
 
-from . import dist as D, ops
+from . import dist as D, losses, ops
 from .dataloader import AlignedIterator, DevicePrefetcher, UnalignedIterator, load_numpy_data, synthetic_data, window_tables
 from .evaluate import eval_mse_A, eval_ubo_B, one_to_three_channels
 from .model import AugmentedCycleGAN, DeferredStep, StochCycleGAN
@@ -181,7 +181,7 @@ class Trainer(object):
             n_sup = int(len(trainA) * o.sup_frac)
             self.sup_it = itertools.cycle(AlignedIterator(trainA[:n_sup], trainB[:n_sup], batch_size=o.batchSize))
             self.log('#supervised images = %d' % n_sup)
-        if getattr(o, "lambda_fss_A", 0.0) > 0 or getattr(o, "lambda_fss_B", 0.0) > 0:
+        if losses.BY_STEM["fss"].on(o):
             self._fss_loss_thresholds(trainA, trainB)
 
     def _fss_loss_thresholds(self, trainA, trainB):

@@ -263,10 +263,10 @@ def test_every_host_side_refusal_comes_before_a_device_is_needed(monkeypatch):
 
 def test_the_paired_step_names_its_options_when_the_thresholds_are_missing():
     import argparse
-    from dtgan_amd import model as M
+    from dtgan_amd import losses, model as M
     opt = argparse.Namespace(lambda_fss_A=0.0, lambda_fss_B=0.5, input_nc=3, output_nc=3)
     with pytest.raises(ValueError, match="fss_loss_thr_A and fss_loss_thr_B"):
-        M._Base._fss_terms(argparse.Namespace(opt=opt), None, None, None, None)
+        losses.add_terms(argparse.Namespace(opt=opt), losses.PAIRED, None, None, None, None, pred=(None, None))
     opt.lambda_fss_B = 0.0
-    assert M._Base._fss_terms(argparse.Namespace(opt=opt), None, None, None, None) is None
+    assert losses.add_terms(argparse.Namespace(opt=opt), losses.PAIRED, None, None, None, None, pred=(None, None)) == (None, [], [])
     assert M._hashable([[0.5, 1], [2, 3]]) == ((0.5, 1), (2, 3)) and M._hashable(0.5) == 0.5 and M._hashable(None) is None

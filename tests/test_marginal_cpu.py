@@ -104,21 +104,24 @@ def test_the_parser_refuses_a_negative_weight_and_a_grid_beyond_the_sort(tmp_pat
 
 
 def test_options_written_before_the_loss_existed_mean_zero():
-    from dtgan_amd import model as M
-    old = argparse.Namespace(lambda_A=1.0, lambda_spec_A=0.5)
-    assert M._Base._marg_lambdas(argparse.Namespace(opt=old)) == (0.0, 0.0)
+    from dtgan_amd import losses
+    marg = losses.BY_STEM["marg"]
+    old = argparse.Namespace(lambda_A=1.0, lambda_ssim_A=0.0)
+    assert marg.weights(old) == (0.0, 0.0) and not marg.on(old)
     new = argparse.Namespace(lambda_marg_A=0.5, lambda_marg_B=0.0)
-    assert M._Base._marg_lambdas(argparse.Namespace(opt=new)) == (0.5, 0.0)
-    off = argparse.Namespace(opt=old, _marg_lambdas=lambda: (0.0, 0.0))
-    assert M._Base._marginal_terms(off, None, None, None, None) is None         # both weights 0: nothing is touched
-    import inspect
-    key = inspect.getsource(M.StepGraph._key)
-    assert '"lambda_marg_A"' in key and '"lambda_marg_B"' in key
+    assert marg.weights(new) == (0.5, 0.0) and marg.on(new)
+    off = argparse.Namespace(opt=old)
+    assert losses.add_terms(off, losses.UNPAIRED, None, None, None, None, fake=(None, None), rec=(None, None)) == (None, [], [])
+    key = losses.key_options()            # (both weights 0: nothing is touched)  what StepGraph._key takes: test_losses_cpu.py
+    assert marg.options() == ["lambda_marg_A", "lambda_marg_B"] and "lambda_marg_A" in key and "lambda_marg_B" in key
 
 
 def test_the_optional_loss_names_for_every_combination_of_the_two_families():
-    from dtgan_amd import model as M
-    assert M.optional_loss_names(False, False) == []
-    assert M.optional_loss_names(True, False) == ["Spec_A", "Spec_B"]
-    assert M.optional_loss_names(False, True) == ["Marg_A", "Marg_B"]
-    assert M.optional_loss_names(True, True) == ["Spec_A", "Spec_B", "Marg_A", "Marg_B"]
+    from dtgan_amd import losses
+
+    def names(spec, marg):
+        return losses.names(argparse.Namespace(lambda_spec_B=float(spec), lambda_marg_A=float(marg)), losses.UNPAIRED)
+    assert names(False, False) == []
+    assert names(True, False) == ["Spec_A", "Spec_B"]
+    assert names(False, True) == ["Marg_A", "Marg_B"]
+    assert names(True, True) == ["Spec_A", "Spec_B", "Marg_A", "Marg_B"]

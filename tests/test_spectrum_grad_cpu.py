@@ -114,10 +114,11 @@ def test_a_positive_weight_refuses_an_unsupported_grid_size(tmp_path, size, caps
 
 def test_options_written_before_the_loss_existed_mean_zero():
     """the model reads both weights with a default: an opt.pkl without them (train.py --continue_train, test.py) builds"""
-    from dtgan_amd import model as M
+    from dtgan_amd import losses
+    spec = losses.BY_STEM["spec"]
     old = argparse.Namespace(lambda_A=1.0)
-    assert M._Base._spec_lambdas(argparse.Namespace(opt=old)) == (0.0, 0.0)
+    assert spec.weights(old) == (0.0, 0.0) and not spec.on(old)
     new = argparse.Namespace(lambda_spec_A=0.5, lambda_spec_B=0.0)
-    assert M._Base._spec_lambdas(argparse.Namespace(opt=new)) == (0.5, 0.0)
-    import inspect
-    assert '"lambda_spec_A"' in inspect.getsource(M.StepGraph._key) and '"lambda_spec_B"' in inspect.getsource(M.StepGraph._key)
+    assert spec.weights(new) == (0.5, 0.0) and spec.on(new)
+    key = losses.key_options()                                                   # what StepGraph._key takes: test_losses_cpu.py
+    assert spec.options() == ["lambda_spec_A", "lambda_spec_B"] and "lambda_spec_A" in key and "lambda_spec_B" in key

@@ -2,7 +2,6 @@
 and against closed forms), of the float32 error the GPU bars are derived from, of the new entry points' declarations, of the
 --lambda_ssim_A / --lambda_ssim_B options, of --metric ssim and of the names a step gives its optional loss scalars."""
 import argparse
-import inspect
 import os
 import pickle
 import re
@@ -172,23 +171,29 @@ def test_the_test_options_accept_the_metric():
 
 
 def test_options_written_before_the_loss_existed_mean_zero():
-    from dtgan_amd import model as M
-    old = argparse.Namespace(lambda_A=1.0, lambda_marg_A=0.5)
-    assert M._Base._ssim_lambdas(argparse.Namespace(opt=old)) == (0.0, 0.0)
+    from dtgan_amd import losses
+    ssim = losses.BY_STEM["ssim"]
+    old = argparse.Namespace(lambda_A=1.0, lambda_fss_A=0.0)
+    assert ssim.weights(old) == (0.0, 0.0) and not ssim.on(old)
     new = argparse.Namespace(lambda_ssim_A=0.5, lambda_ssim_B=0.0)
-    assert M._Base._ssim_lambdas(argparse.Namespace(opt=new)) == (0.5, 0.0)
-    off = argparse.Namespace(opt=old, _ssim_lambdas=lambda: (0.0, 0.0))
-    assert M._Base._ssim_terms(off, None, None, None, None) is None              # both weights 0: nothing is touched
-    key = inspect.getsource(M.StepGraph._key)
-    assert '"lambda_ssim_A"' in key and '"lambda_ssim_B"' in key
+    assert ssim.weights(new) == (0.5, 0.0) and ssim.on(new)
+    off = argparse.Namespace(opt=old)                                            # both weights 0: nothing is touched, in either step
+    assert losses.add_terms(off, losses.UNPAIRED, None, None, None, None, fake=(None, None), rec=(None, None)) == (None, [], [])
+    assert losses.add_terms(off, losses.PAIRED, None, None, None, None, pred=(None, None)) == (None, [], [])
+    key = losses.key_options()                                                   # what StepGraph._key takes: test_losses_cpu.py
+    assert ssim.options() == ["lambda_ssim_A", "lambda_ssim_B"] and "lambda_ssim_A" in key and "lambda_ssim_B" in key
 
 
-def test_the_optional_loss_names_for_all_eight_combinations():
-    from dtgan_amd import model as M
-    spec, marg, ssim = ["Spec_A", "Spec_B"], ["Marg_A", "Marg_B"], ["Ssim_A", "Ssim_B"]
-    for s in (False, True):
-        for m in (False, True):
-            two = (spec if s else []) + (marg if m else [])
-            assert M.optional_loss_names(s, m) == two                            # the two-argument calls: as before
-            assert M.optional_loss_names(s, m, False) == two
-            assert M.optional_loss_names(s, m, True) == two + ssim
+def test_the_optional_loss_names_for_every_combination_of_the_five_families_in_both_steps():
+    import itertools
+    from dtgan_amd import losses
+    unpaired = {"spec": ["Spec_A", "Spec_B"], "marg": ["Marg_A", "Marg_B"], "ssim": ["Ssim_A", "Ssim_B"]}
+    paired = {"ssim": ["S_ssim_A", "S_ssim_B"], "crps": ["S_crps_B", "S_pair_B"], "fss": ["S_fss_A", "S_fss_B"]}
+    stems = ("spec", "marg", "ssim", "crps", "fss")
+    assert tuple(f.stem for f in losses.FAMILIES) == stems
+    for on in itertools.product((False, True), repeat=5):
+        # one positive weight turns a family on, whichever side it is; the B side, since crps has no other
+        opt = argparse.Namespace(**dict(("lambda_%s_B" % s, 0.5) for s, o in zip(stems, on) if o))
+        assert losses.names(opt, losses.UNPAIRED) == [n for s, o in zip(stems, on) if o for n in unpaired.get(s, [])], on
+        assert losses.names(opt, losses.PAIRED) == [n for s, o in zip(stems, on) if o for n in paired.get(s, [])], on
+    assert losses.names(argparse.Namespace(lambda_fss_A=0.5, lambda_spec_A=1.0, lambda_crps_A=1.0), losses.PAIRED) == paired["fss"]
