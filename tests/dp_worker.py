@@ -13,8 +13,8 @@ import torch  # noqa: E402
 import dtgan_amd  # noqa: E402
 from dtgan_amd import dist as D, model as M  # noqa: E402
 from hip_util import load_recipe, t, n  # noqa: E402
+from model_cases import make_opt  # noqa: E402
 from oracle import recipe  # noqa: E402
-from test_hip_step import make_opt  # noqa: E402
 
 out, aug = sys.argv[1], int(sys.argv[2])
 backend = os.environ.get("ACGAN_DP_BACKEND", "gloo")   # "nccl": the one-rank RCCL smoke (ACGAN_DIST_FORCE=1)

@@ -132,3 +132,14 @@ def make_pair(H, W, rows=2, C=3, seed=0):
     x = make_fields("tanh_red", H, W, rows, C, seed)
     y = 0.8 * np.roll(x, (1, 2), axis=(-2, -1)) + 0.05 * make_fields("red", H, W, rows, C, seed + 1)
     return x, np.ascontiguousarray(y, dtype=np.float32)
+
+
+# The bars of the whole-field kernels.  |psd - ref| <= TAU sqrt(ref E) + TAU^2 E per bin, E the field's mean square.  Measured,
+# not chosen: the float32 Bluestein restatement on torch.fft of complex64 on the CPU, binned in float64, needs tau = 3.1424e-4
+# over every bin, kind and shape of SHAPES (`python tools/field_spectrum_bench.py --cpu-tolerance`; the largest is the
+# constant-plus-noise field at 1023 x 513, M = 2048 on both axes: the DC coefficient of 0.7 H W goes through two padded
+# transforms and back).  The constant is 4 x that: a different butterfly order, as spectrum_ref.TAU.
+TAU = 4 * 3.1424e-4
+# |cxy - ref| <= CTAU (sqrt(pxx_ref Ey) + sqrt(pyy_ref Ex)) + CTAU^2 sqrt(Ex Ey) per bin (cross_spectrum_ref.cross_bound): the
+# same run needs 3.7226e-5 for the co-spectrum of make_pair over those shapes (the largest at 1023 x 513); 4 x that.
+CTAU = 4 * 3.7226e-5

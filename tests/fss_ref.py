@@ -11,6 +11,9 @@ import numpy as np
 SIZES = ((1, 1), (5, 7), (16, 16), (33, 31), (64, 64), (65, 130), (256, 256), (321, 321))
 WINDOWS = (1, 3, 9, 33, 65)
 KINDS = ("noise", "shifted", "ties", "nan", "extremes")
+# thresholds (C, T) and windows of the model-level tests (translate_fss on the fields of a tiny generator, in [-1, 1])
+THR = np.array([[-0.1, 0.0, 0.2], [-0.2, 0.05, 0.3], [0.0, 0.1, 0.5]], dtype=np.float32)
+WIN = (1, 3, 9, 33)
 
 
 def events(x, thr):

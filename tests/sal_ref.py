@@ -168,3 +168,15 @@ def make_fields(kind, rows, C, H, W, thr, seed=0):
             u = _weights(H, W, s)
             x[r, c] = np.where(R.mask(kind, H, W, s if kind.startswith("perc") else 0), 0.25 + 0.75 * u[0], -0.5 - u[1])
     return x
+
+
+def check(got, ref, what):
+    """field and obj equal; shape within (n + 8) 2^-52 of the reference, relatively: the terms are non-negative and built from
+    equal integers, the sums differ in the order of n - 1 additions; exactly 0.0 where the reference is"""
+    assert got[0].dtype == got[1].dtype == np.int64 and got[2].dtype == np.float64
+    assert np.array_equal(got[0], ref[0]), (what, np.argwhere(got[0] != ref[0])[:5])
+    assert np.array_equal(got[1], ref[1]), (what, np.argwhere(got[1] != ref[1])[:5])
+    bar = (ref[1][..., :1] + 8) * 2.0 ** -52 * ref[2]
+    err = np.abs(got[2] - ref[2])
+    assert np.all(err <= bar), (what, np.argwhere(~(err <= bar))[:5], err.max())
+    assert np.all(got[2][ref[2] == 0] == 0)

@@ -122,3 +122,18 @@ def tolerance_needed(psd, ref, E):
     b = np.sqrt(ref * E)
     tau = 2.0 * d / (b + np.sqrt(b * b + 4.0 * E * d))               # the stable form of (-b + sqrt(b^2 + 4 E d)) / 2E
     return float(np.max(np.where(d > 0, tau, 0.0)))
+
+
+# The kernel tests' bar: |psd - ref| <= TAU sqrt(ref E) + TAU^2 E per bin, E the field's mean square.  Measured, not chosen:
+# torch.fft.fft2 in float32 on the CPU, binned in float64, needs tau = 1.3214e-4 over every bin, input and size above (`python
+# tools/spectrum_bench.py --cpu-tolerance`; the largest is the constant-plus-noise field at S = 1024, whose DC coefficient of
+# 0.7 S^2 is rounded to fp32: 2^-24 S).  The constant is 4 x that: a different butterfly order.
+TAU = 4 * 1.3214e-4
+
+
+def within(psd, ref, E, what, tau=TAU):
+    """asserts that bar on finite spectra and prints the tau the comparison needed beside it"""
+    d = np.abs(psd.astype(np.float64) - ref)
+    bound = tau * np.sqrt(ref * E[..., None]) + tau ** 2 * E[..., None]
+    print("%s: tau needed %.3e (allowed %.3e)" % (what, tolerance_needed(psd, ref, E), tau))
+    assert np.all(np.isfinite(psd)) and np.all(d <= bound), (what, float((d / bound).max()), np.argwhere(d > bound)[:5])

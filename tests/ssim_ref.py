@@ -22,6 +22,9 @@ TILE_W, TILE_H = 32, 16            # the shipped tile of csrc/ssim.hip (SS_TW x 
 # CASES, measured by tests/test_ssim_ref_cpu.py::test_fp32_bars_over_the_gpu_case_lists, which also checks these numbers:
 FP32_VALUE_ERR = 6.0130e-05        # |mean S - mean S64| and |mean cs - mean cs64|, absolute (a near-flat case)
 FP32_GRAD_ERR = 1.7730e-04         # max |grad - grad64| over a field / max |grad64| over that field (a near-flat case)
+# The bars of the kernels are 4 x those: a different summation order of the same 11- and 121-term sums.
+VALUE_TOL = 4 * FP32_VALUE_ERR     # 4 x 6.0130e-05
+GRAD_TOL = 4 * FP32_GRAD_ERR       # 4 x 1.7730e-04
 
 
 def window(dtype=np.float64):

@@ -2,14 +2,15 @@
 additivity, the holes of ops.components_summary against the labelled holes of minkowski_ref.functionals_brute,
 ops.components_summary / components_distance, the option parser, the header and the host-side refusals of ops.components."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import components_ref as R
 import minkowski_ref as K
+from eval_cases import parse_test
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ZERO = np.zeros((1, 1), np.float32)
@@ -209,8 +210,7 @@ def test_summary_and_distance():
 
 
 def _parse(*extra):
-    from dtgan_amd import options as O
-    return O.TestOptions().parse(["--chk_path", "c", "--dataroot", "d", "--metric", "minkowski"] + list(extra))
+    return parse_test("minkowski", *extra)
 
 
 def test_the_parser_takes_the_connectivity():
@@ -230,11 +230,8 @@ def test_the_parser_takes_the_connectivity():
 
 def test_the_header_declares_both_entries_and_the_binding_matches():
     from dtgan_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     for name, nargs in (("acg_components_workspace_bytes", 5), ("acg_components", 16)):
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]) == nargs, name
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
     mk = open(os.path.join(ROOT, "domain-transfer-gan_amd", "csrc", "Makefile")).read()
     assert "components.hip" in mk
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()

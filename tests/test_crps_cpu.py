@@ -9,8 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 import crps_ref as R
 import ensemble_ref as E
+from model_cases import parse_train as _parse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -98,12 +100,6 @@ def test_crps_weight():
     assert ops.CRPS_MAX_M == 16 and ops.CRPS_MAX_HW == 1024
 
 
-def _parse(tmp_path, *extra):
-    from dtgan_amd import options as O
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--gpu_ids", "-1"]
-                                  + list(extra))
-
-
 def test_the_options_default_to_off_and_are_written(tmp_path):
     opt = _parse(tmp_path)
     assert opt.lambda_crps_B == 0.0 and opt.crps_members == 4 and opt.crps_alpha == 0.95
@@ -143,12 +139,9 @@ def test_the_parser_refuses_what_the_term_cannot_take(tmp_path, capsys):
 
 def test_the_header_the_binding_and_the_documents_agree():
     from dtgan_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     for name, nargs in (("acg_crps_workspace_bytes", 5), ("acg_crps_fwd", 17), ("acg_crps_bwd", 19)):
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]) == nargs, name
-    doubles = [i for i, a in enumerate(re.search(r"int\s+acg_crps_bwd\s*\(([^)]*)\)", hdr).group(1).split(",")) if "double" in a]
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
+    doubles = [i for i, k in enumerate(abi.header_args("acg_crps_bwd")) if k == "double"]
     assert doubles == [i for i, t in enumerate(_lib.SIGNATURES["acg_crps_bwd"][1]) if t is _lib.ctypes.c_double] == [15, 16]
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for word in ("`acg_crps_fwd`", "`acg_crps_bwd`", "acg_crps_workspace_bytes", "ops.crps_loss", "--lambda_crps_B"):

@@ -6,13 +6,8 @@ import pytest
 import torch
 
 import dtgan_amd  # noqa: F401
-from dtgan_amd import options as O
 from dtgan_amd import train as TR
-
-
-def _parse(tmp_path, *extra):
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8",
-                                        "--gpu_ids", "-1"] + list(extra))
+from model_cases import parse_train as _parse
 
 
 def test_defer_scalars_parses_and_defaults_off(tmp_path):

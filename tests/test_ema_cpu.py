@@ -4,15 +4,16 @@ import argparse
 import inspect
 import os
 import pickle
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import dtgan_amd  # noqa: F401
 from dtgan_amd import _lib, networks as N, options as O
 import ema_ref as E
+from model_cases import parse_train as _parse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -43,11 +44,6 @@ def test_a_constant_parameter_sequence_is_a_fixed_point():
     got = E.ema_run([q, p], 0.999, [1, 2], e0=p)
     assert np.array_equal(got[0], e1) and np.array_equal(got[1], e2)
     assert E.bound(3, 1.0) == 24 * 2.0 ** -24
-
-
-def _parse(tmp_path, *extra):
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--gpu_ids", "-1"]
-                                  + list(extra))
 
 
 def test_training_options_default_off_and_are_written(tmp_path):
@@ -112,12 +108,9 @@ def test_options_written_before_the_averaging_existed_mean_off():
 
 
 def test_the_entry_points_are_declared_bound_and_documented():
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
-    assert re.search(r"#define ACG_EMA_MAX_GROUPS 8\b", hdr) and _lib.EMA_MAX_GROUPS == 8
+    assert abi.defines()["ACG_EMA_MAX_GROUPS"] == 8 and _lib.EMA_MAX_GROUPS == 8
     for name in ("acg_ema_multi", "acg_swap_multi"):
-        m = re.search(r"\bint %s\(([^;]*)\);" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+        assert abi.declarations()[name][0] == "int" and len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]), name
         assert name in open(os.path.join(ROOT, "INTEGRATION.md")).read(), name
     assert [f[0] for f in _lib.EmaGroup._fields_] == ["p", "e", "n"]
     import ctypes

@@ -3,12 +3,12 @@ import numpy as np
 import pytest
 
 import dtgan_amd  # noqa: F401
-from dtgan_amd import options as O
 from ensemble_ref import e2_pairs, e2_sorted, ensemble_stats, quantile_linear
+from eval_cases import parse_test
 
 
 def _parse(*extra, metric="ensemble"):
-    return O.TestOptions().parse(["--chk_path", "c", "--dataroot", "d", "--metric", metric] + list(extra))
+    return parse_test(metric, *extra)
 
 
 @pytest.mark.parametrize("M", [1, 2, 3, 7, 16, 33, 64])

@@ -88,7 +88,7 @@ def test_float32_bluestein_restatement_stays_inside_the_gpu_bound(H, W):
     """the yardstick of the GPU tolerance on the shapes that take a moment on the host; the large ones are the tool's"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import field_spectrum_bench as B
-    from test_hip_field_spectrum import CTAU, TAU
+    from field_spectrum_ref import CTAU, TAU
     per, cross = B.restated_tolerances(H, W)
     print("%d x %d: tau %s, cxy %.3e" % (H, W, {k: "%.3e" % v for k, v in per.items()}, cross))
     assert max(per.values()) <= TAU / 4 and cross <= CTAU / 4

@@ -1,15 +1,13 @@
 """CPU tests of the fractions skill score: the numpy reference (tests/fss_ref.py) against brute-force window loops and the
 float definition, ops.fss_summary, the option parsers, the header and the host-side refusals of ops.fss."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
+import abi
 import fss_ref as F
+from eval_cases import parse_test
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LISTED = (1, 3, 5, 9, 17, 33)
 
 
@@ -102,8 +100,7 @@ def test_fss_summary():
 
 
 def _parse(*extra):
-    from dtgan_amd import options as O
-    return O.TestOptions().parse(["--chk_path", "c", "--dataroot", "d", "--metric", "fss"] + list(extra))
+    return parse_test("fss", *extra)
 
 
 def test_the_fss_options():
@@ -133,11 +130,8 @@ def test_thresholds_are_float64_quantiles_per_channel():
 
 def test_the_header_declares_both_entries_and_the_binding_matches():
     from dtgan_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     for name in ("acg_fss_workspace_bytes", "acg_fss"):
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]), name
     assert len(_lib.SIGNATURES["acg_fss"][1]) == 22
     lib = _lib.load()
     # per plane and image row ceil(W / 64) words and one more 16-bit prefix; x's planes, then y's, then for an

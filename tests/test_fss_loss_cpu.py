@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 import fss_loss_ref as R
 import fss_ref as F
+from model_cases import parse_train as _parse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -152,12 +154,6 @@ def test_the_float32_restatement_stays_within_a_quarter_of_the_bars():
     assert any(c[:2] == (5, 7) and 9 in c[5] for c in R.CASES) and any(c[:2] == (33, 31) and {33, 65} <= set(c[5]) for c in R.CASES)
 
 
-def _parse(tmp_path, *extra):
-    from dtgan_amd import options as O
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--gpu_ids", "-1"]
-                                  + list(extra))
-
-
 def test_the_options_default_to_off_and_are_written(tmp_path):
     opt = _parse(tmp_path)
     assert opt.lambda_fss_A == 0.0 and opt.lambda_fss_B == 0.0 and opt.fss_loss_quantiles == (0.9, 0.99)
@@ -193,15 +189,10 @@ def test_the_parser_refuses_what_the_term_cannot_take(tmp_path, capsys):
 
 def test_the_header_the_binding_and_the_documents_agree():
     from dtgan_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
-    assert re.search(r"#define\s+ACG_VERSION\s+118\b", hdr) and _lib.ABI_VERSION == 118
     for name, nargs in (("acg_fss_loss_workspace_bytes", 6), ("acg_fss_loss_fwd", 21), ("acg_fss_loss_bwd", 23)):
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]) == nargs, name
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
     for name, at in (("acg_fss_loss_fwd", 16), ("acg_fss_loss_bwd", 17)):
-        args = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, hdr).group(1).split(",")
-        floats = [i for i, a in enumerate(args) if re.match(r"\s*float\s+\w+$", a)]
+        floats = [i for i, k in enumerate(abi.header_args(name)) if k == "float"]
         assert floats == [i for i, t in enumerate(_lib.SIGNATURES[name][1]) if t is _lib.c_float] == [at], name
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for word in ("`acg_fss_loss_fwd`", "`acg_fss_loss_bwd`", "acg_fss_loss_workspace_bytes", "ops.fss_loss", "--lambda_fss_B"):
@@ -213,7 +204,6 @@ def test_the_header_the_binding_and_the_documents_agree():
     assert "fss_loss.hip" in mk
     assert "acg_fss_loss_fwd" in ops.FssLoss.__doc__ and "acg_fss_loss_bwd" in ops.FssLoss.__doc__
     lib = _lib.load()
-    assert lib.acg_version() == 118
     for args, want in (((16, 3, 256, 256, 2, 3), 4 * 16 * 3 * 2 * 3 * 256 * 256), ((1, 1, 1, 1, 1, 1), 16), ((2, 3, 1, 7, 8, 8), 4 * 2 * 3 * 64 * 7), ((2, 3, 1, 3, 8, 8), 16 * 2 * 3 * 64),
                        ((1, 1, 33, 31, 1, 2), (4 * 2 * 33 * 31 + 15) // 16 * 16)):
         assert lib.acg_fss_loss_workspace_bytes(*args) == want, args

@@ -2,13 +2,14 @@
 Haar decomposition on the padded canvas and against closed forms, ops.fss_scale_summary against the reference, the level
 count, the option parser, the documentation and the header."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import fss_ref as F
 import fss_scales_ref as R
+from eval_cases import parse_test
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HAAR_SIZES = ((1, 1), (1, 7), (5, 1), (2, 2), (3, 5), (63, 65), (64, 64), (65, 64), (100, 37), (321, 321))
@@ -178,8 +179,7 @@ def test_fss_scale_levels():
 
 
 def _parse(*extra):
-    from dtgan_amd import options as O
-    return O.TestOptions().parse(["--chk_path", "c", "--dataroot", "d", "--metric", "fss"] + list(extra))
+    return parse_test("fss", *extra)
 
 
 def test_the_parser_takes_the_option_and_the_documents_name_it():
@@ -199,11 +199,8 @@ def test_the_parser_takes_the_option_and_the_documents_name_it():
 
 def test_the_header_declares_both_entries_and_the_binding_matches():
     from dtgan_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     for name, nargs in (("acg_fss_scales_workspace_bytes", 7), ("acg_fss_scales", 20)):
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]) == nargs, name
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "`acg_fss_scales`" in doc and "acg_fss_scales_workspace_bytes" in doc and "ops.fss_scale_summary" in doc
     lib = _lib.load()

@@ -8,19 +8,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from golden_util import load  # noqa: E402
-from test_hip_step import make_opt  # noqa: E402
-
-
-def _model(aug=True, **kw):
-    from hip_util import load_recipe
-    from dtgan_amd import model as M
-    d = dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4)
-    d.update(kw)
-    opt = make_opt(**d)
-    m = (M.AugmentedCycleGAN if aug else M.StochCycleGAN)(opt, testing=True)
-    for k, net in m._net_dict().items():
-        load_recipe(net, k, 0, "rich")
-    return m
+from model_cases import tiny_model as _model  # noqa: E402
 
 
 def test_supervised_train_instance_matches_reference_golden():

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from golden_util import load, names  # noqa: E402
+from model_cases import REC_TOL, STEP_TOL, build_model, check_digests, make_opt  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAST_HEAD_KERNELS = ("igemm_conv_f32", "igemm_conv_bf16", "conv_patch16_x3", "conv_patchn_x3", "thin_out_conv")
@@ -200,8 +201,7 @@ BCE_RICH_SKIP = (("netG_A_B", "shift_conv"), ("netG_A_B", "scale_conv"))
 
 def _bce_check_digests(m, arr, pre, prec, flavour):
     """test_hip_step's digest check with BCE_RICH_SKIP on 'rich' in both precisions"""
-    import test_hip_step as S
-    S._check_digests(m, arr, pre, prec, flavour, skip=BCE_RICH_SKIP if flavour == "rich" else ())
+    check_digests(m, arr, pre, prec, flavour, skip=BCE_RICH_SKIP if flavour == "rich" else ())
 
 
 # After the first Adam update of the 'init' fixture the latent encoder's gradient norm is the most sensitive quantity of the
@@ -215,12 +215,11 @@ def _check_bce_steps(name, prec):
     """train_instance against a bce_step fixture, at test_hip_step's tolerances (STEP_TOL, REC_TOL, digests).  The fixtures
     store no inputs (oracle.recipe.inputs regenerates them from the seed; their digests are checked) and the images of the
     first meta["vis_samples"][k] samples of step k; losses, gradient norms and digests cover the whole batch."""
-    import test_hip_step as S
     from golden_util import digest
     from hip_util import t, n, rel
     from oracle import recipe
     arr, meta = load(name)
-    m = S.build_model(meta)
+    m = build_model(meta)
     o = m.opt
     pre = {nn_: {k: p.detach().cpu().numpy().copy() for k, p in net.named_parameters()} for nn_, net in m._net_dict().items()}
     for st in range(meta["steps"]):
@@ -229,7 +228,7 @@ def _check_bce_steps(name, prec):
         assert np.array_equal(z, arr["s%d/prior_z_B" % st])
         losses, visuals, gnorms = m.train_instance(t(A), t(B), t(z))
         assert list(losses.keys()) == meta["loss_keys"] and list(gnorms.keys()) == meta["gnorm_keys"]
-        lt, gt, vt = S.STEP_TOL[prec][0 if st == 0 else 1]
+        lt, gt, vt = STEP_TOL[prec][0 if st == 0 else 1]
         if prec == "bf16x3" and meta["flavour"] == "init" and st > 0:
             gt = BCE_X3_INIT_STEP1_GNORM_TOL
         got, ref = np.array(list(losses.values())), arr["s%d/losses" % st]
@@ -237,7 +236,7 @@ def _check_bce_steps(name, prec):
         gg, gr = np.array(list(gnorms.values())), arr["s%d/gnorms" % st]
         assert np.allclose(gg, gr, rtol=gt, atol=1e-6), (st, dict(zip(meta["gnorm_keys"], zip(gg, gr))))
         k = meta["vis_samples"][st]
-        rt = S.REC_TOL[(prec, meta["flavour"])][0 if st == 0 else 1]
+        rt = REC_TOL[(prec, meta["flavour"])][0 if st == 0 else 1]
         for key, tol in (("fake_B", vt), ("fake_A", vt), ("rec_A", rt), ("rec_B", rt)):
             ref = arr["s%d/%s" % (st, key)]
             assert ref.shape[0] == k
@@ -265,7 +264,6 @@ def test_bce_train_instance_matches_reference_golden(name, prec):
 
 # ---------------------------------------------------------------- public API
 def _opt(**kw):
-    from test_hip_step import make_opt
     return make_opt(**dict(dict(input_nc=3, output_nc=3, ngf=8, nef=8, ndf=8, nlatent=4, no_lsgan=True), **kw))
 
 
@@ -301,7 +299,7 @@ import numpy as np, torch
 import dtgan_amd
 from dtgan_amd import model as M
 from hip_util import load_recipe
-from test_hip_step import make_opt
+from model_cases import make_opt
 from oracle import recipe
 res = {}
 for graph in (False, True):

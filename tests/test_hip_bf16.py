@@ -13,8 +13,9 @@ pytestmark = pytest.mark.gpu
 
 from oracle import ops as oops  # noqa: E402
 from oracle.tape import backward, leaf  # noqa: E402
-from test_hip_ops import CONV_CASES, _conv_module  # noqa: E402
+from conv_cases import CONV_CASES, _conv_module, build  # noqa: E402
 from golden_util import load  # noqa: E402
+from model_cases import build_model  # noqa: E402
 
 
 @pytest.fixture(autouse=True)
@@ -96,7 +97,6 @@ def test_conv_transpose_bf16():
 @pytest.mark.parametrize("name", ["G_B_A_s16_nb3", "G_A_B_s16_nb9", "D_B_s40", "E_B_s64"])
 def test_nets_bf16_close_to_reference(name):
     from hip_util import t, n, rel, load_recipe
-    from test_hip_nets import build
     arr, meta = load(name)
     net = load_recipe(build(meta), meta["net"], meta["seed"], meta["flavour"])
     net.train()
@@ -123,7 +123,6 @@ def test_nets_bf16_close_to_reference(name):
 
 def test_step_bf16_close_to_reference():
     from hip_util import t
-    from test_hip_step import build_model
     arr, meta = load("step_aug_small_s64")
     m = build_model(meta)
     A, B, z = (t(arr["s0/%s" % k]) for k in ("real_A", "real_B", "prior_z_B"))

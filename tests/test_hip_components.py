@@ -11,7 +11,7 @@ import torch
 import components_ref as R
 import minkowski_ref as K
 from guard_util import GUARD, Buf
-from test_hip_minkowski import LAYOUTS, _device
+from field_cases import OFFSET_LAYOUTS as LAYOUTS, offset_operand as _device
 
 pytestmark = pytest.mark.gpu
 

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import components_ref as R
-from test_hip_minkowski_eval import S, experiment, model          # noqa: F401  (fixtures: the tiny model, the saved checkpoint)
+from eval_cases import SMOOTH_S as S, smooth_experiment as experiment, smooth_model as model  # noqa: F401  (fixtures: the tiny model, the saved checkpoint)
 
 pytestmark = pytest.mark.gpu
 

@@ -55,7 +55,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from test_hip_fastpath_fuzz import FAST, KROW, ROWS, S16_CASES, WS, _dev_t, _match, _nchw, _nhwc, _pad_c, _ref_device
+from conv_cases import FAST, KROW, ROWS, S16_CASES, WS, _dev_t, _match, _nchw, _nhwc, _pad_c, _ref_device
 
 pytestmark = pytest.mark.gpu
 

@@ -5,8 +5,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,11 +13,13 @@ import torch
 import cross_spectrum_ref as X
 import spectrum_ref as R
 from guard_util import GUARD, Buf
-from test_hip_spectrum import LAYOUTS, TAU, _device, _inputs, _model, _within
+from eval_cases import checkpoint_model, S as EVAL_S, count_sync_warnings as _count_sync_warnings, experiment, run_test  # noqa: F401  (the fixture)
+from field_cases import LAYOUTS, field_operand as _device
+from model_cases import ensemble_inputs as _inputs, ensemble_model as _model
+from spectrum_ref import TAU, within as _within
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = tuple(S for S, _, _ in X.PAIR_CASES)
 # |cxy - ref| <= CTAU (sqrt(pxx_ref Ey) + sqrt(pyy_ref Ex)) + CTAU^2 sqrt(Ex Ey) per bin, Ex, Ey the fields' mean squares: a
 # per-cell transform error of tau sqrt(E) S in each field and Cauchy-Schwarz over a ring.  Measured, not chosen:
@@ -265,7 +265,6 @@ def test_translate_coherence_refusals():
 
 
 def test_translate_coherence_host_syncs_do_not_grow_with_groups():
-    from test_hip_eval_bound import _count_sync_warnings
     m = _model()
     A, B, _ = _inputs(4, seed=7)
     M = 3
@@ -276,20 +275,14 @@ def test_translate_coherence_host_syncs_do_not_grow_with_groups():
 
 
 def test_metric_coherence(experiment):
-    from test_hip_eval_driver import S
-    from dtgan_amd import ops
-    from dtgan_amd import eval_metrics as EM, test as T
+    S = EVAL_S
+    from dtgan_amd import eval_metrics as EM
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
-    env = dict(os.environ, PYTHONPATH=ROOT)
     pat = (r"^DEV_KEFF_B: (\d+\.\d{4}), TEST_KEFF_B: (\d+\.\d{4}), TEST_KEFF_MEAN_B: (\d+\.\d{4}), TEST_KEFF_A: (\d+\.\d{4}), "
            r"TEST_COH_B: (\d+\.\d{4})$")
     runs = []
     for res_dir in ("res_coherence", "res_coherence_again"):
-        cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
-               "coherence", "--n_samples", "4", "--res_dir", res_dir]
-        p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-        out = p.stdout.decode(errors="replace")
-        assert p.returncode == 0, out[-4000:]
+        out = run_test(experiment, "coherence", "--n_samples", "4", "--res_dir", res_dir)
         mt = re.search(pat, out, re.M)
         assert mt, out[-2000:]
         runs.append((mt.groups(), dict(np.load(os.path.join(experiment["expr"], res_dir, "coherence.npz")))))
@@ -321,22 +314,11 @@ def test_metric_coherence(experiment):
     assert abs(float(line[1]) - arr["test_k_eff_members_B"].mean()) < 1e-4
     assert abs(float(line[4]) - arr["test_coh_members_B"][:, 1:].mean()) < 1e-4
     # the same numbers in process, from the same seed
-    import argparse
-    opt = argparse.Namespace(**T.parse_opt_file(os.path.join(experiment["expr"], "opt.pkl")))
-    opt.gpu_ids = [0]
-    prec = ops.get_precision()
-    ops.set_precision(opt.precision)
-    try:
-        model, _ = T._build(opt)
-        model.load(experiment["chk"])
+    with checkpoint_model(experiment) as model:
         torch.manual_seed(12345)
         EM.eval_coherence(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
         test = EM.eval_coherence(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
-    finally:
-        ops.set_precision(prec)
     for k in EM.COHERENCE_PAIRS:
         assert np.allclose(arr["test_sums_" + k], test["sums_" + k], rtol=1e-6), k
         assert np.array_equal(arr["test_k_eff_" + k], test["k_eff_" + k]), k
 
-
-from test_hip_eval_driver import experiment  # noqa: E402,F401  (the module-scoped fixture)

@@ -12,9 +12,8 @@ import pytest
 import torch
 
 import crps_ref as R
+from field_cases import PAIR_LAYOUTS as LAYOUTS, field_operand as _device, shifted as _shifted
 from guard_util import GUARD, Buf
-from test_hip_fss import _device
-from test_hip_fss_scales import LAYOUTS, _shifted
 
 pytestmark = pytest.mark.gpu
 
@@ -163,7 +162,7 @@ def test_guard_words_poisoned_outputs_and_repeatable_bits(H, W, Cp):
     sx, sy = (H * W * Cp, Cp, 1), (C * H * W, 1, H * W)
     runs = []
     for seed in (0, 1):
-        xd, yd = _device(x, "nhwc", C, Cp, seed=seed, nan=seed == 1), _device(y, "nchw", C)
+        xd, yd = _device(x, "nhwc", C, Cp, seed=seed, nan=0.3 * (seed == 1)), _device(y, "nchw", C)
         out = Buf.out(GUARD + 2 * N * C * 2)                       # doubles as pairs of NaN-poisoned words
         ws = Buf(GUARD + need // 4, dtype=np.uint32)               # 0xFFFFFFFF everywhere
         dx = Buf.out(GUARD + rows * H * W * Cp)

@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import ema_ref as E
+from eval_cases import write_dataset
+from model_cases import build_model
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +23,6 @@ AVERAGED = {True: ["netG_A_B", "netG_B_A", "netE_B"], False: ["netG_A_B", "netG_
 
 def _model(aug, tmp_path=None, **opt):
     """as tests/test_hip_step.py builds its graph models; the averages start at the recipe's parameters"""
-    from test_hip_step import build_model
     kw = dict(input_nc=1, output_nc=1, n_blocks=2)
     kw.update(opt)
     if tmp_path is not None:
@@ -270,11 +271,7 @@ def test_the_drivers_train_save_and_evaluate_the_averaged_weights(tmp_path):
     env["PYTHONPATH"] = ROOT
     S = 64
     data = tmp_path / "data"
-    data.mkdir()
-    rs = np.random.RandomState(0)
-    for split, n in (("train", 12), ("test", 5)):
-        for dom in "AB":
-            np.savez(str(data / ("%s%s.npz" % (split, dom))), data=rs.uniform(0, 3, (n, S, S, 3)).astype(np.float32))
+    write_dataset(data, (S, S), 12, 5)
     train = [sys.executable, "-m", "dtgan_amd.train", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--grid_size", str(S),
              "--batchSize", "4", "--niter", "1", "--niter_decay", "0", "--n_blocks", "2", "--step_graph", "--ngf", "8", "--nef", "8",
              "--ndf", "8", "--nlatent", "4", "--print_freq", "4", "--display_freq", "8", "--save_epoch_freq", "1", "--eval_steps", "2",

@@ -2,18 +2,17 @@
 generate_multi and the reference, and `python -m dtgan_amd.test --metric ensemble` in a child process."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from ensemble_ref import ensemble_stats as ref_stats
+from eval_cases import checkpoint_model, S as EVAL_S, count_sync_warnings as _count_sync_warnings, experiment, png_shape as _png_shape, run_test  # noqa: F401  (the fixture)
+from model_cases import ensemble_inputs as _inputs, ensemble_model as _model
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QS = (0.0, 0.05, 0.5, 0.95, 1.0)
 
 
@@ -88,21 +87,6 @@ def test_kernel_refuses_bad_arguments_before_launching():
             assert torch.equal(out[k], sentinel[k]), k                 # nothing was written
 
 
-def _model(kind="aug"):
-    from test_hip_api import _model as api_model
-    m = api_model(aug=kind == "aug")
-    if kind == "cycle_gan":
-        m.ignore_noise = True
-    return m
-
-
-def _inputs(N, S=64, seed=3):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    A = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    B = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    return A, B, g
-
-
 @pytest.mark.parametrize("prec", ["f32", "bf16x3"])
 def test_translate_ensemble_equals_generate_multi_and_the_reference(prec):
     from hip_util import precision
@@ -145,7 +129,6 @@ def test_cycle_gan_gives_a_degenerate_ensemble():
 
 
 def test_translate_ensemble_host_syncs_do_not_grow_with_groups():
-    from test_hip_eval_bound import _count_sync_warnings
     m = _model()
     A, B, _ = _inputs(4, seed=7)
     M = 3
@@ -206,16 +189,10 @@ def test_flags_and_grad_mode_survive_a_raising_consumer(which, monkeypatch):
 
 
 def test_metric_ensemble(experiment):
-    from test_hip_eval_driver import _png_shape, S
-    from dtgan_amd import ops
-    from dtgan_amd import eval_metrics as EM, test as T
+    S = EVAL_S
+    from dtgan_amd import eval_metrics as EM
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
-           "ensemble", "--n_samples", "4", "--res_dir", "res_ensemble"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_test(experiment, "ensemble", "--n_samples", "4", "--res_dir", "res_ensemble")
     pat = r"^DEV_CRPS_B: (\d+\.\d{4}), TEST_CRPS_B: (\d+\.\d{4}), TEST_MSE_MEAN_B: (\d+\.\d{4}), TEST_SPREAD_B: (\d+\.\d{4}), " \
           r"TEST_COVERAGE_B: (\d+\.\d{4})$"
     mt = re.search(pat, out, re.M)
@@ -230,22 +207,11 @@ def test_metric_ensemble(experiment):
         assert h.shape == (5,) and h.sum() == n * 3 * S * S
     assert _png_shape(os.path.join(res, "ensemble_0.png")) == (2 + 6 * (S + 2), 2 + 6 * (S + 2))
     # the same numbers in process, from the same seed
-    import argparse
-    opt = argparse.Namespace(**T.parse_opt_file(os.path.join(experiment["expr"], "opt.pkl")))
-    opt.gpu_ids = [0]
-    prec = ops.get_precision()
-    ops.set_precision(opt.precision)
-    try:
-        model, _ = T._build(opt)
-        model.load(experiment["chk"])
+    with checkpoint_model(experiment) as model:
         _, _, devA, devB, testA, testB = load_numpy_data(experiment["data"], grid_size=S)
         torch.manual_seed(12345)
         EM.eval_ensemble_B(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4, (0.05, 0.5, 0.95))
         test, _ = EM.eval_ensemble_B(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4, (0.05, 0.5, 0.95))
-    finally:
-        ops.set_precision(prec)
     assert abs(float(mt.group(2)) - test["crps"].mean()) < 1e-4, (mt.group(2), test["crps"].mean())
     assert np.allclose(arr["test_crps"], test["crps"], rtol=1e-6)
 
-
-from test_hip_eval_driver import experiment  # noqa: E402,F401  (the module-scoped fixture)

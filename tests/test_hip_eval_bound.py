@@ -3,7 +3,6 @@ NumPy, acg_latent_bound_step against a NumPy restatement of torch's clamp mask a
 evaluate.variational_ubo against the reference's numbers, its host synchronisations, and its scratch next to a captured
 training step."""
 import math
-import warnings
 
 import numpy as np
 import pytest
@@ -12,7 +11,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from golden_util import load  # noqa: E402
-from test_hip_api import _model  # noqa: E402
+from eval_cases import count_sync_warnings as _count_sync_warnings  # noqa: E402
+from model_cases import build_model, tiny_model as _model  # noqa: E402
 
 
 def _ptr(x):
@@ -237,18 +237,6 @@ def test_bound_variants_match_reference_golden(name, prec):
         assert (ubo, kld, bpp) == trace[-1][:3]
 
 
-def _count_sync_warnings(fn):
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return sum("synchroniz" in str(w.message) for w in caught)
-
-
 def test_bound_host_syncs_do_not_grow_with_steps():
     """the per-iterate numbers stay on the device: a batch of the bound synchronises with the host a fixed number of
     times, whatever the number of iterates (the torch tail synchronised twice per iterate)"""
@@ -272,7 +260,6 @@ def test_bound_between_step_graph_replays_keeps_the_graph_scratch():
     (test_hip_step.test_step_graph_owns_its_scratch's pattern)"""
     from dtgan_amd import evaluate as E
     from dtgan_amd import ops
-    from test_hip_step import build_model
     gr = build_model(dict(opt=dict(input_nc=1, output_nc=1, n_blocks=2), aug=True, seed=5, flavour="init"))
     gr.enable_step_graph()
     g = torch.Generator(device="cuda").manual_seed(4)

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 from eval_draws import driver_draws  # noqa: E402
 from golden_util import load  # noqa: E402
-from test_hip_api import _model  # noqa: E402
+from model_cases import tiny_model as _model  # noqa: E402
 
 
 class _FixedNormal(object):

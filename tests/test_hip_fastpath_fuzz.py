@@ -29,6 +29,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from conv_cases import (FAST, KROW, KROW_S, KROWG, PATCHN, PH4, ROWS, RP, S16_CASES, THINROW, THINW, WS, _dev_t, _match, _nchw, _nhwc, _pad_c,  # noqa: E402
+                        _ref_device)
+
 pytestmark = pytest.mark.gpu
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -66,20 +69,7 @@ def wgrad_plan(fam, K, Cx, Cg, N, Ho, Wo):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # module-level cases: (family, inside, K, stride, pad, mode, Ci, Co, N, H, W, transpose)
-# transpose: nn.ConvTranspose2d(Ci, Co, 3, 2, 1, output_padding=1) on an N x Ci x H x W input
-
-ROWS = "conv_rows_x3<32,64>"
-RP = "RP=1"
-WS = "igemm_conv_x3_ws"
-KROW = "=wgrad_x3_krow"              # '=': the whole kernel name (wgrad_x3_krow is a prefix of its siblings)
-KROW_S = "wgrad_x3_krow_s<"
-KROWG = "wgrad_x3_krowg<"
-PH4 = "igemm_conv_ph4"
-THINROW = "conv_thinrow_x3"
-PATCHN = "conv_patchn_x3"
-THINW = "wgrad_thin_patch_x3"
-FAST = [ROWS, RP, WS, "igemm_conv_x3_pre", PH4, "wgrad_x3_krow", THINROW, PATCHN, THINW]
-
+# transpose: nn.ConvTranspose2d(Ci, Co, 3, 2, 1, output_padding=1) on an N x Ci x H x W input; kernel names: conv_cases
 
 def _c(fam, inside, K, s, p, mode, Ci, Co, N, H, W, tr=False):
     return (fam, inside, K, s, p, mode, Ci, Co, N, H, W, tr)
@@ -275,21 +265,6 @@ def test_case_list_is_fixed_and_plans_cover_the_branches():
     assert ns == 12 and per == 1088 and last == 992 and (45 * 96) % per != 0
 
 
-_REF_DEV = []
-
-
-def _ref_device():
-    if not _REF_DEV:
-        dev = "cuda"
-        try:
-            a = torch.ones((1, 1, 3, 3), dtype=torch.float64, device=dev)
-            F.conv2d(a, a, padding=1).sum().item()
-        except RuntimeError:
-            dev = "cpu"
-        _REF_DEV.append(dev)
-    return _REF_DEV[0]
-
-
 def _reference(case, x, w, b, r):
     """fp64 forward + autograd for dx, dw, db"""
     fam, inside, K, s, p, mode, Ci, Co, N, H, W, tr = case
@@ -315,10 +290,6 @@ def _inputs(case):
     Ho, Wo = _out_hw(case)
     r = rs.normal(0, 1, (N, Co, Ho, Wo))
     return x, w, b, r
-
-
-def _match(want, k):
-    return k == want[1:] if want.startswith("=") else want in k
 
 
 def _run_module_case(case, prec):
@@ -378,27 +349,6 @@ def test_fast_path_against_fp64(case, prec):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # fused side outputs through the C ABI
-
-def _nhwc(a):
-    return np.ascontiguousarray(np.transpose(a, (0, 2, 3, 1)))
-
-
-def _nchw(a):
-    return np.transpose(a, (0, 3, 1, 2))
-
-
-def _dev_t(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def _pad_c(a, C, axis):
-    """zero-pad a channel axis to the stored width"""
-    if a.shape[axis] == C:
-        return a
-    pad = [(0, 0)] * a.ndim
-    pad[axis] = (0, C - a.shape[axis])
-    return np.pad(a, pad)
-
 
 # (K, stride, pad, mode, Ci, Co, N, H, W, transpose) whose forward may emit per-tile statistics
 STATS_CASES = [
@@ -564,13 +514,7 @@ def test_data_gradient_sums_against_fp64(case, variant):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# pre-split trunk: (N, H, W, Ci, Co) of a 3x3 reflect pad-1 layer inside acg_conv2d_s16_supported
-S16_CASES = [
-    (1, 8, 32, 128, 128), (2, 13, 96, 128, 256), (3, 40, 64, 256, 128), (1, 63, 128, 128, 128), (2, 64, 96, 128, 128),
-    (1, 64, 128, 128, 128), (2, 96, 256, 128, 128), (1, 64, 384, 256, 128), (3, 64, 128, 128, 256), (1, 128, 640, 128, 128),
-]
-
-
+# pre-split trunk: conv_cases.S16_CASES, (N, H, W, Ci, Co) of a 3x3 reflect pad-1 layer inside acg_conv2d_s16_supported
 def _unpad(N, H, W, Ci, Co):
     return W % 128 == 0 and H % 32 == 0 and H >= 64
 

@@ -13,20 +13,14 @@ import torch
 import cross_spectrum_ref as X
 import field_spectrum_ref as F
 import spectrum_ref as R
-from test_hip_spectrum import LAYOUTS
+from eval_cases import make_experiment
+from field_cases import LAYOUTS, field_operand as _device
+from field_spectrum_ref import CTAU, TAU      # the bars, stated beside the reference
+from model_cases import tiny_model
 
 pytestmark = pytest.mark.gpu
 
 ROWS = 2
-# |psd - ref| <= TAU sqrt(ref E) + TAU^2 E per bin, E the field's mean square.  Measured, not chosen: the float32 Bluestein
-# restatement on torch.fft of complex64 on the CPU, binned in float64, needs tau = 3.1424e-4 over every bin, kind and shape of
-# F.SHAPES (`python tools/field_spectrum_bench.py --cpu-tolerance`; the largest is the constant-plus-noise field at
-# 1023 x 513, M = 2048 on both axes: the DC coefficient of 0.7 H W goes through two padded transforms and back).  The constant
-# is 4 x that: a different butterfly order, as in test_hip_spectrum.
-TAU = 4 * 3.1424e-4
-# |cxy - ref| <= CTAU (sqrt(pxx_ref Ey) + sqrt(pyy_ref Ex)) + CTAU^2 sqrt(Ex Ey) per bin (cross_spectrum_ref.cross_bound): the
-# same run needs 3.7226e-5 for the co-spectrum of F.make_pair over those shapes (the largest at 1023 x 513); 4 x that.
-CTAU = 4 * 3.7226e-5
 EVEN_W = ((18, 30), (31, 16), (20, 28), (1024, 1000))
 
 
@@ -35,17 +29,6 @@ def _case(kind, H, W):
     """the fields (ROWS, 3, H, W), their reference spectra and mean squares"""
     x = F.make_fields(kind, H, W, rows=ROWS, C=3)
     return x, F.rapsd(x), np.mean(x.astype(np.float64) ** 2, axis=(-2, -1))
-
-
-def _device(x, layout, C, Cp, seed=0):
-    """the first C channels of x (rows, 3, H, W) on the device in the layout; NHWC: +-50 garbage in the padded channels"""
-    x = x[:, :C]
-    if layout == "nchw":
-        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    rows, _, H, W = x.shape
-    t = np.random.RandomState(seed).uniform(-50, 50, (rows, H, W, Cp)).astype(np.float32)
-    t[..., :C] = np.moveaxis(x, 1, 3)
-    return torch.from_numpy(t).cuda()
 
 
 def _spectrum(xd, C, layout):
@@ -63,10 +46,7 @@ def _cross(xd, yd, C, lx, ly, x_per_y=1):
 
 
 def _within(psd, ref, E, what):
-    d = np.abs(psd.astype(np.float64) - ref)
-    bound = TAU * np.sqrt(ref * E[..., None]) + TAU ** 2 * E[..., None]
-    print("%s: tau needed %.3e (allowed %.3e)" % (what, R.tolerance_needed(psd, ref, E), TAU))
-    assert np.all(np.isfinite(psd)) and np.all(d <= bound), (what, float((d / bound).max()), np.argwhere(d > bound)[:5])
+    R.within(psd, ref, E, what, TAU)
 
 
 def _same_bits(a, b):
@@ -275,8 +255,7 @@ S = 16
 
 @pytest.fixture(scope="module")
 def model():
-    from test_hip_api import _model
-    return _model(grid_size=S, n_blocks=1)
+    return tiny_model(grid_size=S, n_blocks=1)
 
 
 def _rand(*shape, seed=0):
@@ -330,28 +309,11 @@ def test_whole_fields_equal_a_composition_made_here(model):
 
 
 # ---- the driver ----
-def _dataset(root, hw, n_train, n_test, seed=0):
-    os.makedirs(str(root), exist_ok=True)
-    rs = np.random.RandomState(seed)
-    for split, n in (("train", n_train), ("test", n_test)):
-        for dom in "AB":
-            np.savez(os.path.join(str(root), split + dom + ".npz"), data=rs.uniform(0, 3, (n,) + hw + (3,)).astype(np.float32))
-
-
 @pytest.fixture(scope="module")
 def experiment(tmp_path_factory):
     """20 x 28 fields (6 train -> 3 dev + 3 train, 2 test) and the checkpoint of a seeded 16 x 16 model: the recipe of
     tests/test_hip_translate_field.py"""
-    from dtgan_amd import options as O
-    from dtgan_amd.model import AugmentedCycleGAN
-    root = tmp_path_factory.mktemp("field_spectrum_driver")
-    _dataset(root / "data", (20, 28), n_train=6, n_test=2, seed=1)
-    opt = O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(root), "--dataroot", str(root / "data"),
-                                       "--grid_size", str(S), "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
-                                       "--n_blocks", "1", "--seed", "3", "--native_res"])
-    torch.manual_seed(3)
-    AugmentedCycleGAN(opt).save("latest")
-    return dict(chk=os.path.join(opt.expr_dir, "latest"), data=str(root / "data"), expr=opt.expr_dir)
+    return make_experiment(tmp_path_factory.mktemp("field_spectrum_driver"), S, 6, 2, hw=(20, 28), seed=1, native_res=True)
 
 
 def test_metric_field_spectrum_writes_both_families_and_repeats(experiment, capsys):

@@ -5,36 +5,21 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import fss_ref as F
+from eval_cases import checkpoint_model, S as EVAL_S, count_sync_warnings as _count_sync_warnings, experiment, run_test  # noqa: F401  (the fixture)
+from field_cases import field_operand as _device
 from guard_util import GUARD, Buf
+from model_cases import ensemble_inputs as _inputs, ensemble_model as _model
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # x in every layout crossed with a planar and an NHWC truth: (layout x, stored channels x, layout y, stored channels y)
 LAYOUTS = [(lx, cpx, ly, cpy) for lx, cpx in (("nchw", 0), ("nhwc", 4), ("nhwc", 16)) for ly, cpy in (("nchw", 0), ("nhwc", 4))]
-
-
-def _device(x, layout, C, Cp=0, seed=0, nan=False):
-    """the first C channels of x (rows, >= C, H, W) on the device in the layout; NHWC: +-50 garbage (nan: and NaNs) in the
-    padded channels"""
-    x = x[:, :C]
-    if layout == "nchw":
-        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    rows, _, H, W = x.shape
-    rs = np.random.RandomState(seed)
-    t = rs.uniform(-50, 50, (rows, H, W, Cp)).astype(np.float32)
-    if nan:
-        t[rs.uniform(size=t.shape) < 0.3] = np.nan
-    t[..., :C] = np.moveaxis(x, 1, 3)
-    return torch.from_numpy(t).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,7 +136,7 @@ def test_guard_words_and_padded_channels(H, W):
     need = lib.acg_fss_workspace_bytes(4, M, C, H, W, T, nw, 1)
     assert need % 16 == 0 and need > 0
     for seed in (0, 1):
-        xd, yd = _device(x, "nhwc", C, 4, seed=seed, nan=seed == 1), _device(y, "nhwc", C, 16, seed=10 + seed, nan=seed == 1)
+        xd, yd = _device(x, "nhwc", C, 4, seed=seed, nan=0.3 * (seed == 1)), _device(y, "nhwc", C, 16, seed=10 + seed, nan=0.3 * (seed == 1))
         n_out, n_ens = 4 * C * T * nw * 3, 2 * C * T * nw * 3
         out, ens = Buf.out(GUARD + 2 * n_out, np.uint32), Buf.out(GUARD + 2 * n_ens, np.uint32)
         ws = Buf(GUARD + need // 4, dtype=np.uint32)
@@ -275,20 +260,7 @@ def test_kernel_refuses_bad_arguments_before_launching():
     torch.cuda.synchronize()
 
 
-def _model():
-    from test_hip_spectrum import _model as m
-    return m()
-
-
-def _inputs(N, S, seed=3):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    A = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    B = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    return A, B, g
-
-
-THR = np.array([[-0.1, 0.0, 0.2], [-0.2, 0.05, 0.3], [0.0, 0.1, 0.5]], dtype=np.float32)
-WIN = (1, 3, 9, 33)
+THR, WIN = F.THR, F.WIN
 
 
 @pytest.mark.parametrize("S", (64, 48))
@@ -339,7 +311,6 @@ def test_translate_fss_refusals():
 
 
 def test_translate_fss_host_syncs_do_not_grow_with_groups():
-    from test_hip_eval_bound import _count_sync_warnings
     m = _model()
     A, B, _ = _inputs(4, 64, seed=7)
     M = 3
@@ -351,21 +322,15 @@ def test_translate_fss_host_syncs_do_not_grow_with_groups():
 
 
 def test_metric_fss(experiment):
-    from test_hip_eval_driver import S
-    from dtgan_amd import ops
-    from dtgan_amd import eval_metrics as EM, test as T
+    S = EVAL_S
+    from dtgan_amd import eval_metrics as EM
     from dtgan_amd.dataloader import load_numpy_data
-    env = dict(os.environ, PYTHONPATH=ROOT)
     num = r"(\d+\.\d{4}|nan)"
     pat = (r"^DEV_FSS_B: %s, TEST_FSS_B: %s, TEST_FSS_PROB_B: %s, TEST_FSS_MEAN_B: %s, TEST_FSS_A: %s, TEST_USEFUL_SCALE_B: %s$"
            % ((num,) * 6))
     runs = []
     for res_dir in ("res_fss", "res_fss_again"):
-        cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
-               "fss", "--n_samples", "4", "--fss_windows", "3,9,17", "--res_dir", res_dir]
-        p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-        out = p.stdout.decode(errors="replace")
-        assert p.returncode == 0, out[-4000:]
+        out = run_test(experiment, "fss", "--n_samples", "4", "--fss_windows", "3,9,17", "--res_dir", res_dir)
         mt = re.search(pat, out, re.M)
         assert mt, out[-2000:]
         runs.append((mt.groups(), dict(np.load(os.path.join(experiment["expr"], res_dir, "fss.npz")))))
@@ -408,19 +373,8 @@ def test_metric_fss(experiment):
         assert (line[i] == "nan" and np.all(np.isnan(v))) or abs(float(line[i]) - np.nanmean(v)) < 1e-4, (key, line[i], v)
     assert abs(float(line[5]) - arr["test_useful_scale_members_B"][:, t].mean()) < 1e-4
     # B -> A in process: the reference on predict_A's fields gives the file's sums, exactly
-    import argparse
-    opt = argparse.Namespace(**T.parse_opt_file(os.path.join(experiment["expr"], "opt.pkl")))
-    opt.gpu_ids = [0]
-    prec = ops.get_precision()
-    ops.set_precision(opt.precision)
-    try:
-        model, _ = T._build(opt)
-        model.load(experiment["chk"])
+    with checkpoint_model(experiment) as model:
         with torch.no_grad():
             fake_A = model.predict_A(torch.as_tensor(np.asarray(testB)).cuda()).cpu().numpy()
-    finally:
-        ops.set_precision(prec)
     assert np.array_equal(arr["test_sums_fake_A"], F.triples(fake_A, np.asarray(testA), arr["thresholds_A"], win).sum(0))
 
-
-from test_hip_eval_driver import experiment  # noqa: E402,F401  (the module-scoped fixture)

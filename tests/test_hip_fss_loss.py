@@ -15,8 +15,8 @@ import torch
 
 import fss_loss_ref as R
 import fss_ref as F
+from field_cases import field_operand as _device
 from guard_util import GUARD, Buf
-from test_hip_fss import _device
 
 pytestmark = pytest.mark.gpu
 
@@ -197,7 +197,7 @@ def test_guard_words_poisoned_outputs_and_repeatable_bits(k):
     sx, sy = (H * W * Cp, Cp, 1), (C * H * W, 1, H * W)
     runs = []
     for seed in (0, 1):
-        xd, yd = _device(x, "nhwc", C, Cp, seed=seed, nan=seed == 1), _device(y, "nchw", C)
+        xd, yd = _device(x, "nhwc", C, Cp, seed=seed, nan=0.3 * (seed == 1)), _device(y, "nchw", C)
         out = Buf.out(GUARD + 2 * rows * C * T * nw * 2)           # doubles as pairs of NaN-poisoned words
         ws = Buf(GUARD + need // 4, dtype=np.uint32)               # 0xFFFFFFFF everywhere
         dx = Buf.out(GUARD + rows * H * W * Cp)

@@ -3,26 +3,24 @@ forced one-rank exchange, and `python -m dtgan_amd.train --supervised --lambda_f
 import os
 import pickle
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import fss_loss_ref as R
-from test_hip_ssim_step import S, _flat, _inputs, _model
+from model_cases import (SUP_GNORMS as GNORMS, SUP_KEYS as BASE, check_captured_and_deferred, flat as _flat, forced_pair, run_module,
+                         step_inputs as _inputs, step_model as _model)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BASE = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B']
-GNORMS = ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
 FSS = ['S_fss_A', 'S_fss_B']
 THR = [[0.0, 0.5], [0.1, 0.6], [-0.1, 0.4]]
 WINDOWS, TAU = (3, 9, 17), 0.05
 ON = dict(fss_loss_windows=WINDOWS, fss_tau=TAU, fss_loss_thr_A=THR, fss_loss_thr_B=THR)
+# the options of the forced-exchange worker
+WORKER = dict(lambda_fss_A=0.2, lambda_fss_B=0.1, fss_loss_windows=(3, 9), fss_tau=0.05, fss_loss_thr_A=[[0.0, 0.5]] * 3,
+              fss_loss_thr_B=[[0.0, 0.5]] * 3)
 
 
 def _spy(monkeypatch):
@@ -108,61 +106,16 @@ def test_the_names_come_in_order_with_the_ssim_and_crps_pairs():
 def test_captured_and_deferred_paired_steps_with_the_term_on():
     """two eager warm-up calls, the capture and its replay: the first replayed step equals the eager model's bit for bit; the
     deferred scalars are the synchronous graph's; one capture, and a change of each option captures again"""
-    from dtgan_amd import model as M
-    kw = dict(lambda_fss_A=0.25, lambda_fss_B=0.5, **ON)
-    ref, gr, lazy = _model(True, **kw), _model(True, **kw), _model(True, **kw)
-    gr.enable_step_graph(); lazy.enable_step_graph(defer_scalars=True)
-    g = torch.Generator(device="cuda").manual_seed(11)
-    prev = None
-    for step in range(4):
-        A = torch.rand(4, 3, S, S, device="cuda", generator=g) * 2 - 1
-        B = torch.rand(4, 3, S, S, device="cuda", generator=g) * 2 - 1
-        z = torch.randn(4, 4, 1, 1, device="cuda", generator=g)
-        vr, vg = ref.supervised_train_instance(A, B, z), gr.supervised_train_instance(A, B, z)
-        out = lazy.supervised_train_instance(A, B, z)
-        assert list(vg.keys()) == BASE + FSS + GNORMS == list(vr.keys())
-        if prev is not None:
-            assert prev[0].result() == prev[1]
-            prev = None
-        if isinstance(out, M.DeferredStep):
-            prev = (out, vg)
-        else:
-            assert step < 2 and out == vg
-        if step <= 2:
-            assert vg == vr, (step, vg, vr)
-        else:
-            for k in vr:
-                assert abs(vr[k] - vg[k]) <= 2e-3 * max(1.0, abs(vr[k])), (step, k, vr[k], vg[k])
-    assert prev is not None and prev[0].result() == prev[1]
-    assert gr._sup_step_graph.captures == 1
-    for name, value in (("lambda_fss_B", 0.125), ("fss_tau", 0.1), ("fss_loss_windows", [3, 5]),
-                        ("fss_loss_thr_B", [[0.2, 0.3]] * 3)):
-        before = gr._sup_step_graph.captures
-        setattr(gr.opt, name, value)
-        v = gr.supervised_train_instance(A, B, z)
-        assert gr._sup_step_graph.captures == before + 1 and np.isfinite(v["S_fss_A"]) and np.isfinite(v["S_fss_B"]), name
-    gr.opt.lambda_fss_A = gr.opt.lambda_fss_B = 0.0                # off: the eight keys again
-    assert list(gr.supervised_train_instance(A, B, z).keys()) == BASE + GNORMS
-
-
-def _worker(tmp_path, name, **extra_env):
-    out = str(tmp_path / (name + ".npz"))
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ACGAN_DIST_FORCE")}
-    env.update(extra_env)
-    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, os.path.join(HERE, "fss_loss_dp_worker.py"), out], env=env,
-                       capture_output=True, text=True, timeout=660)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    return np.load(out)
+    check_captured_and_deferred("supervised_train_instance", dict(lambda_fss_A=0.25, lambda_fss_B=0.5, **ON), BASE + FSS + GNORMS,
+                                (("lambda_fss_B", 0.125), ("fss_tau", 0.1), ("fss_loss_windows", [3, 5]), ("fss_loss_thr_B", [[0.2, 0.3]] * 3)),
+                                dict(lambda_fss_A=0.0, lambda_fss_B=0.0), BASE + GNORMS)
 
 
 def test_the_forced_one_rank_exchange_reports_the_same_scalars(tmp_path):
     """S_fss_A / S_fss_B ride in the rank-averaged sums of the encoder's gradient tail: with one rank and every collective
     forced the paired step's scalars are the plain step's, compared as test_hip_crps_step.py compares them: step 0 but for
     the tail's float64 average of one value, 1e-6; step 1 follows an Adam update"""
-    plain = _worker(tmp_path, "plain")
-    forced = _worker(tmp_path, "forced", ACGAN_DIST_FORCE="1", ACGAN_DP_BACKEND="nccl", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
-                     MASTER_ADDR="127.0.0.1", MASTER_PORT="29578", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    assert int(plain["forced"]) == 0 and int(forced["forced"]) == 1
+    plain, forced = forced_pair(tmp_path, "supervised_train_instance", WORKER, "29578")
     assert list(plain["s0/names"]) == BASE + FSS + GNORMS == list(forced["s0/names"])
     print("step 0 largest relative difference %.3e" % np.max(np.abs(forced["s0/values"] - plain["s0/values"]) / np.abs(plain["s0/values"])))
     assert np.allclose(forced["s0/values"], plain["s0/values"], rtol=1e-6, atol=1e-9), (forced["s0/values"], plain["s0/values"])
@@ -171,15 +124,10 @@ def test_the_forced_one_rank_exchange_reports_the_same_scalars(tmp_path):
 
 def test_train_driver_with_the_fss_term(tmp_path):
     """--sup_frac 0.5: four of the eight synthetic pairs form the paired batch (the default tenth of eight is none)"""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    env["PYTHONPATH"] = ROOT
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "dtgan_amd.train", "--name", "fss", "--checkpoints_dir", str(tmp_path),
-           "--synthetic", "8", "--grid_size", "64", "--batchSize", "4", "--supervised", "--lambda_fss_B", "0.5", "--sup_frac", "0.5",
-           "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4", "--niter", "1", "--niter_decay", "0", "--eval_steps", "1",
-           "--num_multi", "2", "--print_freq", "4", "--display_freq", "8", "--seed", "1"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=660)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_module("train", "--name", "fss", "--checkpoints_dir", tmp_path,
+                     "--synthetic", "8", "--grid_size", "64", "--batchSize", "4", "--supervised", "--lambda_fss_B", "0.5", "--sup_frac", "0.5",
+                     "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4", "--niter", "1", "--niter_decay", "0", "--eval_steps", "1",
+                     "--num_multi", "2", "--print_freq", "4", "--display_freq", "8", "--seed", "1")
     d = os.path.join(str(tmp_path), "fss")
     log = open(os.path.join(d, "results.txt")).read()
     for side in "AB":                                              # U(-1, 1): the 0.9 and 0.99 quantiles, per channel

@@ -5,8 +5,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,26 +12,13 @@ import torch
 
 import fss_ref as F
 import fss_scales_ref as R
+from eval_cases import checkpoint_model, S as EVAL_S, count_sync_warnings as _count_sync_warnings, experiment, run_test  # noqa: F401  (the fixture)
+from field_cases import PAIR_LAYOUTS as LAYOUTS, field_operand as _device, shifted as _shifted
+from fss_ref import THR, WIN
 from guard_util import GUARD, Buf
-from test_hip_fss import THR, WIN, _device, _inputs, _model
+from model_cases import ensemble_inputs as _inputs, ensemble_model as _model
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# (layout x, stored channels x, floats x starts off the 16-byte grid, layout y, stored channels y): planar, a pixel's channels
-# in one 16-byte load, and the pixel-by-pixel path for a wide pixel and for an unaligned one
-LAYOUTS = (("nchw", 0, 0, "nchw", 0), ("nhwc", 4, 0, "nhwc", 4), ("nhwc", 16, 0, "nchw", 0), ("nhwc", 4, 1, "nhwc", 4))
-
-
-def _shifted(t, off):
-    """the same tensor `off` floats behind a 16-byte boundary"""
-    if not off:
-        return t
-    flat = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
-    assert flat.data_ptr() % 16 == 0
-    flat[off:off + t.numel()].copy_(t.reshape(-1))
-    return flat[off:off + t.numel()].view(t.shape)
-
 
 @functools.lru_cache(maxsize=None)
 def _case(kind, H, W):
@@ -153,7 +138,7 @@ def test_guard_words_and_padded_channels(H, W):
     need = lib.acg_fss_scales_workspace_bytes(4, M, C, H, W, T, 1)
     assert need % 16 == 0 and need > 0
     for seed in (0, 1):
-        xd, yd = _device(x, "nhwc", C, 4, seed=seed, nan=seed == 1), _device(y, "nhwc", C, 16, seed=10 + seed, nan=seed == 1)
+        xd, yd = _device(x, "nhwc", C, 4, seed=seed, nan=0.3 * (seed == 1)), _device(y, "nhwc", C, 16, seed=10 + seed, nan=0.3 * (seed == 1))
         n_out, n_ens = 4 * C * T * nl * 3, 2 * C * T * nl * 3
         out, ens = Buf.out(GUARD + 2 * n_out, np.uint32), Buf.out(GUARD + 2 * n_ens, np.uint32)
         ws = Buf(GUARD + need // 4, dtype=np.uint32)               # 0xFFFFFFFF everywhere
@@ -285,7 +270,6 @@ def test_translate_fss_scales_equals_generate_multi_and_the_reference(prec, S):
 
 
 def test_translate_fss_scales_host_syncs_do_not_grow_with_groups():
-    from test_hip_eval_bound import _count_sync_warnings
     m = _model()
     A, B, _ = _inputs(4, 64, seed=7)
     M = 3
@@ -298,18 +282,13 @@ def test_translate_fss_scales_host_syncs_do_not_grow_with_groups():
 
 
 def _run(experiment, res_dir, *extra):
-    cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric", "fss",
-           "--n_samples", "4", "--fss_windows", "3,9,17", "--res_dir", res_dir] + list(extra)
-    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_test(experiment, "fss", "--n_samples", "4", "--fss_windows", "3,9,17", "--res_dir", res_dir, *extra)
     return out, dict(np.load(os.path.join(experiment["expr"], res_dir, "fss.npz")))
 
 
 def test_metric_fss_with_scales(experiment):
-    from test_hip_eval_driver import S
-    from dtgan_amd import ops
-    from dtgan_amd import eval_metrics as EM, test as T
+    S = EVAL_S
+    from dtgan_amd import eval_metrics as EM
     from dtgan_amd.dataloader import load_numpy_data
     out0, arr0 = _run(experiment, "res_fss_scales_off", "--fss_scales", "0")
     out1, arr1 = _run(experiment, "res_fss_scales_on", "--fss_scales", "1")
@@ -365,20 +344,9 @@ def test_metric_fss_with_scales(experiment):
     for i, k in enumerate(EM.FSS_PAIRS):
         assert abs(float(line[2 + i]) - arr1["test_skill_scale_" + k][:, t].mean()) < 1e-4, k
     # B -> A in process: the reference on predict_A's fields gives the file's sums, exactly, on both splits
-    import argparse
-    opt = argparse.Namespace(**T.parse_opt_file(os.path.join(experiment["expr"], "opt.pkl")))
-    opt.gpu_ids = [0]
-    prec = ops.get_precision()
-    ops.set_precision(opt.precision)
-    try:
-        model, _ = T._build(opt)
-        model.load(experiment["chk"])
+    with checkpoint_model(experiment) as model:
         for split, A, B in (("dev", devA, devB), ("test", testA, testB)):
             with torch.no_grad():
                 fake_A = model.predict_A(torch.as_tensor(np.asarray(B)).cuda()).cpu().numpy()
             assert np.array_equal(arr1[split + "_scale_sums_fake_A"], R.triples(fake_A, np.asarray(A), arr1["thresholds_A"]).sum(0)), split
-    finally:
-        ops.set_precision(prec)
 
-
-from test_hip_eval_driver import experiment  # noqa: E402,F401  (the module-scoped fixture)

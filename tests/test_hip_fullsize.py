@@ -19,7 +19,8 @@ import torch.nn as nn
 
 pytestmark = pytest.mark.gpu
 
-from test_hip_step import make_opt  # noqa: E402
+from conv_cases import _ORACLE_CACHE, _matches_oracle, _oracle_step, _run_cfg  # noqa: E402
+from model_cases import make_opt  # noqa: E402
 
 FULL = dict(input_nc=3, output_nc=3, ngf=32, nef=32, ndf=64, nlatent=16, n_blocks=9)
 S, N = 256, 4  # >= 3: the latent discriminator / encoder end in BatchNorm over the batch
@@ -151,22 +152,6 @@ CFG5_FUSED = {"conv_fwd_s16": 18, "conv_fwd_s16_relu_bitmask": 6, "wgrad_s16": 2
               "packed_weights_multi": 32}
 
 
-def _run_cfg(kw, S, Nb, prec, steps=1, seed=0, in_seed=60):
-    from hip_util import t, n, precision, load_recipe
-    from dtgan_amd import model as M
-    from oracle import recipe
-    with precision(prec):
-        m = M.AugmentedCycleGAN(make_opt(**kw), testing=True)
-        for k, net in m._net_dict().items():
-            load_recipe(net, k, seed, "init")
-        out = []
-        for s in range(steps):
-            A, B, z = recipe.inputs(in_seed + s, Nb, kw["input_nc"], kw["output_nc"], S, 16)
-            losses, visuals, gnorms = m.train_instance(t(A), t(B), t(z))
-            out.append((dict(losses), {k: n(v) for k, v in visuals.items()}, dict(gnorms)))
-    return out
-
-
 def _agree(rx3, r32):
     from hip_util import rel
     (lx3, vx3, gx3), (l32, v32, g32) = rx3, r32
@@ -188,46 +173,6 @@ def test_config2_full_batch_step_fp32():
         assert visuals["rec_B"].shape == (16, 3, 128, 128) and np.abs(visuals["fake_A"]).max() <= 1.0
     assert r32[0][0] != r32[1][0]                      # the update was applied
     _agree(_run_cfg(CFG2, 128, 16, "bf16x3")[0], r32[0])
-
-
-_ORACLE_CACHE = {}
-
-
-def _oracle_step(kw, S, Nb, seed, in_seed):
-    """the oracle's step on what _run_cfg(kw, S, Nb, prec, seed=seed, in_seed=in_seed) runs, computed once for both precisions"""
-    key = ("step", tuple(sorted(kw.items())), S, Nb, seed, in_seed)
-    if key not in _ORACLE_CACHE:
-        from oracle import recipe, step
-        o = step.AugStep(step.Opt(**kw))
-        o.load({k: recipe.values_for(net.shapes, k, seed, "init") for k, net in o.nets().items()})
-        _ORACLE_CACHE[key] = o.train_instance(*recipe.inputs(in_seed, Nb, kw["input_nc"], kw["output_nc"], S, 16))
-    return _ORACLE_CACHE[key]
-
-
-# step 0 against the oracle: (losses, gradient norms, images) — exact fp32 pins indexing and fusion logic, bf16x3 is held to
-# the north-star bar (test_hip_step.STEP_TOL's first row)
-ORACLE_TOL = {"f32": (2e-4, 1e-3, 1e-4), "bf16x3": (1e-3, 3e-3, 1e-3)}
-
-
-def _matches_oracle(got, ref, prec, case, gnorm_tol=None):
-    """asserts the whole step — 13 losses, 6 gradient norms, 4 images — within ORACLE_TOL[prec] of the oracle's, and prints the
-    worst relative error of each group beside its bound.  `gnorm_tol`: {gradient norm: relative bound} replacing the group's
-    bound for single gradient norms (a measured conditioning allowance)"""
-    from hip_util import rel
-    (l1, v1, g1), (l0, v0, g0) = got, ref
-    lt, gt, vt = ORACLE_TOL[prec]
-    gts = np.array([(gnorm_tol or {}).get(k, gt) for k in g0])
-    assert list(l1.keys()) == list(l0.keys()) and list(g1.keys()) == list(g0.keys())
-    worst = lambda a, b: max(abs(a[k] - b[k]) / max(abs(b[k]), 1e-30) for k in b)
-    ev = max(rel(v1[k], v0[k]) for k in ("fake_A", "fake_B", "rec_A", "rec_B"))
-    print("oracle_err case=%s prec=%s losses=%.2e/%.0e gnorms=%.2e/%.0e images=%.2e/%.0e gnorm_G_A_B=%.2e"
-          % (case, prec, worst(l1, l0), lt, worst(g1, g0), gt, ev, vt, worst({0: g1["gnorm_G_A_B"]}, {0: g0["gnorm_G_A_B"]})))
-    assert np.allclose(list(l1.values()), list(l0.values()), rtol=lt, atol=2e-6), (l1, l0)
-    a, b = np.array(list(g1.values())), np.array(list(g0.values()))
-    assert np.all(np.abs(a - b) <= gts * np.abs(b) + 1e-6), (g1, g0)
-    for k in ("fake_A", "fake_B", "rec_A", "rec_B"):
-        assert v1[k].shape == v0[k].shape, k
-        assert rel(v1[k], v0[k]) < vt, (k, rel(v1[k], v0[k]))
 
 
 def _oracle_cfg2_step():

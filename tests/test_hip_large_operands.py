@@ -53,95 +53,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import (BASE_127, C_LARGE, EDGE, KERNELS, LARGE_CONV_CASES as CONV_CASES, LARGE_NORM_CASES as NORM_CASES,  # noqa: E402
+                        LAYERS, NGF, NLATENT, PERIOD, SIZES, _ref_device, conv_id, expected_kernel, image_class, layer_shapes, norm_id)
+from model_cases import tiny_model  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-NGF = 32
-C_LARGE = 2 * NGF                                  # channels of the widest full-resolution tensor (stored as cpad: 64)
-SIZES = ((129, 256, 256), (255, 256, 256), (131, 250, 262))
-BASE_SIZE = (127, 256, 256)                        # every byte offset below 2^31: where the summed-gradient bars are measured
-PERIOD = 12
-NLATENT = 16
-EDGE = 1e-5   # |pre-activation| below which the ReLU behind a norm counts as sitting on its kink (see _mask_edges)
-
-# name: (input channels, output channels, stride, transposed, the side the large tensor is on)
-LAYERS = {
-    "conv32to64": (32, 64, 1, False, "out"),
-    "conv64to128s2": (64, 128, 2, False, "in"),
-    "convT128to64": (128, 64, 2, True, "out"),
-    "conv64to32": (64, 32, 1, False, "in"),
-}
-PASSES = ("fwd", "dgrad", "wgrad")
-NORMS = ("in", "cin")
-NORM_PASSES = ("eval_fwd", "train_fwd_dx", "train_params")
-
-# short name in the test id -> substring of acg_last_kernel
-KERNELS = {"rows": "conv_rows_x3<32,64>", "rp": "RP=1", "ws": "igemm_conv_x3_ws", "ph4": "igemm_conv_ph4", "krow_s": "wgrad_x3_krow_s<",
-           "krowg": "wgrad_x3_krowg<NT=3,IS=2,BCI=64>", "bf16tile": "igemm_conv_bf16<", "wgrad_bf16": "wgrad_bf16<",
-           "f32tile": "igemm_conv_f32<", "wgrad_f32": "wgrad_f32"}
-_FAST = {   # bf16x3, W a multiple of 128: (forward, data gradient, weight gradient)
-    "conv32to64": ("rows", "rp", "krow_s"), "conv64to128s2": ("ws", "ph4", "krowg"),
-    "convT128to64": ("ph4", "ws", "krowg"), "conv64to32": ("rp", "rows", "krow_s")}
-_FALLBACK = {   # bf16x3, W = 262: the wave-specialised tile has no width condition, the others fall to the generic tiles
-    "conv32to64": ("bf16tile", "bf16tile", "wgrad_bf16"), "conv64to128s2": ("ws", "bf16tile", "wgrad_bf16"),
-    "convT128to64": ("bf16tile", "ws", "wgrad_bf16"), "conv64to32": ("bf16tile", "bf16tile", "wgrad_bf16")}
-
-# max-abs error / max-abs value of the summed gradients at 127 x 256 x 256 against float64 (measured on one MI355X)
-BASE_127 = {
-    ("conv32to64", "bf16x3"): {"dw": 5.67e-06, "db": 6.22e-07}, ("conv32to64", "f32"): {"dw": 3.49e-06, "db": 1.09e-06},
-    ("conv64to128s2", "bf16x3"): {"dw": 4.90e-06, "db": 6.00e-07}, ("conv64to128s2", "f32"): {"dw": 3.78e-06, "db": 8.19e-07},
-    ("convT128to64", "bf16x3"): {"dw": 5.76e-06, "db": 5.74e-07}, ("convT128to64", "f32"): {"dw": 4.08e-06, "db": 3.88e-07},
-    ("conv64to32", "bf16x3"): {"dw": 6.55e-06, "db": 4.57e-07}, ("conv64to32", "f32"): {"dw": 3.69e-06, "db": 9.24e-07},
-    ("in", "norm"): {"dscale": 3.08e-07, "dshift": 2.93e-07},
-    ("cin", "norm"): {"dscale_w": 2.08e-07, "dscale_b": 3.45e-07, "dshift_w": 2.75e-07, "dshift_b": 2.97e-07},
-}
-
-
-def expected_kernel(layer, what, size, prec):
-    """short name (KERNELS) of the kernel the dispatcher must take for this pass"""
-    if prec == "f32":
-        return "wgrad_f32" if what == "wgrad" else "f32tile"
-    return (_FAST if size[2] % 128 == 0 else _FALLBACK)[layer][PASSES.index(what)]
-
-
-def layer_shapes(layer, size):
-    """-> (input shape, output shape), NHWC, of `layer` when its large side is the 64-channel tensor of `size`"""
-    Ci, Co, stride, tr, side = LAYERS[layer]
-    N, H, W = size
-    assert (Co if side == "out" else Ci) == C_LARGE
-    if stride == 1:
-        return (N, H, W, Ci), (N, H, W, Co)
-    assert H % 2 == 0 and W % 2 == 0
-    if tr:
-        return (N, H // 2, W // 2, Ci), (N, H, W, Co)
-    return (N, H, W, Ci), (N, H // 2, W // 2, Co)
-
-
-def nbytes(shape):
-    n = 4
-    for s in shape:
-        n *= s
-    return n
-
-
-def image_class(i):
-    """-> (k, s): image i is s * base_k"""
-    return i % 3, 2.0 ** ((i % 4) - 1)
-
-
-CONV_CASES = [(layer, what, size, prec) for layer in LAYERS for what in PASSES for size in SIZES for prec in ("bf16x3", "f32")]
-NORM_CASES = [(kind, what, size) for kind in NORMS for what in NORM_PASSES for size in SIZES]
-
-
-def conv_id(case):
-    layer, what, size, prec = case
-    return "%s_%s_%dx%dx%d_%s_%s" % ((layer, what) + size + (prec, expected_kernel(layer, what, size, prec)))
-
-
-def norm_id(case):
-    kind, what, size = case
-    entry = {"eval_fwd": "norm_stats+norm_apply", "train_fwd_dx": "norm_apply+norm_bwd", "train_params": "norm_bwd"}[what]
-    return "%s_%s_%dx%dx%d_%s" % ((kind, what) + size + (entry,))
-
 
 # ---------------------------------------------------------------------------------------------------------------------
 # device-side helpers
@@ -210,11 +126,6 @@ def _compare_all(got, ref12, bar, what):
 
 def _rel(a, b):
     return float((a.double() - b).abs().max() / (b.abs().max() + 1e-300))
-
-
-def _ref_device():
-    from test_hip_fastpath_fuzz import _ref_device as dev
-    return dev()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -479,8 +390,7 @@ E2E_INPUTS, E2E_M, E2E_S = 85, 3, 256
 def ensemble_runs():
     """85 inputs x 3 samples at 256 x 256 through an ngf-32, one-block CINResnetGenerator (built as test_hip_ensemble builds its
     own): translate_ensemble with the default chunk and with chunk=51 -> (outputs, outputs, images per generator pass of each)"""
-    from test_hip_api import _model
-    m = _model(ngf=NGF, n_blocks=1)
+    m = tiny_model(ngf=NGF, n_blocks=1)
     g = _gen("end to end")
     A = torch.rand(E2E_INPUTS, 3, E2E_S, E2E_S, device="cuda", generator=g) * 2 - 1
     B = torch.rand(E2E_INPUTS, 3, E2E_S, E2E_S, device="cuda", generator=g) * 2 - 1

@@ -34,133 +34,10 @@ import pytest
 
 import latent_mlp_ref as R
 from guard_util import Buf, rejected
+from latent_mlp_ref import (ACT_NONE, ACT_SIGMOID, BAR, BAR_ACC, CASES, CONTRACT, EPS, EXTRA, MODULE_CASES, MOMENTUM, STAGE_ONLY,
+                            assert_values, cid, draw, module_key, reference, relerr, supported)
 
 gpu = pytest.mark.gpu
-
-EPS, MOMENTUM = 1e-5, 0.1
-BAR = 2e-5                      # activations, statistics, running buffers, output, dz; gradients on the scale of gmax
-BAR_OWN, OWN_FROM = 1e-4, 0.05  # gradient tensors whose own maximum is at least OWN_FROM * gmax, on their own scale
-BAR_ACC = 1e-6                  # accumulate = 1 against g0 + (accumulate = 0), on the scale of gmax
-ACT_NONE, ACT_SIGMOID = 0, 4
-
-J_INSTANCES = (1, 2, 4, 8, 16)
-MLP_JMAX = 16
-LDS_BUDGET = 160 * 1024 - 1024
-LDS_DEFAULT = 64 * 1024
-
-
-# ---------------------------------------------------------------- the launch plan, restated
-def lds_bytes(N, H):
-    """(forward, backward) dynamic LDS: [N][H + 1] activations, [H][H + 1] weights, two fold buffers of 256; the backward
-    adds the linear layer's input and da, [N][H + 1] each"""
-    fwd = N * (H + 1) + H * (H + 1) + 2 * 256
-    return 4 * fwd, 4 * (fwd + 2 * N * (H + 1))
-
-
-def supported(N, I, H):
-    return (N > 0 and I > 0 and 16 <= H <= 256 and I <= H and 256 % H == 0 and N * H <= 256 * MLP_JMAX
-            and lds_bytes(N, H)[1] <= LDS_BUDGET)
-
-
-def plan(N, I, H):
-    need = -(-N * H // 256)
-    J = min(j for j in J_INSTANCES if j >= need)
-    nstep = 256 // H
-    fwd, bwd = lds_bytes(N, H)
-    nk_first, nk = -(-I // nstep), H // nstep                  # columns per thread of the weight-gradient block, K = I and K = H
-    return dict(J=J, need=need, full=(N * H == 256 * J), nstep=nstep, idle=max(0, 256 - N * H),
-                kb_first=-(-nk_first // MLP_JMAX), kb=-(-nk // MLP_JMAX), lds_fwd=fwd, lds_bwd=bwd, head_uneven=(N % 4 != 0))
-
-
-# ---------------------------------------------------------------- cases
-# (N, I, H): the smallest shapes that reach each branch; (64,16,16) and (32,8,64) fill the J = 4 and J = 8 tiles completely
-_SHAPES = [(4, 4, 16), (16, 16, 16), (17, 5, 16), (37, 16, 16), (70, 16, 16), (129, 1, 16), (256, 16, 16), (64, 16, 16),
-           (5, 8, 32), (24, 32, 32), (72, 3, 32),
-           (4, 16, 64), (6, 64, 64), (12, 16, 64), (20, 1, 64), (37, 16, 64), (32, 8, 64), (64, 16, 64),
-           (4, 16, 128), (7, 128, 128), (19, 100, 128), (32, 16, 128)]
-CASES = [(N, I, H, i % 3 == 1) for i, (N, I, H) in enumerate(_SHAPES)]           # value-checked; a third with the sigmoid head
-STAGE_ONLY = [(N, 16, H, H == 64) for H in (16, 64, 128) for N in (1, 2, 3)]     # teacher-forced checks only
-CONTRACT = [c for c in CASES if c[:3] in ((17, 5, 16), (72, 3, 32), (64, 16, 64), (7, 128, 128))]
-EXTRA = (0, 3)                                                                   # ldz - I
-MODULE_CASES = [(32, 16, 64), (7, 4, 16), (12, 16, 128)]
-
-
-def module_key(N, nlatent, ndf):
-    return "module %d %d %d" % (N, nlatent, ndf)
-
-
-def cid(c):
-    N, I, H, sig = c
-    p = plan(N, I, H)
-    return "n%di%dh%d-J%d%s-ns%d-kb%d-lds%df%db%s" % (N, I, H, p["J"], "f" if p["full"] else "m", p["nstep"], p["kb"],
-                                                       -(-p["lds_fwd"] // 1024), -(-p["lds_bwd"] // 1024), "-sig" if sig else "")
-
-
-class Draw(object):
-    pass
-
-
-def draw(c, key=None):
-    """weights ~ N(0, 1 / sqrt(fan_in)), gamma ~ N(1, 0.3), beta, biases ~ N(0, 0.3), z ~ N(0, 1.5): float32 values"""
-    N, I, H, sig = c
-    rs = np.random.RandomState(zlib.crc32((key or cid(c)).encode()))
-    f = np.float32
-    d = Draw()
-    d.z = rs.normal(0, 1.5, (N, I)).astype(f)
-    fan = [I, H, H, H]
-    w = [rs.normal(0, fan[l] ** -0.5, ((H if l < 3 else 1), fan[l])).astype(f) for l in range(4)]
-    b = [rs.normal(0, 0.3, (H if l < 3 else 1,)).astype(f) for l in range(4)]
-    gamma = [rs.normal(1, 0.3, H).astype(f) for _ in range(3)]
-    beta = [rs.normal(0, 0.3, H).astype(f) for _ in range(3)]
-    d.params = w + b + gamma + beta
-    d.buffers = [rs.normal(0, 0.5, H).astype(f) for _ in range(3)] + [rs.uniform(0.5, 1.5, H).astype(f) for _ in range(3)]
-    d.dout = rs.normal(0, 1, N).astype(f)
-    return d
-
-
-_REF = {}
-
-
-def reference(c):
-    """the fp64 result of a case, computed once"""
-    k = cid(c)
-    if k not in _REF:
-        d = draw(c)
-        _REF[k] = R.step(d.z, d.params, d.buffers, d.dout, EPS, MOMENTUM, c[3])
-    return _REF[k]
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
-
-
-def value_errors(k, r):
-    """{quantity: error on the scale its bar is stated in} of a result k (attributes as latent_mlp_ref.Result, any float
-    type) against the fp64 result r.  'grad': the worst gradient tensor on the scale of gmax; 'grad_own': the worst of the
-    tensors whose own maximum is at least OWN_FROM * gmax, on their own scale."""
-    e = {}
-    e["a_save"] = max(relerr(k.a[l], r.a[l]) for l in range(3))
-    e["mean"] = max(relerr(k.stats[l][0], r.stats[l][0]) for l in range(3))
-    e["rstd"] = max(relerr(k.stats[l][1], r.stats[l][1]) for l in range(3))
-    e["run_mean"] = max(relerr(k.run_mean[l], r.run_mean[l]) for l in range(3))
-    e["run_var"] = max(relerr(k.run_var[l], r.run_var[l]) for l in range(3))
-    e["out"] = relerr(k.out, r.out)
-    e["dz"] = relerr(k.dz, r.dz)
-    gmax = max(float(np.max(np.abs(g))) for g in r.grads)
-    e["grad"] = max(float(np.max(np.abs(np.asarray(a, np.float64) - b))) for a, b in zip(k.grads, r.grads)) / gmax
-    e["grad_own"] = max(relerr(a, b) for a, b in zip(k.grads, r.grads) if np.max(np.abs(b)) >= OWN_FROM * gmax)
-    return e
-
-
-BARS = dict(a_save=BAR, mean=BAR, rstd=BAR, run_mean=BAR, run_var=BAR, out=BAR, dz=BAR, grad=BAR, grad_own=BAR_OWN)
-
-
-def assert_values(k, r, what):
-    e = value_errors(k, r)
-    print("MEASURED %s %s" % (what, " ".join("%s=%.3g" % kv for kv in sorted(e.items()))))
-    for q, v in e.items():
-        assert v < BARS[q] or (q == "grad" and v <= BARS[q]), (what, q, v, BARS[q])
 
 
 # ---------------------------------------------------------------- the C ABI

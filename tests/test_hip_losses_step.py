@@ -5,7 +5,7 @@ stride-2 stages: 64), the batch 2."""
 import numpy as np
 import pytest
 
-from test_hip_ssim_step import BASE_KEYS, S, _inputs, _model
+from model_cases import BASE_KEYS, S, SUP_GNORMS as PAIRED_GNORMS, SUP_KEYS as PAIRED_BASE, step_inputs as _inputs, step_model as _model
 
 pytestmark = pytest.mark.gpu
 
@@ -17,8 +17,6 @@ PAIRED = [("ssim", ["S_ssim_A", "S_ssim_B"], dict(lambda_ssim_A=0.25, lambda_ssi
           ("crps", ["S_crps_B", "S_pair_B"], dict(lambda_crps_B=0.5, crps_members=2)),
           ("fss", ["S_fss_A", "S_fss_B"], dict(lambda_fss_A=0.25, lambda_fss_B=0.5, fss_loss_windows=(3, 9, 17), fss_tau=0.05,
                                                fss_loss_thr_A=THR, fss_loss_thr_B=THR))]
-PAIRED_BASE = ['S_A', 'S_B', 'KLD_z_B', 'D_z_B']
-PAIRED_GNORMS = ['gnorm_G_A_B', 'gnorm_G_B_A', 'gnorm_E_B', 'gnorm_D_z_B']
 
 
 def _check(families, step, graph, losses_of, head, tail):

@@ -10,6 +10,8 @@ import pytest
 import torch
 
 import marginal_eval_ref as R
+from eval_cases import make_experiment
+from model_cases import tiny_model
 
 pytestmark = pytest.mark.gpu
 
@@ -93,8 +95,7 @@ def test_the_wrappers_refuse_before_a_launch():
 
 @pytest.fixture(scope="module")
 def model():
-    from test_hip_api import _model
-    return _model(grid_size=S, n_blocks=1)
+    return tiny_model(grid_size=S, n_blocks=1)
 
 
 def test_translate_marginal_is_marginal_scores_on_the_same_translations(model):
@@ -153,24 +154,12 @@ def test_translate_marginal_is_marginal_scores_on_the_same_translations(model):
 def experiment(tmp_path_factory):
     """a synthetic .npz split (10 train -> 5 dev + 5 train, 3 test) with mass at 0 in domain B, and the checkpoint
     <expr_dir>/latest of a seeded tiny model: the recipe of tests/test_hip_ssim_step.py at 16 x 16"""
-    from dtgan_amd import options as O
-    from dtgan_amd.model import AugmentedCycleGAN
-    root = tmp_path_factory.mktemp("marginal_metric")
-    data = root / "data"
-    data.mkdir()
-    rs = np.random.RandomState(0)
-    for split, n in (("train", 10), ("test", 3)):
-        for dom in "AB":
-            f = rs.uniform(0, 3, (n, S, S, 3)).astype(np.float32)
-            if dom == "B":
-                f[rs.uniform(size=f.shape) < 0.3] = 0.0
-            np.savez(str(data / ("%s%s.npz" % (split, dom))), data=f)
-    opt = O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(root), "--dataroot", str(data), "--grid_size",
-                                       str(S), "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4", "--n_blocks", "1",
-                                       "--seed", "3"])
-    torch.manual_seed(3)
-    AugmentedCycleGAN(opt).save("latest")
-    return dict(chk=os.path.join(opt.expr_dir, "latest"), data=str(data), expr=opt.expr_dir)
+    def field(rs, i, j, n, draw):
+        f = draw()
+        if j == 1:
+            f[rs.uniform(size=f.shape) < 0.3] = 0.0
+        return f
+    return make_experiment(tmp_path_factory.mktemp("marginal_metric"), S, 10, 3, field=field)
 
 
 def test_metric_marginal_writes_its_file(experiment, capsys):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import minkowski_ref as K
+from field_cases import OFFSET_LAYOUTS as LAYOUTS, offset_operand as _device
 from guard_util import GUARD, Buf
 
 pytestmark = pytest.mark.gpu
@@ -20,27 +21,6 @@ SIZES = ((1, 1), (1, 64), (64, 1), (63, 65), (65, 63), (17, 129), (BAND - 2, 5),
          (321, 321))
 # (T, C): one threshold, two, the evaluator's default and the most; one channel, three and four
 TC = ((1, 1), (2, 3), (31, 4), (255, 3))
-LAYOUTS = (("nchw", 0, 0), ("nhwc", 4, 0), ("nhwc", 16, 0), ("nhwc", 4, 1), ("nchw", 0, 1))       # (layout, stored channels, floats off)
-
-
-def _device(x, layout, Cp=0, off=0, seed=0):
-    """x (rows, C, H, W) on the device in the layout, `off` floats behind a 16-byte boundary; NHWC: +-50 garbage and NaN in the
-    padded channels"""
-    if layout == "nhwc":
-        rows, C, H, W = x.shape
-        rs = np.random.RandomState(seed)
-        t = rs.uniform(-50, 50, (rows, H, W, Cp)).astype(np.float32)
-        t[rs.uniform(size=t.shape) < 0.2] = np.nan
-        t[..., :C] = np.moveaxis(x, 1, 3)
-        x = t
-    flat = torch.empty(x.size + 4, dtype=torch.float32, device="cuda")
-    assert flat.data_ptr() % 16 == 0
-    d = flat[off:off + x.size].view(x.shape)
-    d.copy_(torch.from_numpy(np.array(x, order="C")))           # a copy: the cases are read-only
-    assert d.is_contiguous() and d.data_ptr() % 16 == 4 * off
-    return d
-
-
 @functools.lru_cache(maxsize=None)
 def _case(kind, H, W, T, C):
     """two rows of C fields, their thresholds (with repeats from T = 31 on) and the reference counts; left unchanged"""

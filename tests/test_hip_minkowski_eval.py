@@ -9,17 +9,11 @@ import pytest
 import torch
 
 import minkowski_ref as K
+from eval_cases import SMOOTH_S as S, smooth_experiment as experiment, smooth_model as model  # noqa: F401  (fixtures: the tiny model, the saved checkpoint)
 
 pytestmark = pytest.mark.gpu
 
-S = 32
 FUNCTIONALS = ("area", "perimeter", "euler4", "euler8")
-
-
-@pytest.fixture(scope="module")
-def model():
-    from test_hip_api import _model
-    return _model(grid_size=S, n_blocks=1)
 
 
 def test_translate_minkowski_equals_the_reference_on_generate_multis_members(model):
@@ -95,27 +89,6 @@ def test_the_real_sets_of_eval_minkowski_are_the_references(model):
             assert res["dist_%s_%s" % (f, k)].shape == (3,) and np.array_equal(res["dist_%s_%s" % (f, k)], d[f])
     real = ops.minkowski_summary(res["counts_real_B"], res["cells_real_B"])
     assert all(np.all(v == 0) for v in ops.minkowski_distance(real, real).values())
-
-
-@pytest.fixture(scope="module")
-def experiment(tmp_path_factory):
-    """a synthetic .npz split (10 train -> 5 dev + 5 train, 3 test) of smoothed noise and the checkpoint <expr_dir>/latest of
-    a seeded tiny model"""
-    from dtgan_amd import options as O
-    from dtgan_amd.model import AugmentedCycleGAN
-    root = tmp_path_factory.mktemp("minkowski_metric")
-    data = root / "data"
-    data.mkdir()
-    for i, (split, n) in enumerate((("train", 10), ("test", 3))):
-        for j, dom in enumerate("AB"):
-            f = K.make_fields("smooth", n, 3, S, S, np.zeros((3, 1), np.float32), seed=10 * i + j)
-            np.savez(str(data / ("%s%s.npz" % (split, dom))), data=np.ascontiguousarray(np.moveaxis(f, 1, 3) + 1.5))
-    opt = O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(root), "--dataroot", str(data), "--grid_size",
-                                       str(S), "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4", "--n_blocks", "1",
-                                       "--seed", "3"])
-    torch.manual_seed(3)
-    AugmentedCycleGAN(opt).save("latest")
-    return dict(chk=os.path.join(opt.expr_dir, "latest"), data=str(data), expr=opt.expr_dir)
 
 
 def test_metric_minkowski_writes_its_file(experiment, capsys):

@@ -15,28 +15,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from conv_cases import build  # noqa: E402
 from golden_util import load, names  # noqa: E402
-
-
-def build(meta):
-    from dtgan_amd import networks as N
-    c, n = meta["cfg"], meta["net"]
-    g = [0]
-    if n == "netG_B_A":   # --norm batch / --use_dropout fixtures carry the option in their cfg (options.py:64-65)
-        return N.define_G(c["input_nc"], c["output_nc"], c["ngf"], norm=c.get("norm", "instance"),
-                          use_dropout=c.get("use_dropout", False), gpu_ids=g, n_blocks=c["n_blocks"])
-    if n == "netG_A_B":
-        return N.define_stochastic_G(c["nlatent"], c["input_nc"], c["output_nc"], c["ngf"],
-                                     use_dropout=c.get("use_dropout", False), gpu_ids=g, n_blocks=c["n_blocks"])
-    if n == "netD_B":
-        return N.define_D_B(c["input_nc"], c["ndf"], "basic", "instance", gpu_ids=g)
-    if n == "netD_A":
-        return N.define_D_A(c["input_nc"], c["ndf"], "basic", "instance", gpu_ids=g)
-    if n == "netE_B":
-        return N.define_E(c["nlatent"], c["input_nc"], c["nef"], "batch", gpu_ids=g)
-    if n == "netD_z_B":
-        return N.define_LAT_D(c["nlatent"], c["ndf"], gpu_ids=g)
-    raise KeyError(n)
 
 
 @pytest.mark.parametrize("impl", ["mfma", "direct", "mfma-bf16x3"])

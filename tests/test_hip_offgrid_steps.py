@@ -5,7 +5,7 @@ acg_conv2d_bwd_data_sums_supported, acg_conv2d_fwd_stats_supported; DESIGN.md se
 (ops.ConvStats, SkipGrad, NormSums, the S16 plan) fall back when the producer did not take the fused path.  At these sizes some
 fast paths engage while their neighbours fall back, which no power-of-two size exercises.  Full widths (ngf 32, ndf 64, nef 32,
 nlatent 16), 3 resblocks, batch 3 (the latent BatchNorms need at least 3 samples), both arithmetics at the oracle tolerances of
-configs[1] (test_hip_fullsize.ORACLE_TOL; one measured exception, F32_GNORM_TOL).  In bf16x3 each case asserts the exact
+configs[1] (conv_cases.ORACLE_TOL; one measured exception, F32_GNORM_TOL).  In bf16x3 each case asserts the exact
 ops.FUSED counts and the set of convolution kernels that ran (parenthesised launch details dropped), so a path that silently
 stops engaging — or starts engaging where its predicate says it cannot — fails here.
 
@@ -33,7 +33,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from test_hip_fullsize import _run_cfg, _oracle_step, _matches_oracle  # noqa: E402
+from conv_cases import _run_cfg, _oracle_step, _matches_oracle  # noqa: E402
 
 WIDTHS = dict(ngf=32, nef=32, ndf=64, nlatent=16, n_blocks=3)
 CASES = {192: 3, 384: 3, 324: 1}   # grid size -> image channels
@@ -43,7 +43,7 @@ NB = 3
 # host: fp32 0.0373096, the same step in fp64 0.0372886 (fp32 is 5.6e-4 off), and fp32 with every weight perturbed by 1e-6
 # relative 0.0372481 (1.65e-3 from the unperturbed fp32 value).  The exact-fp32 HIP step lands at 0.0372484, 1.64e-3 from the
 # fp32 oracle and 1.1e-3 from fp64.  In f32 that one gradient norm is held to the bf16x3 bar, 3e-3; every other quantity keeps
-# test_hip_fullsize.ORACLE_TOL.
+# conv_cases.ORACLE_TOL.
 F32_GNORM_TOL = {"gnorm_G_A_B": 3e-3}
 
 # bf16x3, one step: ops.FUSED and the convolution kernels that ran (observed on an MI355X; see the module docstring)

@@ -15,67 +15,9 @@ import torch.nn as nn
 
 pytestmark = pytest.mark.gpu
 
+from conv_cases import CONV_CASES, _conv_module  # noqa: E402
 from oracle import ops as oops  # noqa: E402
 from oracle.tape import T, backward, leaf  # noqa: E402
-
-CONV_CASES = [
-    # K, stride, pad, mode, Ci, Co, N, H, W
-    (3, 1, 1, "zero", 8, 8, 2, 12, 10),
-    (3, 1, 1, "reflect", 32, 32, 2, 9, 11),
-    (7, 1, 3, "reflect", 3, 8, 2, 16, 16),
-    (7, 1, 3, "zero", 8, 3, 2, 16, 16),
-    (3, 2, 1, "zero", 16, 32, 2, 16, 16),
-    (3, 2, 1, "zero", 16, 32, 1, 15, 13),
-    (4, 2, 1, "zero", 3, 16, 2, 16, 16),
-    (4, 1, 1, "zero", 32, 64, 2, 9, 9),
-    (4, 1, 0, "zero", 32, 1, 3, 6, 6),
-    (1, 1, 0, "zero", 64, 16, 2, 3, 3),
-    (3, 1, 1, "reflect", 128, 128, 1, 8, 8),
-    (4, 1, 1, "zero", 256, 256, 1, 6, 6),
-    (3, 2, 1, "zero", 64, 128, 1, 12, 12),
-    (3, 1, 1, "zero", 6, 40, 1, 20, 20),
-    # 3x3 stride-1 128-wide layers: the row-taps weight-gradient kernel (32-pixel row segments, partial tails)
-    (3, 1, 1, "zero", 128, 128, 2, 9, 37),
-    (3, 1, 1, "reflect", 64, 128, 1, 6, 40),
-    (3, 1, 0, "zero", 128, 256, 1, 10, 34),
-    # 32 <-> 3 channel layers: the patch kernel (8x16 output tiles, partial tiles, reflect / zero halo), forward and
-    # as the data gradient of the 3 -> 32 stem
-    (7, 1, 3, "reflect", 32, 3, 2, 20, 37),
-    (7, 1, 3, "zero", 32, 3, 1, 9, 18),
-    (7, 1, 3, "reflect", 3, 32, 2, 18, 21),
-    (3, 1, 1, "zero", 32, 3, 1, 10, 10),
-    # row-patch variant of the wave-specialised kernel: output width 16 / 32 / 64 / 128 (R = 8 / 4 / 2 / 1 rows per tile)
-    (3, 1, 1, "reflect", 128, 128, 1, 16, 16),
-    (3, 1, 1, "zero", 128, 128, 2, 8, 32),
-    (3, 1, 1, "reflect", 64, 128, 1, 4, 64),
-    (4, 1, 1, "zero", 128, 128, 1, 17, 17),
-    (3, 1, 1, "reflect", 128, 256, 1, 2, 128),
-    (4, 1, 1, "zero", 128, 128, 2, 16, 32),   # its DATA gradient (grid = the 16x32 input, taps with descending dx)
-    (3, 1, 1, "zero", 128, 128, 3, 9, 13),    # 13-wide rows: ~11 segments per tile, tiles straddling images
-    (3, 1, 1, "reflect", 160, 128, 2, 11, 130),  # 130-wide rows (the padded data-gradient width), Cin = 5 x 32
-    # kernel-row weight gradient (conv_wgrad_tr.hip): 128-multiple channels, width a multiple of the 32-pixel run
-    (3, 1, 1, "reflect", 128, 128, 2, 6, 32),
-    (3, 1, 1, "zero", 128, 256, 1, 5, 64),
-    (3, 1, 1, "zero", 256, 128, 3, 4, 32),
-    (3, 1, 1, "reflect", 128, 128, 1, 40, 96),   # several splits, runs that cross image rows within a split
-    # its 32 <-> 64 channel variant (128-pixel runs, waves split the pixels)
-    (3, 1, 1, "zero", 32, 64, 1, 3, 128),
-    (3, 1, 1, "reflect", 64, 32, 2, 4, 128),
-    (3, 1, 1, "zero", 64, 32, 2, 20, 128),       # several splits
-    (3, 1, 1, "reflect", 32, 64, 1, 5, 256),
-    # persistent row pipeline (conv_rows.hip): zero-padded 3x3, 32 gathered -> 64 written channels, 128-pixel bands; forward of a
-    # 32 -> 64 layer (two bands, two row chunks per band, an odd chunk) and the data gradient of a 64 -> 32 layer
-    (3, 1, 1, "zero", 32, 64, 2, 21, 256),
-    (3, 1, 1, "zero", 64, 32, 1, 17, 128),
-]
-
-
-def _conv_module(K, stride, pad, mode, Ci, Co):
-    from dtgan_amd import modules as M
-    if mode == "reflect":
-        return M.Sequential(nn.ReflectionPad2d(pad), M.Conv2d(Ci, Co, K, stride=stride, padding=0, bias=True)).cuda()
-    return M.Sequential(M.Conv2d(Ci, Co, K, stride=stride, padding=pad, bias=True)).cuda()
-
 
 class _conv_mode(object):
     """'mfma-bf16x3' | 'mfma-f32' | 'direct' -> implementation + arithmetic for the duration of a test"""

@@ -10,7 +10,8 @@ import torch
 
 import sal_ref as S
 from guard_util import GUARD, Buf
-from test_hip_minkowski import _device
+from field_cases import offset_operand as _device
+from sal_ref import check as _check
 
 pytestmark = pytest.mark.gpu
 
@@ -49,18 +50,6 @@ def _path(layout, Cp, H, W):
     load = "c4" if (layout, Cp) == ("nhwc", 4) else "strided"
     one_tile = H <= TH and W <= TW
     return ("sal_field<%s> + sal_label<%s> + sal_finish" if one_tile else "sal_field<%s> + sal_label<%s> + comp_merge + sal_root + sal_finish") % (load, load)
-
-
-def _check(got, ref, what):
-    """field and obj equal; shape within (n + 8) 2^-52 of the reference, relatively: the terms are non-negative and built from
-    equal integers, the sums differ in the order of n - 1 additions; exactly 0.0 where the reference is"""
-    assert got[0].dtype == got[1].dtype == np.int64 and got[2].dtype == np.float64
-    assert np.array_equal(got[0], ref[0]), (what, np.argwhere(got[0] != ref[0])[:5])
-    assert np.array_equal(got[1], ref[1]), (what, np.argwhere(got[1] != ref[1])[:5])
-    bar = (ref[1][..., :1] + 8) * 2.0 ** -52 * ref[2]
-    err = np.abs(got[2] - ref[2])
-    assert np.all(err <= bar), (what, np.argwhere(~(err <= bar))[:5], err.max())
-    assert np.all(got[2][ref[2] == 0] == 0)
 
 
 @pytest.mark.parametrize("kind", KINDS)

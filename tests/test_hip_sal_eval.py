@@ -11,8 +11,8 @@ import torch
 
 import minkowski_ref as K
 import sal_ref as R
-from test_hip_minkowski_eval import S, experiment, model          # noqa: F401  (fixtures: the tiny model, the saved checkpoint)
-from test_hip_sal import _check
+from eval_cases import SMOOTH_S as S, smooth_experiment as experiment, smooth_model as model  # noqa: F401  (fixtures: the tiny model, the saved checkpoint)
+from sal_ref import check as _check
 
 pytestmark = pytest.mark.gpu
 

@@ -4,25 +4,21 @@ process."""
 import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import spectrum_ref as R
+from eval_cases import checkpoint_model, S as EVAL_S, count_sync_warnings as _count_sync_warnings, experiment, run_test  # noqa: F401  (the fixture)
+from field_cases import LAYOUTS, field_operand as _device
+from model_cases import ensemble_inputs as _inputs, ensemble_model as _model
+from spectrum_ref import within as _within
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = 3
-# |psd - ref| <= TAU sqrt(ref E) + TAU^2 E per bin, E the field's mean square.  Measured, not chosen: torch.fft.fft2 in float32
-# on the CPU, binned in float64, needs tau = 1.3214e-4 over every bin, input and size below (`python tools/spectrum_bench.py
-# --cpu-tolerance`; the largest is the constant-plus-noise field at S = 1024, whose DC coefficient of 0.7 S^2 is rounded to
-# fp32: 2^-24 S).  The constant is 4 x that: a different butterfly order.
-TAU = 4 * 1.3214e-4
-LAYOUTS = [("nhwc", 1, 4), ("nhwc", 3, 4), ("nhwc", 3, 16), ("nchw", 1, 1), ("nchw", 3, 3)]
+TAU = R.TAU                       # the bar of spectrum_ref.within
 
 
 @functools.lru_cache(maxsize=None)
@@ -32,29 +28,11 @@ def _case(kind, S):
     return x, R.rapsd(x), np.mean(x.astype(np.float64) ** 2, axis=(-2, -1))
 
 
-def _device(x, layout, C, Cp, seed=0):
-    """the first C channels of x (rows, 3, S, S) on the device in the layout; NHWC: +-50 garbage in the padded channels"""
-    x = x[:, :C]
-    if layout == "nchw":
-        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    rows, _, S, _ = x.shape
-    t = np.random.RandomState(seed).uniform(-50, 50, (rows, S, S, Cp)).astype(np.float32)
-    t[..., :C] = np.moveaxis(x, 1, 3)
-    return torch.from_numpy(t).cuda()
-
-
 def _spectrum(xd, C, layout):
     from dtgan_amd import ops
     out = ops.radial_spectrum(xd, C, layout)
     torch.cuda.synchronize()
     return out.cpu().numpy()
-
-
-def _within(psd, ref, E, what):
-    d = np.abs(psd.astype(np.float64) - ref)
-    bound = TAU * np.sqrt(ref * E[..., None]) + TAU ** 2 * E[..., None]
-    print("%s: tau needed %.3e (allowed %.3e)" % (what, R.tolerance_needed(psd, ref, E), TAU))
-    assert np.all(np.isfinite(psd)) and np.all(d <= bound), (what, float((d / bound).max()), np.argwhere(d > bound)[:5])
 
 
 @pytest.mark.parametrize("layout,C,Cp", LAYOUTS)
@@ -145,21 +123,6 @@ def test_kernel_refuses_bad_arguments_before_launching():
             ops.radial_spectrum(torch.zeros(shape, device="cuda"), 1, "nchw")
 
 
-def _model(kind="aug"):
-    from test_hip_api import _model as api_model
-    m = api_model(aug=kind == "aug")
-    if kind == "cycle_gan":
-        m.ignore_noise = True
-    return m
-
-
-def _inputs(N, S=64, seed=3):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    A = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    B = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    return A, B, g
-
-
 @pytest.mark.parametrize("prec", ["f32", "bf16x3"])
 def test_translate_spectrum_equals_generate_multi_and_the_reference(prec):
     from hip_util import precision
@@ -213,7 +176,6 @@ def test_cycle_gan_gives_identical_member_spectra():
 
 
 def test_translate_spectrum_host_syncs_do_not_grow_with_groups():
-    from test_hip_eval_bound import _count_sync_warnings
     m = _model()
     A, B, _ = _inputs(4, seed=7)
     M = 3
@@ -224,16 +186,10 @@ def test_translate_spectrum_host_syncs_do_not_grow_with_groups():
 
 
 def test_metric_spectrum(experiment):
-    from test_hip_eval_driver import S
-    from dtgan_amd import ops
-    from dtgan_amd import eval_metrics as EM, test as T
+    S = EVAL_S
+    from dtgan_amd import eval_metrics as EM
     from dtgan_amd.dataloader import AlignedIterator, load_numpy_data
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "dtgan_amd.test", "--chk_path", experiment["chk"], "--dataroot", experiment["data"], "--metric",
-           "spectrum", "--n_samples", "4", "--res_dir", "res_spectrum"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_test(experiment, "spectrum", "--n_samples", "4", "--res_dir", "res_spectrum")
     pat = r"^DEV_LSD_B: (\d+\.\d{4}), TEST_LSD_B: (\d+\.\d{4}), TEST_LSD_MEAN_B: (\d+\.\d{4}), TEST_LSD_A: (\d+\.\d{4})$"
     mt = re.search(pat, out, re.M)
     assert mt, out[-2000:]
@@ -256,21 +212,10 @@ def test_metric_spectrum(experiment):
         ref, E = R.rapsd(data).mean(0), np.mean(data.astype(np.float64) ** 2, axis=(-2, -1)).max()
         assert np.all(np.abs(arr[key] - ref) <= TAU * np.sqrt(ref * E) + TAU ** 2 * E), key
     # the same numbers in process, from the same seed
-    import argparse
-    opt = argparse.Namespace(**T.parse_opt_file(os.path.join(experiment["expr"], "opt.pkl")))
-    opt.gpu_ids = [0]
-    prec = ops.get_precision()
-    ops.set_precision(opt.precision)
-    try:
-        model, _ = T._build(opt)
-        model.load(experiment["chk"])
+    with checkpoint_model(experiment) as model:
         torch.manual_seed(12345)
         EM.eval_spectrum(AlignedIterator(devA, devB, batch_size=len(devA)), model, 4)
         test = EM.eval_spectrum(AlignedIterator(testA, testB, batch_size=len(testA)), model, 4)
-    finally:
-        ops.set_precision(prec)
     assert abs(float(mt.group(2)) - test["lsd_B"]) < 1e-4, (mt.group(2), test["lsd_B"])
     assert np.allclose(arr["test_lsd_B_per_input"], test["lsd_B_per_input"], rtol=1e-6)
 
-
-from test_hip_eval_driver import experiment  # noqa: E402,F401  (the module-scoped fixture)

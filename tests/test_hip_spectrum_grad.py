@@ -3,8 +3,6 @@ ops.spectral_loss against the same, the training step with --lambda_spec_A / --l
 under the forced one-rank exchange) and `python -m dtgan_amd.train --lambda_spec_B` in a child process."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,13 +10,14 @@ import torch
 
 import spectrum_grad_ref as G
 import spectrum_ref as R
+from eval_cases import write_dataset
+from field_cases import LAYOUTS, field_operand as _device, strides, valid as _valid
 from guard_util import Buf
-from test_hip_spectrum import LAYOUTS, ROWS, _device
+from model_cases import BASE_KEYS, check_captured_and_deferred, flat as _flat, forced_pair, run_module, step_inputs as _inputs, step_model as _model
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
+ROWS = 3
 # max |gx - ref| / (2 max_b |g[b] / count[b]| rms(x)) per field.  Measured, not chosen: 2 Re ifft2(w fft2(x)) with torch.fft in
 # float32 on the CPU needs 8.1906e-7 over every size, field and cotangent below (`python tools/spectrum_bench.py
 # --cpu-grad-tolerance`; the largest is the tanh(red) field at S = 1024).  The constant is 4 x that: a different butterfly order.
@@ -30,17 +29,13 @@ LOSS_VALUE_TOL = 4 * 1.7881e-7
 LOSS_GRAD_TOL = 4 * 6.404e-7
 
 
-def _strides(layout, C, Cp, S):
-    return (S * S * Cp, Cp, 1) if layout == "nhwc" else (C * S * S, 1, S * S)
-
-
 def _bwd(xd, g, C, layout, ws=None):
     """acg_radial_spectrum_bwd through the C ABI into a NaN-poisoned, guarded buffer -> gx as x is laid out (host)"""
     from dtgan_amd import _lib, ops
     lib = _lib.load()
     S = xd.shape[2]
     rows, Cp = xd.shape[0], (xd.shape[3] if layout == "nhwc" else C)
-    st = _strides(layout, C, Cp, S)
+    st = strides(layout, C, Cp, S, S)
     gd = torch.from_numpy(np.ascontiguousarray(g, dtype=np.float32)).cuda()
     out = Buf.out(xd.numel())
     need = lib.acg_radial_spectrum_bwd_workspace_bytes(rows, C, S)
@@ -49,11 +44,6 @@ def _bwd(xd, g, C, layout, ws=None):
                                      ops._stream())
     assert rc == 0, lib.acg_last_error().decode()
     return out.host(tuple(xd.shape))
-
-
-def _valid(gx, layout, C):
-    """(rows, C, S, S) of a result in its layout"""
-    return np.moveaxis(gx[..., :C], 3, 1) if layout == "nhwc" else gx
 
 
 @pytest.mark.parametrize("S", R.FIELD_SIZES)
@@ -209,26 +199,6 @@ def test_spectral_loss_and_its_gradient_match_the_reference(kind, S):
 
 
 # --------------------------------------------------------------------------------------------------------------- step
-def _model(aug=True, **kw):
-    from test_hip_api import _model as api_model
-    return api_model(aug=aug, n_blocks=2, **kw)
-
-
-def _inputs(seed=3, N=4, S=64, nl=4):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    A = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    B = torch.tanh(torch.randn(N, 3, S, S, device="cuda", generator=g))
-    return A, B, torch.randn(N, nl, 1, 1, device="cuda", generator=g)
-
-
-def _flat(m):
-    return {k: getattr(m, k).p.clone() for k in ("f_G_A_B", "f_G_B_A", "f_D_A", "f_D_B") + (("f_D_z_B", "f_E_B") if hasattr(m, "f_E_B") else ())}
-
-
-BASE_KEYS = {True: ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'],
-             False: ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B']}
-
-
 @pytest.mark.parametrize("prec", ["f32", "bf16x3"])
 @pytest.mark.parametrize("aug", [True, False])
 def test_step_reports_the_reference_losses_and_the_term_enters_loss_G_only(aug, prec):
@@ -266,66 +236,15 @@ def test_captured_and_deferred_steps_with_the_loss_on(aug):
     """two eager warm-up calls, the capture and its replay: the first replayed step runs the eager step's kernels on the eager
     step's numbers, so everything it reports equals the eager model's bit for bit (later steps carry the ulp of the device-side
     bias correction, test_hip_step.py); the deferred scalars are the synchronous graph's; a change of either weight re-captures"""
-    from dtgan_amd import model as M
-    kw = dict(lambda_spec_A=0.25, lambda_spec_B=0.5)
-    ref, gr, lazy = _model(aug, **kw), _model(aug, **kw), _model(aug, **kw)
-    gr.enable_step_graph(); lazy.enable_step_graph(defer_scalars=True)
-    g = torch.Generator(device="cuda").manual_seed(11)
-    prev = None
-    for step in range(5):
-        A = torch.rand(4, 3, 64, 64, device="cuda", generator=g) * 2 - 1
-        B = torch.rand(4, 3, 64, 64, device="cuda", generator=g) * 2 - 1
-        z = torch.randn(4, 4, 1, 1, device="cuda", generator=g)
-        lr_, vr, gn_r = ref.train_instance(A, B, z)
-        lg, vg, gn_g = gr.train_instance(A, B, z)
-        out = lazy.train_instance(A, B, z)
-        assert list(lg.keys()) == BASE_KEYS[aug] + ["Spec_A", "Spec_B"] == list(lr_.keys())
-        if prev is not None:
-            assert prev[0].result()[0] == prev[1] and prev[0].result()[2] == prev[2]
-            prev = None
-        if isinstance(out, M.DeferredStep):
-            prev = (out, lg, gn_g)
-        else:
-            assert step < 2 and out[0] == lg
-        worst = max(abs(lr_[k] - lg[k]) for k in lr_)
-        print("step %d aug=%d: largest loss difference graph - eager %.3e" % (step, aug, worst))
-        if step <= 2:
-            assert lg == lr_ and gn_g == gn_r, (step, lg, lr_)
-            for k in vr:
-                assert torch.equal(vr[k], vg[k]), (step, k)
-        else:
-            for k in lr_:
-                assert abs(lr_[k] - lg[k]) <= 2e-3 * max(1.0, abs(lr_[k])), (step, k, lr_[k], lg[k])
-    assert prev is not None and prev[0].result()[0] == prev[1]
-    assert gr._step_graph.captures == 1
-    for name, value in (("lambda_spec_B", 0.125), ("lambda_spec_A", 0.0)):
-        before = gr._step_graph.captures
-        setattr(gr.opt, name, value)
-        l, _, _ = gr.train_instance(A, B, z)
-        assert gr._step_graph.captures == before + 1 and np.isfinite(l["Spec_A"]) and np.isfinite(l["Spec_B"]), name
-    gr.opt.lambda_spec_B = 0.0                                                  # both off: the 13 (10) keys again
-    l, _, _ = gr.train_instance(A, B, z)
-    assert list(l.keys()) == BASE_KEYS[aug]
-
-
-def _worker(tmp_path, name, **extra_env):
-    out = str(tmp_path / (name + ".npz"))
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ACGAN_DIST_FORCE")}
-    env.update(extra_env)
-    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, os.path.join(HERE, "spectrum_dp_worker.py"), out], env=env,
-                       capture_output=True, text=True, timeout=660)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    return np.load(out)
+    check_captured_and_deferred("train_instance", dict(lambda_spec_A=0.25, lambda_spec_B=0.5), BASE_KEYS[aug] + ["Spec_A", "Spec_B"],
+                                (("lambda_spec_B", 0.125), ("lambda_spec_A", 0.0)), dict(lambda_spec_B=0.0), BASE_KEYS[aug], aug=aug, steps=5)
 
 
 def test_the_forced_one_rank_exchange_reports_the_same_scalars(tmp_path):
     """Spec_A / Spec_B ride in the rank-averaged sums of the gradient tail: with one rank and every collective forced
     (test_hip_dp.test_rccl_backend_one_rank_group) the step's scalars are the plain step's.  Step 0 is the same arithmetic on
     the same numbers but for the tail's float64 average of one value: 1e-6 (8 ulp of fp32); step 1 follows an Adam update."""
-    plain = _worker(tmp_path, "plain")
-    forced = _worker(tmp_path, "forced", ACGAN_DIST_FORCE="1", ACGAN_DP_BACKEND="nccl", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
-                     MASTER_ADDR="127.0.0.1", MASTER_PORT="29571", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    assert int(plain["forced"]) == 0 and int(forced["forced"]) == 1
+    plain, forced = forced_pair(tmp_path, "train_instance", dict(lambda_spec_A=0.05, lambda_spec_B=0.1), "29571")
     assert list(plain["s0/names"][-2:]) == ["Spec_A", "Spec_B"] and list(forced["s0/names"]) == list(plain["s0/names"])
     print("step 0 largest relative difference %.3e" % np.max(np.abs(forced["s0/losses"] - plain["s0/losses"]) / np.abs(plain["s0/losses"])))
     for k in ("s0/losses", "s0/gnorms"):
@@ -336,32 +255,20 @@ def test_the_forced_one_rank_exchange_reports_the_same_scalars(tmp_path):
 
 # ------------------------------------------------------------------------------------------------------------- driver
 def test_train_driver_with_the_spectral_loss_and_the_evaluator_on_its_checkpoint(tmp_path):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    env["PYTHONPATH"] = ROOT
     S = 64
     data = tmp_path / "data"
-    data.mkdir()
-    rs = np.random.RandomState(0)
-    for split, n in (("train", 12), ("test", 5)):
-        for dom in "AB":
-            np.savez(str(data / ("%s%s.npz" % (split, dom))), data=rs.uniform(0, 3, (n, S, S, 3)).astype(np.float32))
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "dtgan_amd.train", "--name", "spec", "--checkpoints_dir", str(tmp_path),
-           "--synthetic", "16", "--grid_size", str(S), "--batchSize", "4", "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
-           "--niter", "1", "--niter_decay", "0", "--print_freq", "8", "--display_freq", "16", "--save_epoch_freq", "1",
-           "--eval_steps", "2", "--num_multi", "2", "--seed", "1", "--lambda_spec_B", "0.1"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=960)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    write_dataset(data, (S, S), 12, 5)
+    out = run_module("train", "--name", "spec", "--checkpoints_dir", tmp_path,
+                     "--synthetic", "16", "--grid_size", S, "--batchSize", "4", "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
+                     "--niter", "1", "--niter_decay", "0", "--print_freq", "8", "--display_freq", "16", "--save_epoch_freq", "1",
+                     "--eval_steps", "2", "--num_multi", "2", "--seed", "1", "--lambda_spec_B", "0.1", limit=900)
     d = os.path.join(str(tmp_path), "spec")
     log = open(os.path.join(d, "results.txt")).read()
     lines = [ln for ln in log.splitlines() if re.search(r"\) D_A: ", ln)]          # the loss lines (not the gnorm_D_A ones)
     assert lines and all(re.search(r"P_f_B: \S+ Spec_A: \d+\.\d{3} Spec_B: \d+\.\d{3} $", ln) for ln in lines), lines
     assert "lambda_spec_B: 0.1" in open(os.path.join(d, "opt.txt")).read().splitlines()
     assert re.search(r"Spec_B: \d+\.\d{3}", out)                               # the print line as well
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "dtgan_amd.test", "--chk_path", os.path.join(d, "latest"), "--dataroot",
-           str(data), "--metric", "spectrum", "--n_samples", "2", "--res_dir", "res_spectrum"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=660)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_module("test", "--chk_path", os.path.join(d, "latest"), "--dataroot", data, "--metric", "spectrum", "--n_samples", "2",
+                     "--res_dir", "res_spectrum")
     assert re.search(r"TEST_LSD_B: \d+\.\d{4}", out), out[-2000:]
     assert os.path.exists(os.path.join(d, "res_spectrum", "spectrum.npz"))

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import ssim_ref as R
+from field_cases import field_operand, strides as _strides, valid as _valid
 from guard_util import Buf
 
 pytestmark = pytest.mark.gpu
@@ -14,9 +15,8 @@ pytestmark = pytest.mark.gpu
 # The bars are measured, not chosen: the same separable formula in NumPy float32 with the textbook E[x^2] - mu^2 needs, over
 # ssim_ref.CASES (the near-flat field off zero and the step among them), 6.0130e-05 on the mean S / mean cs (absolute) and
 # 1.7730e-04 on the gradient relative to its field's largest entry (tests/test_ssim_ref_cpu.py measures and pins both).  The
-# constants are 4 x those: a different summation order of the same 11- and 121-term sums.
-VALUE_TOL = 4 * R.FP32_VALUE_ERR                                    # 4 x 6.0130e-05
-GRAD_TOL = 4 * R.FP32_GRAD_ERR                                      # 4 x 1.7730e-04
+# bars (ssim_ref.VALUE_TOL, GRAD_TOL) are 4 x those.
+VALUE_TOL, GRAD_TOL = R.VALUE_TOL, R.GRAD_TOL
 EPS = 2.0 ** -24
 # (layout of x, C, Cp)
 LAYOUTS = [("nhwc", 3, 4), ("nhwc", 1, 4), ("nhwc", 1, 16), ("nchw", 3, 3), ("nchw", 1, 1)]
@@ -24,22 +24,8 @@ ROWS = (1, 3)
 
 
 def _device(x, layout, C, Cp, fill="nan"):
-    """the first C channels of x (rows, >= C, H, W) on the device in the layout; NHWC: NaN in the padded channels"""
-    x = x[:, :C]
-    if layout == "nchw":
-        return torch.from_numpy(np.array(x, order="C")).cuda()
-    rows, _, H, W = x.shape
-    t = np.full((rows, H, W, Cp), np.nan if fill == "nan" else 37.5, np.float32)
-    t[..., :C] = np.moveaxis(x, 1, 3)
-    return torch.from_numpy(t).cuda()
-
-
-def _strides(layout, C, Cp, H, W):
-    return (H * W * Cp, Cp, 1) if layout == "nhwc" else (C * H * W, 1, H * W)
-
-
-def _valid(gx, layout, C):
-    return np.moveaxis(gx[..., :C], 3, 1) if layout == "nhwc" else gx
+    """the first C channels of x (rows, >= C, H, W) on the device in the layout; NHWC: NaN (or 37.5) in the padded channels"""
+    return field_operand(x, layout, C, Cp, fill=np.nan if fill == "nan" else 37.5)
 
 
 @functools.lru_cache(maxsize=None)

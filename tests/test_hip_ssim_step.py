@@ -3,40 +3,18 @@
 process on a saved tiny checkpoint and `python -m dtgan_amd.train --lambda_ssim_B` in a child process."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import ssim_ref as R
-from test_hip_ssim import VALUE_TOL
+from eval_cases import make_experiment
+from model_cases import BASE_KEYS, S, check_captured_and_deferred, flat as _flat, run_module, step_inputs as _inputs, step_model as _model
+from ssim_ref import VALUE_TOL
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-S = 64
-
-
-def _model(aug=True, **kw):
-    from test_hip_api import _model as api_model
-    return api_model(aug=aug, n_blocks=2, **kw)
-
-
-def _inputs(seed=3, N=4, nl=4):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    A = torch.rand(N, 3, S, S, device="cuda", generator=g) * 2 - 1
-    B = torch.tanh(torch.randn(N, 3, S, S, device="cuda", generator=g))
-    return A, B, torch.randn(N, nl, 1, 1, device="cuda", generator=g)
-
-
-def _flat(m):
-    return {k: getattr(m, k).p.clone() for k in ("f_G_A_B", "f_G_B_A", "f_D_A", "f_D_B") + (("f_D_z_B", "f_E_B") if hasattr(m, "f_E_B") else ())}
-
-
-BASE_KEYS = {True: ['D_A', 'G_A', 'Cyc_A', 'Cyc_z_B', 'KLD_z_B', 'D_B', 'G_B', 'Cyc_B', 'D_z_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B'],
-             False: ['D_A', 'G_A', 'Cyc_A', 'D_B', 'G_B', 'Cyc_B', 'P_t_A', 'P_f_A', 'P_t_B', 'P_f_B']}
 SSIM = ["Ssim_A", "Ssim_B"]
 
 
@@ -85,47 +63,9 @@ def test_every_family_names_its_scalars_in_order(aug):
 
 @pytest.mark.parametrize("aug", [True, False])
 def test_captured_and_deferred_steps_with_the_loss_on(aug):
-    """two eager warm-up calls, the capture and its replay: the first replayed step runs the eager step's kernels on the eager
-    step's numbers, so everything it reports equals the eager model's bit for bit (later steps carry the ulp of the device-side
-    bias correction, test_hip_step.py); the deferred scalars are the synchronous graph's; a change of either weight re-captures"""
-    from dtgan_amd import model as M
-    kw = dict(lambda_ssim_A=0.25, lambda_ssim_B=0.5)
-    ref, gr, lazy = _model(aug, **kw), _model(aug, **kw), _model(aug, **kw)
-    gr.enable_step_graph(); lazy.enable_step_graph(defer_scalars=True)
-    g = torch.Generator(device="cuda").manual_seed(11)
-    prev = None
-    for step in range(4):
-        A = torch.rand(4, 3, S, S, device="cuda", generator=g) * 2 - 1
-        B = torch.rand(4, 3, S, S, device="cuda", generator=g) * 2 - 1
-        z = torch.randn(4, 4, 1, 1, device="cuda", generator=g)
-        lr_, vr, gn_r = ref.train_instance(A, B, z)
-        lg, vg, gn_g = gr.train_instance(A, B, z)
-        out = lazy.train_instance(A, B, z)
-        assert list(lg.keys()) == BASE_KEYS[aug] + SSIM == list(lr_.keys())
-        if prev is not None:
-            assert prev[0].result()[0] == prev[1] and prev[0].result()[2] == prev[2]
-            prev = None
-        if isinstance(out, M.DeferredStep):
-            prev = (out, lg, gn_g)
-        else:
-            assert step < 2 and out[0] == lg
-        if step <= 2:
-            assert lg == lr_ and gn_g == gn_r, (step, lg, lr_)
-            for k in vr:
-                assert torch.equal(vr[k], vg[k]), (step, k)
-        else:
-            for k in lr_:
-                assert abs(lr_[k] - lg[k]) <= 2e-3 * max(1.0, abs(lr_[k])), (step, k, lr_[k], lg[k])
-    assert prev is not None and prev[0].result()[0] == prev[1]
-    assert gr._step_graph.captures == 1
-    for name, value in (("lambda_ssim_B", 0.125), ("lambda_ssim_A", 0.0)):
-        before = gr._step_graph.captures
-        setattr(gr.opt, name, value)
-        l, _, _ = gr.train_instance(A, B, z)
-        assert gr._step_graph.captures == before + 1 and np.isfinite(l["Ssim_A"]) and np.isfinite(l["Ssim_B"]), name
-    gr.opt.lambda_ssim_B = 0.0                                                  # both off: the 13 (10) keys again
-    l, _, _ = gr.train_instance(A, B, z)
-    assert list(l.keys()) == BASE_KEYS[aug]
+    """a change of either weight re-captures; both off: the 13 (10) keys again"""
+    check_captured_and_deferred("train_instance", dict(lambda_ssim_A=0.25, lambda_ssim_B=0.5), BASE_KEYS[aug] + SSIM,
+                                (("lambda_ssim_B", 0.125), ("lambda_ssim_A", 0.0)), dict(lambda_ssim_B=0.0), BASE_KEYS[aug], aug=aug)
 
 
 def test_the_paired_step_names_the_terms_and_keeps_its_gradient_norms():
@@ -177,21 +117,7 @@ def test_translate_ssim():
 @pytest.fixture(scope="module")
 def experiment(tmp_path_factory):
     """a synthetic .npz split (10 train -> 5 dev + 5 train, 3 test) and the checkpoint <expr_dir>/latest of a seeded tiny model"""
-    from dtgan_amd import options as O
-    from dtgan_amd.model import AugmentedCycleGAN
-    root = tmp_path_factory.mktemp("ssim_metric")
-    data = root / "data"
-    data.mkdir()
-    rs = np.random.RandomState(0)
-    for split, n in (("train", 10), ("test", 3)):
-        for dom in "AB":
-            np.savez(str(data / ("%s%s.npz" % (split, dom))), data=rs.uniform(0, 3, (n, S, S, 3)).astype(np.float32))
-    opt = O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(root), "--dataroot", str(data), "--grid_size",
-                                       str(S), "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4", "--n_blocks", "1",
-                                       "--seed", "3"])
-    torch.manual_seed(3)
-    AugmentedCycleGAN(opt).save("latest")
-    return dict(chk=os.path.join(opt.expr_dir, "latest"), data=str(data), expr=opt.expr_dir)
+    return make_experiment(tmp_path_factory.mktemp("ssim_metric"), S, 10, 3)
 
 
 def test_metric_ssim_writes_its_file(experiment, capsys):
@@ -219,15 +145,10 @@ def test_metric_ssim_writes_its_file(experiment, capsys):
 
 
 def test_train_driver_with_the_ssim_loss(tmp_path):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    env["PYTHONPATH"] = ROOT
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "dtgan_amd.train", "--name", "ssim", "--checkpoints_dir", str(tmp_path),
-           "--synthetic", "8", "--grid_size", "64", "--batchSize", "4", "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
-           "--niter", "1", "--niter_decay", "0", "--eval_steps", "1", "--num_multi", "2", "--lambda_ssim_B", "0.1",
-           "--print_freq", "4", "--display_freq", "8", "--seed", "1"]
-    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=660)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0, out[-4000:]
+    out = run_module("train", "--name", "ssim", "--checkpoints_dir", tmp_path,
+                     "--synthetic", "8", "--grid_size", "64", "--batchSize", "4", "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
+                     "--niter", "1", "--niter_decay", "0", "--eval_steps", "1", "--num_multi", "2", "--lambda_ssim_B", "0.1",
+                     "--print_freq", "4", "--display_freq", "8", "--seed", "1")
     d = os.path.join(str(tmp_path), "ssim")
     log = open(os.path.join(d, "results.txt")).read()
     lines = [ln for ln in log.splitlines() if re.search(r"\) D_A: ", ln)]          # the loss lines (not the gnorm_D_A ones)

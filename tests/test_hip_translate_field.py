@@ -12,6 +12,8 @@ import pytest
 import torch
 
 import window_ref as R
+from eval_cases import make_experiment, write_dataset
+from model_cases import tiny_model
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +23,7 @@ BAR = 2e-6
 
 @pytest.fixture(scope="module")
 def model():
-    from test_hip_api import _model
-    return _model(grid_size=S, n_blocks=1)
+    return tiny_model(grid_size=S, n_blocks=1)
 
 
 def _rand(*shape, seed=0):
@@ -118,16 +119,6 @@ def test_refusals(model):
     assert torch.is_grad_enabled()
 
 
-def _dataset(root, hw, n_train, n_test, same=False, seed=0):
-    os.makedirs(str(root), exist_ok=True)
-    rs = np.random.RandomState(seed)
-    for split, n in (("train", n_train), ("test", n_test)):
-        a = rs.uniform(0, 3, (n,) + hw + (3,)).astype(np.float32)
-        b = a if same else rs.uniform(0, 3, (n,) + hw + (3,)).astype(np.float32)
-        np.savez(os.path.join(str(root), split + "A.npz"), data=a)
-        np.savez(os.path.join(str(root), split + "B.npz"), data=b)
-
-
 def _train_two_steps(root, name):
     """one epoch of 2 batches (each followed by the paired step) on 72 x 80 fields whose A and B hold the same data ->
     (the inputs the four steps saw, their losses, the generator's parameters after them)"""
@@ -154,7 +145,7 @@ def _train_two_steps(root, name):
 
 
 def test_trainer_cuts_random_windows_reproducibly_and_pairs_share_theirs(tmp_path):
-    _dataset(tmp_path / "data", (72, 80), n_train=8, n_test=2, same=True)
+    write_dataset(tmp_path / "data", (72, 80), n_train=8, n_test=2, same=True)
     seen, losses, params, tr = _train_two_steps(tmp_path, "one")
     assert [k for k, _, _ in seen] == ["train_instance", "supervised_train_instance"] * 2
     fields = torch.from_numpy(tr.train_it.data_A)
@@ -179,16 +170,7 @@ def test_trainer_cuts_random_windows_reproducibly_and_pairs_share_theirs(tmp_pat
 @pytest.fixture(scope="module")
 def experiment(tmp_path_factory):
     """20 x 28 fields (6 train -> 3 dev + 3 train, 2 test) and the checkpoint of a seeded 16 x 16 model"""
-    from dtgan_amd import options as O
-    from dtgan_amd.model import AugmentedCycleGAN
-    root = tmp_path_factory.mktemp("translate_driver")
-    _dataset(root / "data", (20, 28), n_train=6, n_test=2, seed=1)
-    opt = O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(root), "--dataroot", str(root / "data"),
-                                       "--grid_size", str(S), "--ngf", "8", "--nef", "8", "--ndf", "8", "--nlatent", "4",
-                                       "--n_blocks", "1", "--seed", "3", "--native_res"])
-    torch.manual_seed(3)
-    AugmentedCycleGAN(opt).save("latest")
-    return dict(chk=os.path.join(opt.expr_dir, "latest"), data=str(root / "data"), expr=opt.expr_dir)
+    return make_experiment(tmp_path_factory.mktemp("translate_driver"), S, 6, 2, hw=(20, 28), seed=1, native_res=True)
 
 
 def test_metric_translate_writes_whole_fields_and_repeats(experiment, capsys):

@@ -394,7 +394,7 @@ def test_large_operand_cases_straddle_2_gib_and_stay_inside_the_launchers_limit(
     """the case generators of tests/test_hip_large_operands.py (no GPU): every size puts the 64-channel tensor past byte 2^31 and
     under 2^32, the middle one is ensemble_chunk itself, both operands of every convolution pass are inside the launchers' 4 GiB
     ACG_REQUIRE, the baseline size is below 2^31, and the image classes have the period the wrap argument needs"""
-    import test_hip_large_operands as L
+    import conv_cases as L
     from dtgan_amd.model import ensemble_chunk
     from dtgan_amd.ops import cpad
     assert cpad(2 * L.NGF) == L.C_LARGE == 64
@@ -415,9 +415,9 @@ def test_large_operand_cases_straddle_2_gib_and_stay_inside_the_launchers_limit(
     assert len(set(L.image_class(i) for i in range(12))) == 12 == L.PERIOD and L.image_class(12) == L.image_class(0)
     for wrap in (128, 256):
         assert all(L.image_class(i)[0] != L.image_class(i + wrap)[0] for i in range(12))
-    ids = [L.conv_id(c) for c in L.CONV_CASES] + [L.norm_id(c) for c in L.NORM_CASES]
+    ids = [L.conv_id(c) for c in L.LARGE_CONV_CASES] + [L.norm_id(c) for c in L.LARGE_NORM_CASES]
     assert len(set(ids)) == len(ids) == 4 * 3 * 3 * 2 + 2 * 3 * 3
-    assert all(L.expected_kernel(l, w, s, p) in L.KERNELS for l, w, s, p in L.CONV_CASES)
+    assert all(L.expected_kernel(l, w, s, p) in L.KERNELS for l, w, s, p in L.LARGE_CONV_CASES)
     # the fast paths are expected exactly where W is a multiple of 128 in the bf16x3 arithmetic
     assert L.expected_kernel("conv32to64", "fwd", L.SIZES[0], "bf16x3") == "rows"
     assert L.expected_kernel("conv32to64", "fwd", L.SIZES[2], "bf16x3") == "bf16tile"

@@ -1,4 +1,4 @@
-"""tests/latent_mlp_ref.py and the case list of tests/test_hip_latent_mlp.py, checked without a GPU:
+"""tests/latent_mlp_ref.py and the case list it keeps for tests/test_hip_latent_mlp.py, checked without a GPU:
   - the reference against a torch.nn.Sequential of the same modules in float64 with autograd, two training steps: 1e-10;
   - conditioning: a float32 restatement of the reference stays under HALF of every bar the GPU test holds the kernel to, at
     every value-checked case (a condition on the inputs: a case that fails it gets another seed or scale, never another bar);
@@ -10,7 +10,8 @@ import pytest
 import torch
 
 import latent_mlp_ref as R
-import test_hip_latent_mlp as G
+
+G = R          # the case list, the launch plan and the bars stand beside the reference
 
 TORCH_BAR = 1e-10
 

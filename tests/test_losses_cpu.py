@@ -3,7 +3,8 @@ and the refusals TrainOptions.parse runs over them."""
 import pytest
 
 import dtgan_amd  # noqa: F401
-from dtgan_amd import losses, model as M, options as O
+from dtgan_amd import losses, model as M
+from model_cases import parse_train as _parse
 
 # the options StepGraph._key named one by one before the records existed: every one must still be in the key
 KEY_BEFORE = ["max_gnorm", "lambda_A", "lambda_B", "lambda_z_B", "lambda_sup_A", "lambda_sup_B", "stoch_enc", "z_gan", "beta1",
@@ -64,11 +65,6 @@ def test_the_step_graph_key_holds_every_option_it_held_and_takes_the_families_fr
         hash(g._key(x, x, x))
         setattr(m.opt, name, 0.0)
     assert g._key(x, x, x) == base
-
-
-def _parse(tmp_path, *extra):
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--gpu_ids", "-1"]
-                                  + list(extra))
 
 
 @pytest.mark.parametrize("fam", losses.FAMILIES, ids=lambda f: f.stem)

@@ -4,15 +4,15 @@ step gives its optional loss scalars."""
 import argparse
 import os
 import pickle
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import dtgan_amd  # noqa: F401
-from dtgan_amd import options as O
 import marginal_ref as R
+from model_cases import parse_train as _parse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("acg_field_sort_workspace_bytes", "acg_field_sort", "acg_marginal_loss_workspace_bytes", "acg_marginal_loss_fwd",
@@ -63,20 +63,12 @@ def test_identical_batches_give_exactly_zero():
 
 def test_the_header_declares_the_entries_and_the_binding_matches():
     from dtgan_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in ENTRIES:
-        m = re.search(r"\b(?:size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+        assert len(abi.header_args(name)) == len(_lib.SIGNATURES[name][1]), name
         assert name in doc, name
     mk = open(os.path.join(ROOT, "domain-transfer-gan_amd", "csrc", "Makefile")).read()
     assert "marginal.hip" in mk
-
-
-def _parse(tmp_path, *extra):
-    return O.TrainOptions().parse(argv=["--name", "exp", "--checkpoints_dir", str(tmp_path), "--synthetic", "8", "--gpu_ids", "-1"]
-                                  + list(extra))
 
 
 def test_the_options_default_to_zero_and_are_written(tmp_path):

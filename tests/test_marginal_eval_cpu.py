@@ -2,11 +2,11 @@
 distance, numpy.searchsorted and closed forms), of marginal_edges and ops.marginal_summary, of the new entry point's
 declaration and of the --metric marginal options."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import dtgan_amd  # noqa: F401
 from dtgan_amd import ops
 from dtgan_amd import options as O
@@ -138,12 +138,10 @@ def test_check_levels_and_the_limits():
 
 def test_the_header_declares_the_entry_and_the_binding_matches():
     from dtgan_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acgan_hip.h")).read()
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    m = re.search(r"\bint\s+acg_marginal_scores\s*\(([^)]*)\)\s*;", hdr)
-    assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES["acg_marginal_scores"][1]) == 14
+    assert abi.declarations()["acg_marginal_scores"][0] == "int"
+    assert len(abi.header_args("acg_marginal_scores")) == len(_lib.SIGNATURES["acg_marginal_scores"][1]) == 14
     assert "acg_marginal_scores" in doc
-    assert re.search(r"#define ACG_VERSION 118\b", hdr) and _lib.ABI_VERSION == 118      # an added entry: no signature changed
 
 
 def test_the_parser_takes_the_metric_with_its_defaults():
