@@ -1,4 +1,5 @@
-"""ctypes binding of libacgan_hip.so (C ABI declared in include/acgan_hip.h).
+"""ctypes binding of libacgan_hip.so (C ABI declared in include/acgan_hip.h; verification-only entry points in
+include/acgan_verif.h).
 
 The shared object is built in-tree (csrc/Makefile, `__graft_entry__.build()`); there is
 no CPU or eager fallback: if the library is missing or a kernel call fails, this module
@@ -234,8 +235,19 @@ SIGNATURES = {
     "acg_swap_multi": (c_int, [ctypes.POINTER(EmaGroup), c_int, _P]),
 }
 
+# the verification-only entry points of the same library (include/acgan_verif.h): a table and a version of their own, so
+# the training ABI above does not move when the evaluator gains a score
+VERIF_SIGNATURES = {
+    "acg_verif_version": (c_int, []),
+    "acg_reliability_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "acg_reliability": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
+                                ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, ctypes.POINTER(c_int), c_int, _P, _P,
+                                c_size_t, _P]),
+}
+
 _lib = None
 ABI_VERSION = 118   # include/acgan_hip.h ACG_VERSION this binding was written against
+VERIF_ABI_VERSION = 1   # include/acgan_verif.h ACG_VERIF_VERSION
 
 
 class AcgError(RuntimeError):
@@ -258,6 +270,16 @@ def load():
     if got != ABI_VERSION:   # a stale build would take shifted arguments instead of failing cleanly
         raise AcgError("%s reports ABI version %d, this binding expects %d — rebuild it (make -C %s)"
                        % (LIB_PATH, got, ABI_VERSION, os.path.join(_HERE, "csrc")))
+    for name, (res, args) in VERIF_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:   # a build from before include/acgan_verif.h
+            raise AcgError("%s does not export %s (include/acgan_verif.h) — rebuild it (make -C %s)"
+                           % (LIB_PATH, name, os.path.join(_HERE, "csrc")))
+        fn.restype, fn.argtypes = res, args
+    got = lib.acg_verif_version()
+    if got != VERIF_ABI_VERSION:
+        raise AcgError("%s reports verification ABI version %d, this binding expects %d — rebuild it (make -C %s)"
+                       % (LIB_PATH, got, VERIF_ABI_VERSION, os.path.join(_HERE, "csrc")))
     _lib = lib
     return lib
 

@@ -28,8 +28,16 @@
 //           of tile row r, level 0 is popcounts, level 1 the 2-bit fields of x - ((x >> 1) & 0x55..), and each further level
 //           adds neighbouring blocks in the lane and then the lane 2^(l-1) away (6 levels: 63 exchanges per side), the first
 //           lane of every 2^l squaring.  The tile totals go to LDS; one thread per block forms levels 7 .. 10 from them.
+// The reliability tables of the same events (ops.reliability, --fss_rel; include/acgan_verif.h; tests/reliability_ref.py):
+//   rel     acg_reliability shares events.  The neighbourhood event of a cell is the OR of the events in its window (the
+//           window count is positive); table[k][o] counts the cells where k of the M members and o of the truth have it.
+//           One workgroup per (truth row, c, t, window), one thread per 64-bit word at a time: dilate the word of each of
+//           the M + 1 planes (OR down the rows of the window, then shifts along the row with the two neighbouring words;
+//           windows stop at 65), carry-save add the member words in registers, and per k add two popcounts to integer
+//           counters in LDS.  fss_rel<lds> while the M + 1 planes' words fit FSS_REL_LDS_MAX, fss_rel<global> above.
 #include "common.h"
 #include "field.h"
+#include "../../include/acgan_verif.h"
 #include <stdint.h>
 
 #define FSS_MAX_HW 1024
@@ -43,6 +51,9 @@
 #define FSS_SCALE_THREADS 256
 #define FSS_TILE_LEVELS 7                  // levels 0 .. 6 lie inside a 64 x 64 tile: one word per lane of a wave
 #define FSS_MAX_TILES 256                  // (FSS_MAX_HW / 64)^2
+#define FSS_REL_THREADS 1024
+#define FSS_REL_MAX_WINDOW 65              // radius 32: a dilated word depends on itself and its two neighbours only
+#define FSS_REL_LDS_MAX (FSS_LDS_MAX - 512) // fss_rel's counters take 520 bytes of static LDS
 
 typedef unsigned long long u64;
 
@@ -495,5 +506,140 @@ extern "C" int acg_fss_scales(const float *x, const float *y, int rows, int x_pe
     acg_note_kernel("fss_events<%s>%s%s", f[0].mode == FIELD_C4 ? "c4" : "strided", out != nullptr ? " + fss_scales" : "",
                     ens_out == nullptr ? "" : x_per_y == 1 ? " + fss_scales_ens" : " + fss_slices + fss_scales_ens");
     ACG_CHECK_LAUNCH("acg_fss_scales");
+    return ACG_OK;
+}
+
+// ---- reliability tables of the same events (include/acgan_verif.h; ops.reliability, --fss_rel) ----
+
+// One word of a plane's neighbourhood events: the OR of the events within r <= 32 rows and columns of each of the 64 cells
+// of word w of row i, inside the domain.  plane: H rows of WW words whose bits past W are 0 (fss_events writes them so).
+// Dilation separates: first the OR down the rows of the word and its two neighbours, then along the row by shifts; `valid`
+// (the cells of the word inside W) takes off what the shifts carried past W.
+__device__ __forceinline__ u64 fss_rel_dilate(const u64 *plane, int i, int w, int H, int WW, int r, u64 valid)
+{
+    const int i0 = max(i - r, 0), i1 = min(i + r, H - 1);
+    u64 c = 0, l = 0, h = 0;                                       // the word, the one before it, the one after it
+    if (r == 0) return plane[(long long)i * WW + w] & valid;
+    for (int ii = i0; ii <= i1; ++ii) {
+        const u64 *row = plane + (long long)ii * WW;
+        c |= row[w];
+        if (w > 0) l |= row[w - 1];
+        if (w + 1 < WW) h |= row[w + 1];
+    }
+    u64 d = c;
+    for (int s = 1; s <= r; ++s)                                   // 64 - s lies in 32 .. 63: no shift by the word's width
+        d |= (c << s) | (l >> (64 - s)) | (c >> s) | (h << (64 - s));
+    return d & valid;
+}
+
+// One workgroup per (truth plane q = (g, c, t), window blockIdx.y): table[k][o] of its H W cells, k the members among the
+// M of truth row g whose neighbourhood event holds, o the truth's.  Thread by thread over the (row, word) items: the M
+// dilated member words go through a carry-save counter (bit b of k in s[b], as in fss_slices_kernel), mask_k is the AND of
+// the slices or their complements, and the two popcounts of every k go to 32-bit counters in LDS (integer adds: any order
+// gives the same sums; a counter holds at most H W <= 2^20).  LDS: the M + 1 planes' words are copied into dynamic LDS
+// first (members, then the truth).
+template <bool LDS>
+__global__ __launch_bounds__(FSS_REL_THREADS) void fss_rel_kernel(FssPlanes px, FssPlanes py, int CT, int M, int NS, int H, int W,
+                                                                 FssWindows win, long long *__restrict__ table)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fss_lds[];
+    __shared__ unsigned cnt[2 * (FSS_MAX_M + 1)];
+    const int WW = (W + 63) >> 6, r = win.r[blockIdx.y];
+    const long long q = blockIdx.x, g = q / CT, p0 = g * M * CT + (q - g * CT);  // member m's plane lies m CT planes after p0
+    const long long nb = (long long)H * WW;
+    const u64 *xb = px.bits + p0 * nb, *yb = py.bits + q * nb;
+    long long xs = (long long)CT * nb;                             // the words between two members' planes
+    for (int t = threadIdx.x; t < 2 * (M + 1); t += blockDim.x) cnt[t] = 0;
+    if constexpr (LDS) {
+        u64 *lb = reinterpret_cast<u64 *>(fss_lds);
+        for (int m = 0; m < M; ++m)
+            for (int t = threadIdx.x; t < nb; t += blockDim.x) lb[m * nb + t] = xb[m * xs + t];
+        for (int t = threadIdx.x; t < nb; t += blockDim.x) lb[M * nb + t] = yb[t];
+        xb = lb, yb = lb + M * nb, xs = nb;
+    }
+    __syncthreads();
+    for (int item = threadIdx.x; item < nb; item += blockDim.x) {
+        const int i = item / WW, w = item - i * WW, left = W - w * 64;
+        const u64 valid = left >= 64 ? ~0ull : (1ull << left) - 1ull;
+        const u64 o = fss_rel_dilate(yb, i, w, H, WW, r, valid);
+        u64 s[FSS_MAX_NS];
+#pragma unroll
+        for (int b = 0; b < FSS_MAX_NS; ++b) s[b] = 0;
+        for (int m = 0; m < M; ++m) {
+            u64 carry = fss_rel_dilate(xb + m * xs, i, w, H, WW, r, valid);
+#pragma unroll
+            for (int b = 0; b < FSS_MAX_NS; ++b) {
+                const u64 t = s[b] & carry;
+                s[b] ^= carry;
+                carry = t;
+            }
+        }
+        for (int k = 0; k <= M; ++k) {
+            u64 mk = valid;
+#pragma unroll
+            for (int b = 0; b < FSS_MAX_NS; ++b)
+                if (b < NS) mk &= (k >> b) & 1 ? s[b] : ~s[b];
+            if (mk == 0) continue;
+            const unsigned n1 = __popcll(mk & o), n0 = __popcll(mk & ~o);
+            if (n0) atomicAdd(&cnt[2 * k], n0);
+            if (n1) atomicAdd(&cnt[2 * k + 1], n1);
+        }
+    }
+    __syncthreads();
+    long long *out = table + (q * gridDim.y + blockIdx.y) * 2 * (M + 1);
+    for (int t = threadIdx.x; t < 2 * (M + 1); t += blockDim.x) out[t] = (long long)cnt[t];
+}
+
+extern "C" int acg_verif_version(void) { return ACG_VERIF_VERSION; }
+
+// acg_fss's planes of x and of y, no slices: the members are added word by word in registers
+extern "C" size_t acg_reliability_workspace_bytes(int rows, int x_per_y, int C, int H, int W, int T, int nw)
+{
+    return fss_shape_ok(rows, x_per_y, C, H, W, T, nw) ? fss_planes_bytes(rows, x_per_y, C, H, W, T, 0) : 0;
+}
+
+extern "C" int acg_reliability(const float *x, const float *y, int rows, int x_per_y, int C, int H, int W, long long x_row_stride,
+                               int x_pix_stride, long long x_chan_stride, long long y_row_stride, int y_pix_stride,
+                               long long y_chan_stride, const float *thr, int T, const int *windows, int nw, long long *table,
+                               void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "acg_reliability";
+    Field f[2] = {{x, x_row_stride, x_chan_stride, x_pix_stride, FIELD_SCALAR}, {y, y_row_stride, y_chan_stride, y_pix_stride, FIELD_SCALAR}};
+    FIELD_CHECK(field_refuse_operands(fn, rows, C, f, 2));
+    FIELD_CHECK(field_refuse_pairing(fn, rows, x_per_y, FSS_MAX_M));
+    ACG_REQUIRE(x != nullptr && y != nullptr && thr != nullptr && windows != nullptr && table != nullptr, "acg_reliability: null tensor");
+    ACG_REQUIRE(H >= 1 && W >= 1 && H <= FSS_MAX_HW && W <= FSS_MAX_HW,
+                "acg_reliability: fields must be H x W with 1 <= H, W <= %d (got %d x %d)", FSS_MAX_HW, H, W);
+    ACG_REQUIRE(T >= 1 && T <= FSS_MAX_T, "acg_reliability: need 1 <= T <= %d thresholds (T=%d)", FSS_MAX_T, T);
+    ACG_REQUIRE(nw >= 1 && nw <= FSS_MAX_NW, "acg_reliability: need 1 <= nw <= %d windows (nw=%d)", FSS_MAX_NW, nw);
+    ACG_REQUIRE((long long)rows * C * T <= 0x7fffffffLL && (long long)rows * H <= 0x7fffffffLL,
+                "acg_reliability: too many planes (rows=%d, C=%d, T=%d, H=%d)", rows, C, T, H);
+    FssWindows win;
+    win.n = nw;
+    for (int k = 0; k < FSS_MAX_NW; ++k) win.r[k] = 0;
+    for (int k = 0; k < nw; ++k) {
+        const int n = windows[k];
+        ACG_REQUIRE(n >= 1 && n % 2 == 1 && n <= FSS_REL_MAX_WINDOW,
+                    "acg_reliability: windows must be odd and lie in 1..%d (window %d is %d)", FSS_REL_MAX_WINDOW, k, n);
+        win.r[k] = n / 2;
+    }
+    FIELD_CHECK(field_refuse_workspace(fn, ws, ws_bytes, acg_reliability_workspace_bytes(rows, x_per_y, C, H, W, T, nw)));
+    for (Field &o : f) o.mode = field_load_mode(o, C);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_y = rows / x_per_y, CT = C * T, NS = fss_slices(x_per_y);
+    const size_t npx = (size_t)rows * CT, npy = (size_t)rows_y * CT;
+    const FssSpace space = fss_carve(ws, npx, npy, 0, H, W);
+    fss_events(st, f[0], rows, C, H, W, thr, T, space.px);
+    fss_events(st, f[1], rows_y, C, H, W, thr, T, space.py);
+    const size_t lds = (size_t)(x_per_y + 1) * H * fss_ww(W) * sizeof(u64);
+    const bool resident = lds <= FSS_REL_LDS_MAX;
+    if (resident)
+        hipLaunchKernelGGL(fss_rel_kernel<true>, dim3((unsigned)npy, nw), dim3(FSS_REL_THREADS), lds, st, space.px, space.py, CT,
+                           x_per_y, NS, H, W, win, table);
+    else
+        hipLaunchKernelGGL(fss_rel_kernel<false>, dim3((unsigned)npy, nw), dim3(FSS_REL_THREADS), 0, st, space.px, space.py, CT,
+                           x_per_y, NS, H, W, win, table);
+    acg_note_kernel("fss_events<%s> + fss_rel<%s>", f[0].mode == FIELD_C4 ? "c4" : "strided", resident ? "lds" : "global");
+    ACG_CHECK_LAUNCH("acg_reliability");
     return ACG_OK;
 }

@@ -308,7 +308,10 @@ def fss_thresholds(train, quantiles, explicit=None):
     return np.quantile(x, np.asarray(quantiles, dtype=np.float64), axis=1).T.astype(np.float32)
 
 
-def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use_gpu=True, scales=False):
+REL_PAIRS = ('ens_prob_B', 'members_B', 'ens_mean_B', 'fake_A')
+
+
+def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use_gpu=True, scales=False, reliability=None):
     """fractions-skill-score triples on an aligned split, one read of the sums per batch.  A -> B: n_samples members per
     input, the ensemble as a probability and the ensemble mean (model.translate_fss) against the paired real B; B -> A:
     predict_A against the paired real A.  The int64 triples of every comparison are summed over the split (over the members
@@ -317,13 +320,19 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
     scales: the intensity-scale triples of the same events too (ops.fss_scales; nl dyadic levels), summed like the others: per
     k scale_sums_k (C, T, nl, 3) int64 and mse_scale_k, iss_k, en_rel_k (C, T, nl), mse_random_k (C, T), skill_scale_k (C, T)
     int64 of ops.fss_scale_summary (ens_prob_B with members=n_samples and the members' events); False: none of them, and no
-    launch more than before"""
+    launch more than before.
+    reliability: None, or a tuple of odd windows of at most 65: the reliability tables of the same events too (ops.reliability;
+    the same members, no random draw more), and the return is the pair (the dict above, rel): per comparison k of REL_PAIRS
+    table_k, the int64 tables summed over the split (ens_prob_B (C, T, nwr, M + 1, 2): cells by the number of members in the
+    neighbourhood event and by the truth's; the others (C, T, nwr, 2, 2), members_B summed over the members too), and every
+    entry of ops.reliability_summary as <entry>_k"""
     sums = {k: _Sum() for k in FSS_PAIRS}
+    tables = {k: _Sum() for k in REL_PAIRS}
     scale = {k: _Sum() for k in FSS_PAIRS}
     thresholds = _domain_tables(thresholds_B, thresholds_A)
     for real_A, real_B in _batches(dataset, use_gpu):
         thr_B, thr_A = thresholds(real_B, real_A)
-        r = model.translate_fss(real_A, n_samples, real_B, thr_B, windows, scales=scales)
+        r = model.translate_fss(real_A, n_samples, real_B, thr_B, windows, scales=scales, reliability=reliability)
         with torch.no_grad():
             pred_A = model.predict_A(real_B)
             fake_A = ops.fss(pred_A, real_A, real_A.size(1), "nchw", "nchw", thr_A, windows)
@@ -335,6 +344,11 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
                      ops.fss_scales(pred_A, real_A, real_A.size(1), "nchw", "nchw", thr_A))
             for k, v in zip(FSS_PAIRS, _read_back(parts)):
                 scale[k].add(v)
+        if reliability is not None:
+            parts = (r['ens_rel'], r['members_rel'].flatten(0, 1), r['ens_mean_rel'],
+                     ops.reliability(pred_A, real_A, real_A.size(1), "nchw", "nchw", thr_A, reliability))
+            for k, v in zip(REL_PAIRS, _read_back(parts)):
+                tables[k].add(v)
     res = {}
     for k in FSS_PAIRS:
         res['sums_' + k] = np.asarray(sums[k].total, dtype=np.int64)
@@ -346,7 +360,13 @@ def eval_fss(dataset, model, n_samples, thresholds_B, thresholds_A, windows, use
             ens = dict(members=n_samples, forecast_events=scale['members_B'].total[..., 0, 0]) if k == 'ens_prob_B' else {}
             summary = ops.fss_scale_summary(scale[k].total, sums[k].cells, **ens)
             res.update(('%s_%s' % ('mse_scale' if name == 'mse' else name, k), v) for name, v in summary.items())
-    return res
+    if reliability is None:
+        return res
+    rel = {}
+    for k in REL_PAIRS:
+        rel['table_' + k] = np.asarray(tables[k].total, dtype=np.int64)
+        rel.update(('%s_%s' % (name, k), v) for name, v in ops.reliability_summary(rel['table_' + k]).items())
+    return res, rel
 
 
 SAL_PAIRS = ('members_B', 'ens_mean_B', 'fake_A')
@@ -581,6 +601,7 @@ _COHERENCE = Metric('coherence', False, 200, None, _plain_prepare(eval_coherence
 
 def _fss_record():
     sal = []          # prepare -> report, with --fss_sal: the header of sal.npz, then what eval_sal gave on dev and on test
+    rel = []          # the same with --fss_rel: the header of reliability.npz, then eval_fss's second dict of dev and of test
 
     def _fss_prepare(opt, model, arrays):
         thr_B = fss_thresholds(arrays[1], opt.fss_quantiles, opt.fss_thresholds)     # once: dev and test share the climatology
@@ -591,6 +612,16 @@ def _fss_record():
         if scales:                                                     # 2^j, j = 0 .. L, of the fields the splits hold
             header['scales'] = 2 ** np.arange(ops.fss_scale_levels(*np.shape(arrays[3])[-2:]), dtype=np.int64)
         evaluate = lambda d: eval_fss(d, model, opt.n_samples, thr_B, thr_A, win, scales=scales)
+        if int(getattr(opt, 'fss_rel', 0)):
+            rwin = ops.check_rel_windows(opt.rel_windows)
+            del rel[:]
+            rel.append(dict(n_samples=np.int64(opt.n_samples), windows=np.array(rwin, dtype=np.int64), thresholds_B=thr_B,
+                            thresholds_A=thr_A))
+
+            def evaluate(dataset):                                     # the same members in the same launches' order: fss.npz keeps its bits
+                res, tables = eval_fss(dataset, model, opt.n_samples, thr_B, thr_A, win, scales=scales, reliability=rwin)
+                rel.append(tables)
+                return res
         if not int(getattr(opt, 'fss_sal', 0)):
             return header, evaluate
         del sal[:]
@@ -636,6 +667,18 @@ def _fss_record():
                      "TEST_SAL_A: %.4f %.4f %.4f (S, A, L)"
                      % (medians(sal_dev, 'members_B') + medians(sal_test, 'members_B') + medians(sal_test, 'ens_mean_B')
                         + medians(sal_test, 'fake_A')))
+        if int(getattr(opt, 'fss_rel', 0)):
+            header, rel_dev, rel_test = rel
+            arrays = dict(header)
+            for split, res in (('dev', rel_dev), ('test', rel_test)):
+                arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
+            np.savez(os.path.join(opt.res_dir, 'reliability.npz'), **arrays)
+            w1 = list(header['windows']).index(1) if 1 in header['windows'] else 0
+            at = lambda res, name, k: _chan_mean(res['%s_%s' % (name, k)][:, t, w1])
+            three = lambda res: tuple(at(res, name, 'ens_prob_B') for name in ('bss', 'reliability', 'auc'))
+            line += ("\nDEV_REL_PROB_B: %.4f %.4f %.4f, TEST_REL_PROB_B: %.4f %.4f %.4f (BSS, reliability, AUC), TEST_BSS_B: %.4f, "
+                     "TEST_BSS_MEAN_B: %.4f, TEST_BSS_A: %.4f"
+                     % (three(rel_dev) + three(rel_test) + tuple(at(rel_test, 'bss', k) for k in REL_PAIRS[1:])))
         return line
 
     return Metric('fss', False, 200, None, _fss_prepare, _fss_report, """\
@@ -687,7 +730,26 @@ def _fss_record():
               mean_abs_A_k, mean_L_k and defined_k, the fraction of pairs whose S and L exist, with n_samples, thresholds_B,
               thresholds_A, floor, conn -> <res_dir>/sal.npz, a file of its own.  The mean of an ensemble is smoother than
               its members: a positive S.  One more line is printed: the medians of S, A and L at the highest threshold, the
-              channel means, for the members on dev and test, the ensemble mean and B -> A.  1 <= H, W <= 1024""")
+              channel means, for the members on dev and test, the ensemble mean and B -> A.  1 <= H, W <= 1024.
+              --fss_rel 1 (default 0: off, fss.npz and the lines before as without it) asks what a forecaster asks first of
+              the ensemble as a probability: when k of the M = --n_samples members say "event", how often does it happen
+              (Murphy 1973)?  Per channel, threshold (those of the fss entries) and odd window n of --rel_windows (default
+              1,5,17; at most 8, each at most 65) the neighbourhood event of a cell is any event inside the centred n x n
+              window (the neighbourhood maximum ensemble probability, Schwartz & Sobash 2017; n = 1: the cell), and
+              ops.reliability (HIP, exact; acg_reliability of include/acgan_verif.h) counts the cells by k and by the truth's
+              neighbourhood event: table[k][o], (M + 1, 2) int64, every table summing to H W.  The same members in the same
+              group loop (model.translate_fss(reliability=...)), no random draw more.  Comparisons (REL_PAIRS): ens_prob_B
+              (M + 1 forecast values k / M), every single member (members_B), the ensemble mean (ens_mean_B) and B -> A
+              (fake_A: predict_A against the paired A at thresholds_A), the last three as 2 x 2 contingency tables.  Summed
+              over the split, then (ops.reliability_summary, float64 on the host) per comparison k: table_k, n_k, prob_k,
+              obs_freq_k (the reliability diagram; n_k is its sharpness histogram), base_rate_k, brier_k and its
+              decomposition reliability_k - resolution_k + uncertainty_k (exact: nothing is binned), bss_k = 1 - brier /
+              uncertainty, brier_fair_k (Ferro 2014: what infinitely many members would score; NaN for one), roc_hit_k,
+              roc_false_k (M + 2 points) and auc_k (trapezoid; the Mann-Whitney statistic), with n_samples, windows,
+              thresholds_B, thresholds_A -> <res_dir>/reliability.npz, a file of its own.  One more line is printed: the
+              Brier skill score, the reliability term and the AUC of ens_prob_B at the highest threshold and window 1 (the
+              first listed if 1 is absent) on dev and test, then the test BSS of a single member, of the ensemble mean and
+              of B -> A, channel means""")
 
 
 def _translate_record():

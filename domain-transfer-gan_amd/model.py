@@ -673,7 +673,7 @@ class _Base(object):
                 ops.sorted_scores(sb, None, lv, e, out={k: g.rows(v) for k, v in out["target"].items()})
         return out
 
-    def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None, scales=False):
+    def translate_fss(self, real_A, n_samples, real_B, thresholds, windows, z=None, chunk=None, scales=False, reliability=None):
         """Whether A -> B puts its threshold exceedances close enough: the fractions-skill-score triples (ops.fss: per
         channel, threshold and window the sums of cf^2, co^2 and cf co of the window counts of the events, x the translation,
         y the paired real_B) of each of n_samples translations of every input, of the ensemble as a probability (the summed
@@ -685,7 +685,12 @@ class _Base(object):
         scales=True: the intensity-scale triples of the same events too (ops.fss_scales, nl = ops.fss_scale_levels(H, W)
         dyadic levels in place of the windows), of the same members in the same group loop, as members_scale
         (N, M, C, T, nl, 3), ens_prob_scale and ens_mean_scale (N, C, T, nl, 3), for ops.fss_scale_summary; with False
-        neither the entries nor their launches exist.  Nothing is read back to the host."""
+        neither the entries nor their launches exist.  reliability: None, or a tuple of odd windows of at most 65
+        (ops.check_rel_windows): the reliability tables of the same events too (ops.reliability: cells by the number of members
+        in the neighbourhood event and by the truth's), of the same members in the same group loop with no random draw of
+        their own, as ens_rel (N, C, T, nwr, M + 1, 2) of the ensemble (x_per_y = M), members_rel (N, M, C, T, nwr, 2, 2) and
+        ens_mean_rel (N, C, T, nwr, 2, 2) of single fields, for ops.reliability_summary; with None neither the entries nor
+        their launches exist.  Nothing is read back to the host."""
         M, N, C, H, W, z, per = plan_ensemble("translate_fss", self.opt, real_A, n_samples, z, real_B, chunk, need_B=True)
         win = ops.check_windows(windows)
         thr = ops.channel_table("translate_fss", ValueError, "thresholds", thresholds, C, ops.FSS_MAX_T, real_A.device, cast=True)
@@ -697,6 +702,11 @@ class _Base(object):
             nl = ops.fss_scale_levels(H, W)
             out.update(members_scale=torch.empty((N, M, C, T, nl, 3), **i64), ens_prob_scale=torch.empty((N, C, T, nl, 3), **i64),
                        ens_mean_scale=torch.empty((N, C, T, nl, 3), **i64))
+        if reliability is not None:
+            rwin = ops.check_rel_windows(reliability)
+            nwr = len(rwin)
+            out.update(ens_rel=torch.empty((N, C, T, nwr, M + 1, 2), **i64), members_rel=torch.empty((N, M, C, T, nwr, 2, 2), **i64),
+                       ens_mean_rel=torch.empty((N, C, T, nwr, 2, 2), **i64))
         with eval_state(self.netG_A_B), torch.no_grad():
             for members, g in self._groups(real_A, z, M, per, real_B):
                 ops.fss(members, g.b, C, "nhwc", "nchw", thr, win, x_per_y=M, ensemble=True,
@@ -707,6 +717,11 @@ class _Base(object):
                     ops.fss_scales(members, g.b, C, "nhwc", "nchw", thr, x_per_y=M, ensemble=True,
                                    out=(g.flat(out["members_scale"]), g.rows(out["ens_prob_scale"])))
                     ops.fss_scales(mean, g.b, C, "nchw", "nchw", thr, out=g.rows(out["ens_mean_scale"]))
+                if reliability is not None:
+                    ops.reliability(members, g.b, C, "nhwc", "nchw", thr, rwin, x_per_y=M, out=g.rows(out["ens_rel"]))
+                    ops.reliability(members, _each_n_times(g.b, M), C, "nhwc", "nchw", thr, rwin,   # a table per member: a truth row each
+                                    out=g.flat(out["members_rel"]))
+                    ops.reliability(mean, g.b, C, "nchw", "nchw", thr, rwin, out=g.rows(out["ens_mean_rel"]))
         return out
 
     def translate_minkowski(self, real_A, n_samples, thresholds, z=None, chunk=None, components=0):

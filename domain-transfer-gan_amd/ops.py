@@ -2327,6 +2327,97 @@ def fss_scale_summary(sums, cells, members=1, forecast_events=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# reliability tables of the fss events (--metric fss --fss_rel 1; include/acgan_verif.h; tests/reliability_ref.py)
+# ----------------------------------------------------------------------------------------------
+REL_MAX_WINDOW = 65
+
+
+def check_rel_windows(windows):
+    """check_windows with the reliability kernel's cap -> the widths as a tuple of ints; ValueError unless 1..8 odd widths in
+    1..65 (a dilated 64-bit word then depends on itself and its two neighbours only)"""
+    w = check_windows(windows)
+    if any(v > REL_MAX_WINDOW for v in w):
+        raise ValueError("windows must be at most %d wide (got %s)" % (REL_MAX_WINDOW, w))
+    return w
+
+
+def reliability(x, y, C, layout_x, layout_y, thresholds, windows, x_per_y=1, out=None):
+    """acg_reliability: the reliability tables of the C valid channels of x against y -> (rows / x_per_y, C, T, nw, M + 1, 2)
+    int64 on the device, M = x_per_y.  The events are fss's, [x >= thresholds[c][t]] (NaN is no event); the neighbourhood event
+    of a cell at the odd window n <= 65 holds iff any cell of the centred n x n window inside the domain is an event (the
+    neighbourhood maximum ensemble probability of Schwartz & Sobash 2017; n = 1 is the cell itself).  table[k][o] is the number
+    of the H x W cells where k of the M members of a truth have the neighbourhood event and the truth has it (o = 1) or not
+    (o = 0): every (M + 1, 2) block sums to H W, and with M = 1 it is the 2 x 2 contingency table.  Exact integers, the same
+    bits in every layout.  Row r of x pairs with row r / x_per_y of y.  thresholds: (C, T) float32 on the device, or a host
+    array (copied to the device).  `out`: the int64 tensor to write.  Sum the tables over a set of pairs, then
+    ops.reliability_summary.  Nothing is read back to the host.  Not differentiable."""
+    x, y, rows, rows_y, C, _, (H, W), sx, sy, x_per_y = _paired_fields("reliability", x, y, C, layout_x, layout_y, _fss_size,
+                                                                       x_per_y, max_per=FSS_MAX_M, size_y=True)
+    try:
+        win = check_rel_windows(windows)
+    except ValueError as e:
+        raise _lib.AcgError("reliability: %s" % e)
+    thr = channel_table("reliability", _lib.AcgError, "thresholds", thresholds, C, FSS_MAX_T, None)
+    T, nw = int(thr.size(1)), len(win)
+    shape = (rows_y, C, T, nw, x_per_y + 1, 2)
+    _refuse_out("reliability", out, shape, torch.int64)
+    if not torch.is_tensor(thresholds):                            # a host array goes to the device; a tensor is where it has to be
+        thr = thr.to(x.device)
+    _check(x, y, thr)                                              # after the refusals that need no device
+    out = _out_or_new(out, shape, torch.int64, x.device)
+    ws, nbytes = _metric_workspace("acg_reliability_workspace_bytes", rows, x_per_y, C, H, W, T, nw)
+    _lib.call("acg_reliability", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
+              (ctypes.c_int * nw)(*win), nw, _ptr(out), ws, nbytes, _stream())
+    return out
+
+
+def reliability_summary(table):
+    """(..., M + 1, 2) int64 tables of ops.reliability summed over a set of pairs -> dict of float64 arrays on the host (n:
+    int64).  The forecast probability takes the M + 1 values k / M, so nothing is binned (Murphy 1973):
+      n (..., M + 1)        cells with k members in the event; prob (M + 1,) = k / M
+      obs_freq (..., M + 1) the observed frequency among them (the reliability diagram), NaN where n_k = 0
+      base_rate (...)       observed events / cells
+      brier (...)           mean of (k / M - o)^2
+      reliability, resolution, uncertainty (...)  sum_k n_k (k / M - obs_freq_k)^2 / cells, sum_k n_k (obs_freq_k - base_rate)^2
+                            / cells, base_rate (1 - base_rate): brier = reliability - resolution + uncertainty exactly
+      bss (...)             1 - brier / uncertainty, NaN where the uncertainty is 0
+      brier_fair (...)      brier - sum_k n_k k (M - k) / (M^2 (M - 1)) / cells, the score an infinite ensemble of the same
+                            distribution would get (Ferro 2014); NaN for M = 1
+      roc_hit, roc_false (..., M + 2)  hit rate and false-alarm rate of "at least j members", j = M + 1 (none) .. 0 (all); NaN
+                            where the class (events, non-events) is empty
+      auc (...)             the area under that curve by the trapezoid rule: the Mann-Whitney statistic with ties counted
+                            half; NaN where a class is empty."""
+    import numpy as np
+    t = np.asarray(table)
+    if t.ndim < 2 or t.shape[-1] != 2 or t.shape[-2] < 2:
+        raise ValueError("reliability_summary: need (..., M + 1, 2) tables with M >= 1 (got %s)" % (t.shape,))
+    M = t.shape[-2] - 1
+    t = t.astype(np.int64)
+    n = t[..., 0] + t[..., 1]
+    k = np.arange(M + 1, dtype=np.float64)
+    prob = k / M
+    t0, t1, nf = t[..., 0].astype(np.float64), t[..., 1].astype(np.float64), n.astype(np.float64)
+    cells, events = nf.sum(-1), t1.sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        obs = np.where(n > 0, t1 / nf, np.nan)
+        base = events / cells
+        brier = (t1 * (prob - 1.0) ** 2 + t0 * prob ** 2).sum(-1) / cells
+        rel = np.where(n > 0, nf * (prob - obs) ** 2, 0.0).sum(-1) / cells
+        res = np.where(n > 0, nf * (obs - base[..., None]) ** 2, 0.0).sum(-1) / cells
+        unc = base * (1.0 - base)
+        bss = np.where(unc > 0, 1.0 - brier / unc, np.nan)
+        fair = brier - (nf * k * (M - k)).sum(-1) / (float(M) * M * (M - 1)) / cells if M > 1 else np.full(brier.shape, np.nan)
+        zero = np.zeros(t.shape[:-2] + (1,))
+        hit = np.concatenate([zero, np.cumsum(t1[..., ::-1], -1)], -1) / events[..., None]
+        false = np.concatenate([zero, np.cumsum(t0[..., ::-1], -1)], -1) / (cells - events)[..., None]
+        hit = np.where((events > 0)[..., None], hit, np.nan)
+        false = np.where((cells - events > 0)[..., None], false, np.nan)
+        auc = (0.5 * (hit[..., 1:] + hit[..., :-1]) * (false[..., 1:] - false[..., :-1])).sum(-1)
+    return dict(n=n, prob=prob, obs_freq=obs, base_rate=base, brier=brier, reliability=rel, resolution=res, uncertainty=unc,
+                bss=bss, brier_fair=fair, roc_hit=hit, roc_false=false, auc=auc)
+
+
+# ----------------------------------------------------------------------------------------------
 # the fractions-skill-score training loss (the paired step under --lambda_fss_A / --lambda_fss_B; tests/fss_loss_ref.py)
 # ----------------------------------------------------------------------------------------------
 FSS_LOSS_MAX_WINDOW = 65

@@ -224,7 +224,9 @@ class TestOptions(object):
     metric `minkowski` (area, perimeter and Euler characteristic of the excursion sets, unpaired, reuses --n_samples) with
     --mink_bins, and --mink_components (the connected components of the same sets: objects, holes, object sizes); --fss_sal (with
     the metric `fss`: the SAL score, structure, amplitude and location of the objects of the same paired translations, into a
-    file of its own) with --sal_quantiles, --sal_thresholds, --sal_floor and --sal_conn."""
+    file of its own) with --sal_quantiles, --sal_thresholds, --sal_floor and --sal_conn; --fss_rel (with the metric `fss`: the
+    reliability tables of the ensemble's neighbourhood events - Brier score and its decomposition, reliability diagram, ROC -
+    into a file of its own) with --rel_windows."""
 
     def __init__(self):
         from .eval_metrics import METRICS      # here, not at the top: it imports train.py, which imports this module
@@ -280,6 +282,12 @@ class TestOptions(object):
                                       '(finite, default -1)')
         self.parser.add_argument('--sal_conn', type=int, choices=[4, 8], default=8,
                                  help='--metric fss --fss_sal 1: the connectivity of the objects, 4 (shared edges) or 8 (edges or corners)')
+        self.parser.add_argument('--fss_rel', type=int, choices=[0, 1], default=0,
+                                 help='--metric fss: 1 also counts, per number of members in the neighbourhood event, the cells '
+                                      'where the truth has it (Brier score, reliability, resolution, ROC) -> reliability.npz; 0: off')
+        self.parser.add_argument('--rel_windows', type=_rel_windows, default=(1, 5, 17),
+                                 help='--metric fss --fss_rel 1: comma-separated odd neighbourhood widths in cells, at most 8, each '
+                                      'at most 65; the neighbourhood event of a cell is any event inside the window')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
@@ -379,6 +387,13 @@ def _fss_windows(s):
     if len(w) > 8:
         raise argparse.ArgumentTypeError("--fss_windows: at most 8 widths, 1 included (got %r)" % s)
     return tuple(w)
+
+
+def _rel_windows(s):
+    w = tuple(_split("--rel_windows", s, int, "integers"))
+    if not 1 <= len(w) <= 8 or any(v < 1 or v % 2 == 0 or v > 65 for v in w):
+        raise argparse.ArgumentTypeError("--rel_windows: 1 to 8 odd widths of at most 65 cells (got %r)" % s)
+    return w
 
 
 def _fss_loss_windows(s):
