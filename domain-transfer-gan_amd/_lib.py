@@ -1,5 +1,5 @@
 """ctypes binding of libacgan_hip.so (C ABI declared in include/acgan_hip.h; verification-only entry points in
-include/acgan_verif.h).
+include/acgan_verif.h, per-cell ones in include/acgan_cell.h).
 
 The shared object is built in-tree (csrc/Makefile, `__graft_entry__.build()`); there is
 no CPU or eager fallback: if the library is missing or a kernel call fails, this module
@@ -245,9 +245,25 @@ VERIF_SIGNATURES = {
                                 c_size_t, _P]),
 }
 
+# the per-cell (climatology map) entry points (include/acgan_cell.h), bound like the verification ones
+CELL_SIGNATURES = {
+    "acg_cell_version": (c_int, []),
+    "acg_cell_stats": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong,
+                               ctypes.c_longlong, c_int, ctypes.c_longlong, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 ABI_VERSION = 118   # include/acgan_hip.h ACG_VERSION this binding was written against
 VERIF_ABI_VERSION = 1   # include/acgan_verif.h ACG_VERIF_VERSION
+CELL_ABI_VERSION = 1   # include/acgan_cell.h ACG_CELL_VERSION
+
+
+def _tables():
+    """(table, version symbol, expected version, header, the word before "ABI version" in the message), in binding order;
+    header None: the training table, whose missing symbols raise AttributeError"""
+    return ((SIGNATURES, "acg_version", ABI_VERSION, None, ""),
+            (VERIF_SIGNATURES, "acg_verif_version", VERIF_ABI_VERSION, "include/acgan_verif.h", "verification "),
+            (CELL_SIGNATURES, "acg_cell_version", CELL_ABI_VERSION, "include/acgan_cell.h", "per-cell "))
 
 
 class AcgError(RuntimeError):
@@ -263,23 +279,16 @@ def load():
         raise AcgError("libacgan_hip.so not found at %s — build it with `make -C %s` "
                        "(or __graft_entry__.build()); there is no fallback path." % (LIB_PATH, os.path.join(_HERE, "csrc")))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype, fn.argtypes = res, args
-    got = lib.acg_version()
-    if got != ABI_VERSION:   # a stale build would take shifted arguments instead of failing cleanly
-        raise AcgError("%s reports ABI version %d, this binding expects %d — rebuild it (make -C %s)"
-                       % (LIB_PATH, got, ABI_VERSION, os.path.join(_HERE, "csrc")))
-    for name, (res, args) in VERIF_SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:   # a build from before include/acgan_verif.h
-            raise AcgError("%s does not export %s (include/acgan_verif.h) — rebuild it (make -C %s)"
-                           % (LIB_PATH, name, os.path.join(_HERE, "csrc")))
-        fn.restype, fn.argtypes = res, args
-    got = lib.acg_verif_version()
-    if got != VERIF_ABI_VERSION:
-        raise AcgError("%s reports verification ABI version %d, this binding expects %d — rebuild it (make -C %s)"
-                       % (LIB_PATH, got, VERIF_ABI_VERSION, os.path.join(_HERE, "csrc")))
+    rebuild = "rebuild it (make -C %s)" % os.path.join(_HERE, "csrc")
+    for table, version, expected, header, word in _tables():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name) if header is None else getattr(lib, name, None)  # AttributeError if the .so does not export it
+            if fn is None:   # a build from before the header
+                raise AcgError("%s does not export %s (%s) — %s" % (LIB_PATH, name, header, rebuild))
+            fn.restype, fn.argtypes = res, args
+        got = getattr(lib, version)()
+        if got != expected:   # a stale build would take shifted arguments instead of failing cleanly
+            raise AcgError("%s reports %sABI version %d, this binding expects %d — %s" % (LIB_PATH, word, got, expected, rebuild))
     _lib = lib
     return lib
 

@@ -74,17 +74,95 @@ def _cells(t):
 ENSEMBLE_SCORES = ('crps', 'crps_fair', 'mse_mean', 'spread', 'coverage')
 
 
-def eval_ensemble_B(dataset, model, n_samples, quantiles, use_gpu=True):
+MAP_PAIRS = ('members_B', 'fake_A')
+MAP_STATE_LIMIT = 2 << 30          # bytes of whole-split per-cell state on the device
+_MAP_PARTS = ('mom', 'evt', 'hist_x', 'hist_y')
+
+
+def plan_ens_maps(opt, arrays):
+    """--ens_maps 1: what the per-cell maps need before a split is touched -> the record eval_ensemble_B takes as `maps`:
+    thresholds_B / thresholds_A (C, T) float32 or None (fss_thresholds of --map_quantiles / --map_thresholds on trainB /
+    trainA), edges_B / edges_A (C, B - 1) float32 or None (marginal_edges of --map_bins), levels.  arrays = (trainA, trainB,
+    devA, devB, testA, testB).  ValueError for a state of both directions above MAP_STATE_LIMIT on the device, and for a
+    split whose rows times --n_samples pass the 2^31 - 1 an int32 histogram count holds."""
+    trainA, trainB, devA, devB, testA, testB = arrays
+    quant, explicit, bins = tuple(opt.map_quantiles), opt.map_thresholds, int(opt.map_bins)
+    tables = {}
+    for d, train in (('B', trainB), ('A', trainA)):
+        none = explicit is None and not quant
+        tables['thresholds_' + d] = None if none else fss_thresholds(train, quant, explicit)
+        tables['edges_' + d] = marginal_edges(train, bins) if bins else None
+    T = 0 if tables['thresholds_B'] is None else tables['thresholds_B'].shape[1]
+    if T > ops.CELL_MAX_T or not (bins == 0 or 2 <= bins <= ops.CELL_MAX_E + 1):
+        raise ValueError("--ens_maps: at most %d thresholds and --map_bins 0 or in 2..%d (got %d, %d)"
+                         % (ops.CELL_MAX_T, ops.CELL_MAX_E + 1, T, bins))
+    E = max(bins - 1, 0)
+    need = sum(ops.cell_state_bytes(np.shape(a)[1], np.shape(a)[2], np.shape(a)[3], T, E) for a in (devB, devA))
+    if need > MAP_STATE_LIMIT:
+        raise ValueError("--ens_maps: the per-cell state of a split needs %d bytes (%.2f GiB) on the device, above %d GiB; fewer "
+                         "--map_bins (0: no histograms) and fewer --map_quantiles / --map_thresholds shrink it"
+                         % (need, need / float(1 << 30), MAP_STATE_LIMIT >> 30))
+    rows = max(len(devB), len(testB)) * int(opt.n_samples)
+    if rows > 2 ** 31 - 1:
+        raise ValueError("--ens_maps: %d member rows per cell pass the 2^31 - 1 an int32 histogram count holds" % rows)
+    tables['levels'] = tuple(opt.map_levels)
+    return tables
+
+
+def _maps_result(states, crps_sum, maps):
+    """the states of MAP_PAIRS (device) -> the entries of a split in ensemble_maps.npz: per pair k the raw state (mom_k, evt_k,
+    hist_x_k, hist_y_k, n_k, members_k) and every map of ops.cell_summary as <map>_k; crps_B.  One copy per dtype"""
+    host = {k: dict(n=states[k]['n'], M=states[k]['M']) for k in MAP_PAIRS}
+    for part in _MAP_PARTS:
+        have = [k for k in MAP_PAIRS if states[k][part] is not None]
+        extra = [crps_sum] if part == 'mom' else []
+        got = _read_back([states[k][part] for k in have] + extra) if have else []
+        for k, v in zip(have, got):
+            host[k][part] = v
+        for k in MAP_PAIRS:
+            host[k].setdefault(part, None)
+        if extra:
+            crps = got[-1]
+    res = {'crps_B': crps / float(max(host['members_B']['n'], 1))}
+    for k in MAP_PAIRS:
+        d = k[-1]
+        res.update(('%s_%s' % (part, k), host[k][part]) for part in _MAP_PARTS if host[k][part] is not None)
+        res['n_' + k], res['members_' + k] = np.int64(host[k]['n']), np.int64(host[k]['M'])
+        summary = ops.cell_summary(host[k], maps['thresholds_' + d], maps['edges_' + d], maps['levels'])
+        res.update(('%s_%s' % (name, k), v) for name, v in summary.items())
+    return res
+
+
+def eval_ensemble_B(dataset, model, n_samples, quantiles, use_gpu=True, maps=None):
     """the per-input ensemble scores of A -> B on an aligned split (model.translate_ensemble, one read of the numbers per
-    batch) -> ({score: (N,) array for every input}, rank histogram pooled over the split (n_samples + 1,))"""
+    batch) -> ({score: (N,) array for every input}, rank histogram pooled over the split (n_samples + 1,)).
+    maps: None, or the record of plan_ens_maps: the per-cell statistics of the same members too (ops.cell_stats after every
+    group's ensemble_stats, no random draw more; the state lives on the device for the whole split), and of B -> A
+    (model.translate_cell_stats_A), and the return gains a third entry, the dict of _maps_result"""
     per, hist = {k: [] for k in ENSEMBLE_SCORES}, np.zeros(n_samples + 1, dtype=np.int64)
+    states, crps_sum, tables = None, None, None
     for real_A, real_B in _batches(dataset, use_gpu):
-        r = model.translate_ensemble(real_A, n_samples, real_B=real_B, quantiles=quantiles)
+        cell = None
+        if maps is not None:
+            if states is None:
+                T = 0 if maps['thresholds_B'] is None else maps['thresholds_B'].shape[1]
+                E = 0 if maps['edges_B'] is None else maps['edges_B'].shape[1]
+                states = {k: ops.cell_state(t.size(1), t.size(2), t.size(3), T, E, t.device)
+                          for k, t in zip(MAP_PAIRS, (real_B, real_A))}
+                up = lambda a, t: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(t.device)
+                tables = {d: (up(maps['thresholds_' + d], t), up(maps['edges_' + d], t)) for d, t in (('B', real_B), ('A', real_A))}
+                crps_sum = torch.zeros(real_B.shape[1:], dtype=torch.float64, device=real_B.device)
+            cell = (states['members_B'],) + tables['B']
+        r = model.translate_ensemble(real_A, n_samples, real_B=real_B, quantiles=quantiles, cell_stats=cell)
         *scores, ranks = _read_back([r[k].double() for k in ENSEMBLE_SCORES + ('rank_hist',)])
         for k, v in zip(ENSEMBLE_SCORES, scores):
             per[k].append(v)
         hist += ranks.sum(0).astype(np.int64)
-    return {k: np.concatenate(v) for k, v in per.items()}, hist
+        if maps is not None:
+            crps_sum += r['crps_map'].double().sum(0)
+            model.translate_cell_stats_A(real_B, real_A, states['fake_A'], *tables['A'])
+    res = {k: np.concatenate(v) for k, v in per.items()}, hist
+    return res if maps is None else res + (_maps_result(states, crps_sum, maps),)
 
 
 def visualize_ensemble(opt, real_A, real_B, model, name):
@@ -536,25 +614,69 @@ def _ensemble_record():
 
     def prepare(opt, model, arrays):
         run.update(model=model, devA=arrays[2], devB=arrays[3])
+        header = dict(n_samples=np.int64(opt.n_samples), quantiles=np.array(opt.quantiles, dtype=np.float64))
+        if not int(getattr(opt, 'ens_maps', 0)):
+            def scored(dataset):
+                scores, hist = eval_ensemble_B(dataset, model, opt.n_samples, opt.quantiles)
+                return dict(scores, rank_hist=hist)
+            return header, scored
+        try:
+            maps = plan_ens_maps(opt, arrays)
+        except ValueError as e:
+            raise SystemExit(e.args[0])
+        run['maps'] = [maps]                                       # then what the maps gave on dev and on test
 
-        def scored(dataset):
-            scores, hist = eval_ensemble_B(dataset, model, opt.n_samples, opt.quantiles)
+        def scored(dataset):                                       # the same members in the same launches' order: ensemble.npz keeps its bits
+            scores, hist, cells = eval_ensemble_B(dataset, model, opt.n_samples, opt.quantiles, maps=maps)
+            run['maps'].append(cells)
             return dict(scores, rank_hist=hist)
-        return dict(n_samples=np.int64(opt.n_samples), quantiles=np.array(opt.quantiles, dtype=np.float64)), scored
+        return header, scored
 
     def report(opt, dev, test):
         model, devA, devB = run.pop('model'), run.pop('devA'), run.pop('devB')
         vis = next(iter(AlignedIterator(devA, devB, batch_size=max(min(10, len(devA)), 1))))
         visualize_ensemble(opt, vis['A'].cuda(), vis['B'].cuda(), model, 'ensemble_0.png')
-        return ("DEV_CRPS_B: %.4f, TEST_CRPS_B: %.4f, TEST_MSE_MEAN_B: %.4f, TEST_SPREAD_B: %.4f, TEST_COVERAGE_B: %.4f"
+        line = ("DEV_CRPS_B: %.4f, TEST_CRPS_B: %.4f, TEST_MSE_MEAN_B: %.4f, TEST_SPREAD_B: %.4f, TEST_COVERAGE_B: %.4f"
                 % (dev['crps'].mean(), test['crps'].mean(), test['mse_mean'].mean(), _pooled_spread(test['spread']),
                    test['coverage'].mean()))
+        if 'maps' in run:
+            maps, cells_dev, cells_test = run.pop('maps')
+            arrays = dict(n_samples=np.int64(opt.n_samples), levels=np.array(maps['levels'], dtype=np.float64))
+            arrays.update((k, v) for k, v in maps.items() if k != 'levels' and v is not None)
+            for split, res in (('dev', cells_dev), ('test', cells_test)):
+                arrays.update(('%s_%s' % (split, k), v) for k, v in res.items())
+            np.savez(os.path.join(opt.res_dir, 'ensemble_maps.npz'), **arrays)
+            four = lambda res: (_chan_mean(np.abs(res['bias_members_B'])), _chan_mean(res['rmse_mean_members_B']),
+                                _chan_mean(res['spread_skill_members_B']),
+                                _chan_mean(res['brier_members_B'][:, -1]) if 'brier_members_B' in res else float('nan'))
+            line += ("\nDEV_MAP_B: %.4f %.4f %.4f %.4f, TEST_MAP_B: %.4f %.4f %.4f %.4f (domain means of |bias|, RMSE of the ensemble "
+                     "mean, spread / skill, Brier score at the highest threshold)" % (four(cells_dev) + four(cells_test)))
+        return line
     return Metric('ensemble', False, 200, None, prepare, report, """\
   ensemble    (new) the stochastic direction scored as a distribution: --n_samples translations A -> B of every dev and test
               input (model.translate_ensemble), per input the CRPS, its fair form, the MSE of the ensemble mean, the spread
               and the coverage of the outer --quantiles band against the paired B, and the rank histogram of B among the
               members -> <res_dir>/ensemble.npz, and grids of A, B, mean, std and the outer quantiles for the first dev batch
-              of 10 (ensemble_0.png)""")
+              of 10 (ensemble_0.png).
+              --ens_maps 1 (default 0: off, ensemble.npz, ensemble_0.png and the line above as without it) draws the first
+              figures of a model on a fixed grid: maps with one value per cell, taken across the inputs of the split.  Every
+              cell keeps running sums over the rows of every batch (ops.cell_stats, HIP, acg_cell_stats of
+              include/acgan_cell.h: doubles and exact integers added in a fixed order, the same bits whatever the layout or
+              the batching), of the same members in the same group loop (model.translate_ensemble(cell_stats=...)), no random
+              draw more; the state of a split stays on the device (refused above 2 GiB) and is read back once.  Pairs
+              (MAP_PAIRS): members_B (the --n_samples members against the paired B; it carries the ensemble-mean and spread
+              maps) and fake_A (predict_A against the paired A, one member).  Events at the quantile levels --map_quantiles
+              (default 0.9,0.99; at most 8; "none": no events) of the real training fields per channel, or at
+              --map_thresholds; histograms between the B - 1 quantiles k / B of the training fields, B = --map_bins (default
+              32; 0: none; at most 64); quantile maps at --map_levels (default 0.5,0.95,0.99).  Per split and pair k: the raw
+              state mom_k (9, C, H, W: Sx, Sxx, Sy, Syy, Sxy, S|x - y|, SS, SSy, Sw), evt_k (C, T, 4, H, W), hist_x_k,
+              hist_y_k (C, B, H, W), n_k, members_k, and (ops.cell_summary, float64 on the host) mean_x_k, mean_y_k, bias_k,
+              std_x_k, std_y_k, std_ratio_k, corr_k, rmse_k, mae_k, rmse_mean_k, corr_mean_k, spread_k, spread_skill_k
+              (C, H, W), freq_x_k, freq_y_k, freq_bias_k, brier_k, hit_rate_k, csi_k (C, T, H, W), cdf_x_k, cdf_y_k
+              (C, B - 1, H, W), ks_k, q_x_k, q_y_k (C, levels, H, W); crps_B (C, H, W), the mean of translate_ensemble's
+              crps_map; with n_samples, thresholds_B, thresholds_A, edges_B, edges_A, levels -> <res_dir>/ensemble_maps.npz,
+              a file of its own.  One more line is printed: the domain means of |bias|, the RMSE of the ensemble mean, spread
+              / skill and the Brier score at the highest threshold, for dev and test.  1 <= H, W <= 1024""")
 
 
 def _plain_prepare(eval_split, rings=False):

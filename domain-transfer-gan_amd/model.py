@@ -558,15 +558,22 @@ class _Base(object):
         for g0, n, members in self.ensemble_groups(real_A, z, M, per):
             yield members, _Group(g0, n, M, real_B)
 
-    def translate_ensemble(self, real_A, n_samples, z=None, real_B=None, quantiles=(0.05, 0.5, 0.95), chunk=None):
+    def translate_ensemble(self, real_A, n_samples, z=None, real_B=None, quantiles=(0.05, 0.5, 0.95), chunk=None, cell_stats=None):
         """The distribution of A -> B: n_samples translations of every input, summarised per pixel on the device.
         z: (N*n_samples, nlatent, 1, 1) codes in generate_multi's order (input n takes rows n*M .. n*M + M - 1; default N(0, 1)
         from torch's generator); chunk: the most images one generator pass may hold (default: ensemble_chunk).  Arguments are
         settled by plan_ensemble and the members come group by group from ensemble_groups, in eval state under no_grad; each
         group is followed by one acg_ensemble_stats launch into slices of the outputs.  Returns device tensors: mean, std
         (N, C, H, W) and quantiles (N, nq, C, H, W); with real_B also the per-input crps, crps_fair (NaN for one sample),
-        mse_mean, spread, coverage (N,), rank_hist (N, M + 1) and crps_map (N, C, H, W).  Nothing is read back to the host."""
-        M, N, C, H, W, z, per = plan_ensemble("translate_ensemble", self.opt, real_A, n_samples, z, real_B, chunk)
+        mse_mean, spread, coverage (N,), rank_hist (N, M + 1) and crps_map (N, C, H, W).  Nothing is read back to the host.
+        cell_stats: None, or a record (state, thresholds, edges) of ops.cell_state and the tables ops.cell_stats takes (real_B
+        required): each group's ensemble_stats launch is followed by one ops.cell_stats launch that adds the same members
+        against the same NHWC truth to the state, per cell of the grid across the inputs, in input order.  No generator pass
+        and no random draw of its own; what is returned keeps its bits."""
+        if cell_stats is not None and real_B is None:
+            raise ValueError("translate_ensemble: cell_stats needs the paired real_B")
+        M, N, C, H, W, z, per = plan_ensemble("translate_ensemble", self.opt, real_A, n_samples, z, real_B, chunk,
+                                              need_B=cell_stats is not None)
         q = ops.check_quantiles(quantiles)
         out = ops.ensemble_outputs(N, M, C, H, W, len(q), real_B is not None, real_A.device)
         with eval_state(self.netG_A_B), torch.no_grad():
@@ -575,6 +582,9 @@ class _Base(object):
                 if real_B is not None:
                     tgt = ops.ToNHWC.apply(real_B[g0:g0 + n], members.shape[-1] == ops.cimg(C))
                 ops.ensemble_stats(members, tgt, M, C, q, out={k: v[g0:g0 + n] for k, v in out.items()})
+                if cell_stats is not None:
+                    state, thr, edges = cell_stats
+                    ops.cell_stats(members, tgt, C, "nhwc", "nhwc", state, thresholds=thr, edges=edges, x_per_y=M)
         if real_B is None:
             return out
         sums, cells = out.pop("sums"), float(C * H * W)
@@ -585,6 +595,23 @@ class _Base(object):
         out["spread"] = torch.sqrt(sums[:, 3] / cells)
         out["coverage"] = sums[:, 4] / cells
         return out
+
+    def translate_cell_stats_A(self, real_B, real_A, state, thresholds, edges, chunk=None):
+        """B -> A per cell of the grid: the deterministic netG_B_A's translation of every real_B against the paired real_A,
+        added to a state of ops.cell_state with M = 1 (ops.cell_stats; thresholds, edges as it takes them), in eval state under
+        no_grad, in groups of at most `chunk` inputs (default ensemble_chunk), in input order -> the state.  ValueError for a
+        real_A that does not pair.  Nothing is read back to the host."""
+        if real_A.dim() != 4 or real_B.dim() != 4 or real_A.size(0) != real_B.size(0) or real_A.shape[2:] != real_B.shape[2:]:
+            raise ValueError("translate_cell_stats_A: real_A %s does not pair with real_B %s" % (tuple(real_A.shape), tuple(real_B.shape)))
+        chunk = ensemble_chunk(self.opt.ngf, real_B.size(2), real_B.size(3)) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("translate_cell_stats_A: chunk must be positive (got %d)" % chunk)
+        real_A = real_A.detach().contiguous()
+        with eval_state(self.netG_B_A), torch.no_grad():
+            for g0 in range(0, real_B.size(0), chunk):
+                pred = self.predict_A(real_B[g0:g0 + chunk])
+                ops.cell_stats(pred, real_A[g0:g0 + chunk], real_A.size(1), "nchw", "nchw", state, thresholds=thresholds, edges=edges)
+        return state
 
     def translate_spectrum(self, real_A, n_samples, z=None, real_B=None, chunk=None):
         """The variance of A -> B at every spatial scale: the radially averaged power spectrum (ops.radial_spectrum) of each

@@ -2418,6 +2418,175 @@ def reliability_summary(table):
 
 
 # ----------------------------------------------------------------------------------------------
+# per-cell climatology maps of ensembles (--metric ensemble --ens_maps 1; include/acgan_cell.h; tests/cell_stats_ref.py)
+# ----------------------------------------------------------------------------------------------
+CELL_MAX_HW, CELL_MAX_T, CELL_MAX_E, CELL_MAX_M = 1024, 8, 63, 64
+CELL_MOMENTS = ("Sx", "Sxx", "Sy", "Syy", "Sxy", "Sad", "SS", "SSy", "Sw")        # the planes of mom, in order
+_CELL_PARTS = (("mom", torch.float64), ("evt", torch.int64), ("hist_x", torch.int32), ("hist_y", torch.int32))
+
+
+def _cell_size(H, W):
+    if not (1 <= H <= CELL_MAX_HW and 1 <= W <= CELL_MAX_HW):
+        raise _lib.AcgError("cell_stats: fields must be H x W with 1 <= H, W <= %d (got %d x %d)" % (CELL_MAX_HW, H, W))
+    return H, W
+
+
+def _cell_shapes(C, H, W, T, E):
+    return dict(mom=(9, C, H, W), evt=(C, T, 4, H, W) if T else None, hist_x=(C, E + 1, H, W) if E else None,
+                hist_y=(C, E + 1, H, W) if E else None)
+
+
+def cell_state_bytes(C, H, W, T, E):
+    """the bytes of a cell_state on the device"""
+    return C * H * W * (9 * 8 + 4 * 8 * T + (2 * 4 * (E + 1) if E else 0))
+
+
+def cell_state(C, H, W, T, E, device):
+    """The zeroed state ops.cell_stats adds to: dict mom (9, C, H, W) float64 (the planes CELL_MOMENTS), evt (C, T, 4, H, W)
+    int64 (None for T = 0), hist_x, hist_y (C, E + 1, H, W) int32 (None for E = 0), n (the truth rows so far) and M (the
+    members per truth, 0 until the first call fixes it), Python ints.  ValueError outside C >= 1, 1 <= H, W <= 1024,
+    0 <= T <= 8, 0 <= E <= 63."""
+    C, H, W, T, E = (int(v) for v in (C, H, W, T, E))
+    if C < 1 or not (1 <= H <= CELL_MAX_HW and 1 <= W <= CELL_MAX_HW) or not 0 <= T <= CELL_MAX_T or not 0 <= E <= CELL_MAX_E:
+        raise ValueError("cell_state: need C >= 1, 1 <= H, W <= %d, 0 <= T <= %d, 0 <= E <= %d (got C=%d, %d x %d, T=%d, E=%d)"
+                         % (CELL_MAX_HW, CELL_MAX_T, CELL_MAX_E, C, H, W, T, E))
+    shapes = _cell_shapes(C, H, W, T, E)
+    state = {k: None if shapes[k] is None else torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _CELL_PARTS}
+    state.update(n=0, M=0)
+    return state
+
+
+def cell_stats(x, y, C, layout_x, layout_y, state, thresholds=None, edges=None, x_per_y=1):
+    """acg_cell_stats: one launch sequence that ADDS the rows of x (rows = Ny M fields, member m of truth n at row n M + m,
+    M = x_per_y) against y (Ny truths) to a state of ops.cell_state, per cell (c, i, j) of the fixed grid, and adds Ny to
+    state['n'] -> the state.  mom: the double sums Sx, Sxx, Sy, Syy, Sxy, Sad (|x - y|), SS (S^2, S the members' sum of a truth),
+    SSy (S y), Sw (M Q - S^2, Q the members' sum of squares), every float converted to double and every operation rounded
+    once, truths in row order and members in order inside: the same bits in every layout and whatever the split of the rows
+    into calls.  evt[c][t] += (k, o, k o, k k), k the members with x >= thresholds[c][t] and o = [y >= thresholds[c][t]], in
+    float32, NaN no event.  hist_x / hist_y[c][b] += 1 with b = #{e : edges[c][e] <= v}, NaN in bin 0; an int32 count holds
+    2^31 - 1 rows.  thresholds (C, T), edges (C, E, ascending): float32 on the device (a tensor's order is the caller's
+    contract) or host arrays (checked, copied to the device); None where the state has no such part.  Refused on the host, by
+    name (AcgError "cell_stats: ..."): a state of another shape, dtype or M, thresholds or edges that disagree with it,
+    operands that do not pair.  Subnormal float32 inputs are outside the equality claim.  Nothing is read back to the host.
+    Not differentiable."""
+    what = "cell_stats"
+    x, y, rows, rows_y, C, _, (H, W), sx, sy, x_per_y = _paired_fields(what, x, y, C, layout_x, layout_y, _cell_size, x_per_y,
+                                                                       max_per=CELL_MAX_M, size_y=True)
+    if not isinstance(state, dict) or any(k not in state for k in ("mom", "evt", "hist_x", "hist_y", "n", "M")):
+        raise _lib.AcgError("%s: state must be a dict of ops.cell_state (mom, evt, hist_x, hist_y, n, M)" % what)
+    thr = channel_table(what, _lib.AcgError, "thresholds", [[]] * C if thresholds is None else thresholds, C, CELL_MAX_T, None,
+                        none_if_empty=True)
+    edg = channel_table(what, _lib.AcgError, "edges", [[]] * C if edges is None else edges, C, CELL_MAX_E, None,
+                        none_if_empty=True, ordered=True)
+    T, E = 0 if thr is None else int(thr.size(1)), 0 if edg is None else int(edg.size(1))
+    shapes = _cell_shapes(C, H, W, T, E)
+    for k, dt in _CELL_PARTS:
+        t = state[k]
+        if (t is None) != (shapes[k] is None):
+            raise _lib.AcgError("%s: state[%r] is %s but the call has T=%d thresholds and E=%d edges"
+                                % (what, k, "absent" if t is None else "present", T, E))
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shapes[k] or t.dtype != dt or not t.is_contiguous()):
+            raise _lib.AcgError("%s: state[%r] %s %s is not a contiguous %s %s"
+                                % (what, k, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                   str(dt).replace("torch.", ""), shapes[k]))
+    if state["M"] not in (0, x_per_y):
+        raise _lib.AcgError("%s: the state holds ensembles of M=%d members, the call has x_per_y=%d" % (what, state["M"], x_per_y))
+    if not torch.is_tensor(thresholds) and thr is not None:       # a host array goes to the device; a tensor is where it has to be
+        thr = thr.to(x.device)
+    if not torch.is_tensor(edges) and edg is not None:
+        edg = edg.to(x.device)
+    _check(x, y, thr, edg)                                         # after the refusals that need no device
+    for k, _ in _CELL_PARTS:
+        if state[k] is not None and not state[k].is_cuda:
+            raise _lib.AcgError(_NO_CPU_PATH % state[k].device)
+    _lib.call("acg_cell_stats", _ptr(x), _ptr(y), rows, x_per_y, C, H, W, sx[0], sx[1], sx[2], sy[0], sy[1], sy[2], _ptr(thr), T,
+              _ptr(edg), E, _ptr(state["mom"]), _ptr(state["evt"]), _ptr(state["hist_x"]), _ptr(state["hist_y"]), _stream())
+    state["n"] += rows_y
+    state["M"] = x_per_y
+    return state
+
+
+def cell_summary(state, thresholds=None, edges=None, levels=()):
+    """A state of ops.cell_stats whose tensors are host arrays (read back by the caller) -> dict of float64 maps on the host,
+    (C, H, W) unless said otherwise.  With n truth rows, M members each and N = n M member rows:
+      mean_x = Sx / N, mean_y = Sy / n, bias = mean_x - mean_y
+      std_x, std_y     sqrt of the population variances Sxx / N - mean_x^2, Syy / n - mean_y^2, clamped at 0
+      std_ratio        std_x / std_y; NaN where the variance of y is 0
+      corr             (Sxy / N - mean_x mean_y) / (std_x std_y), members against the truth in time; NaN where a variance is 0
+      rmse             sqrt(max(Sxx + M Syy - 2 Sxy, 0) / N); mae = Sad / N
+      rmse_mean        the ensemble mean against the truth: sqrt(max((SS / M^2 - 2 SSy / M + Syy) / n, 0))
+      corr_mean        (SSy / (M n) - mean_x mean_y) / sqrt(var_mean var_y), var_mean = SS / (M^2 n) - mean_x^2 clamped at 0;
+                       NaN where a variance is 0
+      spread           sqrt(max(Sw, 0) / (M (M - 1) n)), the root of the mean unbiased ensemble variance; NaN for M = 1
+      spread_skill     sqrt((M + 1) / M) spread / rmse_mean; NaN for M = 1 and where rmse_mean is 0
+    With events (thresholds (C, T), needed only for its shape), each (C, T, H, W):
+      freq_x = sum k / N, freq_y = sum o / n, freq_bias = freq_x / freq_y (NaN where freq_y is 0),
+      brier = (sum k^2 - 2 M sum k o + M^2 sum o) / (M^2 n), the mean of (k / M - o)^2,
+      hit_rate = sum k o / (M sum o) (NaN where the truth never has the event),
+      csi = sum k o / (sum k + M sum o - sum k o) (NaN where neither ever has it)
+    With histograms (edges (C, E) required):
+      cdf_x, cdf_y (C, E, H, W)  the fraction of values below edge e (the bins 0 .. e; a NaN value lies in bin 0)
+      ks                         the largest |cdf_x - cdf_y| over the edges
+      q_x, q_y (C, L, H, W)      per level of `levels` the first edge whose CDF reaches it, NaN if none does
+    A state with n = 0 gives NaN everywhere (0 / 0).  A NaN in the sums of a cell stays a NaN in its maps.  No map is inf
+    where a denominator is 0: it is NaN."""
+    import numpy as np
+    mom = np.asarray(state["mom"], dtype=np.float64)
+    n, M = int(state["n"]), int(state["M"])
+    if mom.ndim != 4 or mom.shape[0] != 9:
+        raise ValueError("cell_summary: mom must be (9, C, H, W) (got %s)" % (mom.shape,))
+    C = mom.shape[1]
+    Sx, Sxx, Sy, Syy, Sxy, Sad, SS, SSy, Sw = mom
+    N = n * M
+    res = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nf, Nf, Mf = np.float64(n), np.float64(N), np.float64(M)
+        mean_x, mean_y = Sx / Nf, Sy / nf
+        var_x = np.maximum(Sxx / Nf - mean_x * mean_x, 0.0)     # np.maximum keeps a NaN
+        var_y = np.maximum(Syy / nf - mean_y * mean_y, 0.0)
+        std_x, std_y = np.sqrt(var_x), np.sqrt(var_y)
+        res.update(mean_x=mean_x, mean_y=mean_y, bias=mean_x - mean_y, std_x=std_x, std_y=std_y,
+                   std_ratio=np.where(var_y == 0, np.nan, std_x / std_y),
+                   corr=np.where((var_x == 0) | (var_y == 0), np.nan, (Sxy / Nf - mean_x * mean_y) / (std_x * std_y)),
+                   rmse=np.sqrt(np.maximum(Sxx + Mf * Syy - 2.0 * Sxy, 0.0) / Nf), mae=Sad / Nf)
+        rmse_mean = np.sqrt(np.maximum((SS / (Mf * Mf) - 2.0 * SSy / Mf + Syy) / nf, 0.0))
+        var_mean = np.maximum(SS / (Mf * Mf * nf) - mean_x * mean_x, 0.0)
+        corr_mean = np.where((var_mean == 0) | (var_y == 0), np.nan,
+                             (SSy / (Mf * nf) - mean_x * mean_y) / np.sqrt(var_mean * var_y))
+        spread = np.sqrt(np.maximum(Sw, 0.0) / (Mf * (Mf - 1.0) * nf)) if M > 1 else np.full(Sw.shape, np.nan)
+        skill = np.where(rmse_mean == 0, np.nan, np.sqrt((Mf + 1.0) / Mf) * spread / rmse_mean) if M >= 1 else spread
+        res.update(rmse_mean=rmse_mean, corr_mean=corr_mean, spread=spread, spread_skill=skill)
+        if state.get("evt") is not None:
+            evt = np.asarray(state["evt"]).astype(np.float64)
+            if evt.ndim != 5 or evt.shape[0] != C or evt.shape[2] != 4 or evt.shape[3:] != mom.shape[2:]:
+                raise ValueError("cell_summary: evt must be (C, T, 4, H, W) (got %s)" % (evt.shape,))
+            if thresholds is not None and np.shape(thresholds) != (C, evt.shape[1]):
+                raise ValueError("cell_summary: thresholds %s do not match evt %s" % (np.shape(thresholds), evt.shape))
+            k, o, ko, kk = evt[:, :, 0], evt[:, :, 1], evt[:, :, 2], evt[:, :, 3]
+            freq_x, freq_y = k / Nf, o / nf
+            union = k + Mf * o - ko
+            res.update(freq_x=freq_x, freq_y=freq_y, freq_bias=np.where(freq_y == 0, np.nan, freq_x / freq_y),
+                       brier=(kk - 2.0 * Mf * ko + Mf * Mf * o) / (Mf * Mf * nf),
+                       hit_rate=np.where(o == 0, np.nan, ko / (Mf * o)), csi=np.where(union == 0, np.nan, ko / union))
+        if state.get("hist_x") is not None:
+            hx, hy = np.asarray(state["hist_x"]).astype(np.float64), np.asarray(state["hist_y"]).astype(np.float64)
+            if edges is None or hx.shape != hy.shape or hx.ndim != 4 or np.shape(edges) != (C, hx.shape[1] - 1):
+                raise ValueError("cell_summary: histograms %s, %s need edges (C, E) with E + 1 bins (got %s)"
+                                 % (hx.shape, hy.shape, None if edges is None else np.shape(edges)))
+            ed = np.asarray(edges, dtype=np.float64)
+            lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+            cdf_x = np.cumsum(hx, axis=1)[:, :-1] / hx.sum(axis=1, keepdims=True)
+            cdf_y = np.cumsum(hy, axis=1)[:, :-1] / hy.sum(axis=1, keepdims=True)
+            res.update(cdf_x=cdf_x, cdf_y=cdf_y, ks=np.abs(cdf_x - cdf_y).max(axis=1))
+            for name, cdf in (("q_x", cdf_x), ("q_y", cdf_y)):
+                reach = cdf[:, None] >= lv[None, :, None, None, None]                # (C, L, E, H, W)
+                first = reach.argmax(axis=2)
+                q = np.take_along_axis(np.broadcast_to(ed[:, None, :, None, None], reach.shape), first[:, :, None], axis=2)[:, :, 0]
+                res[name] = np.where(reach.any(axis=2), q, np.nan)
+    return res
+
+
+# ----------------------------------------------------------------------------------------------
 # the fractions-skill-score training loss (the paired step under --lambda_fss_A / --lambda_fss_B; tests/fss_loss_ref.py)
 # ----------------------------------------------------------------------------------------------
 FSS_LOSS_MAX_WINDOW = 65

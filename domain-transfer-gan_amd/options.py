@@ -226,7 +226,9 @@ class TestOptions(object):
     the metric `fss`: the SAL score, structure, amplitude and location of the objects of the same paired translations, into a
     file of its own) with --sal_quantiles, --sal_thresholds, --sal_floor and --sal_conn; --fss_rel (with the metric `fss`: the
     reliability tables of the ensemble's neighbourhood events - Brier score and its decomposition, reliability diagram, ROC -
-    into a file of its own) with --rel_windows."""
+    into a file of its own) with --rel_windows; --ens_maps (with the metric `ensemble`: per-cell climatology maps over the
+    split - bias, RMSE, correlation in time, spread and skill, event frequencies and Brier score, value distributions - into
+    a file of its own) with --map_quantiles, --map_thresholds, --map_bins and --map_levels."""
 
     def __init__(self):
         from .eval_metrics import METRICS      # here, not at the top: it imports train.py, which imports this module
@@ -288,6 +290,23 @@ class TestOptions(object):
         self.parser.add_argument('--rel_windows', type=_rel_windows, default=(1, 5, 17),
                                  help='--metric fss --fss_rel 1: comma-separated odd neighbourhood widths in cells, at most 8, each '
                                       'at most 65; the neighbourhood event of a cell is any event inside the window')
+        self.parser.add_argument('--ens_maps', type=int, choices=[0, 1], default=0,
+                                 help='--metric ensemble: 1 also accumulates, per cell of the grid across the split, the moments, '
+                                      'event counts and histograms of the members against the truth (bias, RMSE, correlation, '
+                                      'spread/skill, Brier, quantile maps) -> ensemble_maps.npz; 0: off')
+        self.parser.add_argument('--map_quantiles', type=_map_quantiles, default=(0.9, 0.99),
+                                 help='--metric ensemble --ens_maps 1: the event thresholds as quantile levels of the real training '
+                                      'fields, per channel (trainB for A -> B, trainA for B -> A); comma-separated, inside [0, 1], at '
+                                      'most 8, sorted ascending before use; "none": no events')
+        self.parser.add_argument('--map_thresholds', type=_map_thresholds, default=None,
+                                 help='--metric ensemble --ens_maps 1: explicit event thresholds in data units, the same for every '
+                                      'channel (comma-separated, finite, at most 8; sorted ascending); overrides --map_quantiles')
+        self.parser.add_argument('--map_bins', type=_map_bins, default=32,
+                                 help='--metric ensemble --ens_maps 1: B = 0 (no histograms) or in 2..64; every cell keeps a histogram '
+                                      'of its values between the B - 1 quantiles k / B of the real training fields, per channel')
+        self.parser.add_argument('--map_levels', type=_map_levels, default=(0.5, 0.95, 0.99),
+                                 help='--metric ensemble --ens_maps 1: comma-separated quantile levels inside [0, 1], at most 16, of '
+                                      'the per-cell quantile maps (resolved to the histogram edges)')
         self.parser.add_argument('--overlap', type=_overlap, default=None,
                                  help='--metric translate / field_spectrum: pixels neighbouring windows share, 0 .. grid_size // 2 '
                                       '(default: grid_size // 4)')
@@ -355,6 +374,21 @@ def _sorted(parse):
 
 _sal_quantiles = _sorted(_floats("--sal_quantiles", _level, "levels inside [0, 1]"))
 _sal_thresholds = _sorted(_floats("--sal_thresholds", _finite, "finite numbers"))
+
+
+_map_thresholds = _sorted(_floats("--map_thresholds", _finite, "finite numbers"))
+_map_levels = _floats("--map_levels", _level, "levels inside [0, 1]", most=16)
+
+
+def _map_quantiles(s):
+    return () if s.strip().lower() == "none" else _sorted(_floats("--map_quantiles", _level, "levels inside [0, 1]"))(s)
+
+
+def _map_bins(s):
+    v = int(s)
+    if v != 0 and not 2 <= v <= 64:
+        raise argparse.ArgumentTypeError("--map_bins must be 0 or lie in 2..64 (got %d)" % v)
+    return v
 
 
 def _sal_floor(s):
